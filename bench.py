@@ -4,8 +4,14 @@
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: this process starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W --full  (everything below, not only the headline)
+    python bench.py ... --dump-outputs DIR                (the headline's last timed step -> DIR/*.npy)
 
-Two multi-GPU routes are timed, on the same workload:
+A plain run sets up, warms up, times the K headline steps and prints the result line (value / ms_per_step / roofline of the
+headline).  Everything else -- the CPU baseline, the operating point and FER sweep, the other configurations, the exact-replay
+figures and the abi_multi / exact_replay_ranks legs -- runs only with --full.
+
+Two multi-GPU routes are timed (abi_multi with --full), on the same workload:
   value / ms_per_step   one process per GPU, torch.distributed over RCCL: decode + count + all-reduce of the 5 counters per step,
                         barrier + synchronize on both sides of the K steps, MAX over ranks (the driver's contract);
   abi_multi             north_star's route: ONE C/C++-style host process, ldpc_hip_open_multi(devices 0..N-1) -- a context, a HIP
@@ -212,6 +218,28 @@ def roofline_block(kernel_name, kernel_ms_avg, launches, sum_iters_per_launch, f
                     "bank_conflict_cycles": p["SQ_LDS_BANK_CONFLICT"]}
         r["binding_roof"] = "valu_issue" if r["valu_issue"]["frac"] >= r["lds"]["frac"] else "lds"
     return r
+
+
+DUMP_HARD_BYTES = 48 << 20   # --dump-outputs: at most this much of hard decisions (float64); the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files --
+    hard_decisions.npy [frames, hard_words] (the packed 32-bit words of ldpc_hip_decode_dev, exact in float64), iterations.npy
+    [frames] (signed: negative = not converged) and error_counters.npy [5] (nse, nde, nue, frames, sum |iters|).  Batches beyond
+    DUMP_HARD_BYTES are written as a fixed, seeded sample of frames (sorted), their indices in frame_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    hard = last["hard"].cpu().numpy()
+    iters = last["iters"].cpu().numpy()
+    rows = None
+    if hard.nbytes * 2 > DUMP_HARD_BYTES:
+        keep = DUMP_HARD_BYTES // (hard.shape[1] * 8)
+        rows = np.sort(np.random.default_rng(1).choice(hard.shape[0], size=keep, replace=False))
+        hard, iters = hard[rows], iters[rows]
+        np.save(os.path.join(out_dir, "frame_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "hard_decisions.npy"), hard.astype(np.float64))
+    np.save(os.path.join(out_dir, "iterations.npy"), iters.astype(np.float64))
+    np.save(os.path.join(out_dir, "error_counters.npy"), last["counters"].cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(H, seconds_budget=12.0):
@@ -461,8 +489,12 @@ def launch_ranks(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--frames", str(args.frames), "--backend", args.backend, "--spawned", "--no-cpu-baseline"]
+    if args.full:
+        cmd.append("--full")
     if args.no_extras:
         cmd.append("--no-extras")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     procs = []
     for r in range(n):
         env = dict(clean_env(), RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
@@ -499,8 +531,9 @@ def launch_ranks(args):
         return 1
     out = json.loads(lines[-1])
     out["launcher"] = "bench.py (parent process without GPU state started one fresh process per rank)"
-    out["abi_multi"] = run_abi_multi_child(args)
-    if not args.no_extras:
+    if args.full:
+        out["abi_multi"] = run_abi_multi_child(args)
+    if args.full and not args.no_extras:
         out["exact_replay_ranks"] = exact_ranks_leg(args)
     print(json.dumps(out))
     return 0
@@ -512,15 +545,24 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=FRAMES_PER_GPU, help="frames per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip operating point, FER sweep and the other configurations (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also measure the CPU baseline, operating point, FER sweep, the other configurations, "
+                         "exact replay and the abi_multi / exact_replay_ranks legs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed (hard decisions, iterations, error counters) to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip operating point, FER sweep and the other configurations (profiling runs)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI, the measured configuration); gloo only rehearses the N>1 code path on a box "
                          "with fewer GPUs than ranks (ranks then share devices and the counters are reduced on the host)")
     ap.add_argument("--leg", default=None, choices=["abi_multi", "exact_ranks"],
                     help="internal: run only the C-ABI multi-device leg / the rank-sharded exact-replay leg and print its JSON")
-    ap.add_argument("--spawned", action="store_true", help="internal: this rank was started by bench.py itself (the parent adds the abi_multi leg)")
+    ap.add_argument("--spawned", action="store_true", help="internal: this rank was started by bench.py itself (with --full the parent adds the abi_multi leg)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
 
     if args.leg == "abi_multi":
         print(json.dumps(abi_multi_leg(args.gpus, args.steps, args.warmup, args.frames)))
@@ -543,7 +585,7 @@ def main():
 
     # the CPU leg first: nothing has touched the GPU yet (no torch.cuda call, libldpc_hip.so not loaded)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(H)
         except Exception as ex:  # the bench line must still be printed
@@ -589,11 +631,12 @@ def main():
 
     pmc, pmc_why = load_pmc()
 
-    def timed(dec, B, snr, steps, warmup, maxiter, modulation=0, dec_b=None):
+    def timed(dec, B, snr, steps, warmup, maxiter, modulation=0, dec_b=None, last=None):
         """W warm-up + K timed steps (decode + count [+ all-reduce]) over batches resident in HBM; returns wall seconds (max over
         ranks), the counter totals and the decode kernel's HIP-event time.  With a second context `dec_b` consecutive steps alternate
         between two HIP streams (one context each), so that two batches are in flight: where frames leave early (operating point) the
-        slots the last long-running frames of one batch leave idle are taken by the next batch."""
+        slots the last long-running frames of one batch leave idle are taken by the next batch.  `last` (a dict) receives the output
+        buffers of the last timed step."""
         nb = min(max(steps, 1), 8)
         if B * dec.N * 8 * nb > 12e9:
             nb = max(1, int(12e9 // (B * dec.N * 8)))
@@ -639,6 +682,9 @@ def main():
         if world > 1:
             all_reduce(t, op=dist.ReduceOp.MAX)
         tot = sum(ln["tot"] for ln in lanes)
+        if last is not None:
+            ln = lanes[(steps - 1) % len(lanes)]
+            last.update(hard=ln["hard"], iters=ln["iters"], counters=ln["cnt"])
         del batches
         return float(t.item()), tot.cpu().tolist(), kms, klaunch
 
@@ -647,7 +693,8 @@ def main():
     dec = ldpc_lib_amd.LdpcHip(DEC_MS, H, M, device=local)
     N, E, R = dec.N, dec.edges * M, dec.R
     bytes_iter = algorithmic_bytes_per_iter("ms", E, R, N)
-    el, tot, kms, klaunch = timed(dec, B, WORST_SNR, args.steps, args.warmup, MAXITER)
+    last = {}
+    el, tot, kms, klaunch = timed(dec, B, WORST_SNR, args.steps, args.warmup, MAXITER, last=last)
     frames_total = tot[3]
     assert frames_total == B * args.steps * world, (frames_total, B, args.steps, world)
     value = frames_total / el
@@ -670,7 +717,10 @@ def main():
                                f"{8 * N} (fp64 LLR in) + {N // 8 + 4} (packed bits + iters out); the binding roof is VALU issue "
                                "(fp64 + half-rate VOP3 / compare / select), see valu_issue / lds / hbm_physical")
 
-    if not args.no_extras:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+
+    if extras:
         osteps = max(4, args.steps // 2)
         el2, tot2, kms2, kl2 = timed(dec, B, OPER_SNR, osteps, 1, MAXITER)
         with ldpc_lib_amd.LdpcHip(DEC_MS, H, M, device=local) as dec_b:   # the same workload with two batches in flight on two streams
@@ -699,7 +749,7 @@ def main():
     dec.close()
 
     # ---------------- the other configurations, same run, one GPU (N = 1 only: they are per-GPU figures)
-    if not args.no_extras and world == 1:
+    if extras and world == 1:
         from ldpc_testlib import load_base_matrix as lbm
         cfgs = {}
         ksteps = max(3, min(args.steps, 6))
@@ -738,18 +788,18 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         try:    # one shard, no communicator: the same entry point the N > 1 leg times
             out["abi_multi"] = abi_multi_leg(1, max(3, min(args.steps, 10)), 1, B)
         except Exception as ex:
             out["abi_multi"] = {"error": repr(ex)}
         out["exact_replay_ranks"] = run_abi_multi_child(args, timeout=480, leg="exact_ranks")   # N = 1: the figures the N > 1 lines must repeat
-    elif world > 1 and not args.spawned:
+    elif world > 1 and not args.spawned and args.full:
         # started by an external launcher: the other ranks are on their way out; a fresh child process (never this one re-executed)
         # opens all N GPUs behind the C-ABI
         torch.cuda.empty_cache()
         out["abi_multi"] = run_abi_multi_child(args)
-        if not args.no_extras:
+        if extras:
             out["exact_replay_ranks"] = run_abi_multi_child(args, timeout=480, leg="exact_ranks")
     print(json.dumps(out))
 

@@ -447,7 +447,7 @@ def test_bench_gpus_2_runs_without_a_launcher(L):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--frames", "8192", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--frames", "8192", "--full", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["value"] > 0 and line["scaling"] == "weak"
@@ -456,6 +456,36 @@ def test_bench_gpus_2_runs_without_a_launcher(L):
     assert "error" not in abi, abi
     assert abi["n_gpus"] == 2 and abi["reduction"] == "host" and abi["value"] > 0 and abi["frames_per_gpu_per_step"] == 8192
     assert abs(abi["fer"] - line["config"]["fer"]) < 0.01 and abi["mean_iters_per_frame"] > 49.9   # the same workload: 0 dB, all iterations
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_its_last_step(L, torch, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (no --full): K timed headline steps, none of the --full figures, and
+    the last timed step's outputs in DIR -- the decoder's hard decisions and iterations equal the CPU oracle on that step's batch."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    B, steps = 4096, 3
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--frames", str(B), "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f64"
+    assert not {"operating_point", "fer_sweep", "configs", "exact_replay", "abi_multi", "exact_replay_ranks"} & set(line)
+    assert line["cpu_baseline"] is None
+    hard, iters, cnt = (np.load(str(tmp_path / f)) for f in ("hard_decisions.npy", "iterations.npy", "error_counters.npy"))
+    assert hard.dtype == iters.dtype == cnt.dtype == np.float64 and not (tmp_path / "frame_index.npy").exists()
+    H = relift(load_base_matrix(), 64)
+    with L.LdpcHip(MS_DEC, H, 64, device=0) as dec:
+        assert hard.shape == (B, dec.hard_words) and iters.shape == (B,)
+        llr = dec.awgn_llr(0.0, seed=1, first_frame=(steps - 1) * B, B=B)   # the batch bench.py's last timed step decoded
+        torch.cuda.synchronize()
+        llr = llr[:8].cpu().numpy()
+    d_ref, it_ref, _ = Oracle(H, 64).decode(MS_DEC, llr, 50, 0)
+    assert np.array_equal(iters[:8], it_ref)
+    assert np.array_equal(hard[:8].astype(np.int64).astype(np.uint32), pack_bits(d_ref))
+    assert cnt[3] == B and cnt[4] == np.abs(iters).sum()
 
 
 @pytest.mark.gpu

@@ -338,19 +338,19 @@ def test_jsonx_reader_follows_upstreams_grammar(tmp_path):
     assert subprocess.run([exe, "jsonx", str(tmp_path / "bad.jsonx"), str(tmp_path / "c.jsonx")], capture_output=True).returncode == 1
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/files"), reason="upstream tree not mounted")
 def test_jsonx_reader_takes_every_file_upstream_ships(tmp_path):
+    """upstream's files/*.jsonx, kept as data fixtures under tests/golden/jsonx/ (the '@' references between them intact)."""
     import glob
     import subprocess
     exe = _ldpc_sim()
-    files = sorted(glob.glob("/root/reference/files/*.jsonx"))
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "jsonx", "*.jsonx")))
     assert len(files) >= 10
     for f in files:
         subprocess.check_call([exe, "jsonx", f, str(tmp_path / "a.jsonx")])
         subprocess.check_call([exe, "jsonx", str(tmp_path / "a.jsonx"), str(tmp_path / "b.jsonx")])
         assert (tmp_path / "a.jsonx").read_text() == (tmp_path / "b.jsonx").read_text(), f
     def get(f, path):
-        return subprocess.check_output([exe, "jsonx-get", "/root/reference/files/" + f, path], text=True).strip()
+        return subprocess.check_output([exe, "jsonx-get", os.path.join(ROOT, "tests", "golden", "jsonx", f), path], text=True).strip()
     assert get("input32_16.jsonx", "decoder_type") == "7" and get("input32_16.jsonx", "permutation_block") == "128"
     assert get("resultq.jsonx", "results/0/_lifting") == "8" and get("resultq.jsonx", "settings/error_minimization/name") == "FER"
 

@@ -31,7 +31,7 @@ def row(label, kern, worst, oper, rf):
 
 
 out = ["## 9. Numbers of this round", "",
-       f"From `profiles/{TAG}_bench.json` (one `python bench.py` run on an MI355X; PMC figures from `profiles/{TAG}_pmc.json`, same sources). "
+       f"From `profiles/{TAG}_bench.json` (one `python bench.py --full` run on an MI355X; PMC figures from `profiles/{TAG}_pmc.json`, same sources). "
        "Worst case = Eb/N0 0 dB, every frame runs all iterations, LLRs resident in HBM.", "",
        "| configuration | kernel | frames/s worst case | frames/s at the operating point | kernel ms / launch | effective §8(d) fraction of 8 TB/s | "
        "VALU-issue fraction (instr. per wave-iteration) | LDS busy | LDS bank-conflict cycles / launch | physical HBM fraction |",

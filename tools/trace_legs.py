@@ -15,7 +15,7 @@ bench = json.load(open(sys.argv[2]))
 seq = collections.defaultdict(list)
 for r in rows:
     seq[r["Kernel_Name"].split("(")[0]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
-print("# rocprofv3 --kernel-trace of `python3 bench.py --no-cpu-baseline`: mean End-Start of the K timed worst-case dispatches of each")
+print("# rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu-baseline`: mean End-Start of the K timed worst-case dispatches of each")
 print("# configuration's decode kernel (trace) next to bench.py's kernel_ms_avg of the same run (HIP events on the launch stream)")
 print(f"# {'configuration':28s} {'kernel':36s} {'K':>3s} {'trace avg ms':>12s} {'bench ms':>9s} {'diff %':>7s}")
 legs = [("cfg2 headline", bench["roofline"]["kernel"].split(" ")[0], bench["warmup"], bench["steps"], bench["roofline"]["kernel_ms_avg"])]
