@@ -35,6 +35,7 @@ extern "C" {
 #define LDPC_HIP_ASP_DEC 2 /* sum_prod_gf2_decod_qc_lm decoders.cpp:2324 (probability-domain flooding sum-product) */
 #define LDPC_HIP_MS_DEC 3  /* min_sum_decod_qc_lm    decoders.cpp:4554 */
 #define LDPC_HIP_IMS_DEC 4 /* imin_sum_decod_qc_lm   decoders.cpp:5430 */
+#define LDPC_HIP_IASP_DEC 5 /* isum_prod_gf2_decod_qc_lm decoders.cpp:3822 (integer advanced sum-product, IASP_FIXED_POINT build) */
 #define LDPC_HIP_TASP_DEC 7 /* tdmp_sum_prod_gf2_decod_qc_lm decoders.cpp:2584 (decoder_type of the shipped scenario files) */
 #define LDPC_HIP_LMS_DEC 8 /* lmin_sum_decod_qc_lm   decoders.cpp:5064 */
 
@@ -51,7 +52,9 @@ int ldpc_hip_device_count(void);
 
 /* Replaces decod_open() + the hd fill + decod_init()  (decoders.h:293-294, decoders.cpp:348,1009,
  * bp_simulation.cpp:353-382).  hd is row-major rh x nh.  device = HIP device ordinal.
- * *out receives the context; NULL on failure (upstream: decod_open returns NULL). */
+ * *out receives the context; NULL on failure (upstream: decod_open returns NULL).
+ * ASP_DEC, IASP_DEC and TASP_DEC refuse codes with a block row of weight < 2 (LDPC_HIP_EUNSUPPORTED): upstream's check-node
+ * routines read an uninitialised forward / backward product for such a row (decoders.cpp:2191-2228, :2235-2271). */
 int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int device, ldpc_hip_ctx **out);
 /* Replaces decod_close() (decoders.h:295, decoders.cpp:1210). */
 void ldpc_hip_close(ldpc_hip_ctx *ctx);
@@ -85,6 +88,9 @@ const char *ldpc_hip_last_launch(const ldpc_hip_ctx *ctx);
  *   BP_DEC:  bp_decod_qc_lm(st, soft, decword, maxiter, decision)                  (d_soft = a-posteriori LLR)
  *   ASP_DEC: sum_prod_gf2_decod_qc_lm(st, soft, decword, maxiter, decision)       (d_soft = a-posteriori P(bit=1))
  *   TASP_DEC: tdmp_sum_prod_gf2_decod_qc_lm(st, soft, decword, maxiter, decision)  (d_soft = final P(bit=1); `decision` dead)
+ *   IASP_DEC: isum_prod_gf2_decod_qc_lm(st, soft, decword, maxiter, decision)     (d_soft = soft_out / 65536, the u16 Q16
+ *            a-posteriori word as upstream's decision == 1 output; hard bit = soft_out >> 15.  Integer arithmetic throughout:
+ *            bit for bit with no libm argument except the channel transform's exp, which is glibc's)
  * All pointers are DEVICE pointers on ctx's device; the work is enqueued on `stream` (a hipStream_t, NULL =
  * default stream) and is asynchronous.  maxiter must be >= 1 (upstream's behaviour for maxiter <= 0 is an artefact of
  * stale state and is not reproduced: LDPC_HIP_EINVAL).  LLRs must be finite.
@@ -118,7 +124,8 @@ int ldpc_hip_set_bp_chain(ldpc_hip_ctx *ctx, int on, int reset_carry);
 int ldpc_hip_set_ims_params(ldpc_hip_ctx *ctx, double thr, int qbits, int dbits);
 
 /* Same with HOST pointers, laid out exactly like upstream's per-frame arrays (PCIe-inclusive, synchronous):
- *   llr [B][N] in (for SP it is overwritten like upstream's soft[] when clobber_sp_input != 0),
+ *   llr [B][N] in (for SP it is overwritten like upstream's soft[] when clobber_sp_input != 0; for ASP and TASP it then holds
+ *   P(bit = 1) of the channel, for IASP 1 / (1 + exp(clamp(llr, -20, 20))) as decoders.cpp:3858-3863 leaves it),
  *   decword [B][N] float64 out (0.0/1.0 when decision==0, a-posteriori values when decision==1), iters [B]. */
 int ldpc_hip_decode_host(ldpc_hip_ctx *ctx, double *llr, long long B, int maxiter, int decision, double alpha,
                          double *decword, int32_t *iters, int clobber_sp_input);

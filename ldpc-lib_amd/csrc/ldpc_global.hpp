@@ -13,6 +13,8 @@
 //   bp_global_kernel   bp_decod_qc_lm        decoders.cpp:1708-1920, with the frame chain of the resident kernel.
 //   asp_global_kernel  sum_prod_gf2_decod_qc_lm  decoders.cpp:2324-2581 (the general branch, and the branch for codes whose block
 //                      columns all hold exactly two circulants, :2431-2480).
+//   iasp_global_kernel isum_prod_gf2_decod_qc_lm  decoders.cpp:3822-4121 (integer advanced sum-product, decoder 5; both branches,
+//                      u16 / i16 state in the workspace).
 //   tasp_global_kernel tdmp_sum_prod_gf2_decod_qc_lm  decoders.cpp:2584-2744 (decoder 7, the decoder of upstream's shipped scenarios):
 //                      per-edge lambda / rho / forward / backward products in the workspace instead of VGPRs, so row weight and
 //                      the number of circulants are unbounded (the resident tasp_body holds the Z state of ~300 circulants in the registers of two lanes per check).
@@ -47,7 +49,8 @@ struct GlobArgs {
     uint32_t *synd_out;       // same layout: what this frame leaves behind, or null
     const int *frame_idx;     // [slots] frame decoded by each workgroup slot, or null = the slot index
     long long slots;          // workgroup slots of this launch (B, or the number of frames of a re-decode pass)
-    int asp_cw2;              // asp_global_kernel: every block column holds exactly two circulants -> upstream's own branch (decoders.cpp:2431-2480)
+    int asp_cw2;              // asp_global_kernel / iasp_global_kernel: every block column holds exactly two circulants -> upstream's own branch
+                              // (decoders.cpp:2431-2480 / :3915-3977)
     const double *ims_coef;   // ims_global_kernel: [B] sqrt(N / sum y^2) per frame (ims_coef_kernel: the sum is sequential, its rounding is part of the result)
 };
 
@@ -611,6 +614,118 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
             steps = steps + 1;
         }
         glob_outputs<1>(a, w, fr, synd ? -steps : steps);                           // 0: codeword at the input; converged after `steps`; else -steps
+        __syncthreads();
+    }
+}
+
+// isum_prod_gf2_decod_qc_lm, decoders.cpp:3822-4121 (integer advanced sum-product, decoder 5): the general branch :3978-4100 and --
+// GlobArgs::asp_cw2 -- the branch for codes whose block columns all hold exactly two circulants (:3915-3977).  The arithmetic is
+// ldpc_spec::iasp (shared with the resident iasp_body).  Workspace (glob_ws_bytes with one edge array): state u16 [ne][M] and
+// imap_bin's forward products i16 [ne][M] in tmp, the a-posteriori word u16 [N] in soft, the channel word u16 [N] in aux.
+__global__ void __launch_bounds__(kGlobThreads) iasp_global_kernel(const GlobArgs g) {
+    namespace I = ldpc_spec::iasp;
+    const DecArgs &a = g.d;
+    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
+    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
+    uint16_t *const ST = reinterpret_cast<uint16_t *>(w.tmp);
+    int16_t *const SF = reinterpret_cast<int16_t *>(ST + (size_t)ne * M);          // 4 B per slot of the 8 B edge array
+    uint16_t *const so = reinterpret_cast<uint16_t *>(w.soft), *const ych = reinterpret_cast<uint16_t *>(w.aux);
+    auto syndrome = [&]() -> int {                                                  // icheck_syndrome :3772-3803
+        int fail = 0;
+        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
+            const int j = chk / M, n = chk - j * M;
+            int synd = 0;
+            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
+                const uint32_t d = a.edges[e];
+                int i = n + (int)(d & 0xffffu);
+                if (i >= M) i -= M;
+                synd ^= so[(int)(d >> 16) * M + i] >> 15;
+            }
+            fail |= synd;
+        }
+        return __syncthreads_or(fail);
+    };
+    for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
+        for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                    // :3858-3897
+            const int k = v / M, t = v - k * M;
+            const uint32_t q = I::q12(I::prior(a.llr[fr * N + v]));
+            for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {             // state <- rotated Q12 value
+                int nn = t - (int)(a.col_edges[c] & 0xffffu);
+                if (nn < 0) nn += M;
+                ST[(size_t)a.col_slot[c] * M + nn] = (uint16_t)q;
+            }
+            so[v] = ych[v] = (uint16_t)(q << 4);                                    // then the words, Q16
+        }
+        __syncthreads();
+        int synd = syndrome();                                                      // :3899-3906
+        int steps = 0;
+        while (synd != 0 && steps < a.maxiter) {
+            for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {          // imap_bin :2235-2271, any row weight >= 2
+                const int j = chk / M, n = chk - j * M;
+                const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
+                auto st = [&](int i) -> uint16_t & { return ST[(size_t)(e0 + i) * M + n]; };
+                auto sf = [&](int i) -> int16_t & { return SF[(size_t)(e0 + i) * M + n]; };
+                int f = I::chk_p(st(0));                                            // forward products SF[0 .. rw-2]
+                sf(0) = (int16_t)f;
+                for (int i = 1; i < rw - 1; ++i) { f = I::i16(I::chk_mul(I::chk_p(st(i)), f)); sf(i) = (int16_t)f; }
+                int sb = 0;                                                         // backward: SB[i+1] while slot i is written
+                for (int i = rw - 1; i >= 0; --i) {
+                    const int p = I::chk_p(st(i));
+                    uint32_t out;
+                    if (i == rw - 1) { out = I::chk_out(sf(rw - 2)); sb = p; }
+                    else if (i == 0) out = I::chk_out(sb);
+                    else { out = I::chk_out(I::chk_mul(sf(i - 1), sb)); sb = I::i16(I::chk_mul(p, sb)); }
+                    st(i) = (uint16_t)out;
+                }
+            }
+            __syncthreads();
+            if (g.asp_cw2) {
+                for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {            // :3915-3977
+                    const int k = v / M, t = v - k * M;
+                    const int c0 = a.col_start[k], c1 = c0 + 1;                     // hci[i][0] < hci[i][1]: rows ascending
+                    int n0 = t - (int)(a.col_edges[c0] & 0xffffu), n1 = t - (int)(a.col_edges[c1] & 0xffffu);
+                    if (n0 < 0) n0 += M;
+                    if (n1 < 0) n1 += M;
+                    const size_t z0 = (size_t)a.col_slot[c0] * M + n0, z1 = (size_t)a.col_slot[c1] * M + n1;
+                    uint32_t s, d0, d1;
+                    I::cw2(ych[v], ST[z0], ST[z1], s, d0, d1);
+                    so[v] = (uint16_t)s;
+                    ST[z0] = (uint16_t)d0;
+                    ST[z1] = (uint16_t)d1;
+                }
+            } else
+            for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                // :3978-4100
+                const int k = v / M, t = v - k * M;
+                uint32_t P1 = (uint32_t)ych[v] << 16, P0 = (65536u - ych[v]) << 16;
+                for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {         // rows ascending
+                    int nn = t - (int)(a.col_edges[c] & 0xffffu);
+                    if (nn < 0) nn += M;
+                    I::col_mul(P1, P0, ST[(size_t)a.col_slot[c] * M + nn]);
+                }
+                const uint32_t s = I::col_soft(P1, P0);
+                so[v] = (uint16_t)s;
+                for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {
+                    int nn = t - (int)(a.col_edges[c] & 0xffffu);
+                    if (nn < 0) nn += M;
+                    const size_t zi = (size_t)a.col_slot[c] * M + nn;
+                    ST[zi] = (uint16_t)I::local_update(s, ST[zi]);
+                }
+            }
+            __syncthreads();
+            synd = syndrome();                                                      // :4104-4113
+            steps = steps + 1;
+        }
+        const int res = synd ? -steps : steps;
+        if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
+        if (a.hard) {
+            for (int wd = threadIdx.x; wd < a.hard_words; wd += (int)blockDim.x) {
+                uint32_t bits = 0;
+                for (int b = 0; b < 32; ++b) if (32 * wd + b < N) bits |= (uint32_t)(so[32 * wd + b] >> 15) << b;
+                a.hard[fr * a.hard_words + wd] = bits;
+            }
+        }
+        if (a.soft_out)                                                             // imake_output :3805-3820, decision 1
+            for (int v = threadIdx.x; v < N; v += (int)blockDim.x) a.soft_out[fr * N + v] = (double)so[v] / 65536.0;
         __syncthreads();
     }
 }

@@ -135,6 +135,7 @@ const AotInstance kAot[] = {
     {LDPC_HIP_SP_DEC, (const void *)sp_spec_appendix_c_m64_kernel, 64 * ldpc_spec::kSpBodyWaves, "sp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_BP_DEC, (const void *)bp_spec_appendix_c_m64_kernel, 512, "bp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_ASP_DEC, (const void *)asp_spec_appendix_c_m64_kernel, 512, "asp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
+    {LDPC_HIP_IASP_DEC, (const void *)iasp_spec_appendix_c_m64_kernel, 512, "iasp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_TASP_DEC, (const void *)tasp_spec_appendix_c_m64_kernel, 128, "tasp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_TASP_DEC, (const void *)tasp_spec_appendix_c_m126_kernel, 256, "tasp_spec_appendix_c_m126_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM126>},
 };
@@ -152,6 +153,12 @@ __global__ void __launch_bounds__(256) channel_prior_kernel(double *x, long long
     }
 }
 
+// What the integer advanced sum-product decoder leaves in its input array (decoders.cpp:3858-3863): 1 / (1 + exp(clamp(x, +-20))).
+__global__ void __launch_bounds__(256) iasp_channel_prior_kernel(double *x, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        x[i] = ldpc_spec::iasp::prior(x[i]);
+}
+
 struct ldpc_hip_ctx {
     int decoder_id = 0, device = 0;
     int rh = 0, nh = 0, M = 0, N = 0, R = 0, ne = 0, hard_words = 0;
@@ -164,7 +171,7 @@ struct ldpc_hip_ctx {
     double ims_thr = 1.4;  // MS_THR, MS_QBITS, MS_DBITS (decoders.h:46-48), see ldpc_hip_set_ims_params
     int ims_qbits = 6, ims_dbits = 8;
     // shape-unlimited tier (ldpc_global.hpp): message state in a workspace in global memory
-    bool asp_cw2 = false;    // ASP_DEC on a code whose block columns all hold two circulants: upstream's own branch, on this tier only
+    bool asp_cw2 = false;    // ASP_DEC / IASP_DEC on a code whose block columns all hold two circulants: upstream's own branch, on this tier only
     bool global_tier = false;
     char *d_glob_ws = nullptr;
     size_t glob_stride = 0;
@@ -349,6 +356,14 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
         if (t.min_rw >= 2 && !all_cw2 && lds <= kLdsBudget) { p.body = "asp_body"; p.threads = 512; p.lds = lds; }
         break;
     }
+    case LDPC_HIP_IASP_DEC: {
+        p.required = true;  // code-specialised instances only; the all-columns-of-weight-2 branch (decoders.cpp:3915-3977) runs on the shape-unlimited tier
+        const size_t lds = (((size_t)2 * t.ne * M + 15) & ~(size_t)15) + (((size_t)N + 15) & ~(size_t)15) + 16;   // u16 state, hard bits, vote
+        bool all_cw2 = true;
+        for (int k = 0; k < t.nh; ++k) all_cw2 = all_cw2 && (t.col_start[k + 1] - t.col_start[k] == 2);
+        if (t.min_rw >= 2 && !all_cw2 && lds <= kLdsBudget) { p.body = "iasp_body"; p.threads = 512; p.lds = lds; }
+        break;
+    }
     case LDPC_HIP_TASP_DEC:
         p.required = true;  // per-edge state lives in VGPRs of the two lanes of a check: code-specialised instances only
         {   // 2 M threads per frame; LDS: a-posteriori probabilities + one spare slot per thread + flag words
@@ -435,8 +450,8 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
     if (out) *out = nullptr;
     if (!out || !hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open: bad argument");
     if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_IMS_DEC &&
-        decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_ASP_DEC && decoder_id != LDPC_HIP_BP_DEC)
-        return fail(LDPC_HIP_EUNSUPPORTED, "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, TASP=7, LMS=8)", decoder_id);
+        decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_ASP_DEC && decoder_id != LDPC_HIP_BP_DEC && decoder_id != LDPC_HIP_IASP_DEC)
+        return fail(LDPC_HIP_EUNSUPPORTED, "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, IASP=5, TASP=7, LMS=8)", decoder_id);
     if (M >= 65536 || nh >= 65536 || rh >= 65536) return fail(LDPC_HIP_EUNSUPPORTED, "M, rh and nh must be < 65536");
     if ((long long)nh * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "code length nh * M = %lld: at most 2^28 - 1 is supported (32-bit indices)", (long long)nh * M);
     int ndev = 0;
@@ -490,12 +505,14 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
     c->have_generic = have_generic;
     if (have_generic) c->generic_name = c->kernel_name;
 
-    bool all_cw2 = true;   // decoder 2 has its own branch for codes whose block columns all hold two circulants (decoders.cpp:1027-1044,
-                           // :2431-2480): the shape-unlimited tier runs it (asp_global_kernel), the resident asp_body is the general branch
+    bool all_cw2 = true;   // decoders 2 and 5 have their own branch for codes whose block columns all hold two circulants (decoders.cpp:1027-1044,
+                           // :2431-2480; :1062-1095, :3915-3977): the shape-unlimited tier runs it (asp_global_kernel, iasp_global_kernel),
+                           // the resident asp_body / iasp_body are the general branch
     for (int k = 0; k < nh; ++k) all_cw2 = all_cw2 && (t.col_start[k + 1] - t.col_start[k] == 2);
-    c->asp_cw2 = decoder_id == LDPC_HIP_ASP_DEC && all_cw2;
+    c->asp_cw2 = (decoder_id == LDPC_HIP_ASP_DEC || decoder_id == LDPC_HIP_IASP_DEC) && all_cw2;
     const bool can_global = decoder_id == LDPC_HIP_BP_DEC || decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_LMS_DEC || decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_IMS_DEC ||
-                            (decoder_id == LDPC_HIP_TASP_DEC && t.min_rw >= 2) || (decoder_id == LDPC_HIP_ASP_DEC && t.min_rw >= 2);
+                            (decoder_id == LDPC_HIP_TASP_DEC && t.min_rw >= 2) || (decoder_id == LDPC_HIP_ASP_DEC && t.min_rw >= 2) ||
+                            (decoder_id == LDPC_HIP_IASP_DEC && t.min_rw >= 2);
 
     // ---- code-specialised instance: ahead of time for the shipped example code, hiprtc for anything else
     const SpecPlan plan = plan_spec(decoder_id, t);
@@ -537,9 +554,9 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         c->global_tier = true;
         c->global_is_fallback = c->jit_job != nullptr;   // until the background instance arrives
         c->spec_aot = nullptr; c->spec_jit = nullptr;
-        c->kernel_name = decoder_id == LDPC_HIP_MS_DEC ? "ms_global_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_global_kernel" : decoder_id == LDPC_HIP_IMS_DEC ? "ims_global_kernel" : decoder_id == LDPC_HIP_ASP_DEC ? "asp_global_kernel" : decoder_id == LDPC_HIP_BP_DEC ? "bp_global_kernel" :
+        c->kernel_name = decoder_id == LDPC_HIP_MS_DEC ? "ms_global_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_global_kernel" : decoder_id == LDPC_HIP_IMS_DEC ? "ims_global_kernel" : decoder_id == LDPC_HIP_ASP_DEC ? "asp_global_kernel" : decoder_id == LDPC_HIP_IASP_DEC ? "iasp_global_kernel" : decoder_id == LDPC_HIP_BP_DEC ? "bp_global_kernel" :
                          decoder_id == LDPC_HIP_SP_DEC ? "sp_global_kernel" : "tasp_global_kernel";
-        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) ? 0 : decoder_id == LDPC_HIP_TASP_DEC ? 4 : decoder_id == LDPC_HIP_ASP_DEC ? 3 : 1);
+        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) ? 0 : decoder_id == LDPC_HIP_TASP_DEC ? 4 : decoder_id == LDPC_HIP_ASP_DEC ? 3 : 1);   // IASP: u16 state + i16 products in the one edge array
     }
     if (decoder_id == LDPC_HIP_IMS_DEC && !c->global_tier)   // parameters beyond int8 may send a launch to the global tier later
         c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, 0);
@@ -547,7 +564,7 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         if (!have_generic)
             return fail(LDPC_HIP_EUNSUPPORTED, "decoder %d, code %dx%d lifting %d: not supported by the generic kernel (limits: %d block rows, "
                         "%d block columns, row weight %d, M <= 512, 160 KiB LDS), no code-specialised instance: %s; the shape-unlimited "
-                        "tier serves every built decoder; decoders 2 and 7 need row weights >= 2",
+                        "tier serves every built decoder; decoders 2, 5 and 7 need row weights >= 2",
                         decoder_id, rh, nh, M, kRHM, kNHM, kRWM, why_not.c_str());
         if (plan.body && c->variant >= 2 && !c->jit_job)
             fprintf(stderr, "[ldpc_hip] code-specialised kernel unavailable (%s); using %s\n", why_not.c_str(), c->kernel_name.c_str());
@@ -687,6 +704,7 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
             case LDPC_HIP_LMS_DEC: hipLaunchKernelGGL(ldpc::lms_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_IMS_DEC: hipLaunchKernelGGL(ldpc::ims_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_ASP_DEC: hipLaunchKernelGGL(ldpc::asp_global_kernel, gg, bb, 0, stream, ga); break;
+            case LDPC_HIP_IASP_DEC: hipLaunchKernelGGL(ldpc::iasp_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_SP_DEC: hipLaunchKernelGGL(ldpc::sp_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_BP_DEC: hipLaunchKernelGGL(ldpc::bp_global_kernel, gg, bb, 0, stream, ga); break;
             default: hipLaunchKernelGGL(ldpc::tasp_global_kernel, gg, bb, 0, stream, ga); break;
@@ -820,6 +838,7 @@ int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter,
     if (int rc = set_device(c)) return rc;
     const bool sp = c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_BP_DEC;  // soft[] is the working array upstream
     const bool tasp = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC;  // probability-domain decoders
+    const bool iasp = c->decoder_id == LDPC_HIP_IASP_DEC;   // the same, its input transform without the * 0.5
     if (c->decoder_id == LDPC_HIP_TASP_DEC) decision = 0;  // upstream ignores `decision` for this decoder: the result is always hard (decoders.cpp:2737-2738)
     const bool need_soft = decision != 0 || (sp && clobber_sp_input);
     if (int rc = ensure_workspace(c, B, need_soft)) return rc;
@@ -847,10 +866,11 @@ int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter,
         }
     }
     if (sp && clobber_sp_input) std::memcpy(llr, soft.data(), sizeof(double) * nllr);  // decoders.cpp:1950,2124
-    if (tasp && clobber_sp_input) {  // decoders.cpp:2611-2618: soft[] is left holding P(bit = 1) of the channel -- same exp() as the decoder's
+    if ((tasp || iasp) && clobber_sp_input) {  // decoders.cpp:2611-2618 / :3858-3863: soft[] is left holding P(bit = 1) of the channel -- same exp() as the decoder's
         long long blocks = ((long long)nllr + 255) / 256;
         if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL(channel_prior_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
+        if (iasp) hipLaunchKernelGGL(iasp_channel_prior_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
+        else hipLaunchKernelGGL(channel_prior_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(llr, c->w_llr, sizeof(double) * nllr, hipMemcpyDeviceToHost));
     }
@@ -1063,7 +1083,8 @@ int ldpc_hip_channel_llr_dev(ldpc_hip_ctx *c, double snr_db, int modulation_type
     a.tx = c->ncw > 0 ? c->d_tx : nullptr; a.ncw = c->ncw > 0 ? c->ncw : 1; a.ntx = c->chain_ntx;
     a.scatter = c->d_scatter;
     a.punct_start = c->N - c->M * punctured_blocks;
-    a.punct_val = (c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC) ? 0.0 : 0.5;  // :700 (sic), out_type :451-466
+    a.punct_val = (c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC ||
+                   c->decoder_id == LDPC_HIP_IASP_DEC) ? 0.0 : 0.5;  // :700 (sic), out_type :451-466
     const int m = modulation_type <= 1 ? 2 : 2 * modulation_type;
     const long long total = B * (long long)((c->N + m - 1) / m);
     long long blocks = (total + 255) / 256;

@@ -119,7 +119,8 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
     static std::mutex mu;
     static std::map<std::string, Kernel> &cache = *new std::map<std::string, Kernel>();   // never destroyed: a background compile may outlive main()
     const std::string code = code_struct(rows, nh, M);
-    const bool eight_waves = std::string(body) == "sp_body" || std::string(body) == "asp_body" || std::string(body) == "bp_body";  // 8 waves per frame, 2 frames per CU
+    const bool eight_waves = std::string(body) == "sp_body" || std::string(body) == "asp_body" || std::string(body) == "iasp_body" ||
+                             std::string(body) == "bp_body";  // 8 waves per frame, 2 frames per CU
     const bool tasp = std::string(body) == "tasp_body";   // two lanes per check; two waves per SIMD while the Z halves + addresses + ~85 temporaries fit 256 registers
     int tasp_regs = 85;
     for (const auto &r : rows) tasp_regs += 2 * (((int)r.size() + 1) / 2) + (((int)r.size() + 1) / 2 + 1) / 2;

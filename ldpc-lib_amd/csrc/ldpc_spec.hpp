@@ -1777,6 +1777,204 @@ __device__ __forceinline__ void asp_body(const SpecArgs &a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Integer advanced sum-product (upstream isum_prod_gf2_decod_qc_lm, decoders.cpp:3822-4121 -- the IASP_FIXED_POINT branch --,
+// decoder id 5): asp_body's dataflow in fixed point.  States are Q12 in u16 (SOFT_FPP 12, ONE_SOFT 4096, MAX_SOFT 4095, :79-91),
+// the channel word and the a-posteriori word Q16 in u16, the general branch's column products Q32 in u32.  The arithmetic below is
+// shared by iasp_body and the shape-unlimited iasp_global_kernel (ldpc_global.hpp): every store upstream makes into a u16 / i16
+// is a truncation here too, and every division is u32 (all operands are non-negative and below 2^32, most below 2^24, so
+// C's signed int division gives the same quotient).  exp() of the channel transform is exp_glibc, so the whole decoder is bit
+// for bit the reference's.
+// ---------------------------------------------------------------------------------------------------------------
+namespace iasp {
+constexpr u32 kOne = 4096, kMax = 4095;
+__device__ __forceinline__ u32 u16(u32 x) { return x & 0xffffu; }
+__device__ __forceinline__ int i16(int x) { return (int)(short)x; }
+__device__ __forceinline__ u32 max1(u32 x) { return x < 1u ? 1u : x; }
+// :3858-3869  y = maxd(mind(x, 20), -20); soft[] <- p = 1 / (1 + exp(y)); q = clamp((int)(p * 4096 + 0.5), 1, 4095).
+// p * 4096 is exact (a power of two), so a contracted multiply-add would round the same way as the two operations.
+__device__ __forceinline__ double prior(double x) {
+    const double m = x < 20.0 ? x : 20.0;
+    const double y = m < -20.0 ? -20.0 : m;
+    return 1.0 / (1.0 + exp_glibc(y));
+}
+__device__ __forceinline__ u32 q12(double p) {
+    const int x = (int)(p * 4096.0 + 0.5);
+    return x > (int)kMax ? kMax : (x < 1 ? 1u : (u32)x);
+}
+// imap_bin (:2235-2271): P = 4096 - 2 s as i16; products div_power2r(P * S, 12) on ints, stored as i16; an output is
+// div_power2r(4096 - Z, 1) stored as u16, then at least 1
+__device__ __forceinline__ int chk_p(u32 s) { return i16((int)kOne - 2 * (int)s); }
+__device__ __forceinline__ int chk_mul(int p, int s) { return (p * s + 2048) >> 12; }
+__device__ __forceinline__ u32 chk_out(int z) { return max1(u16((u32)(((int)kOne - z + 1) >> 1))); }
+// general branch, one edge of a column (:4002-4017): P1 *= d << 4, P0 *= (MAX_SOFT - d) << 4, each (u64 product) >> 16
+__device__ __forceinline__ void col_mul(u32 &P1, u32 &P0, u32 d) {
+    const u32 d1 = u16(d << 4), d0 = u16((kMax - d) << 4);
+    P1 = (u32)(((u64)P1 * d1) >> 16);
+    P0 = (u32)(((u64)P0 * d0) >> 16);
+}
+// :4029-4050 the a-posteriori word (Q16) from the column products
+__device__ __forceinline__ u32 col_soft(u32 P1, u32 P0) {
+    u32 x = P1 >> 1, y = (P0 >> 1) + x;
+    if (y > (kOne << 4)) y >>= 12; else x <<= 12;
+    const u32 s = x / max1(y);                 // < 2^28: C's int s holds it
+    return (s > kMax ? kMax : max1(s)) << 4;
+}
+// :4074-4086 local update of one edge's state from the a-posteriori word
+__device__ __forceinline__ u32 local_update(u32 so16, u32 d) {
+    const u32 so = so16 << 8, sos = max1(d);
+    const u32 p1 = so / sos;
+    const u32 t = sos < kOne ? kOne - sos : 1u;
+    const u32 p0 = (kOne * kOne - so) / t;
+    const u32 y1 = max1((p1 + p0 + 32u) >> 6);
+    const u32 dd = (p1 << 6) / y1;
+    return dd > kMax ? kMax : max1(dd);
+}
+// all-columns-of-weight-2 branch (:3937-3970), one variable: u16 arithmetic that wraps (a p0 that rounds to 0 makes the u16
+// quotient 65536 -> 0 -> 16).  ip1: channel word, d0 / d1: the states of the column's first / second edge (rows ascending).
+__device__ __forceinline__ void cw2(u32 ip1, u32 d0s, u32 d1s, u32 &so, u32 &n0, u32 &n1) {
+    const u32 ip0 = u16(65536u - ip1);
+    const u32 d1 = u16(d1s << 4), d0 = u16(d0s << 4);
+    const u32 t1 = u16(65536u - d1), t0 = u16(65536u - d0);
+    const u32 q10 = u16((ip1 * d1 + 32768u) >> 16), q11 = u16((ip1 * d0 + 32768u) >> 16);
+    u32 q00 = u16((ip0 * t1 + 32768u) >> 16), q01 = u16((ip0 * t0 + 32768u) >> 16);
+    const u32 p1 = u16((q10 * d0 + 32768u) >> 16);
+    const u32 p0 = max1(u16(p1 + u16((q00 * t0 + 32768u) >> 16)));
+    const u32 s = u16((p1 << 16) / p0);
+    so = s < 16u ? 16u : s;
+    q00 = max1(u16(q00 + q10));
+    q01 = max1(u16(q01 + q11));
+    n0 = max1(u16((q10 << 12) / q00));
+    n1 = max1(u16((q11 << 12) / q01));
+}
+}  // namespace iasp
+
+// The resident body of the general branch (codes with a column of weight != 2 -- the host sends all-weight-2 codes to the
+// shape-unlimited tier).  asp_body's work split: 8 waves per frame, block rows dealt round-robin, block columns balanced at
+// compile time; the channel word and the a-posteriori word of a wave's own columns in VGPRs, per-edge state u16 [NE][M] in LDS
+// (upstream's state[slot][check]), hard bits u8 [N].
+//   1 (row units)     imap_bin over the row's edges at check n
+//   2 (column units)  column products -> a-posteriori word -> hard bit; then the local update of every edge's state
+//   3 (row units)     syndrome of the hard bits
+template <class C>
+__device__ __forceinline__ void iasp_body(const SpecArgs &a) {
+    constexpr SpView<C> V{};
+    constexpr int RH = C::RH, NH = C::NH, M = C::M, N = NH * M, CH = (M + 63) / 64, T = kSpWaves * 64;
+    constexpr int NE = V.ne, UMAX = V.units_max;
+    extern __shared__ double lds[];
+    unsigned short *const stb = reinterpret_cast<unsigned short *>(lds);                      // state[e][n] at e*M + n
+    unsigned char *const hb = reinterpret_cast<unsigned char *>(lds) + (((size_t)NE * M * 2 + 15) & ~(size_t)15);  // [N] soft_out >> 15
+    int *const flag = reinterpret_cast<int *>(hb + ((N + 15) & ~15));
+    int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    auto lane_ok = [&](auto CHI) { constexpr int c = decltype(CHI)::value; return (c * 64 + 64 <= M) || (c * 64 + lane < M); };
+    const long long fr = blockIdx.x;
+
+    FrameVote fvote;
+    fvote.init(flag);
+    auto syndrome_fail = [&]() -> bool {                                      // icheck_syndrome :3772-3803
+        bool f = false;
+        static_for<0, RH * CH>([&](auto U) {
+            constexpr int u = decltype(U)::value, j = u / CH, ch = u % CH;
+            if (wave == u % kSpWaves && lane_ok(IC<ch>{})) {
+                const int n = ch * 64 + lane;
+                unsigned sy = 0;
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    int t = n + C::SH[j][s]; if (t >= M) t -= M;
+                    sy ^= hb[C::COL[j][s] * M + t];
+                });
+                f |= sy != 0;
+            }
+        });
+        return f;
+    };
+
+    u32 ych[UMAX], so[UMAX];   // channel word and a-posteriori word (Q16) of this wave's own columns
+    static_for<0, UMAX>([&](auto Q) { ych[decltype(Q)::value] = 0; so[decltype(Q)::value] = 0; });
+    static_for<0, NH * CH>([&](auto U) {
+        constexpr int u = decltype(U)::value, k = u / CH, ch = u % CH, q = V.col_slot[u];
+        if (wave == V.col_wave[u] && lane_ok(IC<ch>{})) {
+            const int t = ch * 64 + lane;
+            const u32 qv = iasp::q12(iasp::prior(a.llr[fr * N + k * M + t]));   // :3858-3869
+            ych[q] = so[q] = qv << 4;                                         // :3872-3897: states take the Q12 value, the words Q16
+            hb[k * M + t] = (unsigned char)((qv << 4) >> 15);
+            static_for<0, V.cw[k]>([&](auto X) {
+                constexpr int x2 = decltype(X)::value;
+                int nn = t - V.cc[k][x2]; if (nn < 0) nn += M;
+                stb[V.ce[k][x2] * M + nn] = (unsigned short)qv;
+            });
+        }
+    });
+    __syncthreads();
+
+    bool fail = fvote(syndrome_fail());                                       // :3899-3906
+    int steps = 0;
+    while (fail && steps < a.maxiter) {
+        asm volatile("" : "+v"(lane));   // see asp_body: keeps the rotated LDS addresses out of the loop-invariant registers
+        // ---- phase 1: check nodes, imap_bin(&state[0][i*m+k], rw[i], r)
+        static_for<0, RH * CH>([&](auto U) {
+            constexpr int u = decltype(U)::value, j = u / CH, ch = u % CH, RW = C::RW[j];
+            static_assert(RW >= 2, "iasp_body: imap_bin needs at least two edges per check");
+            if (wave == u % kSpWaves && lane_ok(IC<ch>{})) {
+                const int n = ch * 64 + lane;
+                int P[RW], SF[RW], SB[RW];
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    P[s] = iasp::chk_p(stb[(V.row_off[j] + s) * M + n]);
+                });
+                SF[0] = P[0];
+                static_for<1, RW - 1>([&](auto I) { constexpr int i = decltype(I)::value; SF[i] = iasp::i16(iasp::chk_mul(P[i], SF[i - 1])); });
+                SB[RW - 1] = P[RW - 1];
+                static_for<0, RW - 2>([&](auto I) { constexpr int i = RW - 2 - decltype(I)::value; SB[i] = iasp::i16(iasp::chk_mul(P[i], SB[i + 1])); });
+                stb[(V.row_off[j] + 0) * M + n] = (unsigned short)iasp::chk_out(SB[1]);
+                static_for<1, RW - 1>([&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    stb[(V.row_off[j] + i) * M + n] = (unsigned short)iasp::chk_out(iasp::chk_mul(SF[i - 1], SB[i + 1]));
+                });
+                stb[(V.row_off[j] + RW - 1) * M + n] = (unsigned short)iasp::chk_out(SF[RW - 2]);
+            }
+        });
+        __syncthreads();
+        // ---- phase 2: symbol nodes (:3978-4052) + local data update (:4054-4100)
+        static_for<0, NH * CH>([&](auto U) {
+            constexpr int u = decltype(U)::value, k = u / CH, ch = u % CH, q = V.col_slot[u], CW = V.cw[k];
+            if (wave == V.col_wave[u] && lane_ok(IC<ch>{})) {
+                const int t = ch * 64 + lane;
+                u32 d[CW];
+                u32 P1 = ych[q] << 16, P0 = (65536u - ych[q]) << 16;
+                static_for<0, CW>([&](auto X) {
+                    constexpr int x = decltype(X)::value;
+                    int nn = t - V.cc[k][x]; if (nn < 0) nn += M;
+                    d[x] = stb[V.ce[k][x] * M + nn];
+                    iasp::col_mul(P1, P0, d[x]);                              // rows ascending
+                });
+                const u32 sov = iasp::col_soft(P1, P0);
+                so[q] = sov;
+                hb[k * M + t] = (unsigned char)(sov >> 15);
+                static_for<0, CW>([&](auto X) {
+                    constexpr int x = decltype(X)::value;
+                    int nn = t - V.cc[k][x]; if (nn < 0) nn += M;
+                    stb[V.ce[k][x] * M + nn] = (unsigned short)iasp::local_update(sov, d[x]);
+                });
+            }
+        });
+        __syncthreads();
+        fail = fvote(syndrome_fail());                                        // :4104-4113
+        steps = steps + 1;
+    }
+    const int res = fail ? -steps : steps;                                    // 0: input codeword; steps+1 upstream == steps here
+
+    if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
+    if (a.hard) pack_hard<N, T>(a.hard + fr * ((N + 31) / 32), threadIdx.x, [&](int v) { return hb[v] != 0; });
+    if (a.soft_out) {                                                         // imake_output :3805-3820, decision 1
+        static_for<0, NH * CH>([&](auto U) {
+            constexpr int u = decltype(U)::value, k = u / CH, ch = u % CH, q = V.col_slot[u];
+            if (wave == V.col_wave[u] && lane_ok(IC<ch>{})) a.soft_out[fr * N + k * M + ch * 64 + lane] = (double)so[q] / 65536.0;
+        });
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Gallager belief propagation in the log domain (upstream bp_decod_qc_lm, decoders.cpp:1708-1920, decoder id 0).
 // Work split of sp_body (8 waves per frame; block rows dealt round-robin, block columns dealt at compile time).
 // Per-edge message ZZ[e][t] (fp64) and sign BB[e][t] are indexed by VARIABLE position like upstream's ZZ[j][k*M+t].
