@@ -290,6 +290,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
     int res = -a.maxiter;                                              // :5424 when the loop runs dry
     bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);  // :5111-5115
     if (!done && !frame_fail) { done = true; res = 1; }                // :5119 at iter 0 -> returns 0+1
+    const bool at_entry = done && inb;                                 // no layer ran: upstream's soft[] is y itself, -0.0 included
     for (int iter = 0; iter < a.maxiter; ++iter) {
         if (MW) { if (done) break; }
         else if (__all(done)) break;
@@ -342,6 +343,8 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
         if (!done && !frame_fail) { done = true; res = iter + 1; }          // :5287, returns iter+1
     }
     write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
+    if (live && at_entry && a.soft_out)
+        for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = a.llr[fr * N + k * M + n];
 }
 
 // ---------------------------------------------------------------------------------------------------------

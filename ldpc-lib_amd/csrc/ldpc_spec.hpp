@@ -1042,6 +1042,7 @@ __device__ __forceinline__ void lms_body(const SpecArgs &a) {
     int res = -a.maxiter;                                  // :5424 when the loop runs dry
     bool fail = vote(syndrome_fail());                     // :5111-5115
     if (!fail) res = 1;                                    // :5119 at iter 0
+    const bool at_entry = !fail;                           // no layer ran: upstream's soft[] is y itself, -0.0 included
     for (int iter = 0; fail && iter < a.maxiter; ++iter) {
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
@@ -1107,7 +1108,7 @@ __device__ __forceinline__ void lms_body(const SpecArgs &a) {
     if (a.soft_out && valid) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            a.soft_out[fr * N + k * M + n] = *reinterpret_cast<const double *>(ldsb + n8 + k * (8 * M));
+            a.soft_out[fr * N + k * M + n] = at_entry ? a.llr[fr * N + k * M + n] : *reinterpret_cast<const double *>(ldsb + n8 + k * (8 * M));
         });
     }
     });
@@ -1167,9 +1168,10 @@ __device__ __forceinline__ void lms_small_body(const SpecArgs &a) {
 
     int res = -a.maxiter;                                  // :5424 when the loop runs dry
     bool done = !live;
+    bool at_entry = false;                                 // no layer ran: upstream's soft[] is y itself, -0.0 included
     {
         const u64 failing = __ballot(!done && (syndrome_word() >> 31) != 0);   // :5111-5115
-        if (!done && (failing & frame_lanes) == 0ull) { done = true; res = 1; } // :5119 at iter 0
+        if (!done && (failing & frame_lanes) == 0ull) { done = true; res = 1; at_entry = true; } // :5119 at iter 0
     }
     for (int iter = 0; iter < a.maxiter; ++iter) {
         if (__ballot(!done) == 0ull) break;
@@ -1238,7 +1240,7 @@ __device__ __forceinline__ void lms_small_body(const SpecArgs &a) {
     if (a.soft_out) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            a.soft_out[fr * N + k * M + n] = *reinterpret_cast<const double *>(ldsb + n8 + k * (8 * M));
+            a.soft_out[fr * N + k * M + n] = at_entry ? a.llr[fr * N + k * M + n] : *reinterpret_cast<const double *>(ldsb + n8 + k * (8 * M));
         });
     }
 }

@@ -346,3 +346,122 @@ def multi_block_code(rng, M, blocks=(4, 4), ninfo=6):
         while (H[j, b:] >= 0).sum() < 1:
             H[j, b + rng.randint(0, ninfo)] = rng.randint(0, M)
     return H
+
+
+# ---- bitwise comparison and adversarial channel values ---------------------------------------------------------------------------
+def assert_bits_equal(got, want, what="", nan_ok=False):
+    """float64 arrays identical bit for bit.  np.array_equal treats +0.0 == -0.0 (and NaN != NaN), so it checks a "bit-identical"
+    claim only up to the sign of zero; this compares the uint64 images and names the first differing index with both values in hex.
+    nan_ok: NaN positions must match exactly and every other value bit for bit; the NaNs' payloads and signs are not compared (the
+    default NaN of x86 arithmetic has the sign bit set, the GPU's does not)."""
+    got = np.ascontiguousarray(np.asarray(got), dtype=np.float64)
+    want = np.ascontiguousarray(np.asarray(want), dtype=np.float64)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
+    g, w = got.view(np.uint64), want.view(np.uint64)
+    bad = g != w
+    if nan_ok:
+        gn, wn = np.isnan(got), np.isnan(want)
+        bad = (bad & ~(gn & wn)) | (gn != wn)
+    if bad.any():
+        flat = np.flatnonzero(bad)
+        i = np.unravel_index(flat[0], got.shape)
+        raise AssertionError(f"{what}: {flat.size} of {got.size} values differ; first at {tuple(int(x) for x in i)}: got {got[i]!r} "
+                             f"(0x{int(g[i]):016x}), want {want[i]!r} (0x{int(w[i]):016x})")
+
+
+# default integer min-sum parameters (decoders.cpp MS_THR / MS_QBITS): the quantiser-boundary frames are tuned for them
+IMS_THR, IMS_QBITS = 1.4, 6
+
+
+def _ims_coef(y):
+    """sqrt(N / en) with en summed in index order, as upstream's quantiser (and every IMS tier) computes it."""
+    en = 0.0
+    for v in (y * y).tolist():
+        en += v
+    return np.sqrt(len(y) / en) if en else np.inf
+
+
+def _quantiser_boundary_frame(rng, N, thr=IMS_THR, qbits=IMS_QBITS):
+    """+-1 everywhere but every 8th value, which is picked so that the energy-normalised quantiser's val * max_quant / thr + 0.5 sits
+    within an ulp of an integer -- where floor() of it differs from floor(val * (max_quant / thr) + 0.5): the order of the
+    multiply and the divide decides the quantised value.  The scale coef depends on the frame's energy, so the picks are iterated
+    until coef no longer moves."""
+    mq = (1 << (qbits - 1)) - 1
+    y = np.where(rng.rand(N) < 0.04, -1.0, 1.0)
+    slots = np.arange(3, N, 8)
+    steps = np.arange(-256, 257, dtype=np.int64)
+    level = rng.randint(1, mq, size=slots.size)
+    target = (level - 0.5) * thr / mq                       # val * coef on the rounding boundary of quantiser level `level`
+    y[slots] = np.copysign(target / np.sqrt((N - (target ** 2).sum()) / (N - slots.size)), y[slots])   # solves en = N / coef^2
+    for _ in range(20):
+        coef = _ims_coef(y)
+        t = (level - 0.5) * thr / (mq * coef)
+        v = (t.view(np.int64)[:, None] + steps[None, :]).view(np.float64)     # t and its 256 neighbours on either side
+        a = np.minimum(v * coef, thr)
+        hit = np.floor(a * mq / thr + 0.5) != np.floor(a * (mq / thr) + 0.5)
+        j = np.where(hit.any(axis=1), hit.argmax(axis=1), 256)                 # a slot without a sensitive neighbour keeps t
+        y[slots] = np.copysign(v[np.arange(slots.size), j], y[slots])
+        if _ims_coef(y) == coef:
+            break
+    return y
+
+
+def adversarial_llr(H, M, seed):
+    """Deterministic batch of finite channel LLRs aimed at the arguments the kernels make at the edges of their input range (the
+    sign bit and the `+ 0.0` canonicalisation, subnormals, the MAX_VAL / INPUT_LIMIT / +-40 clamps, the integer quantiser's
+    en = 0 and en = inf cases, exact min1 == min2 ties, quantiser rounding boundaries, codewords and all-negative frames).  Each
+    family appears as whole frames and mixed into AWGN frames.  Returns (llr [B, N] float64, labels [B])."""
+    rng = np.random.RandomState(seed)
+    rh, nh = np.asarray(H).shape
+    N = nh * M
+    base = awgn_llr(np.asarray(H, dtype=np.int32), M, 2.0, 1000 + seed, 16, burn_codeword=False)
+    nxt = iter(range(len(base)))
+
+    def awgn():
+        return base[next(nxt)].copy()
+
+    def signs(p=0.05):   # the zero codeword's sign pattern (all positive) with a fraction p of flips
+        return np.where(rng.rand(N) < p, -1.0, 1.0)
+
+    def pick(values, p=0.05):
+        return rng.choice(np.asarray(values, dtype=np.float64), size=N) * signs(p)
+
+    lim = [20.0, 40.0, np.nextafter(20.0, 0), np.nextafter(20.0, 99), np.nextafter(40.0, 0), np.nextafter(40.0, 99), 19.999999, 39.999999]
+    families = [
+        ("+0.0", np.zeros(N)),
+        ("-0.0", -np.zeros(N)),
+        ("random +-0.0", np.where(rng.rand(N) < 0.5, -0.0, 0.0)),
+        ("+-1e-310 subnormals", 1e-310 * signs()),
+        ("+-1e-170, squares underflow", 1e-170 * signs()),
+        ("subnormals and exact zeros", pick([1e-310, 5e-324, 2.2e-308, 0.0, -0.0, 0.0])),
+        ("+-1e155", 1e155 * signs(0.08)),
+        ("+-1e200", 1e200 * signs(0.08)),
+        ("+-20 / +-40 and neighbours", pick(lim, 0.08)),
+        ("alphabet {1, 2, 3}", pick([1.0, 2.0, 3.0], 0.04)),
+        ("alphabet {1}: min1 == min2 everywhere", pick([1.0], 0.03)),
+        ("+-1", pick([1.0], 0.08)),
+        ("integer quantiser boundaries", _quantiser_boundary_frame(rng, N)),
+        ("all -1", -np.ones(N)),
+    ]
+    llr, labels = [], []
+    for name, y in families:
+        llr.append(y)
+        labels.append(name)
+    a = awgn()
+    llr.append(a * 1e6); labels.append("awgn x 1e6")
+    a = awgn()
+    llr.append(np.abs(a) + 0.1); labels.append("a codeword")
+    a = awgn()
+    llr.append(-(np.abs(a) + 0.1)); labels.append("all negative")
+    for name, stride, z in (("every 5th -0.0", 5, -0.0), ("every 7th +0.0", 7, 0.0), ("every 5th +0.0", 5, 0.0), ("every 7th -0.0", 7, -0.0)):
+        a = awgn()
+        a[rng.randint(stride)::stride] = z
+        llr.append(a); labels.append("awgn, " + name)
+    for name, y in families[3:10]:   # the value families mixed into AWGN frames
+        a = awgn()
+        m = rng.rand(N) < 0.2
+        a[m] = np.abs(y[m]) * np.sign(a[m])
+        llr.append(a); labels.append("awgn with " + name)
+    llr = np.ascontiguousarray(np.array(llr, dtype=np.float64))
+    assert np.isfinite(llr).all()
+    return llr, labels

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from ldpc_testlib import (ASP_DEC, BP_DEC, GOLDEN_DIR, IMS_DEC, LMS_DEC, MS_DEC, SP_DEC, TASP_DEC, Oracle, awgn_llr, bpsk_sigma, load_base_matrix, pack_bits,
+from ldpc_testlib import (ASP_DEC, BP_DEC, GOLDEN_DIR, IMS_DEC, LMS_DEC, MS_DEC, SP_DEC, TASP_DEC, Oracle, assert_bits_equal, awgn_llr, bpsk_sigma, load_base_matrix, pack_bits,
                           philox_gauss_pairs, relift, syndrome_np, unpack_bits)
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +25,14 @@ _HOST_HAS_FMA = " fma" in open("/proc/cpuinfo").read()
 SP_RTOL = 0.0 if _HOST_HAS_FMA else 4e-15
 TASP_RTOL = 0.0 if _HOST_HAS_FMA else 4e-15
 BP_RTOL, BP_ATOL = (0.0, 0.0) if _HOST_HAS_FMA else (1e-12, 1e-14)
+
+
+def _close(got, want, rtol, atol=0.0, what=""):
+    """Tolerance 0 (an FMA host) means bit for bit, the sign of zero included; otherwise the stated non-FMA tolerance."""
+    if rtol == 0 and atol == 0:
+        assert_bits_equal(got, want, what)
+    else:
+        np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=what)
 
 
 @pytest.fixture(scope="module")
@@ -52,20 +60,20 @@ def test_golden_vectors_host_api(L, name):
         d1, it1, _ = dec.decode_host(g["llr"][:ns], maxiter, decision=1)
         assert np.array_equal(it1, g["iters"][:ns])
         if dec_id == SP_DEC:
-            np.testing.assert_allclose(d1, g["soft"], rtol=SP_RTOL, atol=0)
+            _close(d1, g["soft"], SP_RTOL)
         elif dec_id == BP_DEC:
-            np.testing.assert_allclose(d1, g["soft"], rtol=BP_RTOL, atol=BP_ATOL)   # a-posteriori LLRs
+            _close(d1, g["soft"], BP_RTOL, BP_ATOL)   # a-posteriori LLRs
         elif dec_id == ASP_DEC:
-            np.testing.assert_allclose(d1, g["soft"], rtol=TASP_RTOL, atol=0)   # a-posteriori P(bit=1)
+            _close(d1, g["soft"], TASP_RTOL)   # a-posteriori P(bit=1)
             x = np.clip(g["llr"] * 0.5, -20.0, 20.0)  # the input is left holding the channel P(bit=1) (decoders.cpp:2351-2358)
             np.testing.assert_allclose(after, np.exp(-x) / (np.exp(x) + np.exp(-x)), rtol=1e-14)
         elif dec_id == TASP_DEC:
-            assert np.array_equal(d1, g["soft"])    # `decision` is dead upstream: still the hard decisions
+            assert_bits_equal(d1, g["soft"])    # `decision` is dead upstream: still the hard decisions
             x = np.clip(g["llr"] * 0.5, -20.0, 20.0)  # and the input is left holding P(bit=1) (decoders.cpp:2611-2618)
             np.testing.assert_allclose(after, np.exp(-x) / (np.exp(x) + np.exp(-x)), rtol=1e-14)
         else:
-            assert np.array_equal(d1, g["soft"])  # bit-exact a-posteriori LLRs
-            assert np.array_equal(after, g["llr"])  # MS/LMS leave their input intact
+            assert_bits_equal(d1, g["soft"])  # bit-exact a-posteriori LLRs
+            assert_bits_equal(after, g["llr"])  # MS/LMS leave their input intact
 
 
 @pytest.mark.parametrize("dec_id,M,snrs,frames,maxiter", [
@@ -110,14 +118,14 @@ def test_random_batches_against_oracle(L, torch, dec_id, M, snrs, frames, maxite
         torch.cuda.synchronize()
         assert np.array_equal(iters.cpu().numpy(), it_ref)
         assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref))
-        assert np.array_equal(x.cpu().numpy(), llr)  # the device entry point never modifies its input
+        assert_bits_equal(x.cpu().numpy(), llr)  # the device entry point never modifies its input
         s_ref, _, _ = (Oracle(H, M) if dec_id == BP_DEC else o).decode(dec_id, llr, maxiter, 1)  # BP: state carries between calls
         if dec_id == BP_DEC:
-            np.testing.assert_allclose(soft.cpu().numpy(), s_ref, rtol=BP_RTOL, atol=BP_ATOL)
+            _close(soft.cpu().numpy(), s_ref, BP_RTOL, BP_ATOL)
         elif dec_id in (SP_DEC, ASP_DEC, TASP_DEC):  # exp() on the device vs glibc: a-posteriori values to the stated tolerance
-            np.testing.assert_allclose(soft.cpu().numpy(), s_ref, rtol=SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
+            _close(soft.cpu().numpy(), s_ref, SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
         else:
-            assert np.array_equal(soft.cpu().numpy(), s_ref)
+            assert_bits_equal(soft.cpu().numpy(), s_ref)
 
 
 def test_edge_case_inputs(L, torch):
@@ -155,7 +163,7 @@ def test_edge_case_inputs(L, torch):
         d, it, after = dec.decode_host(llr_sp, 50)
         assert it_ref[0] == 0 and np.array_equal(it, it_ref)
         assert np.array_equal(d, d_ref)
-        np.testing.assert_allclose(after, after_ref, rtol=SP_RTOL)  # upstream clobbers soft[] with the ratios
+        _close(after, after_ref, SP_RTOL)  # upstream clobbers soft[] with the ratios
 
 
 def test_maxiter_one_and_unsupported_shapes(L):
@@ -379,7 +387,7 @@ def test_every_min_sum_kernel_tier_is_bit_exact(L, torch, monkeypatch, variant, 
         torch.cuda.synchronize()
         assert np.array_equal(iters.cpu().numpy(), it_ref)
         assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref))
-        assert np.array_equal(soft.cpu().numpy(), s_ref)
+        assert_bits_equal(soft.cpu().numpy(), s_ref)
 
 
 @pytest.mark.parametrize("chunk,expect", [("1", "ms_chunk_appendix_c_m126_kernel"), ("0", "ms_spec_appendix_c_m126_kernel")])
@@ -394,7 +402,7 @@ def test_both_min_sum_kernels_for_the_shipped_lifting_are_bit_exact(L, monkeypat
         assert np.array_equal(it0, g["iters"]) and np.array_equal(pack_bits(d0), g["hard"])
         ns = g["soft"].shape[0]
         d1, _, _ = dec.decode_host(g["llr"][:ns], int(g["maxiter"]), decision=1)
-        assert np.array_equal(d1, g["soft"])
+        assert_bits_equal(d1, g["soft"])
     H = relift(load_base_matrix(), 126)
     llr = np.concatenate([awgn_llr(H, 126, s, 70 + i, 12) for i, s in enumerate((0.8, 1.6, 2.4))])
     d_ref, it_ref, _ = Oracle(H, 126).decode(MS_DEC, llr, 50, 0)
@@ -419,7 +427,7 @@ def test_small_liftings_share_a_wavefront(L, torch):
                 torch.cuda.synchronize()
                 assert np.array_equal(iters.cpu().numpy(), it_ref), (dec_id, M)
                 assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref)), (dec_id, M)
-                assert np.array_equal(soft.cpu().numpy(), s_ref), (dec_id, M)
+                assert_bits_equal(soft.cpu().numpy(), s_ref), (dec_id, M)
             assert len(set(it_ref.tolist())) > 3      # the frames of a wave really do stop at different iterations
 
 
@@ -572,13 +580,13 @@ def test_decoders_h_call_surface(L, tmp_path, name, layout):
         if decision == 0 or dec_id == TASP_DEC:
             assert np.array_equal(pack_bits(dec), g["hard"][:nfr])
         elif dec_id == BP_DEC:
-            np.testing.assert_allclose(dec, g["soft"], rtol=BP_RTOL, atol=BP_ATOL)
+            _close(dec, g["soft"], BP_RTOL, BP_ATOL)
         elif dec_id in (SP_DEC, ASP_DEC):
-            np.testing.assert_allclose(dec, g["soft"], rtol=SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
+            _close(dec, g["soft"], SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
         else:
-            assert np.array_equal(dec, g["soft"])
+            assert_bits_equal(dec, g["soft"])
         if dec_id not in (BP_DEC, SP_DEC, ASP_DEC, TASP_DEC):
-            assert np.array_equal(after, llr)          # MS/LMS leave y intact (SURVEY 8b ownership)
+            assert_bits_equal(after, llr)          # MS/LMS leave y intact (SURVEY 8b ownership)
         else:
             assert not np.array_equal(after, llr)      # SP clobbers its input like upstream (decoders.cpp:1950)
 
@@ -608,7 +616,7 @@ def test_integer_min_sum_parameters_pick_the_right_kernel(L, torch, thr, qbits, 
         hard, iters, soft = dec.decode(torch.from_numpy(llr).cuda(), 50, alpha=alpha, want_soft=True)
         torch.cuda.synchronize()
         assert np.array_equal(iters.cpu().numpy(), want_it)
-        assert np.array_equal(soft.cpu().numpy(), want_soft)
+        assert_bits_equal(soft.cpu().numpy(), want_soft)
         assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits((want_soft < 0).astype(np.float64)))
         assert expect in dec.last_launch(), dec.last_launch()
 
@@ -648,7 +656,7 @@ def test_layered_min_sum_specialised_instances(L, torch, M, frames):
         torch.cuda.synchronize()
         assert np.array_equal(iters.cpu().numpy(), it_ref)
         assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref))
-        assert np.array_equal(soft.cpu().numpy(), s_ref)
+        assert_bits_equal(soft.cpu().numpy(), s_ref)
     for Maot in (64, 512):
         with L.LdpcHip(LMS_DEC, relift(load_base_matrix(), Maot), Maot) as dec:
             assert "ahead of time" in dec.kernel_name
@@ -670,7 +678,7 @@ def test_sum_product_specialised_instances(L, torch):
         torch.cuda.synchronize()
         assert np.array_equal(iters.cpu().numpy(), it_ref)
         assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref))
-        np.testing.assert_allclose(soft.cpu().numpy(), s_ref, rtol=SP_RTOL)
+        _close(soft.cpu().numpy(), s_ref, SP_RTOL)
 
 
 def test_c_example_runs(L, tmp_path):
@@ -781,11 +789,11 @@ def test_every_decoder_on_random_protographs(L, torch, rh, nh, M, weights, seed)
             assert np.array_equal(hard.cpu().numpy().view(np.uint32), pack_bits(d_ref)), (dec_id, dec.kernel_name)
             s_ref, _, _ = Oracle(H, M).decode(dec_id, llr, 25, 1)
             if dec_id in (MS_DEC, LMS_DEC, IMS_DEC):
-                assert np.array_equal(soft.cpu().numpy(), s_ref), (dec_id, dec.kernel_name)
+                assert_bits_equal(soft.cpu().numpy(), s_ref), (dec_id, dec.kernel_name)
             elif dec_id == BP_DEC:
-                np.testing.assert_allclose(soft.cpu().numpy(), s_ref, rtol=BP_RTOL, atol=BP_ATOL)
+                _close(soft.cpu().numpy(), s_ref, BP_RTOL, BP_ATOL)
             else:
-                np.testing.assert_allclose(soft.cpu().numpy(), s_ref, rtol=SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
+                _close(soft.cpu().numpy(), s_ref, SP_RTOL if dec_id == SP_DEC else TASP_RTOL)
 
 
 @pytest.mark.parametrize("M", [64, 126])
