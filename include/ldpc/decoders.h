@@ -55,10 +55,10 @@ int bp_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxiter, 
 int sum_prod_gf2_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision);
 int imin_sum_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision, double alpha, double thr, int qbits, int dbits);
 int tdmp_sum_prod_gf2_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision);
-/* present for link compatibility with upstream's dispatch (bp_simulation.cpp:716-729); not built: they die() */
 int isum_prod_gf2_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision);
+int lche_decod(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision);   /* soft[] is not modified */
+/* present for link compatibility with upstream's dispatch (bp_simulation.cpp:716-729); not built: they die() */
 int sum_prod_gfq_decod_lm(DEC_STATE *st, double *soft[], short *qhard, double *decword[], int maxiter, double p_thr);
-int lche_decod(DEC_STATE *st, double soft[], double decword[], int maxiter, int decision);
 int encode_NBQCLDPC(DEC_STATE *st, int *msg);
 void left2right(short **matr, int nrow, int ncol);
 

@@ -38,6 +38,7 @@ extern "C" {
 #define LDPC_HIP_IASP_DEC 5 /* isum_prod_gf2_decod_qc_lm decoders.cpp:3822 (integer advanced sum-product, IASP_FIXED_POINT build) */
 #define LDPC_HIP_TASP_DEC 7 /* tdmp_sum_prod_gf2_decod_qc_lm decoders.cpp:2584 (decoder_type of the shipped scenario files) */
 #define LDPC_HIP_LMS_DEC 8 /* lmin_sum_decod_qc_lm   decoders.cpp:5064 */
+#define LDPC_HIP_LCHE_DEC 9 /* lche_decod            decoders.cpp:2899 (low-complexity high-efficiency decoder, layered, LLR domain) */
 
 #define LDPC_HIP_EINVAL (-1)    /* bad argument */
 #define LDPC_HIP_EUNSUPPORTED (-2) /* decoder / code shape not built */
@@ -54,7 +55,9 @@ int ldpc_hip_device_count(void);
  * bp_simulation.cpp:353-382).  hd is row-major rh x nh.  device = HIP device ordinal.
  * *out receives the context; NULL on failure (upstream: decod_open returns NULL).
  * ASP_DEC, IASP_DEC and TASP_DEC refuse codes with a block row of weight < 2 (LDPC_HIP_EUNSUPPORTED): upstream's check-node
- * routines read an uninitialised forward / backward product for such a row (decoders.cpp:2191-2228, :2235-2271). */
+ * routines read an uninitialised forward / backward product for such a row (decoders.cpp:2191-2228, :2235-2271).
+ * LCHE_DEC refuses codes with a block row of weight > 1024: upstream's map_bin_llr keeps a check's edges in static arrays of 1024
+ * (decoders.cpp:2818-2822). */
 int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int device, ldpc_hip_ctx **out);
 /* Replaces decod_close() (decoders.h:295, decoders.cpp:1210). */
 void ldpc_hip_close(ldpc_hip_ctx *ctx);
@@ -91,6 +94,9 @@ const char *ldpc_hip_last_launch(const ldpc_hip_ctx *ctx);
  *   IASP_DEC: isum_prod_gf2_decod_qc_lm(st, soft, decword, maxiter, decision)     (d_soft = soft_out / 65536, the u16 Q16
  *            a-posteriori word as upstream's decision == 1 output; hard bit = soft_out >> 15.  Integer arithmetic throughout:
  *            bit for bit with no libm argument except the channel transform's exp, which is glibc's)
+ *   LCHE_DEC: lche_decod(st, soft, decword, maxiter, decision)                     (d_soft = the final a-posteriori LLRs, upstream's
+ *            lche_soft_out; for a return of 0 it is the input bit for bit, -0.0 included.  The input is never modified, `decision`
+ *            is dead: d_hard is always filled.  Only fp64 adds, compares, exact scalings and table lookups: bit for bit)
  * All pointers are DEVICE pointers on ctx's device; the work is enqueued on `stream` (a hipStream_t, NULL =
  * default stream) and is asynchronous.  maxiter must be >= 1 (upstream's behaviour for maxiter <= 0 is an artefact of
  * stale state and is not reproduced: LDPC_HIP_EINVAL).  LLRs must be finite.

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 
 # decoders.h:16-28 enum DEC_ID
-DEC_BP, DEC_SP, DEC_ASP, DEC_MS, DEC_IMS, DEC_IASP, DEC_TASP, DEC_LMS = 0, 1, 2, 3, 4, 5, 7, 8
+DEC_BP, DEC_SP, DEC_ASP, DEC_MS, DEC_IMS, DEC_IASP, DEC_TASP, DEC_LMS, DEC_LCHE = 0, 1, 2, 3, 4, 5, 7, 8, 9
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG_DIR)
@@ -38,7 +38,7 @@ def build_library(force=False, verbose=False, jobs=None):
     headers = [os.path.join(src_dir, f) for f in os.listdir(src_dir) if f.endswith(".hpp")]
     headers += [os.path.join(_ROOT, "include", "ldpc_hip.h"), os.path.join(_ROOT, "include", "ldpc", "interleaver.h"),
                 os.path.join(_ROOT, "include", "ldpc", "encoder.h")]
-    aot_headers = [os.path.join(src_dir, f) for f in ("ldpc_aot.hpp", "ldpc_spec.hpp", "code_appendix_c_m64.hpp")]
+    aot_headers = [os.path.join(src_dir, f) for f in ("ldpc_aot.hpp", "ldpc_spec.hpp", "lche_table.hpp", "code_appendix_c_m64.hpp")]
     obj_dir = os.path.join(_PKG_DIR, "build")
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

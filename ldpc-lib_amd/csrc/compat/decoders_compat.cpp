@@ -44,7 +44,7 @@ Impl *impl_of(const void *st) {
 }
 
 [[noreturn]] void not_built(const char *what) {
-    fprintf(stderr, "%s is not built in ldpc-lib_amd (built decoders: BP_DEC=0, SP_DEC=1, ASP_DEC=2, MS_DEC=3, IMS_DEC=4, IASP_DEC=5, TASP_DEC=7, LMS_DEC=8)\n", what);
+    fprintf(stderr, "%s is not built in ldpc-lib_amd (built decoders: BP_DEC=0, SP_DEC=1, ASP_DEC=2, MS_DEC=3, IMS_DEC=4, IASP_DEC=5, TASP_DEC=7, LMS_DEC=8, LCHE_DEC=9)\n", what);
     exit(1);  // upstream's die() convention (commons_portable.cpp:181-189)
 }
 
@@ -72,8 +72,8 @@ int decode_common(DEC_STATE *st, int expect_id, double *soft, double *decword, i
 
 DEC_STATE *decod_open(int codec_id, int q_bits, int mh, int nh, int M) {
     if (codec_id != SP_DEC && codec_id != MS_DEC && codec_id != LMS_DEC && codec_id != IMS_DEC && codec_id != TASP_DEC && codec_id != ASP_DEC && codec_id != BP_DEC &&
-        codec_id != IASP_DEC) {
-        fprintf(stderr, "decod_open: decoder id %d is not built in ldpc-lib_amd (built: BP_DEC=0, SP_DEC=1, ASP_DEC=2, MS_DEC=3, IMS_DEC=4, IASP_DEC=5, TASP_DEC=7, LMS_DEC=8)\n", codec_id);
+        codec_id != IASP_DEC && codec_id != LCHE_DEC) {
+        fprintf(stderr, "decod_open: decoder id %d is not built in ldpc-lib_amd (built: BP_DEC=0, SP_DEC=1, ASP_DEC=2, MS_DEC=3, IMS_DEC=4, IASP_DEC=5, TASP_DEC=7, LMS_DEC=8, LCHE_DEC=9)\n", codec_id);
         return NULL;  // decoders.cpp:786: unknown id -> NULL
     }
     if (mh <= 0 || nh <= 0 || M <= 0) return NULL;
@@ -169,6 +169,8 @@ int sum_prod_gfq_decod_lm(DEC_STATE *, double *[], short *, double *[], int, dou
 int tdmp_sum_prod_gf2_decod_qc_lm(DEC_STATE *st, double soft[], double decword[], int maxsteps, int decision) {
     return decode_common(st, TASP_DEC, soft, decword, nullptr, 1, maxsteps, decision, 0.0);  // soft[] is clobbered, result always hard
 }
-int lche_decod(DEC_STATE *, double[], double[], int, int) { not_built("lche_decod (LCHE_DEC)"); }
+int lche_decod(DEC_STATE *st, double soft[], double decword[], int maxsteps, int decision) {
+    return decode_common(st, LCHE_DEC, soft, decword, nullptr, 1, maxsteps, decision, 0.0);  // soft[] is not modified, result always hard
+}
 int encode_NBQCLDPC(DEC_STATE *, int *) { not_built("encode_NBQCLDPC (GF(q) encoder)"); }
 void left2right(short **, int, int) { not_built("left2right (GF(q) only)"); }

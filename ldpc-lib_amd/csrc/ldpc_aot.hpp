@@ -30,4 +30,5 @@ LDPC_AOT_DECLARE(bp_spec_appendix_c_m64_kernel, 512, 4)
 LDPC_AOT_DECLARE(asp_spec_appendix_c_m64_kernel, 512, 4)
 LDPC_AOT_DECLARE(iasp_spec_appendix_c_m64_kernel, 512, 4)
 LDPC_AOT_DECLARE(tasp_spec_appendix_c_m64_kernel, 128, 2)
+LDPC_AOT_DECLARE(lche_spec_appendix_c_m64_kernel, 128, 2)
 LDPC_AOT_DECLARE(tasp_spec_appendix_c_m126_kernel, 256, 2)

@@ -15,6 +15,8 @@
 //                      columns all hold exactly two circulants, :2431-2480).
 //   iasp_global_kernel isum_prod_gf2_decod_qc_lm  decoders.cpp:3822-4121 (integer advanced sum-product, decoder 5; both branches,
 //                      u16 / i16 state in the workspace).
+//   lche_global_kernel lche_decod  decoders.cpp:2899-3012 (decoder 9): per-edge Z in the workspace, any row weight up to 1024
+//                      (0 and 1 included), any number of block rows, any lifting.
 //   tasp_global_kernel tdmp_sum_prod_gf2_decod_qc_lm  decoders.cpp:2584-2744 (decoder 7, the decoder of upstream's shipped scenarios):
 //                      per-edge lambda / rho / forward / backward products in the workspace instead of VGPRs, so row weight and
 //                      the number of circulants are unbounded (the resident tasp_body holds the Z state of ~300 circulants in the registers of two lanes per check).
@@ -322,6 +324,79 @@ __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArg
             }
         }
         glob_outputs<1>(a, w, fr, synd ? -steps : steps);                        // :2734-2743 (0 when the input was a codeword)
+        __syncthreads();
+    }
+}
+
+// lche_decod, decoders.cpp:2899-3012 (low-complexity high-efficiency decoder, decoder 9): the arithmetic of ldpc_spec::lche
+// (shared with the resident lche_body), tables read from global memory.  Workspace (glob_ws_bytes with one edge array): the
+// a-posteriori LLRs L [N] in soft, Z [e * M + k] in tmp.  A thread owns a check of the current layer and walks its edges twice:
+// the first pass forms the hard-bit parity and `sum` in edge order, the second recomputes u and p (L is unchanged until the
+// check writes it, and the checks of a layer touch disjoint variables) and writes L and Z.
+__global__ void __launch_bounds__(kGlobThreads) lche_global_kernel(const GlobArgs g) {
+    namespace E = ldpc_spec::lche;
+    const DecArgs &a = g.d;
+    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
+    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
+    double *const Z = w.tmp;
+    const double *const T = E::kLcheTab, *const S = E::kLcheStep;
+    auto syndrome = [&]() -> int {                                                  // check_syndrome :793-814 on L < 0
+        int fail = 0;
+        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
+            const int j = chk / M, n = chk - j * M;
+            int synd = 0;
+            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
+                const uint32_t d = a.edges[e];
+                int i = n + (int)(d & 0xffffu);
+                if (i >= M) i -= M;
+                synd ^= (int)(w.soft[(int)(d >> 16) * M + i] < 0);
+            }
+            fail |= synd;
+        }
+        return __syncthreads_or(fail);
+    };
+    for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
+        for (int v = threadIdx.x; v < N; v += (int)blockDim.x) w.soft[v] = a.llr[fr * N + v];   // :2923-2924
+        for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) Z[i] = 0.0;      // :2919-2921
+        __syncthreads();
+        int synd = syndrome();                                                      // :2928-2937
+        int steps = 0;
+        if (synd != 0) {
+            while (steps < a.maxiter) {
+                for (int j = 0; j < a.rh; ++j) {                                    // layers in sequence (:2946)
+                    const int e0 = a.row_start[j], e1 = a.row_start[j + 1];
+                    for (int k = threadIdx.x; k < M; k += (int)blockDim.x) {
+                        auto var = [&](int e) -> double & {
+                            const uint32_t d = a.edges[e];
+                            int i = k + (int)(d & 0xffffu);
+                            if (i >= M) i -= M;
+                            return w.soft[(int)(d >> 16) * M + i];
+                        };
+                        bool par = false;
+                        double sum = 0.0;
+                        for (int e = e0; e < e1; ++e) {                             // map_bin_llr :2836-2855
+                            const double u = var(e) - Z[(size_t)e * M + k];
+                            par ^= u < 0;
+                            sum += E::logexp(u < 0.0 ? -u : u, T, S);
+                        }
+                        for (int e = e0; e < e1; ++e) {                             // :2857-2863, :2974-2988
+                            double &x = var(e);
+                            const double u = x - Z[(size_t)e * M + k];
+                            const double p = E::logexp(u < 0.0 ? -u : u, T, S);
+                            const double av = E::logexp(p - sum, T, S);
+                            const double c2v = ((u < 0) != par) ? av : -av;
+                            x = c2v + u;
+                            Z[(size_t)e * M + k] = c2v;
+                        }
+                    }
+                    __syncthreads();
+                }
+                synd = syndrome();                                                  // :2995-3001
+                steps = steps + 1;
+                if (synd == 0) break;
+            }
+        }
+        glob_outputs(a, w, fr, synd ? -steps : steps);                              // :3005-3011 (0 when the input was a codeword)
         __syncthreads();
     }
 }

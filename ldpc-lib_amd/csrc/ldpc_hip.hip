@@ -136,6 +136,7 @@ const AotInstance kAot[] = {
     {LDPC_HIP_BP_DEC, (const void *)bp_spec_appendix_c_m64_kernel, 512, "bp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_ASP_DEC, (const void *)asp_spec_appendix_c_m64_kernel, 512, "asp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_IASP_DEC, (const void *)iasp_spec_appendix_c_m64_kernel, 512, "iasp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
+    {LDPC_HIP_LCHE_DEC, (const void *)lche_spec_appendix_c_m64_kernel, 128, "lche_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_TASP_DEC, (const void *)tasp_spec_appendix_c_m64_kernel, 128, "tasp_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
     {LDPC_HIP_TASP_DEC, (const void *)tasp_spec_appendix_c_m126_kernel, 256, "tasp_spec_appendix_c_m126_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM126>},
 };
@@ -376,6 +377,16 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
             if (M <= 256 && t.min_rw >= 2 && t.rh <= 64 && regs <= 480 && lds <= kLdsBudget) { p.body = "tasp_body"; p.threads = th; p.lds = lds; }
         }
         break;
+    case LDPC_HIP_LCHE_DEC:
+        p.required = true;  // tasp_body's layout: per-edge Z in VGPRs of the two lanes of a check, code-specialised instances only
+        {   // LDS: a-posteriori LLRs + one spare slot per thread + flag words + the phi tables and step sums
+            const int th = 64 * ((2 * M + 63) / 64);
+            const size_t lds = sizeof(double) * ((size_t)N + (size_t)th) + 16 + sizeof(double) * (ldpc_spec::lche::kTabWords + ldpc_spec::lche::kStepWords);
+            int regs = 85;   // the same estimate as TASP's (ldpc_jit.hpp)
+            for (int j = 0; j < t.rh; ++j) { const int L = (t.row_start[j + 1] - t.row_start[j] + 1) / 2; regs += 2 * L + (L + 1) / 2; }
+            if (M <= 256 && t.min_rw >= 1 && t.rh <= 64 && regs <= 480 && lds <= kLdsBudget) { p.body = "lche_body"; p.threads = th; p.lds = lds; }
+        }
+        break;
     default: break;
     }
     return p;
@@ -450,8 +461,9 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
     if (out) *out = nullptr;
     if (!out || !hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open: bad argument");
     if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_IMS_DEC &&
-        decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_ASP_DEC && decoder_id != LDPC_HIP_BP_DEC && decoder_id != LDPC_HIP_IASP_DEC)
-        return fail(LDPC_HIP_EUNSUPPORTED, "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, IASP=5, TASP=7, LMS=8)", decoder_id);
+        decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_ASP_DEC && decoder_id != LDPC_HIP_BP_DEC && decoder_id != LDPC_HIP_IASP_DEC &&
+        decoder_id != LDPC_HIP_LCHE_DEC)
+        return fail(LDPC_HIP_EUNSUPPORTED, "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, IASP=5, TASP=7, LMS=8, LCHE=9)", decoder_id);
     if (M >= 65536 || nh >= 65536 || rh >= 65536) return fail(LDPC_HIP_EUNSUPPORTED, "M, rh and nh must be < 65536");
     if ((long long)nh * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "code length nh * M = %lld: at most 2^28 - 1 is supported (32-bit indices)", (long long)nh * M);
     int ndev = 0;
@@ -459,6 +471,8 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open: device %d of %d", device, ndev);
 
     const CodeTables t(rh, nh, M, hd);
+    if (decoder_id == LDPC_HIP_LCHE_DEC && t.max_rw > 1024)   // map_bin_llr's static arrays hold 1024 edges (decoders.cpp:2818-2822)
+        return fail(LDPC_HIP_EUNSUPPORTED, "LCHE_DEC: row weight %d, at most 1024 is supported (upstream's map_bin_llr overflows beyond)", t.max_rw);
     std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M; c->ne = t.ne;
@@ -512,7 +526,7 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
     c->asp_cw2 = (decoder_id == LDPC_HIP_ASP_DEC || decoder_id == LDPC_HIP_IASP_DEC) && all_cw2;
     const bool can_global = decoder_id == LDPC_HIP_BP_DEC || decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_LMS_DEC || decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_IMS_DEC ||
                             (decoder_id == LDPC_HIP_TASP_DEC && t.min_rw >= 2) || (decoder_id == LDPC_HIP_ASP_DEC && t.min_rw >= 2) ||
-                            (decoder_id == LDPC_HIP_IASP_DEC && t.min_rw >= 2);
+                            (decoder_id == LDPC_HIP_IASP_DEC && t.min_rw >= 2) || decoder_id == LDPC_HIP_LCHE_DEC;
 
     // ---- code-specialised instance: ahead of time for the shipped example code, hiprtc for anything else
     const SpecPlan plan = plan_spec(decoder_id, t);
@@ -555,8 +569,9 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         c->global_is_fallback = c->jit_job != nullptr;   // until the background instance arrives
         c->spec_aot = nullptr; c->spec_jit = nullptr;
         c->kernel_name = decoder_id == LDPC_HIP_MS_DEC ? "ms_global_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_global_kernel" : decoder_id == LDPC_HIP_IMS_DEC ? "ims_global_kernel" : decoder_id == LDPC_HIP_ASP_DEC ? "asp_global_kernel" : decoder_id == LDPC_HIP_IASP_DEC ? "iasp_global_kernel" : decoder_id == LDPC_HIP_BP_DEC ? "bp_global_kernel" :
+                         decoder_id == LDPC_HIP_LCHE_DEC ? "lche_global_kernel" :
                          decoder_id == LDPC_HIP_SP_DEC ? "sp_global_kernel" : "tasp_global_kernel";
-        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) ? 0 : decoder_id == LDPC_HIP_TASP_DEC ? 4 : decoder_id == LDPC_HIP_ASP_DEC ? 3 : 1);   // IASP: u16 state + i16 products in the one edge array
+        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) ? 0 : decoder_id == LDPC_HIP_TASP_DEC ? 4 : decoder_id == LDPC_HIP_ASP_DEC ? 3 : 1);   // IASP: u16 state + i16 products in the one edge array; LCHE: Z
     }
     if (decoder_id == LDPC_HIP_IMS_DEC && !c->global_tier)   // parameters beyond int8 may send a launch to the global tier later
         c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, 0);
@@ -564,7 +579,7 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         if (!have_generic)
             return fail(LDPC_HIP_EUNSUPPORTED, "decoder %d, code %dx%d lifting %d: not supported by the generic kernel (limits: %d block rows, "
                         "%d block columns, row weight %d, M <= 512, 160 KiB LDS), no code-specialised instance: %s; the shape-unlimited "
-                        "tier serves every built decoder; decoders 2, 5 and 7 need row weights >= 2",
+                        "tier serves every built decoder; decoders 2, 5 and 7 need row weights >= 2, decoder 9 row weights <= 1024",
                         decoder_id, rh, nh, M, kRHM, kNHM, kRWM, why_not.c_str());
         if (plan.body && c->variant >= 2 && !c->jit_job)
             fprintf(stderr, "[ldpc_hip] code-specialised kernel unavailable (%s); using %s\n", why_not.c_str(), c->kernel_name.c_str());
@@ -705,6 +720,7 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
             case LDPC_HIP_IMS_DEC: hipLaunchKernelGGL(ldpc::ims_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_ASP_DEC: hipLaunchKernelGGL(ldpc::asp_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_IASP_DEC: hipLaunchKernelGGL(ldpc::iasp_global_kernel, gg, bb, 0, stream, ga); break;
+            case LDPC_HIP_LCHE_DEC: hipLaunchKernelGGL(ldpc::lche_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_SP_DEC: hipLaunchKernelGGL(ldpc::sp_global_kernel, gg, bb, 0, stream, ga); break;
             case LDPC_HIP_BP_DEC: hipLaunchKernelGGL(ldpc::bp_global_kernel, gg, bb, 0, stream, ga); break;
             default: hipLaunchKernelGGL(ldpc::tasp_global_kernel, gg, bb, 0, stream, ga); break;
@@ -839,7 +855,8 @@ int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter,
     const bool sp = c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_BP_DEC;  // soft[] is the working array upstream
     const bool tasp = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC;  // probability-domain decoders
     const bool iasp = c->decoder_id == LDPC_HIP_IASP_DEC;   // the same, its input transform without the * 0.5
-    if (c->decoder_id == LDPC_HIP_TASP_DEC) decision = 0;  // upstream ignores `decision` for this decoder: the result is always hard (decoders.cpp:2737-2738)
+    if (c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC) decision = 0;  // upstream ignores `decision` for these decoders: the
+                                                                                                 // result is always hard (decoders.cpp:2737-2738, :3005-3006)
     const bool need_soft = decision != 0 || (sp && clobber_sp_input);
     if (int rc = ensure_workspace(c, B, need_soft)) return rc;
     const size_t nllr = (size_t)B * c->N;
@@ -1084,7 +1101,7 @@ int ldpc_hip_channel_llr_dev(ldpc_hip_ctx *c, double snr_db, int modulation_type
     a.scatter = c->d_scatter;
     a.punct_start = c->N - c->M * punctured_blocks;
     a.punct_val = (c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC ||
-                   c->decoder_id == LDPC_HIP_IASP_DEC) ? 0.0 : 0.5;  // :700 (sic), out_type :451-466
+                   c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC) ? 0.0 : 0.5;  // :700 (sic), out_type :451-466
     const int m = modulation_type <= 1 ? 2 : 2 * modulation_type;
     const long long total = B * (long long)((c->N + m - 1) / m);
     long long blocks = (total + 255) / 256;

@@ -121,7 +121,7 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
     const std::string code = code_struct(rows, nh, M);
     const bool eight_waves = std::string(body) == "sp_body" || std::string(body) == "asp_body" || std::string(body) == "iasp_body" ||
                              std::string(body) == "bp_body";  // 8 waves per frame, 2 frames per CU
-    const bool tasp = std::string(body) == "tasp_body";   // two lanes per check; two waves per SIMD while the Z halves + addresses + ~85 temporaries fit 256 registers
+    const bool tasp = std::string(body) == "tasp_body" || std::string(body) == "lche_body";   // two lanes per check; two waves per SIMD while the Z halves + addresses + ~85 temporaries fit 256 registers
     int tasp_regs = 85;
     for (const auto &r : rows) tasp_regs += 2 * (((int)r.size() + 1) / 2) + (((int)r.size() + 1) / 2 + 1) / 2;
     const int threads = eight_waves ? 512 : std::string(body) == "ms_chunk_body" ? 64 : tasp ? ((2 * M + 63) / 64) * 64 : ((M + 63) / 64) * 64;
@@ -146,6 +146,12 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
     std::stringstream hs;
     hs << hf.rdbuf();
     const std::string hdr = hs.str();
+    const std::string tab_path = this_library_dir() + "/csrc/lche_table.hpp";   // generated tables ldpc_spec.hpp includes
+    std::ifstream tf(tab_path);
+    if (!tf) { err = "cannot read " + tab_path; return nullptr; }
+    std::stringstream ts;
+    ts << tf.rdbuf();
+    const std::string tab = ts.str();
     const std::string src = "#include \"ldpc_spec.hpp\"\nnamespace {\n" + code +
                             "}\nextern \"C\" __global__ void __launch_bounds__(" + std::to_string(threads) + (eight_waves ? ", 4" : ((tasp && tasp_regs > 256) || std::string(body) == "ms_chunk_body") ? ", 1" : ", 2") + ") spec_jit(const ldpc_spec::SpecArgs a) {\n"
                             "    ldpc_spec::" + body + "<Code>(a);\n}\n";
@@ -165,7 +171,7 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
         const char *dir = cache_dir.c_str();
         unsigned long long h = 1469598103934665603ull;   // FNV-1a 64
         auto mix = [&](const std::string &t) { for (unsigned char ch : t) { h ^= ch; h *= 1099511628211ull; } };
-        mix(src); mix(hdr); mix("gfx950 -O3 -ffp-contract=off");
+        mix(src); mix(hdr); mix(tab); mix("gfx950 -O3 -ffp-contract=off");
         // ... and on who compiled it for what: the runtime / compiler version and the device's own architecture string, so that an
         // upgrade of ROCm (or another GPU in the box) never picks up an object made by an older compiler
         int rt_version = 0;
@@ -190,9 +196,9 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
     Rtc *r = rtc(err);
     if (!r) return nullptr;
     hiprtcProgram prog = nullptr;
-    const char *hdr_src[] = {hdr.c_str()};
-    const char *hdr_name[] = {"ldpc_spec.hpp"};
-    if (r->CreateProgram(&prog, src.c_str(), "ldpc_spec_jit.hip", 1, hdr_src, hdr_name) != 0) { err = "hiprtcCreateProgram failed"; return nullptr; }
+    const char *hdr_src[] = {hdr.c_str(), tab.c_str()};
+    const char *hdr_name[] = {"ldpc_spec.hpp", "lche_table.hpp"};
+    if (r->CreateProgram(&prog, src.c_str(), "ldpc_spec_jit.hip", 2, hdr_src, hdr_name) != 0) { err = "hiprtcCreateProgram failed"; return nullptr; }
     // -ffp-contract=off is part of the numerics contract (two roundings in y + s*alpha)
     const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
     const int rc = r->CompileProgram(prog, 4, opts);

@@ -7,6 +7,7 @@
 //   ims_body        integer (int8) min-sum (ims_small_body: M <= 32, several frames per wavefront)
 //   sp_body / asp_body / bp_body   flooding sum-product in the likelihood-ratio / probability / log domain (8 waves per frame)
 //   tasp_body       TDMP (layered) sum-product in the probability domain
+//   lche_body       low-complexity high-efficiency decoder: TDMP's schedule in the LLR domain, phi by table lookup
 //
 // The Tanner graph is a compile-time constant of this kernel: a `Code` type carries the base matrix (block row
 // weights, block column and shift of every circulant) as constexpr tables, so the instruction stream contains
@@ -22,12 +23,14 @@
 // See ldpc_ms_fast.hpp for the arguments behind: sign-bit tests, LDS fp64 atomics in ascending block-row order, the
 // first edge of a block column storing instead of adding, and MAX_VAL clamping folded into the min1/min2 start value.
 //
-// This header must stay self-contained (hiprtc compiles it without the rest of the tree).
+// This header must stay self-contained (hiprtc compiles it without the rest of the tree) but for the generated tables of
+// lche_table.hpp, which hiprtc is given alongside.
 #pragma once
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
+#include "lche_table.hpp"
 
 namespace ldpc_spec {
 
@@ -2460,5 +2463,156 @@ __device__ __forceinline__ void ims_body_t(const SpecArgs &a) {
 
 template <class C> __device__ __forceinline__ void ims_body(const SpecArgs &a) { ims_body_t<C, false>(a); }
 template <class C> __device__ __forceinline__ void ims_small_body(const SpecArgs &a) { ims_body_t<C, true>(a); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Low-complexity high-efficiency decoder (upstream lche_decod, decoders.cpp:2899-3012, decoder id 9): TDMP's layered schedule
+// in the LLR domain.  Per check, over its edges in ascending block column (map_bin_llr :2815-2890):
+//     u = y = L[idx] - Z[e];  hard = (u < 0) ^ XOR(all u < 0);  p = logexp_int(|u|);  sum = p_0 + p_1 + ... (edge order)
+//     u = (2 hard - 1) * logexp_int(p - sum);  L[idx] = u + y;  Z[e] = u
+// Every step is an fp64 add, compare, exact power-of-two scaling or table lookup, so the results are upstream's bit for bit.
+// The arithmetic below is shared by lche_body and the shape-unlimited lche_global_kernel (ldpc_global.hpp).
+// ---------------------------------------------------------------------------------------------------------------
+namespace lche {
+
+// logexp_int (:2777-2813), phi(x) = -ln tanh(x / 2) by lookup; T = kLcheTab, S = kLcheStep (in LDS or global memory).
+// Upstream's small-argument loop `while (x < 1/512) { x *= 32; s -= 3.46; }` runs k = ceil((-8 - e) / 5) times for
+// x = f * 2^e, f in [0.5, 1): the scaling is exact (x * 32^k = ldexp(x, 5k), normal again) and s after k passes is S[k].
+// For x > 1/512, e >= -8 and k = 0: x is unscaled and s = 0, and 0 - T[i] is upstream's -T[i].
+template <class P, class Q>
+__device__ __forceinline__ double logexp(double x, P T, Q S) {
+    x = x <= 0.0 ? 1.0 / 4096.0 : x;                  // -0.0 <= 0 too
+    x = x > 16.0 ? 16.0 : x;
+    int k = (-4 - __builtin_amdgcn_frexp_exp(x)) / 5;   // C division: 0 for every e >= -8
+    k = k < 0 ? 0 : k;
+    const double xs = __builtin_amdgcn_ldexp(x, 5 * k);
+    const double f = x >= 2.0 ? 2.0 : x > 1.0 / 16.0 ? 16.0 : 512.0;
+    const int base = x >= 2.0 ? 0 : x > 1.0 / 16.0 ? 32 : 64;
+    return S[k] - T[base + (int)(f * xs + 0.5) - 1];
+}
+
+}  // namespace lche
+
+// Resident tier, on tasp_body's skeleton: 2 M threads per frame, two lanes per check (lanes 0-31 of a wave the A halves of 32
+// consecutive checks, lanes 32-63 their B halves), the a-posteriori LLRs in LDS, every edge's Z in the registers of its lane,
+// one barrier per layer.  Lane A holds the first ceil(RW/2) edges of its row, lane B the rest, both in ascending block column
+// (an odd row pads B's last slot).  fp64 addition is not associative, so `sum` is formed in upstream's order: A's partial sum goes
+// to B with one permlane32 swap, B continues it over its edges, and the total goes back to A with a second swap.  The hard-bit
+// parity is combined the same way.  The 96 table words and the 214 step sums live in LDS (divergent indices).  Rows of weight
+// >= 1, liftings up to 256.  LDS: [N] LLRs, one spare slot per thread, flag words, tables.
+template <class C>
+__device__ __forceinline__ void lche_body(const SpecArgs &a) {
+    constexpr int RH = C::RH, NH = C::NH, M = C::M, N = NH * M, TH = ((2 * M + 63) / 64) * 64, LMAX = (C::WMAX + 1) / 2;
+    constexpr bool WIDE = (size_t)N * 8 + (size_t)TH * 8 + 16 > 65536;
+    constexpr int AS = WIDE ? 3 : 0;
+    static_assert(((size_t)N * 8 + (size_t)TH * 8 + 16) >> AS <= 65536, "lche_body: 16-bit packed LDS addresses");
+    extern __shared__ double lds[];
+    char *const ldsb = reinterpret_cast<char *>(lds);
+    int *const flag = reinterpret_cast<int *>(ldsb + (size_t)N * 8 + (size_t)TH * 8);
+    double *const tab = reinterpret_cast<double *>(ldsb + (size_t)N * 8 + (size_t)TH * 8 + 16);
+    const double *const T = tab, *const S = tab + lche::kTabWords;
+    const int t = threadIdx.x, n = (t >> 6) * 32 + (t & 31);
+    const bool isB = (t & 32) != 0, valid = n < M;
+    const u32 spare = (u32)N * 8u + (u32)t * 8u;
+    const long long fr = blockIdx.x;
+
+    u32 pk[RH][(LMAX + 1) / 2];   // LDS address of local edge k of block row j for this lane, two to a register
+    static_for<0, RH>([&](auto J) {
+        constexpr int j = decltype(J)::value, RW = C::RW[j], L = (RW + 1) / 2, LB = RW / 2;
+        static_assert(RW >= 1, "lche_body: rows of weight 0 run on the shape-unlimited tier");
+        static_for<0, (LMAX + 1) / 2>([&](auto H) { pk[j][decltype(H)::value] = (spare >> AS) | ((spare >> AS) << 16); });
+        static_for<0, L>([&](auto K) {
+            constexpr int k = decltype(K)::value, sA = k, sB = k < LB ? L + k : 0;   // B ascending
+            int nA = n + C::SH[j][sA]; if (nA >= M) nA -= M;
+            int nB = n + C::SH[j][sB]; if (nB >= M) nB -= M;
+            const u32 adA = (u32)(C::COL[j][sA] * M + nA) * 8u, adB = k < LB ? (u32)(C::COL[j][sB] * M + nB) * 8u : spare;
+            const u32 ad = (valid ? (isB ? adB : adA) : spare) >> AS;
+            if constexpr (k % 2 == 0) pk[j][k / 2] = (pk[j][k / 2] & 0xffff0000u) | ad;
+            else pk[j][k / 2] = (pk[j][k / 2] & 0x0000ffffu) | (ad << 16);
+        });
+    });
+    auto adr = [&](auto J, auto K) -> u32 {
+        constexpr int j = decltype(J)::value, k = decltype(K)::value;
+        if constexpr (k % 2 == 0) return (pk[j][k / 2] & 0xffffu) << AS;
+        else return (pk[j][k / 2] >> 16) << AS;
+    };
+    auto padded = [&](auto J, auto K) -> bool {   // the padded slot of an odd row on the B lane (and only there)
+        constexpr int j = decltype(J)::value, k = decltype(K)::value;
+        if constexpr (k >= C::RW[j] / 2) return isB; else return false;
+    };
+
+    FrameVote fvote;
+    fvote.init(flag);
+    auto syndrome_fail = [&]() -> bool {                                    // check_syndrome :793-814 on L < 0
+        bool f = false;
+        static_for<0, RH>([&](auto J) {
+            constexpr int j = decltype(J)::value, L = (C::RW[j] + 1) / 2;
+            u32 sy = 0;
+            static_for<0, L>([&](auto K) {
+                const bool one = *reinterpret_cast<const double *>(ldsb + adr(J, K)) < 0;
+                sy ^= (u32)(one && !padded(J, K));
+            });
+            sy ^= swap_halves(sy, isB);
+            f |= sy != 0;
+        });
+        return valid && f;
+    };
+
+    for (int i = t; i < lche::kTabWords + lche::kStepWords; i += TH) tab[i] = i < lche::kTabWords ? lche::kLcheTab[i] : lche::kLcheStep[i - lche::kTabWords];
+    for (int v = t; v < N; v += TH) lds[v] = a.llr[fr * N + v];            // :2923-2924, the input as it is
+    *reinterpret_cast<double *>(ldsb + spare) = 0.0;
+    double Z[RH][LMAX];
+    static_for<0, RH>([&](auto J) {
+        static_for<0, (C::RW[decltype(J)::value] + 1) / 2>([&](auto K) { Z[decltype(J)::value][decltype(K)::value] = 0.0; });  // :2919-2921
+    });
+    __syncthreads();
+
+    bool fail = fvote(syndrome_fail());                                     // :2928-2937: already a codeword -> 0
+    int steps = 0;
+    while (fail && steps < a.maxiter) {
+        static_for<0, RH>([&](auto J) {
+            constexpr int j = decltype(J)::value, RW = C::RW[j], L = (RW + 1) / 2;
+            static_for<0, (L + 1) / 2>([&](auto H) { u32 w = pk[j][decltype(H)::value]; asm volatile("" : "+v"(w)); pk[j][decltype(H)::value] = w; });   // unpack per layer
+            double y[L], p[L];
+            u32 par = 0;
+            static_for<0, L>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                const bool pad = padded(J, K) || !valid;                    // idle slots see 0.0: their values stay finite and unused
+                const double x = pad ? 0.0 : *reinterpret_cast<const double *>(ldsb + adr(J, K));
+                const double u = x - Z[j][k];                                // :2965
+                y[k] = u;
+                par ^= (u32)(u < 0 && !pad);                                 // :2836-2845
+                p[k] = lche::logexp(u < 0.0 ? -u : u, T, S);                 // :2847-2851
+            });
+            double s0 = 0.0;                                                 // :2853-2855, edges in order: A's part ...
+            static_for<0, L>([&](auto K) { constexpr int k = decltype(K)::value; s0 = padded(J, K) ? s0 : s0 + p[k]; });
+            double s1 = swap_halves(s0, isB);                                // ... continued on B ...
+            static_for<0, L>([&](auto K) { constexpr int k = decltype(K)::value; s1 = padded(J, K) ? s1 : s1 + p[k]; });
+            const double s2 = swap_halves(s1, isB);                          // ... and the total back to A
+            const double sum = isB ? s1 : s2;
+            par ^= swap_halves(par, isB);
+            static_for<0, L>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                const double av = lche::logexp(p[k] - sum, T, S);           // :2857-2863
+                const bool hard = (y[k] < 0) != (par != 0);
+                const double u = hard ? av : -av;                            // (2 * hard - 1) * a
+                Z[j][k] = u;                                                 // :2984-2985
+                *reinterpret_cast<double *>(ldsb + adr(J, K)) = u + y[k];
+            });
+            __syncthreads();
+        });
+        fail = fvote(syndrome_fail());                                       // :2995-3001
+        steps = steps + 1;
+    }
+    const int res = fail ? -steps : steps;                                   // :3009-3011
+
+    if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
+    if (a.hard) {
+        constexpr int HW = (N + 31) / 32;
+        pack_hard<N, TH>(a.hard + fr * HW, threadIdx.x, [&](int v) { return lds[v] < 0; });   // :3005-3006
+    }
+    if (a.soft_out) {
+        for (int v = t; v < N; v += TH) a.soft_out[fr * N + v] = lds[v];
+    }
+}
 
 }  // namespace ldpc_spec
