@@ -314,7 +314,7 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
     if (!t.all_cols_used || t.max_rw > 16 || t.rh > 64 || t.nh > 64) return p;
     switch (decoder_id) {
     case LDPC_HIP_MS_DEC:
-        if (M == 64) { p.body = "ms_m64_body"; p.threads = 64; p.lds = sizeof(double) * (size_t)N; }
+        if (M == 64) { p.body = "ms_m64_body"; p.threads = 64; p.lds = ldpc_spec::kMsM64LdsBytes((size_t)N); }
         else if (M <= 32) {   // several frames per wavefront
             p.body = "ms_small_body"; p.threads = 64; p.frames_per_block = 64 / M; p.lds = sizeof(double) * (size_t)N * (size_t)(64 / M);
         }

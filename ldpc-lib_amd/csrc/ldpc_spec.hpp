@@ -102,6 +102,19 @@ __device__ __forceinline__ u32 twice(u32 x) {
 __device__ __forceinline__ double sel64(double if0, double if1, mask64 m) {
     return mk(sel32(hi32(if0), hi32(if1), m), sel32(lo32(if0), lo32(if1), m));
 }
+// sel32 whose result also depends on `tie`, which the instruction does not read.  With a `tie` that is opaque per block row and
+// state, a select between loop-invariant operands is neither hoisted out of the iteration loop into a long-lived VGPR nor shared
+// between STATE1 and STATE3 -- and, unlike an opaque copy of an operand, the dependence costs no instruction.
+__device__ __forceinline__ u32 sel32_tied(u32 if0, u32 if1, mask64 m, u32 tie) {
+    u32 d;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(if0), "v"(if1), "s"(m), "v"(tie));
+    return d;
+}
+// LDS byte address <-> pointer.  An address formed as an integer reaches ds_* as it is: register + constant = the instruction's
+// offset field, and no late `v_add_u32 v, <base of the dynamic LDS>, v` per access (the base resolves to 0 but is not folded).
+typedef __attribute__((address_space(3))) double lds_f64;
+__device__ __forceinline__ u32 lds_addr(const double *p) { return (u32)(unsigned long)(const lds_f64 *)p; }
+__device__ __forceinline__ double *lds_at(u32 addr) { return (double *)(lds_f64 *)(unsigned long)addr; }
 
 // Frame-wide "does any check fail?" for workgroups of several waves with ONE barrier: two flag words used alternately.  The
 // word a vote uses was cleared by thread 0 during the previous vote, after that vote's barrier (by then every wave has read
@@ -394,25 +407,34 @@ __device__ __forceinline__ void pack_hard(u32 *dst, const int tid, Pred pred) {
 }
 
 
+// Dynamic LDS of ms_m64_body per workgroup (= frame): the fp64 image of the N variables and one block column (512 B) in front of it,
+// see `at` below.  16 896 B at N = 2048: eight frames per CU stay resident (135 168 of 163 840 B).
+constexpr unsigned long kMsM64LdsBytes(unsigned long n) { return sizeof(double) * n + 512; }
+
 template <class C>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    extern __shared__ double lds[];  // [N] soft / acc (fp64)
-    char *const ldsb = reinterpret_cast<char *>(lds);
+    extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
-    const u32 n8 = (u32)lane * 8u;
     const double alpha = a.alpha;
     long long fr = blockIdx.x;  // one wave per frame; with a.queue the wave goes on to further frames (uniform: an SGPR pair)
 
-    // LDS byte offset (inside a block column) of variable (lane + shift) mod 64.  `base` is an opaque per-row copy of
-    // n8: it keeps the compiler from hoisting/CSE-ing the ~40 distinct rotated addresses out of the iteration loop
-    // into long-lived VGPRs (that costs more in spills than the two integer ops per non-zero shift it saves).
-    auto rot = [&](u32 base, auto S) -> u32 {
-        constexpr int c = decltype(S)::value;
-        if constexpr (c == 0) return base;
-        else return (base + 8u * (u32)c) & 511u;
+    // The image starts one block column (512 B) into the allocation, so a rotation needs no wrap arithmetic: variable
+    // (lane + c) mod 64 of block column k is at  base + 512 k + 8 c  with  base = hi  for the lanes with lane + c < 64 and
+    // base = lo = hi - 512  for those that wrap.  Which lanes wrap is a compile-time lane mask (an SGPR-pair constant), so a
+    // rotated address is ONE select between two long-lived registers, 512 k + 8 c (<= 32 760) sits in the ds_* offset field, and
+    // shift 0 is `hi` itself.  (Before: add, and, add-the-LDS-base -- three VOP2 -- per rotated edge and state, a copy + an add per
+    // block row.)  The ~40 distinct rotated addresses must still not be hoisted out of the iteration loop into long-lived VGPRs
+    // (that costs more in spills than the select it saves): `tie`, see sel32_tied.
+    const u32 lo = lds_addr(lds) + (u32)lane * 8u, hi = lo + 512u;
+    auto at = [&](u32 tie, auto S, auto K) -> double * {
+        constexpr int c = decltype(S)::value, k = decltype(K)::value;
+        static_assert(c >= 0 && c < 64 && k * 512 + c * 8 < 65536, "shift / block column out of range");
+        if constexpr (c == 0) return lds_at(hi + (u32)(k * 512));
+        else return lds_at(sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8));
     };
+    auto own = [&](auto K) -> double * { return lds_at(hi + (u32)(decltype(K)::value * 512)); };   // this lane's variable of block column k
 
   while (fr < a.nframes) {   // one pass without a queue
     const double *const yrow = a.llr + fr * N + lane;  // this frame's channel LLRs, variable (k, lane) at yrow[64 k]
@@ -439,22 +461,21 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            u32 mt = meta[j], nb = n8;
+            u32 mt = meta[j];
             // A volatile asm is ordered with the LDS operations around it, and everything this block row computes
-            // depends on its outputs: the row's ALU work therefore stays between the previous row's LDS operations
+            // depends on its output: the row's ALU work therefore stays between the previous row's LDS operations
             // and its own (otherwise instruction selection emits all 112 c2v computations first and spills them).
-            asm volatile("" : "+v"(mt), "+v"(nb));
+            asm volatile("" : "+v"(mt));
             const u32 pos = mt & 0xffu;
             // sign of the c2v on slot s = (own v2c sign) xor (row sign); slot s sits on bit RW-1-s of the row word.
             // Wt carries slot 0 on bit 31; every further slot is one full-rate add (Wt += Wt) instead of a shift.
             u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
             static_for<0, C::RW[j]>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                constexpr int k = C::COL[j][s];
                 const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
                 const double cv = signed_mag(aa, Wt);
                 Wt = twice(Wt);
-                double *p = reinterpret_cast<double *>(ldsb + rot(nb, IC<C::SH[j][s]>{}) + k * 512);
+                double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
                 if constexpr (C::FIRST[j][s]) *p = cv;
                 else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             });
@@ -463,7 +484,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         // ---------------- STATE2 (:4670-4685): soft = y + acc*alpha (two roundings)
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            double *p = reinterpret_cast<double *>(ldsb + n8 + k * 512);
+            double *p = own(K);
             const double pr = *p * alpha;
             *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
             if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // 8 columns in flight, not 32 (VGPR budget)
@@ -483,12 +504,10 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
-            u32 nb = n8;
-            asm volatile("" : "+v"(nb));
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                r[s] = *reinterpret_cast<const double *>(ldsb + rot(nb, IC<C::SH[j][s]>{}) + C::COL[j][s] * 512);
+                r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
             });
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
@@ -499,10 +518,16 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 const double tt = r[s] - x;              // v2c
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);  // (nS << 1) | sign(tt): slot s lands on bit RW-1-s
                 const double v = fabs(tt);
-                const mask64 c1 = lanes_lt(v, nm1);      // strict: the first minimum keeps the position
-                nm2 = fmin(fmax(v, nm1), nm2);           // = c1 ? nm1 : min(v, nm2)
-                npos = sel32(npos, (u32)s, c1);
-                nm1 = fmin(v, nm1);
+                if constexpr (s == 0) {
+                    // from nm1 = nm2 = K, npos = 0 the general step gives nm2 = min(max(v, K), K) = K and npos = sel(0, 0) = 0 for
+                    // every v (NaN included): only nm1 moves.  The compiler does not see that; 16 x (max, min, cmp, select) fewer.
+                    nm1 = fmin(v, kMaxVal);
+                } else {
+                    const mask64 c1 = lanes_lt(v, nm1);  // strict: the first minimum keeps the position
+                    nm2 = fmin(fmax(v, nm1), nm2);       // = c1 ? nm1 : min(v, nm2)
+                    npos = sel32(npos, (u32)s, c1);
+                    nm1 = fmin(v, nm1);
+                }
             });
             failw |= sy;
             m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
@@ -517,7 +542,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         u64 mine = 0ull;
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            const u64 b = __ballot((hi32(*reinterpret_cast<const double *>(ldsb + n8 + k * 512)) >> 31) != 0);
+            const u64 b = __ballot((hi32(*own(K)) >> 31) != 0);
             if (lane == k) mine = b;
         });
         // block column k = variables 64k..64k+63 = packed words 2k, 2k+1
@@ -526,7 +551,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     if (a.soft_out) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            a.soft_out[fr * N + k * 64 + lane] = *reinterpret_cast<const double *>(ldsb + n8 + k * 512);
+            a.soft_out[fr * N + k * 64 + lane] = *own(K);
         });
     }
     if (!a.queue) break;
