@@ -29,13 +29,15 @@ extern "C" {
 
 #define LDPC_HIP_ABI_VERSION 4
 
-/* decoders.h:16-28 enum DEC_ID (only the binary decoders on the hot path are built) */
+/* decoders.h:16-28 enum DEC_ID (all ten are built; the nine binary decoders through ldpc_hip_open, FHT_DEC through ldpc_hip_open_gfq) */
 #define LDPC_HIP_BP_DEC 0  /* bp_decod_qc_lm         decoders.cpp:1708 (Gallager BP, log domain) */
 #define LDPC_HIP_SP_DEC 1  /* sum_prod_decod_qc_lm   decoders.cpp:1923 */
 #define LDPC_HIP_ASP_DEC 2 /* sum_prod_gf2_decod_qc_lm decoders.cpp:2324 (probability-domain flooding sum-product) */
 #define LDPC_HIP_MS_DEC 3  /* min_sum_decod_qc_lm    decoders.cpp:4554 */
 #define LDPC_HIP_IMS_DEC 4 /* imin_sum_decod_qc_lm   decoders.cpp:5430 */
 #define LDPC_HIP_IASP_DEC 5 /* isum_prod_gf2_decod_qc_lm decoders.cpp:3822 (integer advanced sum-product, IASP_FIXED_POINT build) */
+#define LDPC_HIP_FHT_DEC 6  /* sum_prod_gfq_decod_lm   decoders.cpp:7036 (GF(q) sum-product, check nodes in the Walsh-Hadamard domain): its own
+                             * entry points, ldpc_hip_open_gfq / ldpc_hip_decode_gfq_*, below; ldpc_hip_open(6, ...) has no coefficient matrix and fails */
 #define LDPC_HIP_TASP_DEC 7 /* tdmp_sum_prod_gf2_decod_qc_lm decoders.cpp:2584 (decoder_type of the shipped scenario files) */
 #define LDPC_HIP_LMS_DEC 8 /* lmin_sum_decod_qc_lm   decoders.cpp:5064 */
 #define LDPC_HIP_LCHE_DEC 9 /* lche_decod            decoders.cpp:2899 (low-complexity high-efficiency decoder, layered, LLR domain) */
@@ -343,6 +345,41 @@ int ldpc_hip_mt_advance_multi(ldpc_hip_multi *m, double snr_db, int modulation_t
 int ldpc_hip_mt_frames_multi(ldpc_hip_multi *m, double snr_db, int modulation_type, int punctured_blocks, int maxiter, double alpha,
                              long long B, int32_t *frame_info, int32_t *iters);
 void ldpc_hip_multi_mt_stats(const ldpc_hip_multi *m, long long *sharded_rounds, long long *fallback_rounds);
+
+/* ---- FHT_DEC: QC-LDPC codes over GF(q), q = 2^q_bits -------------------------------------------------------------------------
+ * Replaces decod_open(FHT_DEC, q_bits, ...) + the hb / hc fill + fht_ncols2convert + decod_init (decoders.cpp:348-433, 1104-1161;
+ * bp_simulation.cpp:357-394).  hb [rh][nh]: circulant shifts, -1 = empty, reduced mod M.  hc [rh][nh]: the coefficient of each circulant as
+ * an element 1 .. q - 1 of GF(q) in natural (bit pattern) representation over the first primitive polynomial of upstream's bank
+ * (decoders.cpp:6594: 7, 13, 19, 37, 67, 131, 285, 529, 1033 for q_bits 2 .. 10); entries of empty circulants are ignored.  ncols2convert:
+ * upstream makes its tables from hc as given and only THEN rewrites the first ncols2convert columns of hc as alog[hc] (:1151-1159); the
+ * decoder is not affected, ldpc_hip_gfq_coefficients returns the rewritten matrix.
+ * LDPC_HIP_EUNSUPPORTED for what upstream cannot do itself: a block row of weight < 2 (map_graph reads products it never set,
+ * :6355-6360) or > 1024 (RWMAX), q_bits < 2 or > 10 (QMAX), a coefficient 0 (its logarithm is read past the end of the table, :6692).
+ * ldpc_hip_close, ldpc_hip_n / _r / _edges, ldpc_hip_kernel_name and ldpc_hip_profile_* work on such a context; every entry point of
+ * the binary decoders and of their simulation chain returns LDPC_HIP_EINVAL on it.  The environment variable LDPC_HIP_GFQ_GENERIC=1
+ * (read here) selects the generic kernel also for q = 16 and q = 64; LDPC_HIP_GFQ_SLOTS=n (read per call) caps the frames in flight. */
+int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, const int16_t *hc, int ncols2convert, int device,
+                      ldpc_hip_ctx **out);
+int ldpc_hip_gfq_q(const ldpc_hip_ctx *ctx);      /* q, 0 for a binary context */
+/* The matrix decod_init leaves in hc (what bp_simulation.cpp:384-389 copies back to the caller): HOST array [rh][nh] out. */
+int ldpc_hip_gfq_coefficients(const ldpc_hip_ctx *ctx, int16_t *hc_out);
+/* Batched sum_prod_gfq_decod_lm(st, soft, qhard, decword, maxiter, p_thr) (decoders.h:306, decoders.cpp:7036-7694, dispatch
+ * bp_simulation.cpp:724).  DEVICE pointers, asynchronous on `stream`; one launch decodes the whole batch for all iterations.
+ *   d_soft  [B][q][N] float64 in, NOT modified: per frame upstream's qy[s][i], the probability of symbol s at position i
+ *           (bp_simulation.cpp:644-676)
+ *   d_qhard [B][N] int16 out, or NULL: upstream's qhard -- first index of the strict maximum of the a-posteriori vector the last
+ *           syndrome check saw (decoders.cpp:7124-7143)
+ *   d_iters [B] int32 out, or NULL: upstream's return value: >= 0 the iteration before which the syndrome was zero (0 = the input
+ *           was already a codeword), < 0 = -maxiter, not converged
+ *   d_post  [B][q][N] float64 out, or NULL: upstream's fht_soft_out when the call returns (the input itself for a return of 0)
+ * p_thr must be 0 (the only value bp_simulation.cpp:341 passes; LDPC_HIP_EINVAL otherwise), maxiter >= 1.
+ * Numerics: all three outputs equal upstream's bit for bit, Inf / NaN from degenerate inputs included: fp64 in upstream's operation
+ * order, no contraction, correctly rounded division, no transcendental anywhere on this path. */
+int ldpc_hip_decode_gfq_dev(ldpc_hip_ctx *ctx, const double *d_soft, long long B, int maxiter, double p_thr, int16_t *d_qhard,
+                            int32_t *d_iters, double *d_post, void *stream);
+/* Same with HOST pointers (PCIe-inclusive, synchronous; large batches are staged in pieces). */
+int ldpc_hip_decode_gfq_host(ldpc_hip_ctx *ctx, const double *soft, long long B, int maxiter, double p_thr, int16_t *qhard,
+                             int32_t *iters, double *post);
 
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */

@@ -11,6 +11,7 @@ import numpy as np
 
 # decoders.h:16-28 enum DEC_ID
 DEC_BP, DEC_SP, DEC_ASP, DEC_MS, DEC_IMS, DEC_IASP, DEC_TASP, DEC_LMS, DEC_LCHE = 0, 1, 2, 3, 4, 5, 7, 8, 9
+DEC_FHT = 6   # GF(q) codes: class LdpcHipGfq (ldpc_hip_open_gfq), not LdpcHip
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG_DIR)
@@ -171,6 +172,11 @@ def load_library():
     lib.ldpc_hip_mt_shard_abandon.restype = None
     lib.ldpc_hip_multi_mt_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.ldpc_hip_multi_mt_stats.restype = None
+    lib.ldpc_hip_open_gfq.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_gfq_q.argtypes = [vp]
+    lib.ldpc_hip_gfq_coefficients.argtypes = [vp, vp]
+    lib.ldpc_hip_decode_gfq_dev.argtypes = [vp, vp, i64, i32, f64, vp, vp, vp, vp]
+    lib.ldpc_hip_decode_gfq_host.argtypes = [vp, vp, i64, i32, f64, vp, vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -429,6 +435,90 @@ class LdpcHip:
     def profile_read(self, reset=True):
         ms, n = C.c_double(), C.c_longlong()
         _check(self.lib, self.lib.ldpc_hip_profile_read(self.h, C.byref(ms), C.byref(n), 1 if reset else 0), "ldpc_hip_profile_read")
+        return ms.value, n.value
+
+
+class LdpcHipGfq:
+    """One opened QC-LDPC code over GF(q), q = 2^q_bits, on one GPU == upstream's DEC_STATE of decod_open(FHT_DEC, q_bits, ...) with hb,
+    hc and fht_ncols2convert filled in and decod_init done.  hb: shifts (-1 empty), hc: coefficients 1 .. q-1 in natural representation."""
+
+    def __init__(self, q_bits, hb, hc, M, ncols2convert=0, device=0):
+        self.lib = load_library()
+        hb = np.ascontiguousarray(hb, dtype=np.int16)
+        hc = np.ascontiguousarray(hc, dtype=np.int16)
+        assert hb.ndim == 2 and hb.shape == hc.shape
+        self.rh, self.nh = hb.shape
+        self.M, self.q_bits, self.device = int(M), int(q_bits), int(device)
+        h = C.c_void_p()
+        rc = self.lib.ldpc_hip_open_gfq(self.q_bits, self.rh, self.nh, self.M, hb.ctypes.data, hc.ctypes.data, int(ncols2convert), self.device, C.byref(h))
+        _check(self.lib, rc, "ldpc_hip_open_gfq")
+        self.h = h
+        self.N = self.lib.ldpc_hip_n(h)
+        self.R = self.lib.ldpc_hip_r(h)
+        self.edges = self.lib.ldpc_hip_edges(h)
+        self.q = self.lib.ldpc_hip_gfq_q(h)
+        self.kernel_name = self.lib.ldpc_hip_kernel_name(h).decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ldpc_hip_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def coefficients(self):
+        """hc as decod_init leaves it (the first ncols2convert columns in natural representation)."""
+        out = np.empty((self.rh, self.nh), dtype=np.int16)
+        _check(self.lib, self.lib.ldpc_hip_gfq_coefficients(self.h, out.ctypes.data), "ldpc_hip_gfq_coefficients")
+        return out
+
+    def decode(self, soft, maxiter, p_thr=0.0, want_qhard=True, want_post=False, stream=None):
+        """soft: torch float64 CUDA tensor [B, q, N] (not modified).  Returns (qhard int16 [B, N] | None, iters int32 [B],
+        post float64 [B, q, N] | None)."""
+        import torch
+        assert soft.is_cuda and soft.dtype == torch.float64 and soft.is_contiguous() and tuple(soft.shape[1:]) == (self.q, self.N)
+        B = soft.shape[0]
+        qhard = torch.empty((B, self.N), dtype=torch.int16, device=soft.device) if want_qhard else None
+        iters = torch.empty((B,), dtype=torch.int32, device=soft.device)
+        post = torch.empty((B, self.q, self.N), dtype=torch.float64, device=soft.device) if want_post else None
+        rc = self.lib.ldpc_hip_decode_gfq_dev(self.h, soft.data_ptr(), B, int(maxiter), float(p_thr), qhard.data_ptr() if qhard is not None else None,
+                                              iters.data_ptr(), post.data_ptr() if post is not None else None, _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_decode_gfq_dev")
+        return qhard, iters, post
+
+    def decode_host(self, soft, maxiter, p_thr=0.0, want_post=True):
+        """soft: numpy float64 [B, q, N], laid out per frame like upstream's qy (not modified).  Returns (qhard int16 [B, N],
+        iters int32 [B], post float64 [B, q, N] | None)."""
+        soft = np.ascontiguousarray(soft, dtype=np.float64)
+        if soft.ndim == 2:
+            soft = soft[None]
+        assert soft.shape[1:] == (self.q, self.N)
+        B = soft.shape[0]
+        qhard = np.empty((B, self.N), dtype=np.int16)
+        iters = np.empty(B, dtype=np.int32)
+        post = np.empty_like(soft) if want_post else None
+        rc = self.lib.ldpc_hip_decode_gfq_host(self.h, soft.ctypes.data, B, int(maxiter), float(p_thr), qhard.ctypes.data, iters.ctypes.data,
+                                               post.ctypes.data if post is not None else None)
+        _check(self.lib, rc, "ldpc_hip_decode_gfq_host")
+        return qhard, iters, post
+
+    def profile(self, enable=True):
+        _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")
+
+    def profile_read(self, reset=True):
+        """(total milliseconds, launches) of the decode launches timed with HIP events since the last reset."""
+        ms, n = C.c_double(), C.c_longlong()
+        _check(self.lib, self.lib.ldpc_hip_profile_read(self.h, C.byref(ms), C.byref(n), int(reset)), "ldpc_hip_profile_read")
         return ms.value, n.value
 
 

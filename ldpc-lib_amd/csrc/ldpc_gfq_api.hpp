@@ -1,0 +1,268 @@
+// Host side of FHT_DEC (decoder id 6, ldpc_gfq.hpp): what decod_open(FHT_DEC, q_bits, ...) + decod_init build once per context
+// (decoders.cpp:1104-1161) and the ldpc_hip_*gfq* entry points.  Included at the end of ldpc_hip.hip.
+#pragma once
+
+struct ldpc_gfq_state {
+    int q_bits = 0, q = 0, ncoef = 0, cw2 = 0, max_rw = 0;
+    int ql = 0, lpc = 0;          // check-node mapping of the kernel this context launches
+    bool spec = false;            // q = 16 / q = 64 instance
+    std::vector<int16_t> hc_after;   // hc as decod_init leaves it (ncols2convert applied)
+    int32_t *d_i32 = nullptr;     // row_start | e_col | e_circ | e_rl | col_start | ce_edge
+    int16_t *d_i16 = nullptr;     // mul | div
+    size_t off_e_col = 0, off_e_circ = 0, off_e_rl = 0, off_col_start = 0, off_ce_edge = 0, off_div = 0;
+    char *d_ws = nullptr;
+    int ws_slots = 0;
+    int num_cu = 0;
+};
+
+void ldpc_gfq_release(ldpc_gfq_state *g) {
+    if (!g) return;
+    if (g->d_i32) (void)hipFree(g->d_i32);
+    if (g->d_i16) (void)hipFree(g->d_i16);
+    if (g->d_ws) (void)hipFree(g->d_ws);
+    delete g;
+}
+
+namespace {
+
+// first primitive polynomial of each degree in upstream's bank (decoders.cpp:6594, asked for with {q_bits, 1})
+constexpr int kGfqPoly[11] = {0, 3, 7, 13, 19, 37, 67, 131, 285, 529, 1033};
+
+// logarithm / antilogarithm tables as decoders.cpp:6636 leaves them in zeroed arrays: alog[q - 1] = 0, log[0] = -1
+void gfq_field(int q_bits, std::vector<int> &lg, std::vector<int> &alog) {
+    const int q = 1 << q_bits;
+    lg.assign(q, 0);
+    alog.assign(q, 0);
+    lg[0] = -1;
+    int e = 1;
+    for (int i = 0; i < q - 1; ++i) {
+        alog[i] = e;
+        lg[e] = i;
+        e <<= 1;
+        if (e >= q) e ^= kGfqPoly[q_bits];
+    }
+}
+
+template <int QL, int LPC>
+int gfq_launch(const ldpc_gfq::Args &a, int grid, int threads, hipStream_t stream) {
+    hipLaunchKernelGGL((ldpc_gfq::gfq_kernel<QL, LPC>), dim3((unsigned)grid), dim3((unsigned)threads), 0, stream, a);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, const int16_t *hc, int ncols2convert, int device,
+                      ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (!out || !hb || !hc || rh <= 0 || nh <= 0 || M <= 0 || ncols2convert < 0 || ncols2convert > nh)
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_gfq: bad argument");
+    if (q_bits < 2) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: q_bits = %d, GF(q) needs q_bits >= 2 (binary codes: ldpc_hip_open)", q_bits);
+    if (q_bits > 10) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: q = 2^%d, at most q = 1024 is supported (upstream's QMAX, decoders.cpp:74)", q_bits);
+    if (M >= 65536 || nh >= 65536 || rh >= 65536) return fail(LDPC_HIP_EUNSUPPORTED, "M, rh and nh must be < 65536");
+    if ((long long)nh * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "code length nh * M = %lld: at most 2^28 - 1 is supported", (long long)nh * M);
+    const int q = 1 << q_bits;
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_gfq: device %d of %d", device, ndev);
+
+    // rows: edges in ascending column order; the coefficients in use, ascending (find_list_of_symbols, decoders.cpp:867-901)
+    std::vector<int32_t> row_start(rh + 1, 0), e_col, e_circ, e_coef;
+    std::vector<char> used(q, 0);
+    int max_rw = 0;
+    for (int j = 0; j < rh; ++j) {
+        for (int k = 0; k < nh; ++k) {
+            const int s = hb[(size_t)j * nh + k], v = hc[(size_t)j * nh + k];
+            if (v >= q) return fail(LDPC_HIP_EINVAL, "FHT_DEC: coefficient %d at (%d, %d) is not an element of GF(%d)", v, j, k, q);
+            if (s < 0) continue;
+            if (v < 0) return fail(LDPC_HIP_EINVAL, "FHT_DEC: circulant (%d, %d) has no coefficient", j, k);
+            if (v == 0)   // upstream files it under index q and then reads its logarithm table one entry past the end (decoders.cpp:884, :6692)
+                return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: coefficient 0 at (%d, %d): upstream's tables are undefined for it", j, k);
+            e_col.push_back(k); e_circ.push_back(s % M); e_coef.push_back(v);
+            used[v] = 1;
+        }
+        row_start[j + 1] = (int32_t)e_col.size();
+        const int rw = row_start[j + 1] - row_start[j];
+        if (rw < 2)   // map_graph reads Sigma_backH[1] / Sigma_forwardH[rw-2] it never set (decoders.cpp:6355-6360)
+            return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: block row %d has weight %d; upstream's check node needs at least 2", j, rw);
+        if (rw > 1024) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: row weight %d, at most 1024 is supported (upstream's RWMAX, decoders.cpp:73)", rw);
+        if (rw > max_rw) max_rw = rw;
+    }
+    const int E = (int)e_col.size();
+    if ((long long)E * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: %lld edges, at most 2^28 - 1 are supported", (long long)E * M);
+    std::vector<int> coef_index(q, -1), coefs;
+    for (int v = 1; v < q; ++v)
+        if (used[v]) { coef_index[v] = (int)coefs.size(); coefs.push_back(v); }
+    std::vector<int32_t> e_rl(E);
+    for (int e = 0; e < E; ++e) e_rl[e] = coef_index[e_coef[e]];
+
+    // columns: edges in ascending row order, and upstream's "every block column has weight 2" (find_column_weight, :837-865)
+    std::vector<int32_t> col_start(nh + 1, 0), ce_edge;
+    int cw2 = 1;
+    for (int k = 0; k < nh; ++k) {
+        for (int j = 0; j < rh; ++j)
+            for (int e = row_start[j]; e < row_start[j + 1]; ++e)
+                if (e_col[e] == k) ce_edge.push_back(e);
+        col_start[k + 1] = (int32_t)ce_edge.size();
+        if (col_start[k + 1] - col_start[k] != 2) cw2 = 0;
+    }
+
+    // field and the tables per used coefficient (p2table, :6673-6750): mul[c][s] = s * coef, div[c][s] = s / coef, row 0 stays 0
+    std::vector<int> lg, alog;
+    gfq_field(q_bits, lg, alog);
+    const int ncoef = (int)coefs.size(), mod = q - 1;
+    std::vector<int16_t> tab((size_t)2 * ncoef * q, 0);
+    for (int c = 0; c < ncoef; ++c)
+        for (int s = 1; s < q; ++s) {
+            const int x = lg[s], y = lg[coefs[c]];
+            int r = x + y;
+            if (r >= mod) r -= mod;
+            tab[(size_t)c * q + s] = (int16_t)alog[r];
+            r = x - y;
+            if (r < 0) r += mod;
+            tab[(size_t)(ncoef + c) * q + s] = (int16_t)alog[r];
+        }
+
+    std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
+    c->decoder_id = LDPC_HIP_FHT_DEC; c->device = device;
+    c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M; c->ne = E;
+    c->hard_words = (c->N + 31) / 32;
+    ldpc_gfq_state *g = c->gfq = new ldpc_gfq_state();
+    g->q_bits = q_bits; g->q = q; g->ncoef = ncoef; g->cw2 = cw2; g->max_rw = max_rw;
+    // the matrix decod_init leaves in hc: the first ncols2convert columns go from power to natural representation AFTER the
+    // tables were made from the values as given (:1151-1159)
+    g->hc_after.assign(hc, hc + (size_t)rh * nh);
+    for (int j = 0; j < rh; ++j)
+        for (int k = 0; k < ncols2convert; ++k)
+            if (g->hc_after[(size_t)j * nh + k] > -1) g->hc_after[(size_t)j * nh + k] = (int16_t)alog[g->hc_after[(size_t)j * nh + k]];
+
+    const char *genv = getenv("LDPC_HIP_GFQ_GENERIC");
+    const bool force_generic = genv && atoi(genv) != 0;
+    if (!force_generic && q == 16) { g->spec = true; g->ql = 16; g->lpc = 1; }
+    else if (!force_generic && q == 64) { g->spec = true; g->ql = 16; g->lpc = 4; }
+    else { g->ql = q <= 256 ? 4 : q / 64; g->lpc = q / g->ql; }
+    char name[64];
+    snprintf(name, sizeof name, "gfq_kernel<%sq=%d,%dx%d>", g->spec ? "" : "generic,", q, g->ql, g->lpc);
+    c->kernel_name = name;
+    c->last_launch = "";
+
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    g->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+    std::vector<int32_t> i32;
+    auto put = [&](const std::vector<int32_t> &v) { const size_t at = i32.size(); i32.insert(i32.end(), v.begin(), v.end()); return at; };
+    put(row_start);
+    g->off_e_col = put(e_col); g->off_e_circ = put(e_circ); g->off_e_rl = put(e_rl);
+    g->off_col_start = put(col_start); g->off_ce_edge = put(ce_edge);
+    g->off_div = (size_t)ncoef * q;
+    HIP_TRY(hipMalloc(&g->d_i32, sizeof(int32_t) * i32.size()));
+    HIP_TRY(hipMemcpy(g->d_i32, i32.data(), sizeof(int32_t) * i32.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&g->d_i16, sizeof(int16_t) * (tab.size() + 1)));
+    if (!tab.empty()) HIP_TRY(hipMemcpy(g->d_i16, tab.data(), sizeof(int16_t) * tab.size(), hipMemcpyHostToDevice));
+    *out = c.release();
+    return 0;
+}
+
+int ldpc_hip_gfq_q(const ldpc_hip_ctx *c) { return c && c->gfq ? c->gfq->q : 0; }
+
+int ldpc_hip_gfq_coefficients(const ldpc_hip_ctx *c, int16_t *hc_out) {
+    if (!c || !c->gfq || !hc_out) return fail(LDPC_HIP_EINVAL, "ldpc_hip_gfq_coefficients: not a GF(q) context, or null output");
+    std::memcpy(hc_out, c->gfq->hc_after.data(), sizeof(int16_t) * c->gfq->hc_after.size());
+    return 0;
+}
+
+int ldpc_hip_decode_gfq_dev(ldpc_hip_ctx *c, const double *d_soft, long long B, int maxiter, double p_thr, int16_t *d_qhard,
+                            int32_t *d_iters, double *d_post, void *stream_) {
+    if (!c || !c->gfq || B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_dev: not a GF(q) context (ldpc_hip_open_gfq), or bad argument");
+    if (p_thr != 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_dev: p_thr = %g; only 0 is supported (the only value upstream's harness passes)", p_thr);
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_dev: maxiter must be >= 1 (got %d)", maxiter);
+    if (B == 0) return 0;
+    if (!d_soft) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_dev: null input");
+    if (B > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "batch too large");
+    ldpc_gfq_state *g = c->gfq;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = (hipStream_t)stream_;
+
+    // one workgroup per frame slot; a batch beyond the slots is worked off inside the launch, slot by slot
+    const long long items = std::max((long long)c->R * g->lpc, (long long)c->N);
+    const int threads = (int)std::min(256LL, std::max(64LL, (items + 63) / 64 * 64));
+    const size_t stride = ldpc_gfq::slot_bytes(c->ne, c->M, c->N, g->q);
+    long long slots = (long long)g->num_cu * 1024 / threads;
+    if (const char *e = getenv("LDPC_HIP_GFQ_SLOTS")) { if (atoll(e) > 0) slots = atoll(e); }
+    while (slots > 1 && (size_t)slots * stride > ((size_t)4 << 30)) slots /= 2;
+    if (slots > B) slots = B;
+    if (slots > g->ws_slots) {
+        if (g->d_ws) (void)hipFree(g->d_ws);
+        g->d_ws = nullptr; g->ws_slots = 0;
+        HIP_TRY(hipMalloc(&g->d_ws, (size_t)slots * stride));
+        g->ws_slots = (int)slots;
+    }
+    ldpc_gfq::Args a{};
+    a.soft = d_soft; a.qhard = d_qhard; a.iters = d_iters; a.post = d_post;
+    a.ws = g->d_ws; a.ws_stride = stride; a.B = B; a.maxiter = maxiter;
+    a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.R = c->R; a.E = c->ne; a.q = g->q; a.lpc = g->lpc; a.cw2 = g->cw2;
+    a.row_start = g->d_i32; a.e_col = g->d_i32 + g->off_e_col; a.e_circ = g->d_i32 + g->off_e_circ; a.e_rl = g->d_i32 + g->off_e_rl;
+    a.col_start = g->d_i32 + g->off_col_start; a.ce_edge = g->d_i32 + g->off_ce_edge;
+    a.mul = g->d_i16; a.div = g->d_i16 + g->off_div;
+
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (c->prof) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+    }
+    c->last_launch = c->kernel_name.c_str();
+    if (g->spec && g->lpc == 1) gfq_launch<16, 1>(a, (int)slots, threads, stream);
+    else if (g->spec) gfq_launch<16, 4>(a, (int)slots, threads, stream);
+    else if (g->ql == 4) gfq_launch<4, 0>(a, (int)slots, threads, stream);
+    else if (g->ql == 8) gfq_launch<8, 0>(a, (int)slots, threads, stream);
+    else gfq_launch<16, 0>(a, (int)slots, threads, stream);
+    HIP_TRY(hipGetLastError());
+    if (c->prof) {
+        HIP_TRY(hipEventRecord(ev1, stream));
+        c->events.emplace_back(ev0, ev1);
+    }
+    return 0;
+}
+
+int ldpc_hip_decode_gfq_host(ldpc_hip_ctx *c, const double *soft, long long B, int maxiter, double p_thr, int16_t *qhard, int32_t *iters,
+                             double *post) {
+    if (!c || !c->gfq || B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_host: not a GF(q) context (ldpc_hip_open_gfq), or bad argument");
+    if (B == 0) return 0;
+    if (!soft) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_gfq_host: null input");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per = (size_t)c->gfq->q * c->N;   // doubles per frame
+    long long chunk = (long long)(((size_t)1 << 30) / (sizeof(double) * per));   // staging: at most 1 GiB in, 1 GiB out
+    if (chunk < 1) chunk = 1;
+    if (chunk > B) chunk = B;
+    double *d_in = nullptr, *d_post = nullptr;
+    int16_t *d_qh = nullptr;
+    int32_t *d_it = nullptr;
+    int rc = 0;
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_in, sizeof(double) * per * chunk));
+        if (post) HIP_TRY(hipMalloc(&d_post, sizeof(double) * per * chunk));
+        HIP_TRY(hipMalloc(&d_qh, sizeof(int16_t) * (size_t)c->N * chunk));
+        HIP_TRY(hipMalloc(&d_it, sizeof(int32_t) * (size_t)chunk));
+        for (long long b0 = 0; b0 < B; b0 += chunk) {
+            const long long nb = std::min(chunk, B - b0);
+            HIP_TRY(hipMemcpy(d_in, soft + per * b0, sizeof(double) * per * nb, hipMemcpyHostToDevice));
+            if (int r = ldpc_hip_decode_gfq_dev(c, d_in, nb, maxiter, p_thr, d_qh, d_it, d_post, nullptr)) return r;
+            HIP_TRY(hipDeviceSynchronize());
+            if (qhard) HIP_TRY(hipMemcpy(qhard + (size_t)c->N * b0, d_qh, sizeof(int16_t) * (size_t)c->N * nb, hipMemcpyDeviceToHost));
+            if (iters) HIP_TRY(hipMemcpy(iters + b0, d_it, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost));
+            if (post) HIP_TRY(hipMemcpy(post + per * b0, d_post, sizeof(double) * per * nb, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    };
+    rc = body();
+    if (d_in) (void)hipFree(d_in);
+    if (d_post) (void)hipFree(d_post);
+    if (d_qh) (void)hipFree(d_qh);
+    if (d_it) (void)hipFree(d_it);
+    return rc;
+}
+
+}  // extern "C"

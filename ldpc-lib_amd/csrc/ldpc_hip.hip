@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include "ldpc_sumprod.hpp"
 #include "ldpc_mt.hpp"
 #include "ldpc_encode.hpp"
+#include "ldpc_gfq.hpp"
 
 namespace {
 
@@ -160,8 +162,12 @@ __global__ void __launch_bounds__(256) iasp_channel_prior_kernel(double *x, long
         x[i] = ldpc_spec::iasp::prior(x[i]);
 }
 
+struct ldpc_gfq_state;                       // FHT_DEC (GF(q)) contexts: ldpc_gfq_api.hpp
+void ldpc_gfq_release(ldpc_gfq_state *g);
+
 struct ldpc_hip_ctx {
     int decoder_id = 0, device = 0;
+    ldpc_gfq_state *gfq = nullptr;           // set by ldpc_hip_open_gfq: the context decodes with ldpc_hip_decode_gfq_* only
     int rh = 0, nh = 0, M = 0, N = 0, R = 0, ne = 0, hard_words = 0;
     // generic (table-driven) kernel geometry
     int F = 1;         // frames per workgroup (M <= 64: floor(64/M))
@@ -270,7 +276,10 @@ void adopt_jit(ldpc_hip_ctx *c) {
     c->jit_job.reset();
 }
 
+// every entry point of the binary decoders and of their simulation chain comes through here
 int set_device(const ldpc_hip_ctx *c) {
+    if (c->gfq)
+        return fail(LDPC_HIP_EINVAL, "this entry point serves binary codes; a GF(q) context (ldpc_hip_open_gfq) decodes with ldpc_hip_decode_gfq_dev / _host");
     HIP_TRY(hipSetDevice(c->device));
     return 0;
 }
@@ -626,6 +635,7 @@ void ldpc_hip_close(ldpc_hip_ctx *c) {
     if (c->d_scatter) (void)hipFree(c->d_scatter);
     if (c->d_cw_bytes) (void)hipFree(c->d_cw_bytes);
     if (c->d_hd_enc) (void)hipFree(c->d_hd_enc);
+    ldpc_gfq_release(c->gfq);
     ldpc_mt::release(c->mt);
     for (auto &ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     delete c;
@@ -1288,7 +1298,7 @@ int ldpc_hip_profile_enable(ldpc_hip_ctx *c, int enable) {
 
 int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches, int reset) {
     if (!c) return fail(LDPC_HIP_EINVAL, "null ctx");
-    if (int rc = set_device(c)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
     for (auto &ev : c->events) {
         HIP_TRY(hipEventSynchronize(ev.second));
         float ms = 0;
@@ -1309,3 +1319,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 
 #include "ldpc_mt_api.hpp"
 #include "ldpc_multi.hpp"
+#include "ldpc_gfq_api.hpp"
