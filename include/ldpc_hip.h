@@ -381,6 +381,62 @@ int ldpc_hip_decode_gfq_dev(ldpc_hip_ctx *ctx, const double *d_soft, long long B
 int ldpc_hip_decode_gfq_host(ldpc_hip_ctx *ctx, const double *soft, long long B, int maxiter, double p_thr, int16_t *qhard,
                              int32_t *iters, double *post);
 
+/* ---- The transmit side of FHT_DEC: what bp_simulation.cpp does around sum_prod_gfq_decod_lm for q_mod > 2, on the device -----------
+ * left2right(matr, nrow, ncol) (decoders.cpp:174-195) on a row-major HOST array [rh][nh], in place: the new column order is
+ * rh .. nh-1, then rh-1, then 0 .. rh-2.  bp_simulation.cpp:391-394 applies it to hb and to hc before it encodes; here the caller does
+ * that and opens the context on the result.  LDPC_HIP_EINVAL for nh < rh or a non-positive size. */
+int ldpc_hip_gfq_left2right(int16_t *matr, int rh, int nh);
+int ldpc_hip_gfq_k(const ldpc_hip_ctx *ctx);      /* message symbols per frame, K = (nh - rh) * M; 0 for a binary context */
+/* Batched encode_NBQCLDPC(st, msg) (decoders.cpp:1381-1705): systematic encoding over the dual-diagonal parity part, on the matrix
+ * ldpc_hip_gfq_coefficients returns (upstream's encoder reads st->hc as decod_init left it), the context's hb and the context's field.
+ * DEVICE pointers, asynchronous on `stream`, one launch per batch.
+ *   d_msg      [B][K] int16 in: symbols 0 .. q-1 (a precondition; the bits above q are dropped)
+ *   d_codeword [B][N] int16 out: message, then the special block (column nh-rh), then the rh-1 blocks of the recursion -- for a
+ *              frame with ok = 0 what upstream leaves in st->codeword
+ *   d_ok       [B] int32 out, or NULL: upstream's return value, 1 = the full re-check (:1646-1692) found a codeword, 0 = "bad coding"
+ * All three schemes of the special column are served: weight 2; weight 3 with shifts (d, .., 0, .., d) (XOX); weight 3 with shifts
+ * (0, .., d2, .., 0) (OXO, the block rotated by M - d2).  The weight-3 shape complaint (:1486-1490) only prints upstream and is not
+ * an error here either: the re-check decides.
+ * LDPC_HIP_EUNSUPPORTED, decided on the first encode call and then cached (the context keeps decoding), with the rule in the
+ * message: where upstream returns 0 before any work (a coefficient of hc that is not 1 .. q-1, :1421-1425; a weight-2 special column
+ * with equal coefficients or non-zero shifts, :1461-1471; a weight-3 one with different end coefficients, :1477-1481; any other
+ * weight, :1493-1495), and where it would index a table with -1 or read outside the matrix: rh < 2, nh <= rh, an empty circulant
+ * at (0, nh-rh), at (rh-1, nh-rh) or at (j, nh-rh+1+j), j = 0 .. rh-2.  Also a shift below -1 (decoder and encoder would read it
+ * differently) and a code whose frame state (N + R + M symbols per frame) does not fit 64 KB of LDS. */
+int ldpc_hip_encode_gfq_dev(ldpc_hip_ctx *ctx, const int16_t *d_msg, long long B, int16_t *d_codeword, int32_t *d_ok, void *stream);
+/* Same with HOST pointers (synchronous). */
+int ldpc_hip_encode_gfq_host(ldpc_hip_ctx *ctx, const int16_t *msg, long long B, int16_t *codeword, int32_t *ok);
+/* sqrt(pow(10, -snr_db / 10) / 2 / ((nh - rh) / (double)nh)): bp_simulation.cpp:444-445 with punctured_blocks = 0.  0 for a binary context. */
+double ldpc_hip_gfq_sigma(const ldpc_hip_ctx *ctx, double snr_db);
+/* The q-ary BPSK / AWGN channel and the symbol probabilities of bp_simulation.cpp:581-582, :638-676 for B frames, DEVICE pointers,
+ * asynchronous, one launch.  Per position i the q_bits bits of the symbol go out most significant first (word2bin) as
+ * x_k = sigma * g + 2.0 * bit - 1.0; for every symbol s, lh starts at 0 and takes +-x_k in the order k = 0 .. q_bits-1,
+ * LH = lh / (sigma * sigma), qy[s] = exp(LH); the sum ascends over s and every qy[s] is divided by it.  No contraction, correctly
+ * rounded division, glibc's exp, so the output equals upstream's on the same Gaussians bit for bit, Inf / NaN at absurd SNR included
+ * (|LH| in [512, 745] takes glibc's special path, which is not restated: there the last bit may differ).
+ *   d_codeword [B][N] int16, or NULL = the all-zero word
+ *   d_noise    [B][N * q_bits] float64 Gaussians g, or NULL = draw them: Philox4x32-10 + Box-Muller (the generator of the binary chain,
+ *              stream tag 3), keyed by (seed, first_frame + f, bit index within the frame) -- the values do not depend on how a
+ *              run is cut into calls
+ *   d_soft     [B][q][N] float64 out, the input layout of ldpc_hip_decode_gfq_dev */
+int ldpc_hip_gfq_channel_dev(ldpc_hip_ctx *ctx, const int16_t *d_codeword, const double *d_noise, double sigma, uint64_t seed,
+                             long long first_frame, long long B, double *d_soft, void *stream);
+/* Symbol errors of bp_simulation.cpp:746-755 and the bookkeeping of :805-810, with the counters and frame_info of the binary
+ * ldpc_hip_count_errors_dev: d_counters[5] (DEVICE, accumulated) = nse (symbol errors at positions i >= R, summed over errored
+ * frames), nde (errored frames), nue (errored frames with iters >= 0), frames, sum |iters|;
+ * d_frame_info [B] or NULL = info_errors | (any_error << 30).  d_codeword NULL = the all-zero word. */
+int ldpc_hip_count_errors_gfq_dev(ldpc_hip_ctx *ctx, const int16_t *d_qhard, const int16_t *d_codeword, const int32_t *d_iters, long long B,
+                                  unsigned long long *d_counters, int32_t *d_frame_info, void *stream);
+/* Frames [first_frame, first_frame + B) through encode -> channel -> ldpc_hip_decode_gfq_dev -> count, no host traffic per frame;
+ * synchronous, counters[5] is a HOST array that is ACCUMULATED into.  random_messages = 0 sends the all-zero word and runs no
+ * encoder (upstream's zero_codeword); 1 draws K uniform symbols per frame (Philox, stream tag 4, keyed by the global frame index;
+ * symbol i is word i % 4 of block i / 4, reduced mod q) and encodes them; a frame whose encoding reports ok = 0 goes out as the
+ * all-zero word (bp_simulation.cpp:552-556).  sigma = ldpc_hip_gfq_sigma(snr_db).  The run is cut into pieces whose [q][N] float64
+ * workspace stays under 1 GiB (LDPC_HIP_GFQ_PIECE=n, read per call, caps the frames per piece further); the result does not depend
+ * on the pieces, on LDPC_HIP_GFQ_SLOTS, or on how B is split over calls with consecutive first_frame. */
+int ldpc_hip_simulate_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame, long long B,
+                          int random_messages, unsigned long long counters[5]);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

@@ -177,6 +177,15 @@ def load_library():
     lib.ldpc_hip_gfq_coefficients.argtypes = [vp, vp]
     lib.ldpc_hip_decode_gfq_dev.argtypes = [vp, vp, i64, i32, f64, vp, vp, vp, vp]
     lib.ldpc_hip_decode_gfq_host.argtypes = [vp, vp, i64, i32, f64, vp, vp, vp]
+    lib.ldpc_hip_gfq_left2right.argtypes = [vp, i32, i32]
+    lib.ldpc_hip_gfq_k.argtypes = [vp]
+    lib.ldpc_hip_gfq_sigma.argtypes = [vp, f64]
+    lib.ldpc_hip_gfq_sigma.restype = f64
+    lib.ldpc_hip_encode_gfq_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.ldpc_hip_encode_gfq_host.argtypes = [vp, vp, i64, vp, vp]
+    lib.ldpc_hip_gfq_channel_dev.argtypes = [vp, vp, vp, f64, u64, i64, i64, vp, vp]
+    lib.ldpc_hip_count_errors_gfq_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+    lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -438,6 +447,16 @@ class LdpcHip:
         return ms.value, n.value
 
 
+def gfq_left2right(matr):
+    """upstream's left2right (decoders.cpp:174-195) on a copy of the [rh, nh] matrix: columns rh .. nh-1, then rh-1, then 0 .. rh-2.
+    bp_simulation.cpp:391-394 applies it to hb and hc before encoding."""
+    m = np.array(matr, dtype=np.int16, order="C")
+    assert m.ndim == 2
+    lib = load_library()
+    _check(lib, lib.ldpc_hip_gfq_left2right(m.ctypes.data, m.shape[0], m.shape[1]), "ldpc_hip_gfq_left2right")
+    return m
+
+
 class LdpcHipGfq:
     """One opened QC-LDPC code over GF(q), q = 2^q_bits, on one GPU == upstream's DEC_STATE of decod_open(FHT_DEC, q_bits, ...) with hb,
     hc and fht_ncols2convert filled in and decod_init done.  hb: shifts (-1 empty), hc: coefficients 1 .. q-1 in natural representation."""
@@ -457,6 +476,7 @@ class LdpcHipGfq:
         self.R = self.lib.ldpc_hip_r(h)
         self.edges = self.lib.ldpc_hip_edges(h)
         self.q = self.lib.ldpc_hip_gfq_q(h)
+        self.k = self.lib.ldpc_hip_gfq_k(h)
         self.kernel_name = self.lib.ldpc_hip_kernel_name(h).decode()
 
     def close(self):
@@ -511,6 +531,95 @@ class LdpcHipGfq:
                                                post.ctypes.data if post is not None else None)
         _check(self.lib, rc, "ldpc_hip_decode_gfq_host")
         return qhard, iters, post
+
+    # ---- transmit side: encoder, q-ary channel, symbol-error counts, the chain ---------------------------------------------------
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def _to_dev(self, x, dtype, shape_tail, what):
+        """torch CUDA tensor or numpy array -> (contiguous CUDA tensor [B, *shape_tail], was_numpy)."""
+        import torch
+        was_numpy = not isinstance(x, torch.Tensor)
+        t = torch.from_numpy(np.ascontiguousarray(x)).to(self._dev()) if was_numpy else x
+        if t.dim() == len(shape_tail):
+            t = t[None]
+        if not t.is_cuda or tuple(t.shape[1:]) != tuple(shape_tail):
+            raise ValueError(f"{what}: expected a CUDA tensor or numpy array of shape [B, {', '.join(map(str, shape_tail))}], got {tuple(t.shape)}")
+        return t.to(dtype).contiguous(), was_numpy
+
+    def sigma(self, snr_db):
+        """bp_simulation.cpp:444-445 with punctured_blocks = 0."""
+        return self.lib.ldpc_hip_gfq_sigma(self.h, float(snr_db))
+
+    def encode(self, msg, stream=None):
+        """msg [B, k] symbols 0 .. q-1 (torch CUDA tensor or numpy array; host arrays are checked).  Returns (codeword int16 [B, N],
+        ok int32 [B]) -- encode_NBQCLDPC's codeword and return value per frame -- of the kind that was passed in."""
+        import torch
+        if not isinstance(msg, torch.Tensor):
+            m = np.asarray(msg)
+            if m.size and (m.min() < 0 or m.max() >= self.q):
+                raise ValueError(f"encode: message symbols must lie in 0 .. {self.q - 1}")
+        if self.k <= 0:   # nh <= rh: let the library name the rule
+            _check(self.lib, self.lib.ldpc_hip_encode_gfq_dev(self.h, None, 0, None, None, None), "ldpc_hip_encode_gfq_dev")
+        t, was_numpy = self._to_dev(msg, torch.int16, (self.k,), "encode")
+        B = t.shape[0]
+        cw = torch.empty((B, self.N), dtype=torch.int16, device=t.device)
+        ok = torch.empty((B,), dtype=torch.int32, device=t.device)
+        rc = self.lib.ldpc_hip_encode_gfq_dev(self.h, t.data_ptr(), B, cw.data_ptr(), ok.data_ptr(), _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_encode_gfq_dev")
+        return (cw.cpu().numpy(), ok.cpu().numpy()) if was_numpy else (cw, ok)
+
+    def channel(self, codeword=None, noise=None, sigma=None, seed=0, first_frame=0, B=None, stream=None):
+        """Symbol probabilities [B, q, N] (torch CUDA float64) after BPSK + AWGN.  codeword [B, N] or None = the all-zero word; noise
+        [B, N * q_bits] Gaussians or None = drawn on the device, keyed by (seed, first_frame + f, bit)."""
+        import torch
+        assert sigma is not None, "channel: sigma is required (see LdpcHipGfq.sigma)"
+        cw = nz = None
+        if codeword is not None:
+            cw, _ = self._to_dev(codeword, torch.int16, (self.N,), "channel codeword")
+            B = cw.shape[0] if B is None else B
+        if noise is not None:
+            nz, _ = self._to_dev(noise, torch.float64, (self.N * self.q_bits,), "channel noise")
+            B = nz.shape[0] if B is None else B
+        assert B is not None, "channel: B is required when neither codeword nor noise is given"
+        if (cw is not None and cw.shape[0] != B) or (nz is not None and nz.shape[0] != B):
+            raise ValueError("channel: codeword, noise and B disagree on the batch")
+        soft = torch.empty((B, self.q, self.N), dtype=torch.float64, device=self._dev())
+        rc = self.lib.ldpc_hip_gfq_channel_dev(self.h, cw.data_ptr() if cw is not None else None, nz.data_ptr() if nz is not None else None,
+                                               float(sigma), int(seed), int(first_frame), int(B), soft.data_ptr(), _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_gfq_channel_dev")
+        return soft
+
+    def count_errors(self, qhard, codeword, iters, counters=None, stream=None):
+        """qhard [B, N], codeword [B, N] or None = zero, iters [B].  Returns (counters uint64-valued int64 CUDA tensor [5] = nse, nde,
+        nue, frames, sum |iters| -- `counters` itself, accumulated, when one is passed -- and frame_info int32 [B])."""
+        import torch
+        qh, _ = self._to_dev(qhard, torch.int16, (self.N,), "count_errors qhard")
+        B = qh.shape[0]
+        cw = None
+        if codeword is not None:
+            cw, _ = self._to_dev(codeword, torch.int16, (self.N,), "count_errors codeword")
+        it = iters if isinstance(iters, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(iters)).to(self._dev())
+        it = it.reshape(-1).to(torch.int32).contiguous()
+        if it.shape[0] != B or (cw is not None and cw.shape[0] != B):
+            raise ValueError("count_errors: qhard, codeword and iters disagree on the batch")
+        if counters is None:
+            counters = torch.zeros(5, dtype=torch.int64, device=self._dev())
+        assert counters.is_cuda and counters.dtype == torch.int64 and counters.numel() == 5 and counters.is_contiguous()
+        info = torch.empty((B,), dtype=torch.int32, device=self._dev())
+        rc = self.lib.ldpc_hip_count_errors_gfq_dev(self.h, qh.data_ptr(), cw.data_ptr() if cw is not None else None, it.data_ptr(), B,
+                                                    counters.data_ptr(), info.data_ptr(), _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_count_errors_gfq_dev")
+        return counters, info
+
+    def simulate(self, snr_db, maxiter, B, seed, first_frame=0, random_messages=True):
+        """Frames [first_frame, first_frame + B) through encode -> channel -> decode -> count on the device.  Returns the five counters
+        (nse, nde, nue, frames, sum |iters|) as Python ints."""
+        cnt = (C.c_ulonglong * 5)()
+        rc = self.lib.ldpc_hip_simulate_gfq(self.h, float(snr_db), int(maxiter), int(seed), int(first_frame), int(B), 1 if random_messages else 0, cnt)
+        _check(self.lib, rc, "ldpc_hip_simulate_gfq")
+        return [int(v) for v in cnt]
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")

@@ -13,6 +13,18 @@ struct ldpc_gfq_state {
     char *d_ws = nullptr;
     int ws_slots = 0;
     int num_cu = 0;
+    // transmit chain (ldpc_gfq_chain_api.hpp)
+    std::vector<int16_t> hb;      // the shifts as given: the encoder reads hb and hc_after, as upstream's reads st->hb and st->hc
+    int enc_state = 0;            // 0 = not decided yet, 1 = encodable, -1 = refused for enc_why (decided on the first encode call)
+    std::string enc_why;
+    ldpc_gfq::EncArgs enc{};
+    size_t enc_lds = 0;
+    int16_t *d_enc = nullptr;     // shift | log of coefficient | log | alog
+    double *w_soft = nullptr;     // workspace of ldpc_hip_simulate_gfq for w_frames frames
+    int16_t *w_msg = nullptr, *w_cw = nullptr, *w_qh = nullptr;
+    int32_t *w_ok = nullptr, *w_it = nullptr;
+    unsigned long long *w_cnt = nullptr;
+    long long w_frames = 0;
 };
 
 void ldpc_gfq_release(ldpc_gfq_state *g) {
@@ -20,6 +32,9 @@ void ldpc_gfq_release(ldpc_gfq_state *g) {
     if (g->d_i32) (void)hipFree(g->d_i32);
     if (g->d_i16) (void)hipFree(g->d_i16);
     if (g->d_ws) (void)hipFree(g->d_ws);
+    void *chain[] = {g->d_enc, g->w_soft, g->w_msg, g->w_cw, g->w_qh, g->w_ok, g->w_it, g->w_cnt};
+    for (void *p : chain)
+        if (p) (void)hipFree(p);
     delete g;
 }
 
@@ -133,6 +148,7 @@ int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, cons
     // the matrix decod_init leaves in hc: the first ncols2convert columns go from power to natural representation AFTER the
     // tables were made from the values as given (:1151-1159)
     g->hc_after.assign(hc, hc + (size_t)rh * nh);
+    g->hb.assign(hb, hb + (size_t)rh * nh);
     for (int j = 0; j < rh; ++j)
         for (int k = 0; k < ncols2convert; ++k)
             if (g->hc_after[(size_t)j * nh + k] > -1) g->hc_after[(size_t)j * nh + k] = (int16_t)alog[g->hc_after[(size_t)j * nh + k]];

@@ -29,6 +29,7 @@
 #include "ldpc_mt.hpp"
 #include "ldpc_encode.hpp"
 #include "ldpc_gfq.hpp"
+#include "ldpc_gfq_chain.hpp"
 
 namespace {
 
@@ -1320,3 +1321,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_mt_api.hpp"
 #include "ldpc_multi.hpp"
 #include "ldpc_gfq_api.hpp"
+#include "ldpc_gfq_chain_api.hpp"
