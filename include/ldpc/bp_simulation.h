@@ -385,6 +385,92 @@ std::pair<double, double> bp_simulation_throughput_t(int q_mod, Mat const &H, in
     return std::make_pair((double)nse / experiment / (double)(n - r), (double)nde / experiment);
 }
 
+// A set of candidate codes of one shape over the SAME noise, in throughput mode: what a code search does when it calls
+// reset_random() before every candidate.  One pair <BER, FER> per code, each equal to what bp_simulation_throughput_t returns for
+// that matrix alone with the same seed on one GPU (modulation SKIP, permutation_type 0, the all-zero codeword).  Every batch is
+// one ldpc_hip_simulate_codes call for the whole set (C codes x B frames in one launch, the LLRs drawn once); upstream's
+// sequential stopping rule (:591, :805-823) is replayed per code over its ordered records, and a code that has stopped ignores the
+// records of later batches.  decoder_type: MS_DEC or LMS_DEC.  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// no iteration counts, so nue and sum_abs_iters stay 0).
+template <class Mat, class Env>
+std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
+                                                             int n_frame_errors, long long n_experiments, double snr,
+                                                             double reference_frame_error, int decoder_type, int modulation_type,
+                                                             int permutation_type, int punctured_blocks, int show_process,
+                                                             unsigned long long seed, int device = 0,
+                                                             std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                             long long max_batch = 65536) {
+    if (codes.empty()) Env::fail("bp_simulation_codes: empty code set");
+    if (modulation_type != MODULATION_SKIP_) Env::fail("bp_simulation_codes: only MODULATION_SKIP (BPSK) is built for code sets");
+    if (permutation_type != 0) Env::fail("bp_simulation_codes: only permutation_type 0 is built for code sets");
+    if (first_batch < 1 || max_batch < first_batch) Env::fail("bp_simulation_codes: bad batch sizes");
+    const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols(), M = tailbite_length;
+    const long long r = (long long)b * M, n = (long long)c * M;
+    std::vector<int16_t> hd((size_t)C * b * c);
+    for (int q = 0; q < C; ++q) {
+        if (codes[(size_t)q].n_rows() != b || codes[(size_t)q].n_cols() != c) Env::fail("bp_simulation_codes: the codes of a set share one shape");
+        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
+    }
+    ldpc_hip_ctx *ctx = nullptr;
+    if (ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());
+    std::vector<SimCounters> cnt((size_t)C);
+    std::vector<char> running((size_t)C, 1);
+    std::vector<unsigned long long> totals((size_t)C * 5);
+    std::vector<int32_t> info;
+    int n_running = C;
+    long long first = 0, batch = first_batch;
+    while (n_running > 0) {
+        // every running code has replayed the same number of frames so far: `first`
+        const long long room = n_experiments + 1 - first;
+        const long long B = batch < room ? batch : room;
+        if (B <= 0) break;
+        info.resize((size_t)C * (size_t)B);
+        if (ldpc_hip_simulate_codes(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, first, B, totals.data(), info.data()) != 0)
+            Env::fail(ldpc_hip_last_error());
+        for (int q = 0; q < C; ++q) {
+            if (!running[(size_t)q]) continue;
+            SimCounters &k = cnt[(size_t)q];
+            const int32_t *rec = info.data() + (size_t)q * (size_t)B;
+            bool stop = false;
+            for (long long f = 0; f < B; ++f) {                                                  // ordered replay of :591-823
+                if (!(k.nde < n_frame_errors && k.experiment <= n_experiments)) { stop = true; break; }
+                ++k.experiment;
+                if (rec[f] != 0) {                                                               // bit 30: any wrong bit (:805)
+                    k.nse += rec[f] & ((1 << 30) - 1); ++k.nde;
+                    if (show_process)
+                        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse,
+                               (int)k.nde, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
+                    if (k.nde >= 10 && (double)k.nde / k.experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
+                }
+            }
+            if (stop || !(k.nde < n_frame_errors && k.experiment <= n_experiments)) { running[(size_t)q] = 0; --n_running; }
+        }
+        first += B;
+        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+    }
+    ldpc_hip_close(ctx);
+    std::vector<std::pair<double, double>> out((size_t)C);
+    for (int q = 0; q < C; ++q)
+        out[(size_t)q] = std::make_pair((double)cnt[(size_t)q].nse / cnt[(size_t)q].experiment / (double)(n - r),
+                                        (double)cnt[(size_t)q].nde / cnt[(size_t)q].experiment);
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+// the standalone form: ldpc::Matrix, same tail as bp_simulation() plus the Philox seed
+inline std::vector<std::pair<double, double>> bp_simulation_codes(std::vector<Matrix> const &codes, int tailbite_length, int max_iterations,
+                                                                  int n_frame_errors, int n_experiments, double snr,
+                                                                  double reference_frame_error, int decoder_type, int modulation_type,
+                                                                  int permutation_type, int permutation_block, int permutation_inter,
+                                                                  int punctured_blocks, int show_process, unsigned long long seed = 1,
+                                                                  int device = 0, std::vector<SimCounters> *counters_out = nullptr,
+                                                                  long long first_batch = 1024, long long max_batch = 65536) {
+    (void)permutation_block; (void)permutation_inter;   // permutation_type 0 only
+    return bp_simulation_codes_t<Matrix, OwnRngEnv>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr,
+                                                    reference_frame_error, decoder_type, modulation_type, permutation_type, punctured_blocks,
+                                                    show_process, seed, device, counters_out, first_batch, max_batch);
+}
+
 // Standalone entry point with upstream's argument list (bp_simulation.h:9-27); coef_matrix / ncols2convert only
 // matter for q_mod > 2 (not built) and are accepted and ignored.
 std::pair<double, double> bp_simulation(int q_mod, Matrix const &code_generating_matrix, Matrix &coef_matrix,

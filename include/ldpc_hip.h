@@ -437,6 +437,42 @@ int ldpc_hip_count_errors_gfq_dev(ldpc_hip_ctx *ctx, const int16_t *d_qhard, con
 int ldpc_hip_simulate_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame, long long B,
                           int random_messages, unsigned long long counters[5]);
 
+/* ---- Code sets: C candidate codes of one shape x B frames in one launch (csrc/ldpc_codeset.hpp) -----------------------------------
+ * What a code search does (upstream's `search` / `ggp` drivers): many base matrices with the same rh, nh and M, each scored by a short
+ * Monte-Carlo run over the SAME noise.  hd [C][rh][nh]: the C base matrices one after the other, shifts in [0, M), -1 = empty block.
+ * decoder_id: LDPC_HIP_MS_DEC or LDPC_HIP_LMS_DEC; results are bit-identical to a context opened with ldpc_hip_open on the same matrix.
+ * LDPC_HIP_EINVAL: another decoder id, C < 1, M > 512, rh > 16, nh > 32 (MS_DEC), a row weight above 16, an all-empty block row or
+ * column, a shift outside [-1, M); LDPC_HIP_EUNSUPPORTED: nh * M * floor(64 / M) float64 values beyond the 160 KiB LDS image.
+ * The context serves the *_codes* entry points only: the single-code, GF(q) and multi-device entry points return LDPC_HIP_EINVAL
+ * on it, and the *_codes* entry points return LDPC_HIP_EINVAL on any other context.  Close with ldpc_hip_close. */
+int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
+/* The graph table ldpc_hip_open_codes uploads, built on the host (no GPU needed; the same checks and return codes): per code
+ * row_start[rh + 1] (relative to the code's own edge list) followed by its edges (block column << 16) | shift, rows then columns
+ * ascending; offsets [C] = index of each code's row_start[0] in the table.  *length = entries of the table; offsets and table may
+ * be NULL (sizes only), capacity = room in table. */
+int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                              long long capacity, long long *length);
+/* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
+ * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
+ * maxiter >= 1.  Asynchronous on `stream`. */
+int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *ctx, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha,
+                              uint32_t *d_hard, int32_t *d_iters, double *d_soft, void *stream);
+/* ldpc_hip_count_errors_dev per code, against the all-zero codeword: d_frame_info [C][B] or NULL (same encoding, bit 30 = any
+ * wrong bit), d_counters [C][5] (DEVICE, accumulated) = nse, nde, nue, frames, sum |iters|. */
+int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *ctx, const uint32_t *d_hard, const int32_t *d_iters, long long B,
+                                    int32_t *d_frame_info, unsigned long long *d_counters, void *stream);
+/* Frames [first_frame, first_frame + B) of every code through channel -> decode -> count; the BPSK LLRs are drawn ONCE (the noise of
+ * ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word, keyed by seed, global frame and position) and shared by the
+ * codes, so counters[c] equals what ldpc_hip_simulate returns for code c alone with the same seed and frame range.  sigma uses the
+ * common rate (nh - rh) / (nh - punctured_blocks).  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
+ * NULL.  B is worked off in pieces of the context's workspace (LDPC_HIP_CODES_PIECE=n caps the frames per piece); the result does
+ * not depend on the pieces or on how B is split over calls with consecutive first_frame.
+ * The workspace belongs to the context: one ldpc_hip_simulate_codes call at a time per context, on the null stream; callers that
+ * want several streams in flight use ldpc_hip_decode_codes_dev / ldpc_hip_count_errors_codes_dev with buffers of their own. */
+int ldpc_hip_simulate_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed,
+                            long long first_frame, long long B, unsigned long long *counters, int32_t *frame_info);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

@@ -186,6 +186,12 @@ def load_library():
     lib.ldpc_hip_gfq_channel_dev.argtypes = [vp, vp, vp, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_count_errors_gfq_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
+    lib.ldpc_hip_open_codes.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_codes.argtypes = [vp]
+    lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
+    lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
+    lib.ldpc_hip_count_errors_codes_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    lib.ldpc_hip_simulate_codes.argtypes = [vp, f64, i32, i32, f64, u64, i64, i64, vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -620,6 +626,116 @@ class LdpcHipGfq:
         rc = self.lib.ldpc_hip_simulate_gfq(self.h, float(snr_db), int(maxiter), int(seed), int(first_frame), int(B), 1 if random_messages else 0, cnt)
         _check(self.lib, rc, "ldpc_hip_simulate_gfq")
         return [int(v) for v in cnt]
+
+    def profile(self, enable=True):
+        _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")
+
+    def profile_read(self, reset=True):
+        """(total milliseconds, launches) of the decode launches timed with HIP events since the last reset."""
+        ms, n = C.c_double(), C.c_longlong()
+        _check(self.lib, self.lib.ldpc_hip_profile_read(self.h, C.byref(ms), C.byref(n), int(reset)), "ldpc_hip_profile_read")
+        return ms.value, n.value
+
+
+def _code_stack(codes):
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    if codes.ndim == 2:
+        codes = codes[None]
+    assert codes.ndim == 3, "codes: [C, rh, nh] base matrices of one shape"
+    return codes
+
+
+def codes_table(decoder_id, codes, M):
+    """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
+    int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order."""
+    lib = load_library()
+    codes = _code_stack(codes)
+    Cn, rh, nh = codes.shape
+    n = C.c_longlong()
+    _check(lib, lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, None, None, 0, C.byref(n)), "ldpc_hip_codes_table_host")
+    off = np.empty(Cn, dtype=np.int32)
+    tab = np.empty(n.value, dtype=np.int32)
+    _check(lib, lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off.ctypes.data, tab.ctypes.data, n.value, None),
+           "ldpc_hip_codes_table_host")
+    return off, tab
+
+
+class LdpcHipCodes:
+    """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
+    (ldpc_hip_open_codes): what a code search scores.  decoder_id DEC_MS or DEC_LMS; bit-identical to LdpcHip on each matrix."""
+
+    def __init__(self, decoder_id, codes, M, device=0):
+        self.lib = load_library()
+        codes = _code_stack(codes)
+        self.C, self.rh, self.nh = codes.shape
+        self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
+        h = C.c_void_p()
+        rc = self.lib.ldpc_hip_open_codes(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
+        _check(self.lib, rc, "ldpc_hip_open_codes")
+        self.h = h
+        self.N = self.lib.ldpc_hip_n(h)
+        self.R = self.lib.ldpc_hip_r(h)
+        self.hard_words = self.lib.ldpc_hip_hard_words(h)
+        self.kernel_name = self.lib.ldpc_hip_kernel_name(h).decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ldpc_hip_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def decode(self, llr, maxiter, alpha=0.8, shared=True, want_soft=False, stream=None):
+        """llr: torch float64 CUDA tensor, [B, N] (shared=True: every code decodes the same received words) or [C, B, N].  Returns
+        (hard int32 [C, B, W] -- the packed uint32 words --, iters int32 [C, B], soft float64 [C, B, N] | None)."""
+        import torch
+        assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous()
+        want = (self.N,) if shared else (self.C, None, self.N)
+        assert llr.dim() == (2 if shared else 3) and llr.shape[-1] == self.N and (shared or llr.shape[0] == self.C), (tuple(llr.shape), want)
+        B = llr.shape[-2]
+        hard = torch.empty((self.C, B, self.hard_words), dtype=torch.int32, device=llr.device)
+        iters = torch.empty((self.C, B), dtype=torch.int32, device=llr.device)
+        soft = torch.empty((self.C, B, self.N), dtype=torch.float64, device=llr.device) if want_soft else None
+        rc = self.lib.ldpc_hip_decode_codes_dev(self.h, llr.data_ptr(), 1 if shared else 0, B, int(maxiter), float(alpha), hard.data_ptr(),
+                                                iters.data_ptr(), soft.data_ptr() if soft is not None else None, _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_decode_codes_dev")
+        return hard, iters, soft
+
+    def count_errors(self, hard, iters, counters=None, want_frame_info=False, stream=None):
+        """hard [C, B, W], iters [C, B] as decode() returns them.  Returns (counters int64 CUDA tensor [C, 5] = nse, nde, nue, frames,
+        sum |iters| per code -- `counters` itself, accumulated, when one is passed --, frame_info int32 [C, B] | None)."""
+        import torch
+        assert tuple(iters.shape[:1]) == (self.C,) and hard.is_contiguous() and iters.is_contiguous()
+        B = iters.shape[1]
+        if counters is None:
+            counters = torch.zeros((self.C, 5), dtype=torch.int64, device=iters.device)
+        assert counters.is_cuda and counters.dtype == torch.int64 and tuple(counters.shape) == (self.C, 5) and counters.is_contiguous()
+        info = torch.empty((self.C, B), dtype=torch.int32, device=iters.device) if want_frame_info else None
+        rc = self.lib.ldpc_hip_count_errors_codes_dev(self.h, hard.data_ptr(), iters.data_ptr(), B, info.data_ptr() if info is not None else None,
+                                                      counters.data_ptr(), _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_count_errors_codes_dev")
+        return counters, info
+
+    def simulate(self, snr_db, maxiter, seed, first_frame, frames, punctured_blocks=0, alpha=0.8, records=False):
+        """Frames [first_frame, first_frame + frames) of every code over the same noise.  Returns counters uint64 [C, 5] (nse, nde, nue,
+        frames, sum |iters| per code: what LdpcHip.simulate gives for that matrix alone), and with records=True also frame_info
+        int32 [C, frames]."""
+        cnt = np.zeros((self.C, 5), dtype=np.uint64)
+        info = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_simulate_codes(self.h, float(snr_db), int(punctured_blocks), int(maxiter), float(alpha), int(seed), int(first_frame),
+                                              int(frames), cnt.ctypes.data, info.ctypes.data if info is not None else None)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes")
+        return (cnt, info) if records else cnt
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")

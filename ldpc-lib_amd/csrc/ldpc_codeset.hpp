@@ -1,0 +1,334 @@
+// ldpc_codeset.hpp -- C candidate codes of one shape (rh x nh, lifting M) x B frames in ONE launch (gfx950).
+//
+// The caller is a code search: thousands of base matrices with the same rh, nh and M, each scored by a short Monte-Carlo run over
+// the SAME received words.  The table-driven resident kernels of ldpc_kernels.hpp already read the graph from memory, so a code
+// set is one more level of indexing:
+//   * graph data: one concatenated int32 table; code c owns tab[code_off[c] ...] = row_start[rh+1] (relative to its own edge
+//     list) followed by its edges[] in the (block column << 16) | shift row-major format of DecArgs;
+//   * work item (c, w): workgroup blockIdx.x = c * blocks_per_code + w decodes frames w*F .. w*F+F-1 of code c.  A packed wave
+//     (M <= 64, F = floor(64/M) frames) never mixes codes: the last wave of a code is partly filled when B % F != 0.  The code
+//     index comes from blockIdx alone, so the table addresses are wave-uniform and the table loads stay scalar loads;
+//   * LLRs: shared [B][N] (llr_code_stride = 0: every code decodes the same B received words; the LLR traffic of C separate
+//     runs shrinks to 1/C and the frames of different codes hit the same lines in L2) or per code [C][B][N];
+//   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N].
+// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel compute (fp64, reference operation order, contraction
+// off); only the frame index and the table base differ, so the results are bit-identical to a single-code context.
+#pragma once
+
+#include "ldpc_kernels.hpp"
+
+namespace ldpc {
+
+struct CodesetArgs {
+    const double *llr;        // [B][N] (llr_code_stride == 0) or [C][B][N] (llr_code_stride == B * N)
+    uint32_t *hard;           // [C][B][hard_words] or null
+    int32_t *iters;           // [C][B] or null
+    double *soft_out;         // [C][B][N] or null
+    const int32_t *tab;       // concatenated per-code tables
+    const int32_t *code_off;  // [C] offset of code c's row_start[] in tab
+    long long B;              // frames per code
+    long long llr_code_stride;
+    int blocks_per_code;      // ceil(B / F)
+    int C, rh, nh, M, N, F, maxiter, hard_words;
+    double alpha;
+};
+
+// The graph table is read-only for the whole launch and its addresses are wave-uniform: reading it through the constant address
+// space makes every table access a scalar load, in the single-wave kernels too (through a plain global pointer the compiler proves
+// that only for the multi-wave instances and falls back to 64 identical vector loads otherwise).
+typedef const __attribute__((address_space(4))) int32_t *TabPtr;
+__device__ __forceinline__ TabPtr tab_ptr(const void *p) { return (TabPtr)(uintptr_t)p; }
+
+// The single-code argument block of work item (c, w): every pointer moved to code c's slice.  All values are functions of
+// blockIdx.x and kernel arguments only (wave-uniform).
+__device__ __forceinline__ DecArgs codeset_view(const CodesetArgs &s, int &w) {
+    const int c = blockIdx.x / s.blocks_per_code;
+    w = blockIdx.x - c * s.blocks_per_code;
+    const long long fo = (long long)c * s.B;   // first frame of code c in the [C][B] outputs
+    DecArgs a{};
+    a.llr = s.llr + (long long)c * s.llr_code_stride;
+    a.hard = s.hard ? s.hard + fo * s.hard_words : nullptr;
+    a.iters = s.iters ? s.iters + fo : nullptr;
+    a.soft_out = s.soft_out ? s.soft_out + fo * s.N : nullptr;
+    a.row_start = s.tab + tab_ptr(s.code_off)[c];
+    a.edges = reinterpret_cast<const uint32_t *>(a.row_start + s.rh + 1);
+    a.B = s.B; a.rh = s.rh; a.nh = s.nh; a.M = s.M; a.N = s.N; a.F = s.F; a.maxiter = s.maxiter; a.hard_words = s.hard_words;
+    a.alpha = s.alpha;
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Flooding normalised min-sum: ms_flood_kernel's body (ldpc_kernels.hpp; decoders.cpp:4554-4767) on work item (c, w)
+// ---------------------------------------------------------------------------------------------------------
+template <int RHM, int NHM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_codes_kernel(const CodesetArgs s) {
+    extern __shared__ double lds[];  // [N][F] soft / acc, then one flag word
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
+    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
+    int *const sh_flag = (int *)(lds + (size_t)N * F);
+    const double alpha = a.alpha;
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;   // frame of THIS code
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+
+    double y[NHM];
+#pragma unroll
+    for (int k = 0; k < NHM; ++k) y[k] = (k < nh && live) ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
+
+    double m1[RHM], m2[RHM];
+    uint32_t meta[RHM];
+#pragma unroll
+    for (int j = 0; j < RHM; ++j) { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }
+
+    bool done = !inb;
+    int res = -a.maxiter;
+
+    for (int iter = 0; iter < a.maxiter; ++iter) {
+        const bool wr = !done && valid;
+        // ---- STATE1
+        if (wr) {
+#pragma unroll
+            for (int k = 0; k < NHM; ++k) if (k < nh) lds[(k * M + n) * F + f] = 0.0;
+        }
+        if (MW) __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RHM; ++j) {
+            if (j < rh) {
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
+                const uint32_t mt = meta[j];
+                const uint32_t par = __popc(mt & 0xffffu) & 1u;
+                const uint32_t pos = mt >> kRowBits;
+                for (int idx = 0; idx < rw; ++idx) {
+                    const uint32_t d = (uint32_t)ed[e0 + idx];
+                    const int k = d >> 16, c = d & 0xffffu;
+                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                    const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
+                    const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+                    if (wr) lds[addr] = lds[addr] + cv;
+                }
+                if (MW) __syncthreads();
+            }
+        }
+        // ---- STATE2: multiply, then add -- two roundings (no FMA)
+        if (wr) {
+#pragma unroll
+            for (int k = 0; k < NHM; ++k) {
+                if (k < nh) {
+                    const int o = (k * M + n) * F + f;
+                    const double p = lds[o] * alpha;
+                    lds[o] = y[k] + p;
+                }
+            }
+        }
+        if (MW) __syncthreads();
+        // ---- STATE3
+        uint32_t failw = 0;
+#pragma unroll
+        for (int j = 0; j < RHM; ++j) {
+            if (j < rh) {
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
+                const uint32_t mt = meta[j];
+                const uint32_t par = __popc(mt & 0xffffu) & 1u;
+                const uint32_t pos = mt >> kRowBits;
+                const double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
+                double nm1 = kMaxVal, nm2 = kMaxVal;
+                uint32_t npos = 0, nS = 0, sy = 0;
+                for (int idx = 0; idx < rw; ++idx) {
+                    const uint32_t d = (uint32_t)ed[e0 + idx];
+                    const int k = d >> 16, c = d & 0xffffu;
+                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                    const double r = lds[addr];
+                    sy ^= hi32(r);
+                    const double aa = (pos == (uint32_t)idx) ? a2 : a1;
+                    const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+                    const double t = r - x;
+                    nS |= (hi32(t) >> 31) << idx;
+                    const double v = fmin(fabs(t), kMaxVal);
+                    const bool c1 = v < nm1;
+                    nm2 = fmin(fmax(v, nm1), nm2);
+                    npos = c1 ? (uint32_t)idx : npos;
+                    nm1 = fmin(v, nm1);
+                }
+                failw |= sy;
+                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+            }
+        }
+        const bool fail = valid && (failw >> 31);
+        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
+        if (!done && !frame_fail) { done = true; res = iter + 1; }
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+    }
+    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Layered offset min-sum: lms_layered_kernel's arithmetic (ldpc_kernels.hpp; decoders.cpp:5064-5425) on work item (c, w).
+// One difference in form, none in values: lms_layered_kernel keeps the v2c values and LDS addresses of a layer in tv[16] / addr[16]
+// between the layer's two passes, with both passes unrolled 16 times; the block-row loop around them then is too large to unroll,
+// m1 / m2 / meta are indexed at run time and live in scratch memory (272 bytes per lane).  Here the second pass reads the
+// a-posteriori value again and repeats the subtraction, the passes are run-time loops over the row's edges as in the flooding
+// kernel, the block-row loop unrolls, and the per-row records stay in VGPRs: no scratch.
+// ---------------------------------------------------------------------------------------------------------
+template <int RHM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const CodesetArgs s) {
+    extern __shared__ double lds[];
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
+    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
+    int *const sh_flag = (int *)(lds + (size_t)N * F);
+    const double beta = 0.4;
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+
+    if (valid) {
+        for (int k = 0; k < nh; ++k)
+            lds[(k * M + n) * F + f] = live ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
+    }
+    double m1[RHM], m2[RHM];
+    uint32_t meta[RHM];
+#pragma unroll
+    for (int j = 0; j < RHM; ++j) { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }
+    if (MW) __syncthreads();
+
+    auto syndrome_fail = [&]() -> bool {
+        uint32_t failw = 0;
+        for (int j = 0; j < rh; ++j) {
+            const int e0 = rs[j], e1 = rs[j + 1];
+            uint32_t sy = 0;
+            for (int e = e0; e < e1; ++e) {
+                const uint32_t d = (uint32_t)ed[e];
+                const int k = d >> 16, c = d & 0xffffu;
+                sy ^= hi32(lds[(k * M + rot_idx(n, c, M)) * F + f]);
+            }
+            failw |= sy;
+        }
+        return valid && (failw >> 31);
+    };
+
+    bool done = !inb;
+    int res = -a.maxiter;
+    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);
+    if (!done && !frame_fail) { done = true; res = 1; }
+    const bool at_entry = done && inb;   // no layer ran: upstream's soft[] is y itself, -0.0 included
+    for (int iter = 0; iter < a.maxiter; ++iter) {
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+        const bool wr = !done && valid;
+#pragma unroll
+        for (int j = 0; j < RHM; ++j) {
+            if (j < rh) {
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
+                const uint32_t mt = meta[j];
+                const uint32_t par = __popc(mt & 0xffffu) & 1u;
+                const uint32_t pos = mt >> kRowBits;
+                double nm1 = kMaxVal, nm2 = kMaxVal;
+                uint32_t npos = 0, nS = 0;
+                for (int idx = 0; idx < rw; ++idx) {
+                    const uint32_t d = (uint32_t)ed[e0 + idx];
+                    const int k = d >> 16, c = d & 0xffffu;
+                    const double r = lds[(k * M + rot_idx(n, c, M)) * F + f];
+                    const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
+                    const double pc = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+                    const double t = r - pc;
+                    nS |= (hi32(t) >> 31) << idx;   // sign kept even when the magnitude clips to 0
+                    double mag = fabs(t) - beta;
+                    mag = mag < 0 ? 0 : mag;
+                    const bool c1 = mag < nm1;
+                    nm2 = fmin(fmax(mag, nm1), nm2);
+                    npos = c1 ? (uint32_t)idx : npos;
+                    nm1 = fmin(mag, nm1);
+                }
+                const uint32_t npar = __popc(nS) & 1u;
+                // second pass: v2c = soft - old c2v once more (same operands, same rounding) instead of 16 values and addresses
+                // held per layer -- see the note above the kernel.  No variable of the layer has been written yet: a lane writes
+                // only the variable it has just read, and the block columns of a row are distinct.
+                for (int idx = 0; idx < rw; ++idx) {
+                    const uint32_t d = (uint32_t)ed[e0 + idx];
+                    const int k = d >> 16, c = d & 0xffffu;
+                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                    const double ao = (pos == (uint32_t)idx) ? m2[j] : m1[j];
+                    const double t = lds[addr] - flip_if(ao, ((mt >> idx) ^ par) & 1u);
+                    const double aa = (npos == (uint32_t)idx) ? nm2 : nm1;
+                    const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
+                    if (wr) lds[addr] = t + cv;
+                }
+                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                if (MW) __syncthreads();
+            }
+        }
+        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);
+        if (!done && !frame_fail) { done = true; res = iter + 1; }
+    }
+    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
+    if (live && at_entry && a.soft_out)
+        for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = a.llr[fr * N + k * M + n];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Error accounting against the all-zero codeword, count_errors_kernel's semantics (ldpc_frontend.hpp; bp_simulation.cpp:731-759,
+// 805-810) per code: one wavefront per (c, f); a workgroup works on one code only, so its totals go out as one atomic per counter.
+// ---------------------------------------------------------------------------------------------------------
+struct CodesetCountArgs {
+    const uint32_t *hard;          // [C][B][hard_words]
+    const int32_t *iters;          // [C][B]
+    int32_t *frame_info;           // [C][B] or null
+    unsigned long long *counters;  // [C][5]: nse, nde, nue, frames, sum |iters|
+    long long B;
+    int blocks_per_code;
+    int hard_words, R;
+};
+
+__global__ void __launch_bounds__(256) count_errors_codes_kernel(const CodesetCountArgs a) {
+    __shared__ unsigned long long part[4][5];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x / a.blocks_per_code, slot = blockIdx.x - c * a.blocks_per_code;
+    unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
+    for (long long fr = (long long)slot * 4 + wv; fr < a.B; fr += (long long)a.blocks_per_code * 4) {
+        const long long g = (long long)c * a.B + fr;
+        uint32_t all = 0, info = 0;
+        for (int w = lane; w < a.hard_words; w += 64) {
+            const uint32_t x = a.hard[g * a.hard_words + w];
+            all += __popc(x);
+            const int lo = 32 * w;   // information bits are indices >= R (bp_simulation.cpp:738)
+            uint32_t m = 0xffffffffu;
+            if (lo + 32 <= a.R) m = 0u;
+            else if (lo < a.R) m = 0xffffffffu << (a.R - lo);
+            info += __popc(x & m);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            all += __shfl_xor(all, o);
+            info += __shfl_xor(info, o);
+        }
+        if (lane == 0) {
+            const int it = a.iters[g];
+            if (a.frame_info) a.frame_info[g] = (int32_t)info | (all ? (1 << 30) : 0);
+            frames += 1;
+            sit += (unsigned long long)(it < 0 ? -it : it);
+            if (all) {
+                nse += info;
+                nde += 1;
+                if (it >= 0) nue += 1;
+            }
+        }
+    }
+    if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+        if (t) atomicAdd(&a.counters[(size_t)c * 5 + threadIdx.x], t);
+    }
+}
+
+}  // namespace ldpc

@@ -1,0 +1,242 @@
+// Host side of the code-set kernels (ldpc_codeset.hpp): the concatenated graph table, the ldpc_hip_*codes* entry points and the
+// shared-noise Monte-Carlo pass.  Included at the end of ldpc_hip.hip.
+#pragma once
+
+struct ldpc_codeset_state {
+    int C = 0;
+    std::vector<int32_t> off, tab;     // host copies of the device tables
+    int32_t *d_off = nullptr, *d_tab = nullptr;
+    // workspace of ldpc_hip_simulate_codes for w_frames frames per code
+    double *w_llr = nullptr;           // [w_frames][N], shared by the codes
+    uint32_t *w_hard = nullptr;        // [C][w_frames][hard_words]
+    int32_t *w_iters = nullptr, *w_info = nullptr;   // [C][w_frames]
+    unsigned long long *w_cnt = nullptr;             // [C][5]
+    long long w_frames = 0;
+};
+
+void ldpc_codeset_release(ldpc_codeset_state *s) {
+    if (!s) return;
+    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+namespace {
+
+// Checks a code set and builds its table: per code row_start[rh+1] (relative to the code's own edge list) then edges[]
+// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].
+int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
+                  std::vector<int32_t> &tab) {
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", who, decoder_id);
+    if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
+    if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
+    if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
+    if (rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels keep %d block rows in registers", who, rh, kRHM);
+    if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
+        return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
+    const int F = M > 64 ? 1 : 64 / M;
+    if (sizeof(double) * (size_t)nh * M * F + 16 > 160 * 1024)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
+    off.clear(); tab.clear();
+    std::vector<char> col_used((size_t)nh);
+    for (int c = 0; c < C; ++c) {
+        const int16_t *h = hd + (size_t)c * rh * nh;
+        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh >= ((size_t)1 << 31))
+            return fail(LDPC_HIP_EINVAL, "%s: the table of %d codes exceeds 2^31 entries", who, C);
+        off.push_back((int32_t)tab.size());
+        const size_t rs = tab.size();
+        tab.resize(rs + (size_t)rh + 1);
+        std::fill(col_used.begin(), col_used.end(), 0);
+        int ne = 0;
+        for (int j = 0; j < rh; ++j) {
+            tab[rs + j] = ne;
+            int rw = 0;
+            for (int k = 0; k < nh; ++k) {
+                const int v = h[(size_t)j * nh + k];
+                if (v < -1 || v >= M) return fail(LDPC_HIP_EINVAL, "%s: code %d, shift %d at (%d, %d) is outside [-1, %d)", who, c, v, j, k, M);
+                if (v == -1) continue;
+                tab.push_back((int32_t)(((uint32_t)k << 16) | (uint32_t)v));
+                col_used[(size_t)k] = 1;
+                ++rw; ++ne;
+            }
+            if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
+            if (rw > kRWM) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
+        }
+        tab[rs + rh] = ne;
+        for (int k = 0; k < nh; ++k)
+            if (!col_used[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
+    }
+    return 0;
+}
+
+int codeset_ctx(const ldpc_hip_ctx *c, const char *who) {
+    if (!c || !c->codes) return fail(LDPC_HIP_EINVAL, "%s: not a code-set context (ldpc_hip_open_codes)", who);
+    return 0;
+}
+
+int codeset_count_launch(const ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
+                         unsigned long long *d_counters, hipStream_t stream) {
+    const int C = c->codes->C;
+    long long bpc = (B + 3) / 4;            // workgroups per code: four frames (waves) each, fewer when there are many codes
+    const long long cap = 2048 / C > 1 ? 2048 / C : 1;
+    if (bpc > cap) bpc = cap;
+    ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, B, (int)bpc, c->hard_words, c->R};
+    hipLaunchKernelGGL(ldpc::count_errors_codes_kernel, dim3((unsigned)(bpc * C)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                              long long capacity, long long *length) {
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build("ldpc_hip_codes_table_host", decoder_id, rh, nh, M, hd, C, off, tab)) return rc;
+    if (length) *length = (long long)tab.size();
+    if (offsets) std::memcpy(offsets, off.data(), sizeof(int32_t) * off.size());
+    if (table) {
+        if (capacity < (long long)tab.size())
+            return fail(LDPC_HIP_EINVAL, "ldpc_hip_codes_table_host: the table has %lld entries, room for %lld", (long long)tab.size(), capacity);
+        std::memcpy(table, tab.data(), sizeof(int32_t) * tab.size());
+    }
+    return 0;
+}
+
+int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (!out) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: bad argument");
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, off, tab)) return rc;
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: device %d of %d", device, ndev);
+    std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
+    ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
+    s->off.swap(off); s->tab.swap(tab);
+    s->C = C;
+    c->decoder_id = decoder_id; c->device = device;
+    c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
+    c->ne = (int)(s->tab.size() - (size_t)C * (rh + 1));   // edges of the whole set
+    c->hard_words = (c->N + 31) / 32;
+    c->multiwave = M > 64;
+    c->F = c->multiwave ? 1 : 64 / M;
+    c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
+    c->lds_bytes = sizeof(double) * (size_t)c->N * c->F + 16;
+    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : "lms_layered_codes_kernel") + (c->multiwave ? "<multiwave>" : "");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMalloc(&s->d_off, sizeof(int32_t) * s->off.size()));
+    HIP_TRY(hipMemcpy(s->d_off, s->off.data(), sizeof(int32_t) * s->off.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s->d_tab, sizeof(int32_t) * s->tab.size()));
+    HIP_TRY(hipMemcpy(s->d_tab, s->tab.data(), sizeof(int32_t) * s->tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s->w_cnt, sizeof(unsigned long long) * 5 * (size_t)C));
+    *out = c.release();
+    return 0;
+}
+
+int ldpc_hip_codes(const ldpc_hip_ctx *c) { return c && c->codes ? c->codes->C : 0; }
+
+int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
+                              int32_t *d_iters, double *d_soft, void *stream_) {
+    if (int rc = codeset_ctx(c, "ldpc_hip_decode_codes_dev")) return rc;
+    if (B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: bad argument");
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
+    if (B == 0) return 0;
+    if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
+    const ldpc_codeset_state *s = c->codes;
+    const long long bpc = (B + c->F - 1) / c->F;
+    if (bpc * s->C > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %d codes x %lld frames is more than one launch takes", s->C, B);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    ldpc::CodesetArgs a{};
+    a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.soft_out = d_soft;
+    a.tab = s->d_tab; a.code_off = s->d_off;
+    a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
+    a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
+    a.alpha = alpha;
+    const void *k;
+    if (c->decoder_id == LDPC_HIP_MS_DEC)
+        k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
+    else
+        k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
+    if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (c->prof) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+    }
+    void *kargs[] = {&a};
+    c->last_launch = c->kernel_name.c_str();
+    HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * s->C)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
+    HIP_TRY(hipGetLastError());
+    if (c->prof) {
+        HIP_TRY(hipEventRecord(ev1, stream));
+        c->events.emplace_back(ev0, ev1);
+    }
+    return 0;
+}
+
+int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
+                                    unsigned long long *d_counters, void *stream_) {
+    if (int rc = codeset_ctx(c, "ldpc_hip_count_errors_codes_dev")) return rc;
+    if (!d_hard || !d_iters || !d_counters || B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_count_errors_codes_dev: bad argument");
+    if (B == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return codeset_count_launch(c, d_hard, d_iters, B, d_frame_info, d_counters, (hipStream_t)stream_);
+}
+
+int ldpc_hip_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed, long long first_frame,
+                            long long B, unsigned long long *counters, int32_t *frame_info) {
+    if (int rc = codeset_ctx(c, "ldpc_hip_simulate_codes")) return rc;
+    if (!counters || B < 0 || first_frame < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes: bad argument");
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes: maxiter must be >= 1 (got %d)", maxiter);
+    ldpc_codeset_state *s = c->codes;
+    const size_t C = (size_t)s->C;
+    ldpc::ChannelArgs ch{};
+    if (int rc = awgn_sigma(c, snr_db, 0, punctured_blocks, &ch.sigma)) return rc;   // the common rate (nh - rh) / (nh - punctured_blocks)
+    HIP_TRY(hipSetDevice(c->device));
+    // frames per piece: at most 65536, and the [C][piece] outputs within 1 GiB
+    const size_t per_frame = C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
+    long long piece = (long long)(((size_t)1 << 30) / per_frame);
+    piece = piece > (1 << 16) ? (1 << 16) : (piece < 1 ? 1 : piece);
+    if (const char *e = getenv("LDPC_HIP_CODES_PIECE")) { if (atoll(e) > 0 && atoll(e) < piece) piece = atoll(e); }
+    if (piece > B) piece = B;
+    if (piece > s->w_frames) {
+        void *old[] = {s->w_llr, s->w_hard, s->w_iters, s->w_info};
+        for (void *p : old)
+            if (p) (void)hipFree(p);
+        s->w_llr = nullptr; s->w_hard = nullptr; s->w_iters = nullptr; s->w_info = nullptr; s->w_frames = 0;
+        HIP_TRY(hipMalloc(&s->w_llr, sizeof(double) * (size_t)piece * c->N));
+        HIP_TRY(hipMalloc(&s->w_hard, sizeof(uint32_t) * C * (size_t)piece * c->hard_words));
+        HIP_TRY(hipMalloc(&s->w_iters, sizeof(int32_t) * C * (size_t)piece));
+        HIP_TRY(hipMalloc(&s->w_info, sizeof(int32_t) * C * (size_t)piece));
+        s->w_frames = piece;
+    }
+    HIP_TRY(hipMemsetAsync(s->w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
+    // the channel of ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word: noise keyed by (seed, global frame, position)
+    ch.llr = s->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
+    ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
+    ch.punct_start = c->N - c->M * punctured_blocks;
+    ch.punct_val = 0.5;   // bp_simulation.cpp:700 for the LLR-domain decoders
+    for (long long done = 0; done < B; done += piece) {
+        const long long nb = (B - done) < piece ? (B - done) : piece;
+        ch.B = nb; ch.first_frame = first_frame + done;
+        long long blocks = (nb * (long long)((c->N + 1) / 2) + 255) / 256;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        hipLaunchKernelGGL(ldpc::channel_llr_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, nullptr, ch);
+        HIP_TRY(hipGetLastError());
+        if (int rc = ldpc_hip_decode_codes_dev(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr)) return rc;
+        if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, frame_info ? s->w_info : nullptr, s->w_cnt, nullptr)) return rc;
+        if (frame_info)   // [C][nb] on the device -> columns [done, done + nb) of the caller's [C][B]
+            HIP_TRY(hipMemcpy2D(frame_info + done, sizeof(int32_t) * (size_t)B, s->w_info, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(counters, s->w_cnt, sizeof(unsigned long long) * 5 * C, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"

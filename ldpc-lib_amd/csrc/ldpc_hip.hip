@@ -22,6 +22,7 @@
 #include "ldpc_frontend.hpp"
 #include "ldpc_jit.hpp"
 #include "ldpc_kernels.hpp"
+#include "ldpc_codeset.hpp"
 #include "ldpc_global.hpp"
 #include "ldpc_ms_fast.hpp"
 #include "ldpc_aot.hpp"   // ldpc_spec.hpp, code_appendix_c_m64.hpp + the declarations of the aot/*.hip kernels
@@ -165,10 +166,13 @@ __global__ void __launch_bounds__(256) iasp_channel_prior_kernel(double *x, long
 
 struct ldpc_gfq_state;                       // FHT_DEC (GF(q)) contexts: ldpc_gfq_api.hpp
 void ldpc_gfq_release(ldpc_gfq_state *g);
+struct ldpc_codeset_state;                   // code-set contexts (C codes of one shape): ldpc_codeset_api.hpp
+void ldpc_codeset_release(ldpc_codeset_state *s);
 
 struct ldpc_hip_ctx {
     int decoder_id = 0, device = 0;
     ldpc_gfq_state *gfq = nullptr;           // set by ldpc_hip_open_gfq: the context decodes with ldpc_hip_decode_gfq_* only
+    ldpc_codeset_state *codes = nullptr;     // set by ldpc_hip_open_codes: the context decodes with ldpc_hip_*_codes* only
     int rh = 0, nh = 0, M = 0, N = 0, R = 0, ne = 0, hard_words = 0;
     // generic (table-driven) kernel geometry
     int F = 1;         // frames per workgroup (M <= 64: floor(64/M))
@@ -281,6 +285,8 @@ void adopt_jit(ldpc_hip_ctx *c) {
 int set_device(const ldpc_hip_ctx *c) {
     if (c->gfq)
         return fail(LDPC_HIP_EINVAL, "this entry point serves binary codes; a GF(q) context (ldpc_hip_open_gfq) decodes with ldpc_hip_decode_gfq_dev / _host");
+    if (c->codes)
+        return fail(LDPC_HIP_EINVAL, "this entry point serves one code; a code-set context (ldpc_hip_open_codes) decodes with ldpc_hip_decode_codes_dev / ldpc_hip_simulate_codes");
     HIP_TRY(hipSetDevice(c->device));
     return 0;
 }
@@ -637,6 +643,7 @@ void ldpc_hip_close(ldpc_hip_ctx *c) {
     if (c->d_cw_bytes) (void)hipFree(c->d_cw_bytes);
     if (c->d_hd_enc) (void)hipFree(c->d_hd_enc);
     ldpc_gfq_release(c->gfq);
+    ldpc_codeset_release(c->codes);
     ldpc_mt::release(c->mt);
     for (auto &ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     delete c;
@@ -1322,3 +1329,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_multi.hpp"
 #include "ldpc_gfq_api.hpp"
 #include "ldpc_gfq_chain_api.hpp"
+#include "ldpc_codeset_api.hpp"
