@@ -390,7 +390,7 @@ std::pair<double, double> bp_simulation_throughput_t(int q_mod, Mat const &H, in
 // that matrix alone with the same seed on one GPU (modulation SKIP, permutation_type 0, the all-zero codeword).  Every batch is
 // one ldpc_hip_simulate_codes call for the whole set (C codes x B frames in one launch, the LLRs drawn once); upstream's
 // sequential stopping rule (:591, :805-823) is replayed per code over its ordered records, and a code that has stopped ignores the
-// records of later batches.  decoder_type: MS_DEC or LMS_DEC.  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// records of later batches.  decoder_type: MS_DEC, LMS_DEC or TASP_DEC (7, ldpc_hip_open_codes_tdmp).  counters_out: nse, nde and experiment per code (the [C][B] records carry
 // no iteration counts, so nue and sum_abs_iters stay 0).
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
@@ -412,7 +412,9 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
         for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
     }
     ldpc_hip_ctx *ctx = nullptr;
-    if (ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());
+    if ((decoder_type == LDPC_HIP_TASP_DEC ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
+                                           : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
+        Env::fail(ldpc_hip_last_error());
     std::vector<SimCounters> cnt((size_t)C);
     std::vector<char> running((size_t)C, 1);
     std::vector<unsigned long long> totals((size_t)C * 5);

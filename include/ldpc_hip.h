@@ -446,8 +446,14 @@ int ldpc_hip_simulate_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_
  * The context serves the *_codes* entry points only: the single-code, GF(q) and multi-device entry points return LDPC_HIP_EINVAL
  * on it, and the *_codes* entry points return LDPC_HIP_EINVAL on any other context.  Close with ldpc_hip_close. */
 int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* The same for TDMP sum-product (LDPC_HIP_TASP_DEC; tdmp_sum_prod_gf2_decod_qc_lm, decoders.cpp:2584-2744, map_bin :2191-2228): an
+ * ordinary code-set context, served by the entry points below (alpha is ignored).  Limits: M <= 512, rh <= 16, row weights 2 .. 16
+ * (LDPC_HIP_EINVAL; map_bin reads SB[1]), no empty block column, any nh; LDPC_HIP_EUNSUPPORTED when the LDS image of a workgroup,
+ * floor(64 / M) * 8 * (nh * M + ne_max * M) + 16 bytes with ne_max the largest number of circulants of a code, exceeds 160 KiB. */
+int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
-/* The graph table ldpc_hip_open_codes uploads, built on the host (no GPU needed; the same checks and return codes): per code
+/* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) upload, built on the host (no GPU
+ * needed; the same checks and return codes): per code
  * row_start[rh + 1] (relative to the code's own edge list) followed by its edges (block column << 16) | shift, rows then columns
  * ascending; offsets [C] = index of each code's row_start[0] in the table.  *length = entries of the table; offsets and table may
  * be NULL (sizes only), capacity = room in table. */
@@ -465,7 +471,7 @@ int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *ctx, const uint32_t *d_hard, c
 /* Frames [first_frame, first_frame + B) of every code through channel -> decode -> count; the BPSK LLRs are drawn ONCE (the noise of
  * ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word, keyed by seed, global frame and position) and shared by the
  * codes, so counters[c] equals what ldpc_hip_simulate returns for code c alone with the same seed and frame range.  sigma uses the
- * common rate (nh - rh) / (nh - punctured_blocks).  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
+ * common rate (nh - rh) / (nh - punctured_blocks); punctured positions carry 0.5, or 0.0 for a TDMP set, as in ldpc_hip_awgn_llr_dev.  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
  * NULL.  B is worked off in pieces of the context's workspace (LDPC_HIP_CODES_PIECE=n caps the frames per piece); the result does
  * not depend on the pieces or on how B is split over calls with consecutive first_frame.
  * The workspace belongs to the context: one ldpc_hip_simulate_codes call at a time per context, on the null stream; callers that

@@ -11,11 +11,13 @@
 //   * LLRs: shared [B][N] (llr_code_stride = 0: every code decodes the same B received words; the LLR traffic of C separate
 //     runs shrinks to 1/C and the frames of different codes hit the same lines in L2) or per code [C][B][N];
 //   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N].
-// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel compute (fp64, reference operation order, contraction
-// off); only the frame index and the table base differ, so the results are bit-identical to a single-code context.
+// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel compute (fp64, reference operation order,
+// contraction off); only the frame index and the table base differ (and, for TDMP, where the state lives), so the results are
+// bit-identical to a single-code context.
 #pragma once
 
 #include "ldpc_kernels.hpp"
+#include "ldpc_spec.hpp"   // exp_glibc
 
 namespace ldpc {
 
@@ -31,6 +33,7 @@ struct CodesetArgs {
     int blocks_per_code;      // ceil(B / F)
     int C, rh, nh, M, N, F, maxiter, hard_words;
     double alpha;
+    int ne_max;               // tasp_layered_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
 };
 
 // The graph table is read-only for the whole launch and its addresses are wave-uniform: reading it through the constant address
@@ -273,6 +276,182 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const 
     write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
     if (live && at_entry && a.soft_out)
         for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = a.llr[fr * N + k * M + n];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// TDMP sum-product (decoder 7): tdmp_sum_prod_gf2_decod_qc_lm (decoders.cpp:2584-2744, map_bin :2191-2228, check_syndrome_thr at
+// 0.5) on work item (c, w), written as tasp_global_kernel (ldpc_global.hpp) writes it -- same expressions, same operand order, the
+// compiler's correctly rounded division -- with the state on chip instead of in a workspace:
+//   * LDS: the a-posteriori probabilities post[N][F], then the per-edge state Z[ne_max][M][F] (e = edge index inside the frame's own
+//     code; Z[e][n] is only ever touched by lane n), then the vote flag: F * 8 * (N + ne_max * M) + 16 bytes;
+//   * one lane owns one check of the current layer.  Y[] (the layer's rho values) and map_bin's forward products SF[] are VGPRs:
+//     the passes over the row are unrolled RWM times under a predicate on the (wave-uniform) row weight, so the arrays have static
+//     indices.  The backward products need no array: the second pass runs from the last edge to the first, carries SB[i + 1] in
+//     one register and finishes edge i (q, clamp, Z, gamma) on the way.  The edges of a row lie in distinct block columns, so the
+//     order in which a row's a-posteriori values are written does not matter; all of them are read before the first is written.
+//   * the two fp64 divisions per edge and layer are chains of about 30 dependent instructions, and the LDS image leaves room for
+//     few waves per CU (one workgroup at 16 x 32, M = 126), so nothing hides their latency but the row's other edges: both passes
+//     work on groups of G = 4 edges in one basic block (the predicate is per group; slots beyond the row's end recompute its
+//     last edge and store nowhere).
+// A converged frame of a packed wave (and a frame beyond B) stores nothing more: its state and outputs stay as they were.
+// ---------------------------------------------------------------------------------------------------------
+template <int RWM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) tasp_layered_codes_kernel(const CodesetArgs s) {
+    extern __shared__ double lds[];
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
+    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
+    double *const post = lds, *const Z = lds + (size_t)N * F;
+    int *const sh_flag = (int *)(Z + (size_t)s.ne_max * M * F);
+    const int spare = s.ne_max * M * F + 1;                                         // index into Z of the second half of the flag's 16 bytes
+    constexpr int G = 4;                                                            // edges of a row worked on side by side
+    static_assert(RWM % G == 0, "tasp_layered_codes_kernel: whole groups");
+    const double T = 0.0001, TT = 0;                                                // :2597-2598
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+    const int ne = rs[rh];
+
+    if (valid) {
+        for (int k = 0; k < nh; ++k) {                                              // :2611-2618
+            double p = 0.5;
+            if (live) {
+                const double x = a.llr[fr * N + k * M + n] * 0.5;
+                const double y = x < 20.0 ? (x < -20.0 ? -20.0 : x) : 20.0;         // maxd(mind(x, INPUT_LIMIT), -INPUT_LIMIT)
+                const double e0 = ldpc_spec::exp_glibc(y), e1 = ldpc_spec::exp_glibc(-y);
+                p = e1 / (e0 + e1);
+            }
+            post[(k * M + n) * F + f] = p;
+        }
+        for (int e = 0; e < ne; ++e) Z[(e * M + n) * F + f] = 0.5;                  // :2637
+    }
+    if (MW) __syncthreads();
+
+    auto syndrome_fail = [&]() -> bool {                                            // check_syndrome_thr :2274-2306, thr 0.5
+        uint32_t sy = 0, failw = 0;
+        for (int j = 0; j < rh; ++j) {
+            const int e0 = rs[j], e1 = rs[j + 1];
+            sy = 0;
+            for (int e = e0; e < e1; ++e) {
+                const uint32_t d = (uint32_t)ed[e];
+                const int k = d >> 16, c = d & 0xffffu;
+                sy ^= (uint32_t)(post[(k * M + rot_idx(n, c, M)) * F + f] > 0.5);
+            }
+            failw |= sy;
+        }
+        return valid && failw;
+    };
+
+    bool done = !inb;
+    int res = -a.maxiter;
+    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);          // :2653-2660
+    if (!done && !frame_fail) { done = true; res = 0; }                             // a codeword at the input: no iteration, 0
+    for (int steps = 0; steps < a.maxiter;) {
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+        const bool wr = !done && valid;
+        for (int j = 0; j < rh; ++j) {                                              // layers in sequence (:2668)
+            const int e0 = rs[j], rw = rs[j + 1] - e0;
+            double Y[RWM], SF[RWM];
+#pragma unroll
+            for (int i = 0; i < RWM; ++i) { Y[i] = 0.0; SF[i] = 0.0; }
+            double sf = 0.0;
+#pragma unroll
+            for (int g0 = 0; g0 < RWM; g0 += G) {                                   // :2676-2697 and map_bin's forward products
+                if (g0 < rw) {
+                    double v[G];
+#pragma unroll
+                    for (int u = 0; u < G; ++u) {                                   // G independent chains; slots beyond the row repeat its last edge
+                        const int i = g0 + u < rw ? g0 + u : rw - 1;
+                        const uint32_t d = (uint32_t)ed[e0 + i];
+                        const int k = d >> 16, c = d & 0xffffu;
+                        const double x = post[(k * M + rot_idx(n, c, M)) * F + f];
+                        const double aa = Z[((e0 + i) * M + n) * F + f];
+                        double t = x * (1.0 - aa) / (aa + x - 2.0 * aa * x);        // rho = gamma - lambda
+                        if (t < TT) t = TT;
+                        if (t > 1 - TT) t = 1 - TT;
+                        v[u] = t;
+                    }
+#pragma unroll
+                    for (int u = 0; u < G; ++u) {                                   // SF of a slot beyond the row is never read; its Y is 0
+                        const int i = g0 + u;
+                        Y[i] = i < rw ? v[u] : 0.0;
+                        const double P = 1 - 2 * v[u];
+                        sf = i == 0 ? P : P * sf;                                   // SF[i] = P[i] * SF[i - 1]
+                        SF[i] = sf;
+                    }
+                }
+            }
+            // SB[i + 1] while edge i is finished.  It starts at 1.0 and a slot beyond the row has P = 1 - 2 * 0 = 1.0: x * 1.0 is x
+            // exactly, so SB[rw - 1] = P[rw - 1] and q[rw - 1] = (1 - SF[rw - 2]) / 2 come out of the general expressions, bit for bit,
+            // without a branch on the row weight inside a group.
+            double sb = 1.0;
+#pragma unroll
+            for (int g0 = RWM - G; g0 >= 0; g0 -= G) {
+                if (g0 < rw) {
+                    double sbn[G], q[G], gm[G];
+                    int zi[G], pi[G];
+#pragma unroll
+                    for (int u = 0; u < G; ++u) {
+                        // Where the group's results go, settled before the divisions so that these stay one basic block.  A lane that
+                        // must not store (a converged frame, a lane beyond M, a slot beyond the row) aims at the spare word behind the
+                        // vote flag, which nothing reads.
+                        const int i = g0 + u;
+                        const bool ok = wr && i < rw;
+                        const int ii = i < rw ? i : rw - 1;
+                        const uint32_t d = (uint32_t)ed[e0 + ii];
+                        const int k = d >> 16, c = d & 0xffffu;
+                        zi[u] = ok ? ((e0 + ii) * M + n) * F + f : spare;
+                        pi[u] = ok ? (k * M + rot_idx(n, c, M)) * F + f : N * F + spare;
+                    }
+#pragma unroll
+                    for (int u = G - 1; u >= 0; --u) {                              // the backward products of the group, last edge first
+                        const int i = g0 + u;
+                        sbn[u] = sb;
+                        const double P = 1 - 2 * Y[i];
+                        sb = P * sb;                                                // SB[i] = P[i] * SB[i + 1]
+                    }
+#pragma unroll
+                    for (int u = 0; u < G; ++u) {                                   // G independent chains again
+                        const int i = g0 + u;
+                        const double y = Y[i];
+                        double t = sbn[u];                                          // i == 0: (1 - SB[1]) / 2
+                        if (i > 0) t = SF[i > 0 ? i - 1 : 0] * sbn[u];                  // (1 - SF[i - 1] * SB[i + 1]) / 2
+                        double qv = (1 - t) / 2;
+                        if (qv < T) qv = T;                                         // :2703-2704
+                        if (qv > 1.0 - T) qv = 1.0 - T;
+                        q[u] = qv;
+                        gm[u] = y * qv / (1.0 - y - qv + 2 * y * qv);               // :2707-2720 gamma = rho + lambda
+                    }
+#pragma unroll
+                    for (int u = 0; u < G; ++u) { Z[zi[u]] = q[u]; post[pi[u]] = gm[u]; }
+                }
+            }
+            if (MW) __syncthreads();
+        }
+        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);           // :2723 (the value after the last layer)
+        ++steps;
+        if (!done && !frame_fail) { done = true; res = steps; }                     // else -steps = -maxiter at the end
+    }
+    // glob_outputs<1>: decword[k] = soft[k] > 0.5 (:2734), the a-posteriori probabilities as the soft output
+    if (!live) return;
+    if (n == 0 && a.iters) a.iters[fr] = res;
+    if (a.hard) {
+        for (int wd = n; wd < a.hard_words; wd += M) {
+            uint32_t bits = 0;
+            for (int b = 0; b < 32; ++b) {
+                const int v = 32 * wd + b;
+                if (v < N) bits |= (uint32_t)(post[v * F + f] > 0.5) << b;
+            }
+            a.hard[fr * a.hard_words + wd] = bits;
+        }
+    }
+    if (a.soft_out)
+        for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = post[(k * M + n) * F + f];
 }
 
 // ---------------------------------------------------------------------------------------------------------

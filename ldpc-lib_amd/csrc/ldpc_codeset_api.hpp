@@ -4,6 +4,7 @@
 
 struct ldpc_codeset_state {
     int C = 0;
+    int ne_max = 0;                    // the largest edge count of a code of the set
     std::vector<int32_t> off, tab;     // host copies of the device tables
     int32_t *d_off = nullptr, *d_tab = nullptr;
     // workspace of ldpc_hip_simulate_codes for w_frames frames per code
@@ -24,23 +25,33 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
 
 namespace {
 
+// Dynamic LDS of the code-set kernels.  MS / LMS: the a-posteriori values of F frames + the vote flag.  TDMP: the a-posteriori
+// probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.
+size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
+    const size_t per_frame = (size_t)nh * M + (decoder_id == LDPC_HIP_TASP_DEC ? (size_t)ne_max * M : 0);
+    return sizeof(double) * per_frame * (size_t)F + 16;
+}
+
 // Checks a code set and builds its table: per code row_start[rh+1] (relative to the code's own edge list) then edges[]
-// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].
+// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  The one place where
+// the limits of the three set kernels live.
 int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
-                  std::vector<int32_t> &tab) {
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", who, decoder_id);
+                  std::vector<int32_t> &tab, int *ne_max_out = nullptr) {
+    const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC;
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels keep %d block rows in registers", who, rh, kRHM);
+    if (rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
     if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
     const int F = M > 64 ? 1 : 64 / M;
-    if (sizeof(double) * (size_t)nh * M * F + 16 > 160 * 1024)
+    if (codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
     off.clear(); tab.clear();
     std::vector<char> col_used((size_t)nh);
+    int ne_max = 0;
     for (int c = 0; c < C; ++c) {
         const int16_t *h = hd + (size_t)c * rh * nh;
         if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh >= ((size_t)1 << 31))
@@ -63,11 +74,18 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
             }
             if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
             if (rw > kRWM) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
+            if (tdmp && rw < 2)   // map_bin reads SB[1] (decoders.cpp:2191-2228)
+                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; TDMP sum-product needs at least 2", who, c, j, rw);
         }
         tab[rs + rh] = ne;
+        ne_max = ne > ne_max ? ne : ne_max;
         for (int k = 0; k < nh; ++k)
             if (!col_used[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
     }
+    if (tdmp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB",
+                    who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
+    if (ne_max_out) *ne_max_out = ne_max;
     return 0;
 }
 
@@ -106,18 +124,23 @@ int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16
     return 0;
 }
 
-int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+}  // extern "C"
+
+namespace {
+
+int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     if (out) *out = nullptr;
-    if (!out) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: bad argument");
+    if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, off, tab)) return rc;
+    int ne_max = 0;
+    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: device %d of %d", device, ndev);
+    if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
     std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
     s->off.swap(off); s->tab.swap(tab);
-    s->C = C;
+    s->C = C; s->ne_max = ne_max;
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
     c->ne = (int)(s->tab.size() - (size_t)C * (rh + 1));   // edges of the whole set
@@ -125,8 +148,9 @@ int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
-    c->lds_bytes = sizeof(double) * (size_t)c->N * c->F + 16;
-    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : "lms_layered_codes_kernel") + (c->multiwave ? "<multiwave>" : "");
+    c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max);
+    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" : "tasp_layered_codes_kernel") +
+                     (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipMalloc(&s->d_off, sizeof(int32_t) * s->off.size()));
     HIP_TRY(hipMemcpy(s->d_off, s->off.data(), sizeof(int32_t) * s->off.size(), hipMemcpyHostToDevice));
@@ -135,6 +159,21 @@ int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd
     HIP_TRY(hipMalloc(&s->w_cnt, sizeof(unsigned long long) * 5 * (size_t)C));
     *out = c.release();
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP sets open through ldpc_hip_open_codes_tdmp
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", decoder_id);
+    return codeset_open("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    return codeset_open("ldpc_hip_open_codes_tdmp", LDPC_HIP_TASP_DEC, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_codes(const ldpc_hip_ctx *c) { return c && c->codes ? c->codes->C : 0; }
@@ -156,9 +195,11 @@ int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_l
     a.tab = s->d_tab; a.code_off = s->d_off;
     a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
     a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
-    a.alpha = alpha;
+    a.alpha = alpha; a.ne_max = s->ne_max;
     const void *k;
-    if (c->decoder_id == LDPC_HIP_MS_DEC)
+    if (c->decoder_id == LDPC_HIP_TASP_DEC)   // alpha is not read
+        k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
+    else if (c->decoder_id == LDPC_HIP_MS_DEC)
         k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
     else
         k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
@@ -221,7 +262,7 @@ int ldpc_hip_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks
     ch.llr = s->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
     ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
     ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = 0.5;   // bp_simulation.cpp:700 for the LLR-domain decoders
+    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
     for (long long done = 0; done < B; done += piece) {
         const long long nb = (B - done) < piece ? (B - done) : piece;
         ch.B = nb; ch.first_frame = first_frame + done;
