@@ -390,7 +390,8 @@ std::pair<double, double> bp_simulation_throughput_t(int q_mod, Mat const &H, in
 // that matrix alone with the same seed on one GPU (modulation SKIP, permutation_type 0, the all-zero codeword).  Every batch is
 // one ldpc_hip_simulate_codes call for the whole set (C codes x B frames in one launch, the LLRs drawn once); upstream's
 // sequential stopping rule (:591, :805-823) is replayed per code over its ordered records, and a code that has stopped ignores the
-// records of later batches.  decoder_type: MS_DEC, LMS_DEC or TASP_DEC (7, ldpc_hip_open_codes_tdmp).  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// records of later batches.  With show_process == 0 the whole run is one ldpc_hip_simulate_codes_stop call instead: the same rule on
+// the device, every launch over the codes still running, no records on the host; the results are the same integers.  decoder_type: MS_DEC, LMS_DEC or TASP_DEC (7, ldpc_hip_open_codes_tdmp).  counters_out: nse, nde and experiment per code (the [C][B] records carry
 // no iteration counts, so nue and sum_abs_iters stay 0).
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
@@ -416,10 +417,21 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
                                            : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
         Env::fail(ldpc_hip_last_error());
     std::vector<SimCounters> cnt((size_t)C);
+    if (!show_process) {   // nothing to print per error frame: the rule runs on the device
+        std::vector<unsigned long long> state((size_t)C * 4);
+        if (ldpc_hip_simulate_codes_stop(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, 0, n_frame_errors, n_experiments,
+                                         reference_frame_error, first_batch, max_batch, state.data()) != 0)
+            Env::fail(ldpc_hip_last_error());
+        for (int q = 0; q < C; ++q) {
+            cnt[(size_t)q].experiment = (long long)state[(size_t)q * 4];
+            cnt[(size_t)q].nse = (long long)state[(size_t)q * 4 + 1];
+            cnt[(size_t)q].nde = (long long)state[(size_t)q * 4 + 2];
+        }
+    }
     std::vector<char> running((size_t)C, 1);
     std::vector<unsigned long long> totals((size_t)C * 5);
     std::vector<int32_t> info;
-    int n_running = C;
+    int n_running = show_process ? C : 0;
     long long first = 0, batch = first_batch;
     while (n_running > 0) {
         // every running code has replayed the same number of frames so far: `first`

@@ -478,6 +478,22 @@ int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *ctx, const uint32_t *d_hard, c
  * want several streams in flight use ldpc_hip_decode_codes_dev / ldpc_hip_count_errors_codes_dev with buffers of their own. */
 int ldpc_hip_simulate_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed,
                             long long first_frame, long long B, unsigned long long *counters, int32_t *frame_info);
+/* A whole Monte-Carlo run of the set with upstream's stopping rule applied per code ON THE DEVICE (bp_simulation.cpp:591 and
+ * :805-823), in frame order: before each frame a code stops unless nde < n_frame_errors && experiment <= n_experiments; otherwise
+ * ++experiment, an error frame adds its wrong information bits to nse and 1 to nde, and the code stops if
+ * nde >= 10 && (double)nde / experiment > 2.5 * reference_frame_error (:820, checked at error frames only).  Frames come in batches
+ * of first_batch, then 4 times as many up to max_batch, capped by n_experiments + 1 - frames so far, over the noise of
+ * ldpc_hip_simulate_codes from first_frame on; a batch is worked off in the pieces of ldpc_hip_simulate_codes
+ * (LDPC_HIP_CODES_PIECE), and after every piece one wavefront per running code walks that code's ordered records.  Each decode
+ * launch covers only the codes still running; the host reads back their number and nothing else.
+ * state [C][4] (HOST, overwritten) = experiment, nse, nde, frames_decoded per code: the first three are what a frame-by-frame loop
+ * over the same noise gives, whatever the batches and pieces; frames_decoded counts every frame launched for the code (the sizes of
+ * the pieces up to the one in which it stopped).  n_frame_errors <= 0 or n_experiments < 0: nothing is decoded, state is zero.
+ * LDPC_HIP_EINVAL: not a code-set context, NULL state, first_frame < 0, first_batch < 1, max_batch < first_batch, maxiter < 1,
+ * punctured_blocks outside [0, nh).  Synchronous, one call at a time per context, on the null stream, as ldpc_hip_simulate_codes. */
+int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed,
+                                 long long first_frame, int n_frame_errors, long long n_experiments, double reference_frame_error,
+                                 long long first_batch, long long max_batch, unsigned long long *state);
 
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */

@@ -193,6 +193,7 @@ def load_library():
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
     lib.ldpc_hip_count_errors_codes_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_codes.argtypes = [vp, f64, i32, i32, f64, u64, i64, i64, vp, vp]
+    lib.ldpc_hip_simulate_codes_stop.argtypes = [vp, f64, i32, i32, f64, u64, i64, i32, i64, f64, i64, i64, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -741,6 +742,19 @@ class LdpcHipCodes:
                                               int(frames), cnt.ctypes.data, info.ctypes.data if info is not None else None)
         _check(self.lib, rc, "ldpc_hip_simulate_codes")
         return (cnt, info) if records else cnt
+
+    def simulate_until(self, snr_db, maxiter, seed, n_frame_errors, n_experiments, reference_frame_error, first_frame=0, first_batch=1024,
+                       max_batch=65536, punctured_blocks=0, alpha=0.8):
+        """A Monte-Carlo run of every code over the same noise with upstream's stopping rule applied per code on the device
+        (ldpc_hip_simulate_codes_stop): batches of first_batch frames, times 4 up to max_batch, each launch over the codes still
+        running.  Returns uint64 [C, 4] = experiment, nse, nde, frames_decoded per code; the first three are what
+        host.replay_stop_rule gives on the code's ordered records, frames_decoded counts the frames launched for it."""
+        state = np.zeros((self.C, 4), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_simulate_codes_stop(self.h, float(snr_db), int(punctured_blocks), int(maxiter), float(alpha), int(seed), int(first_frame),
+                                                   int(n_frame_errors), int(n_experiments), float(reference_frame_error), int(first_batch),
+                                                   int(max_batch), state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes_stop")
+        return state
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")

@@ -10,7 +10,9 @@
 //     index comes from blockIdx alone, so the table addresses are wave-uniform and the table loads stay scalar loads;
 //   * LLRs: shared [B][N] (llr_code_stride = 0: every code decodes the same B received words; the LLR traffic of C separate
 //     runs shrinks to 1/C and the frames of different codes hit the same lines in L2) or per code [C][B][N];
-//   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N].
+//   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N];
+//   * a launch may cover a subset of the codes: code_list[n_active] names the code of every slot blockIdx.x / blocks_per_code (null =
+//     the identity).  The graph table and the per-code LLR slice follow the code, the outputs follow the slot ([n_active][B]...).
 // The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel compute (fp64, reference operation order,
 // contraction off); only the frame index and the table base differ (and, for TDMP, where the state lives), so the results are
 // bit-identical to a single-code context.
@@ -28,6 +30,7 @@ struct CodesetArgs {
     double *soft_out;         // [C][B][N] or null
     const int32_t *tab;       // concatenated per-code tables
     const int32_t *code_off;  // [C] offset of code c's row_start[] in tab
+    const int32_t *code_list; // [grid / blocks_per_code] the code of every slot, or null: slot s decodes code s
     long long B;              // frames per code
     long long llr_code_stride;
     int blocks_per_code;      // ceil(B / F)
@@ -43,11 +46,12 @@ typedef const __attribute__((address_space(4))) int32_t *TabPtr;
 __device__ __forceinline__ TabPtr tab_ptr(const void *p) { return (TabPtr)(uintptr_t)p; }
 
 // The single-code argument block of work item (c, w): every pointer moved to code c's slice.  All values are functions of
-// blockIdx.x and kernel arguments only (wave-uniform).
+// blockIdx.x and kernel arguments only (wave-uniform); the list of codes is read like the table, so c stays in a scalar register.
 __device__ __forceinline__ DecArgs codeset_view(const CodesetArgs &s, int &w) {
-    const int c = blockIdx.x / s.blocks_per_code;
-    w = blockIdx.x - c * s.blocks_per_code;
-    const long long fo = (long long)c * s.B;   // first frame of code c in the [C][B] outputs
+    const int slot = blockIdx.x / s.blocks_per_code;
+    w = blockIdx.x - slot * s.blocks_per_code;
+    const int c = s.code_list ? tab_ptr(s.code_list)[slot] : slot;
+    const long long fo = (long long)slot * s.B;   // first frame of the slot in the [n_active][B] outputs
     DecArgs a{};
     a.llr = s.llr + (long long)c * s.llr_code_stride;
     a.hard = s.hard ? s.hard + fo * s.hard_words : nullptr;
@@ -459,10 +463,11 @@ __global__ void __launch_bounds__(MW ? 512 : 64) tasp_layered_codes_kernel(const
 // 805-810) per code: one wavefront per (c, f); a workgroup works on one code only, so its totals go out as one atomic per counter.
 // ---------------------------------------------------------------------------------------------------------
 struct CodesetCountArgs {
-    const uint32_t *hard;          // [C][B][hard_words]
-    const int32_t *iters;          // [C][B]
-    int32_t *frame_info;           // [C][B] or null
-    unsigned long long *counters;  // [C][5]: nse, nde, nue, frames, sum |iters|
+    const uint32_t *hard;          // [n_active][B][hard_words]
+    const int32_t *iters;          // [n_active][B]
+    int32_t *frame_info;           // [n_active][B] or null
+    unsigned long long *counters;  // [C][5]: nse, nde, nue, frames, sum |iters|; the row of a slot is its code's
+    const int32_t *code_list;      // [n_active] or null (slot s holds code s), as in CodesetArgs
     long long B;
     int blocks_per_code;
     int hard_words, R;
@@ -471,10 +476,11 @@ struct CodesetCountArgs {
 __global__ void __launch_bounds__(256) count_errors_codes_kernel(const CodesetCountArgs a) {
     __shared__ unsigned long long part[4][5];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int c = blockIdx.x / a.blocks_per_code, slot = blockIdx.x - c * a.blocks_per_code;
+    const int cs = blockIdx.x / a.blocks_per_code, slot = blockIdx.x - cs * a.blocks_per_code;
+    const int c = a.code_list ? tab_ptr(a.code_list)[cs] : cs;
     unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
     for (long long fr = (long long)slot * 4 + wv; fr < a.B; fr += (long long)a.blocks_per_code * 4) {
-        const long long g = (long long)c * a.B + fr;
+        const long long g = (long long)cs * a.B + fr;
         uint32_t all = 0, info = 0;
         for (int w = lane; w < a.hard_words; w += 64) {
             const uint32_t x = a.hard[g * a.hard_words + w];
@@ -508,6 +514,86 @@ __global__ void __launch_bounds__(256) count_errors_codes_kernel(const CodesetCo
         const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
         if (t) atomicAdd(&a.counters[(size_t)c * 5 + threadIdx.x], t);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Upstream's sequential stopping rule (bp_simulation.cpp:591, :805-823) over the ordered records of one piece, one wavefront per
+// running slot.  Per code and frame, in frame order:
+//     stop unless nde < n_frame_errors && experiment <= n_experiments;  ++experiment;
+//     a non-zero record:  nse += record & (2^30 - 1), ++nde, stop if nde >= 10 && (double)nde / experiment > 2.5 * reference_frame_error.
+// 64 frames per step: the error flags are one ballot, so lane l knows the nde it would see (the carry + the errors below it) and the
+// experiment it would see (the carry + l) if no frame before it stopped the run, and evaluates both conditions for its own frame;
+// the first lane whose frame stops the run is exact (nothing stopped before it), and it is the find-first-set of the ballot of stop
+// flags.  Frames behind the stop do not reach the state.  frames_decoded grows by B: the piece was decoded for this code.
+// ---------------------------------------------------------------------------------------------------------
+struct CodesetRuleArgs {
+    const int32_t *frame_info;     // [n_active][B]
+    const int32_t *code_list;      // [n_active]
+    unsigned long long *state;     // [C][4]: experiment, nse, nde, frames_decoded
+    int32_t *running;              // [C]: cleared when the code stops
+    long long B;
+    long long n_frame_errors, n_experiments;
+    double reference_frame_error;
+};
+
+__global__ void __launch_bounds__(64) stop_rule_codes_kernel(const CodesetRuleArgs a) {
+    const int lane = threadIdx.x;
+    const int code = tab_ptr(a.code_list)[blockIdx.x];
+    const int32_t *const rec = a.frame_info + (long long)blockIdx.x * a.B;
+    unsigned long long *const st = a.state + 4 * (size_t)code;
+    long long experiment = (long long)st[0], nde = (long long)st[2];
+    unsigned long long nse = st[1];
+    const double thr = 2.5 * a.reference_frame_error;
+    const unsigned long long below = (1ull << lane) - 1;
+    bool stopped = false;
+    for (long long base = 0; base < a.B && !stopped; base += 64) {
+        const bool act = base + lane < a.B;
+        const int32_t r = act ? rec[base + lane] : 0;
+        const bool err = r != 0;                                                     // bit 30: any wrong bit (:805)
+        const unsigned long long em = __ballot(err);
+        const long long d0 = nde + __popcll(em & below);                             // nde and experiment before this lane's frame
+        const long long e0 = experiment + lane;
+        const bool pre = act && !(d0 < a.n_frame_errors && e0 <= a.n_experiments);   // :591, the frame is not consumed
+        const long long d1 = d0 + 1, e1 = e0 + 1;
+        const bool post = act && !pre && err && d1 >= 10 && (double)d1 / (double)e1 > thr;   // :820, the frame is consumed
+        const unsigned long long pm = __ballot(pre), sm = __ballot(pre || post);
+        const long long left = a.B - base;
+        int n = left < 64 ? (int)left : 64;                                          // frames of this step that reach the state
+        if (sm) {
+            const int p = __ffsll((long long)sm) - 1;
+            n = p + (((pm >> p) & 1ull) ? 0 : 1);
+            stopped = true;
+        }
+        const unsigned long long take = n >= 64 ? ~0ull : (1ull << n) - 1;
+        experiment += n;
+        if (em & take) {
+            nde += __popcll(em & take);
+            unsigned long long s = lane < n ? (unsigned long long)(r & ((1 << 30) - 1)) : 0ull;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            nse += s;
+        }
+    }
+    if (!(nde < a.n_frame_errors && experiment <= a.n_experiments)) stopped = true;   // :591 fails before the next frame
+    if (lane == 0) {
+        st[0] = (unsigned long long)experiment; st[1] = nse; st[2] = (unsigned long long)nde; st[3] += (unsigned long long)a.B;
+        if (stopped) a.running[code] = 0;
+    }
+}
+
+// The codes still running, in ascending order, and their number: one wavefront, 64 codes per step.
+__global__ void __launch_bounds__(64) running_codes_kernel(const int32_t *running, int C, int32_t *code_list, int32_t *n_active) {
+    const int lane = threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1;
+    int n = 0;
+    for (int base = 0; base < C; base += 64) {
+        const int c = base + lane;
+        const bool on = c < C && running[c] != 0;
+        const unsigned long long m = __ballot(on);
+        if (on) code_list[n + __popcll(m & below)] = c;
+        n += __popcll(m);
+    }
+    if (lane == 0) *n_active = n;
 }
 
 }  // namespace ldpc

@@ -13,11 +13,15 @@ struct ldpc_codeset_state {
     int32_t *w_iters = nullptr, *w_info = nullptr;   // [C][w_frames]
     unsigned long long *w_cnt = nullptr;             // [C][5]
     long long w_frames = 0;
+    // ldpc_hip_simulate_codes_stop: the per-code state of the stopping rule and the list of the codes still running
+    unsigned long long *w_rule = nullptr;            // [C][4]: experiment, nse, nde, frames_decoded
+    int32_t *w_running = nullptr, *w_list = nullptr; // [C] each
+    int32_t *w_nactive = nullptr;                    // [1]
 };
 
 void ldpc_codeset_release(ldpc_codeset_state *s) {
     if (!s) return;
-    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt};
+    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt, s->w_rule, s->w_running, s->w_list, s->w_nactive};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     delete s;
@@ -94,13 +98,14 @@ int codeset_ctx(const ldpc_hip_ctx *c, const char *who) {
     return 0;
 }
 
+// code_list / n_slots: the codes of the [n_slots][B] inputs (null: all C codes in order), see ldpc_codeset.hpp
 int codeset_count_launch(const ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
-                         unsigned long long *d_counters, hipStream_t stream) {
-    const int C = c->codes->C;
+                         unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0) {
+    const int C = code_list ? n_slots : c->codes->C;
     long long bpc = (B + 3) / 4;            // workgroups per code: four frames (waves) each, fewer when there are many codes
     const long long cap = 2048 / C > 1 ? 2048 / C : 1;
     if (bpc > cap) bpc = cap;
-    ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, B, (int)bpc, c->hard_words, c->R};
+    ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, code_list, B, (int)bpc, c->hard_words, c->R};
     hipLaunchKernelGGL(ldpc::count_errors_codes_kernel, dim3((unsigned)(bpc * C)), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -161,6 +166,96 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     return 0;
 }
 
+// The decode launch over n_slots codes: code_list [n_slots] (DEVICE) names them, null = all C codes in order.  Outputs [n_slots][B]...
+int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
+                          int32_t *d_iters, double *d_soft, hipStream_t stream, const int32_t *code_list, int n_slots) {
+    if (B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: bad argument");
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
+    if (B == 0) return 0;
+    if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
+    const ldpc_codeset_state *s = c->codes;
+    if (!code_list) n_slots = s->C;
+    if (n_slots < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: a launch covers at least one code");   // never a grid of 0 blocks
+    const long long bpc = (B + c->F - 1) / c->F;
+    if (bpc * n_slots > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %d codes x %lld frames is more than one launch takes", n_slots, B);
+    HIP_TRY(hipSetDevice(c->device));
+    ldpc::CodesetArgs a{};
+    a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.soft_out = d_soft;
+    a.tab = s->d_tab; a.code_off = s->d_off; a.code_list = code_list;
+    a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
+    a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
+    a.alpha = alpha; a.ne_max = s->ne_max;
+    const void *k;
+    if (c->decoder_id == LDPC_HIP_TASP_DEC)   // alpha is not read
+        k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
+    else if (c->decoder_id == LDPC_HIP_MS_DEC)
+        k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
+    else
+        k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
+    if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (c->prof) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+    }
+    void *kargs[] = {&a};
+    c->last_launch = c->kernel_name.c_str();
+    HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * n_slots)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
+    HIP_TRY(hipGetLastError());
+    if (c->prof) {
+        HIP_TRY(hipEventRecord(ev1, stream));
+        c->events.emplace_back(ev0, ev1);
+    }
+    return 0;
+}
+
+// Frames per piece of the simulate entry points: at most 65536, the [C][piece] outputs within 1 GiB, LDPC_HIP_CODES_PIECE=n caps it.
+long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
+    const size_t C = (size_t)c->codes->C;
+    const size_t per_frame = C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
+    long long piece = (long long)(((size_t)1 << 30) / per_frame);
+    piece = piece > (1 << 16) ? (1 << 16) : (piece < 1 ? 1 : piece);
+    if (const char *e = getenv("LDPC_HIP_CODES_PIECE")) { if (atoll(e) > 0 && atoll(e) < piece) piece = atoll(e); }
+    return piece > B ? B : piece;
+}
+
+// The context's workspace for `piece` frames per code (grown, never shrunk).
+int codeset_reserve(ldpc_hip_ctx *c, long long piece) {
+    ldpc_codeset_state *s = c->codes;
+    const size_t C = (size_t)s->C;
+    if (piece > s->w_frames) {
+        void *old[] = {s->w_llr, s->w_hard, s->w_iters, s->w_info};
+        for (void *p : old)
+            if (p) (void)hipFree(p);
+        s->w_llr = nullptr; s->w_hard = nullptr; s->w_iters = nullptr; s->w_info = nullptr; s->w_frames = 0;
+        HIP_TRY(hipMalloc(&s->w_llr, sizeof(double) * (size_t)piece * c->N));
+        HIP_TRY(hipMalloc(&s->w_hard, sizeof(uint32_t) * C * (size_t)piece * c->hard_words));
+        HIP_TRY(hipMalloc(&s->w_iters, sizeof(int32_t) * C * (size_t)piece));
+        HIP_TRY(hipMalloc(&s->w_info, sizeof(int32_t) * C * (size_t)piece));
+        s->w_frames = piece;
+    }
+    return 0;
+}
+
+// The channel of ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word for the simulate entry points: noise keyed by
+// (seed, global frame, position), written to the workspace's [piece][N] LLRs (after codeset_reserve).  sigma is the caller's.
+void codeset_channel_args(const ldpc_hip_ctx *c, int punctured_blocks, uint64_t seed, ldpc::ChannelArgs &ch) {
+    ch.llr = c->codes->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
+    ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
+    ch.punct_start = c->N - c->M * punctured_blocks;
+    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+}
+
+int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long long first_frame, long long nb) {
+    ch.B = nb; ch.first_frame = first_frame;
+    long long blocks = (nb * (long long)((c->N + 1) / 2) + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(ldpc::channel_llr_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, nullptr, ch);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,44 +276,7 @@ int ldpc_hip_codes(const ldpc_hip_ctx *c) { return c && c->codes ? c->codes->C :
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
                               int32_t *d_iters, double *d_soft, void *stream_) {
     if (int rc = codeset_ctx(c, "ldpc_hip_decode_codes_dev")) return rc;
-    if (B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: bad argument");
-    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
-    if (B == 0) return 0;
-    if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
-    const ldpc_codeset_state *s = c->codes;
-    const long long bpc = (B + c->F - 1) / c->F;
-    if (bpc * s->C > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %d codes x %lld frames is more than one launch takes", s->C, B);
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    ldpc::CodesetArgs a{};
-    a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.soft_out = d_soft;
-    a.tab = s->d_tab; a.code_off = s->d_off;
-    a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
-    a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
-    a.alpha = alpha; a.ne_max = s->ne_max;
-    const void *k;
-    if (c->decoder_id == LDPC_HIP_TASP_DEC)   // alpha is not read
-        k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
-    else if (c->decoder_id == LDPC_HIP_MS_DEC)
-        k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
-    else
-        k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
-    if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->prof) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
-    void *kargs[] = {&a};
-    c->last_launch = c->kernel_name.c_str();
-    HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * s->C)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
-    HIP_TRY(hipGetLastError());
-    if (c->prof) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        c->events.emplace_back(ev0, ev1);
-    }
-    return 0;
+    return codeset_decode_launch(c, d_llr, shared_llr, B, maxiter, alpha, d_hard, d_iters, d_soft, (hipStream_t)stream_, nullptr, 0);
 }
 
 int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
@@ -240,36 +298,13 @@ int ldpc_hip_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks
     ldpc::ChannelArgs ch{};
     if (int rc = awgn_sigma(c, snr_db, 0, punctured_blocks, &ch.sigma)) return rc;   // the common rate (nh - rh) / (nh - punctured_blocks)
     HIP_TRY(hipSetDevice(c->device));
-    // frames per piece: at most 65536, and the [C][piece] outputs within 1 GiB
-    const size_t per_frame = C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
-    long long piece = (long long)(((size_t)1 << 30) / per_frame);
-    piece = piece > (1 << 16) ? (1 << 16) : (piece < 1 ? 1 : piece);
-    if (const char *e = getenv("LDPC_HIP_CODES_PIECE")) { if (atoll(e) > 0 && atoll(e) < piece) piece = atoll(e); }
-    if (piece > B) piece = B;
-    if (piece > s->w_frames) {
-        void *old[] = {s->w_llr, s->w_hard, s->w_iters, s->w_info};
-        for (void *p : old)
-            if (p) (void)hipFree(p);
-        s->w_llr = nullptr; s->w_hard = nullptr; s->w_iters = nullptr; s->w_info = nullptr; s->w_frames = 0;
-        HIP_TRY(hipMalloc(&s->w_llr, sizeof(double) * (size_t)piece * c->N));
-        HIP_TRY(hipMalloc(&s->w_hard, sizeof(uint32_t) * C * (size_t)piece * c->hard_words));
-        HIP_TRY(hipMalloc(&s->w_iters, sizeof(int32_t) * C * (size_t)piece));
-        HIP_TRY(hipMalloc(&s->w_info, sizeof(int32_t) * C * (size_t)piece));
-        s->w_frames = piece;
-    }
+    const long long piece = codeset_piece(c, B);
+    if (int rc = codeset_reserve(c, piece)) return rc;
     HIP_TRY(hipMemsetAsync(s->w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
-    // the channel of ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word: noise keyed by (seed, global frame, position)
-    ch.llr = s->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
-    ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
-    ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+    codeset_channel_args(c, punctured_blocks, seed, ch);
     for (long long done = 0; done < B; done += piece) {
         const long long nb = (B - done) < piece ? (B - done) : piece;
-        ch.B = nb; ch.first_frame = first_frame + done;
-        long long blocks = (nb * (long long)((c->N + 1) / 2) + 255) / 256;
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL(ldpc::channel_llr_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, nullptr, ch);
-        HIP_TRY(hipGetLastError());
+        if (int rc = codeset_channel_launch(c, ch, first_frame + done, nb)) return rc;
         if (int rc = ldpc_hip_decode_codes_dev(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr)) return rc;
         if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, frame_info ? s->w_info : nullptr, s->w_cnt, nullptr)) return rc;
         if (frame_info)   // [C][nb] on the device -> columns [done, done + nb) of the caller's [C][B]
@@ -277,6 +312,61 @@ int ldpc_hip_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks
                                 hipMemcpyDeviceToHost));
     }
     HIP_TRY(hipMemcpy(counters, s->w_cnt, sizeof(unsigned long long) * 5 * C, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed, long long first_frame,
+                                 int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
+                                 long long max_batch, unsigned long long *state) {
+    if (int rc = codeset_ctx(c, "ldpc_hip_simulate_codes_stop")) return rc;
+    if (!state || first_frame < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: bad argument");
+    if (first_batch < 1 || max_batch < first_batch)
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: batches of %lld .. %lld frames; 1 <= first_batch <= max_batch", first_batch, max_batch);
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: maxiter must be >= 1 (got %d)", maxiter);
+    ldpc_codeset_state *s = c->codes;
+    const size_t C = (size_t)s->C;
+    ldpc::ChannelArgs ch{};
+    if (int rc = awgn_sigma(c, snr_db, 0, punctured_blocks, &ch.sigma)) return rc;   // the common rate (nh - rh) / (nh - punctured_blocks)
+    std::memset(state, 0, sizeof(unsigned long long) * 4 * C);
+    if (n_frame_errors <= 0 || n_experiments < 0) return 0;   // :591 fails before the first frame
+    HIP_TRY(hipSetDevice(c->device));
+    const long long piece = codeset_piece(c, max_batch < n_experiments + 1 ? max_batch : n_experiments + 1);
+    if (int rc = codeset_reserve(c, piece)) return rc;
+    if (!s->w_rule) {
+        HIP_TRY(hipMalloc(&s->w_rule, sizeof(unsigned long long) * 4 * C));
+        HIP_TRY(hipMalloc(&s->w_running, sizeof(int32_t) * C));
+        HIP_TRY(hipMalloc(&s->w_list, sizeof(int32_t) * C));
+        HIP_TRY(hipMalloc(&s->w_nactive, sizeof(int32_t)));
+    }
+    std::vector<int32_t> ident(C), ones(C, 1);
+    for (size_t q = 0; q < C; ++q) ident[q] = (int32_t)q;
+    HIP_TRY(hipMemcpy(s->w_list, ident.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->w_running, ones.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(s->w_rule, 0, sizeof(unsigned long long) * 4 * C, nullptr));
+    HIP_TRY(hipMemsetAsync(s->w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
+    codeset_channel_args(c, punctured_blocks, seed, ch);
+    int32_t n_active = (int32_t)C;
+    long long first = 0, batch = first_batch;   // every running code has consumed the same number of frames: `first`
+    while (n_active > 0) {
+        const long long room = n_experiments + 1 - first;
+        const long long B = batch < room ? batch : room;
+        if (B <= 0) break;
+        for (long long done = 0; done < B && n_active > 0; done += piece) {
+            const long long nb = (B - done) < piece ? (B - done) : piece;
+            if (int rc = codeset_channel_launch(c, ch, first_frame + first + done, nb)) return rc;
+            if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, s->w_list, n_active)) return rc;
+            if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, s->w_info, s->w_cnt, nullptr, s->w_list, n_active)) return rc;
+            const ldpc::CodesetRuleArgs ra{s->w_info, s->w_list, s->w_rule, s->w_running, nb, n_frame_errors, n_experiments, reference_frame_error};
+            hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, s->w_running, (int)C, s->w_list, s->w_nactive);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&n_active, s->w_nactive, sizeof(int32_t), hipMemcpyDeviceToHost));   // the one value the host needs per piece
+        }
+        first += B;
+        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+    }
+    HIP_TRY(hipMemcpy(state, s->w_rule, sizeof(unsigned long long) * 4 * C, hipMemcpyDeviceToHost));
     return 0;
 }
 

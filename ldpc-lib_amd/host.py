@@ -31,6 +31,24 @@ def relift_base_matrix(H, M):
     return H
 
 
+def replay_stop_rule(records, n_frame_errors, n_experiments, reference_frame_error):
+    """The stopping rule of bp_simulation.cpp:591 and :805-823 over ONE code's ordered frame_info records (LdpcHipCodes.simulate with
+    records=True), frame by frame as upstream's loop runs it.  Returns (experiment, nse, nde) as Python ints: what
+    LdpcHipCodes.simulate_until reports for the code when the records cover the frames it consumes (n_experiments + 1 always do)."""
+    experiment = nse = nde = 0
+    for rec in records:
+        if not (nde < n_frame_errors and experiment <= n_experiments):   # :591
+            break
+        experiment += 1
+        rec = int(rec)
+        if rec != 0:                                                     # bit 30: any wrong bit (:805)
+            nse += rec & ((1 << 30) - 1)                                 # :807
+            nde += 1                                                     # :808
+            if nde >= 10 and float(nde) / float(experiment) > 2.5 * reference_frame_error:   # :820, two doubles
+                break
+    return experiment, nse, nde
+
+
 def replay_stopping_rule(frame_info, iters, state, n_frame_errors, n_experiments, reference_frame_error):
     """Apply the frame loop of bp_simulation.cpp:591-823 to one ordered batch of per-frame records.
 
