@@ -385,6 +385,66 @@ std::pair<double, double> bp_simulation_throughput_t(int q_mod, Mat const &H, in
     return std::make_pair((double)nse / experiment / (double)(n - r), (double)nde / experiment);
 }
 
+// The run of an opened code-set context, binary or GF(q): stop(state [C][4]) is the context's *_stop call (the rule on the device),
+// simulate(first, B, totals [C][5], info [C][B]) its simulate call over frames [first, first + B).  show_process == 0 takes the first
+// route, anything else the per-batch loop with the rule replayed on the host and a line per error frame.  info_len: the divisor of
+// the error rate, information bits (or symbols) per frame.
+template <class Env, class Stop, class Simulate>
+std::vector<std::pair<double, double>> run_code_set(int C, long long info_len, int n_frame_errors, long long n_experiments, double snr,
+                                                    double reference_frame_error, int show_process, long long first_batch, long long max_batch,
+                                                    Stop stop_route, Simulate simulate, std::vector<SimCounters> *counters_out) {
+    std::vector<SimCounters> cnt((size_t)C);
+    if (!show_process) {   // nothing to print per error frame: the rule runs on the device
+        std::vector<unsigned long long> state((size_t)C * 4);
+        if (stop_route(state.data()) != 0) Env::fail(ldpc_hip_last_error());
+        for (int q = 0; q < C; ++q) {
+            cnt[(size_t)q].experiment = (long long)state[(size_t)q * 4];
+            cnt[(size_t)q].nse = (long long)state[(size_t)q * 4 + 1];
+            cnt[(size_t)q].nde = (long long)state[(size_t)q * 4 + 2];
+        }
+    }
+    std::vector<char> running((size_t)C, 1);
+    std::vector<unsigned long long> totals((size_t)C * 5);
+    std::vector<int32_t> info;
+    int n_running = show_process ? C : 0;
+    long long first = 0, batch = first_batch;
+    while (n_running > 0) {
+        // every running code has replayed the same number of frames so far: `first`
+        const long long room = n_experiments + 1 - first;
+        const long long B = batch < room ? batch : room;
+        if (B <= 0) break;
+        info.resize((size_t)C * (size_t)B);
+        if (simulate(first, B, totals.data(), info.data()) != 0) Env::fail(ldpc_hip_last_error());
+        for (int q = 0; q < C; ++q) {
+            if (!running[(size_t)q]) continue;
+            SimCounters &k = cnt[(size_t)q];
+            const int32_t *rec = info.data() + (size_t)q * (size_t)B;
+            bool stop = false;
+            for (long long f = 0; f < B; ++f) {                                                  // ordered replay of :591-823
+                if (!(k.nde < n_frame_errors && k.experiment <= n_experiments)) { stop = true; break; }
+                ++k.experiment;
+                if (rec[f] != 0) {                                                               // bit 30: any wrong bit (:805)
+                    k.nse += rec[f] & ((1 << 30) - 1); ++k.nde;
+                    if (show_process)
+                        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse,
+                               (int)k.nde, (double)k.nse / k.experiment / (double)info_len, (double)k.nde / k.experiment);
+                    if (k.nde >= 10 && (double)k.nde / k.experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
+                }
+            }
+            if (stop || !(k.nde < n_frame_errors && k.experiment <= n_experiments)) { running[(size_t)q] = 0; --n_running; }
+        }
+        first += B;
+        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+    }
+    std::vector<std::pair<double, double>> out((size_t)C);
+    for (int q = 0; q < C; ++q)
+        out[(size_t)q] = std::make_pair((double)cnt[(size_t)q].nse / cnt[(size_t)q].experiment / (double)info_len,
+                                        (double)cnt[(size_t)q].nde / cnt[(size_t)q].experiment);
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+
 // A set of candidate codes of one shape over the SAME noise, in throughput mode: what a code search does when it calls
 // reset_random() before every candidate.  One pair <BER, FER> per code, each equal to what bp_simulation_throughput_t returns for
 // that matrix alone with the same seed on one GPU (modulation SKIP, permutation_type 0, the all-zero codeword).  Every batch is
@@ -416,59 +476,76 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
     if ((decoder_type == LDPC_HIP_TASP_DEC ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
                                            : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
         Env::fail(ldpc_hip_last_error());
-    std::vector<SimCounters> cnt((size_t)C);
-    if (!show_process) {   // nothing to print per error frame: the rule runs on the device
-        std::vector<unsigned long long> state((size_t)C * 4);
-        if (ldpc_hip_simulate_codes_stop(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, 0, n_frame_errors, n_experiments,
-                                         reference_frame_error, first_batch, max_batch, state.data()) != 0)
-            Env::fail(ldpc_hip_last_error());
-        for (int q = 0; q < C; ++q) {
-            cnt[(size_t)q].experiment = (long long)state[(size_t)q * 4];
-            cnt[(size_t)q].nse = (long long)state[(size_t)q * 4 + 1];
-            cnt[(size_t)q].nde = (long long)state[(size_t)q * 4 + 2];
-        }
-    }
-    std::vector<char> running((size_t)C, 1);
-    std::vector<unsigned long long> totals((size_t)C * 5);
-    std::vector<int32_t> info;
-    int n_running = show_process ? C : 0;
-    long long first = 0, batch = first_batch;
-    while (n_running > 0) {
-        // every running code has replayed the same number of frames so far: `first`
-        const long long room = n_experiments + 1 - first;
-        const long long B = batch < room ? batch : room;
-        if (B <= 0) break;
-        info.resize((size_t)C * (size_t)B);
-        if (ldpc_hip_simulate_codes(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, first, B, totals.data(), info.data()) != 0)
-            Env::fail(ldpc_hip_last_error());
-        for (int q = 0; q < C; ++q) {
-            if (!running[(size_t)q]) continue;
-            SimCounters &k = cnt[(size_t)q];
-            const int32_t *rec = info.data() + (size_t)q * (size_t)B;
-            bool stop = false;
-            for (long long f = 0; f < B; ++f) {                                                  // ordered replay of :591-823
-                if (!(k.nde < n_frame_errors && k.experiment <= n_experiments)) { stop = true; break; }
-                ++k.experiment;
-                if (rec[f] != 0) {                                                               // bit 30: any wrong bit (:805)
-                    k.nse += rec[f] & ((1 << 30) - 1); ++k.nde;
-                    if (show_process)
-                        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse,
-                               (int)k.nde, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
-                    if (k.nde >= 10 && (double)k.nde / k.experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
-                }
-            }
-            if (stop || !(k.nde < n_frame_errors && k.experiment <= n_experiments)) { running[(size_t)q] = 0; --n_running; }
-        }
-        first += B;
-        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
-    }
+    const auto out = run_code_set<Env>(
+        C, n - r, n_frame_errors, n_experiments, snr, reference_frame_error, show_process, first_batch, max_batch,
+        [&](unsigned long long *state) {
+            return ldpc_hip_simulate_codes_stop(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, 0, n_frame_errors, n_experiments,
+                                                reference_frame_error, first_batch, max_batch, state);
+        },
+        [&](long long first, long long B, unsigned long long *totals, int32_t *info) {
+            return ldpc_hip_simulate_codes(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, first, B, totals, info);
+        },
+        counters_out);
     ldpc_hip_close(ctx);
-    std::vector<std::pair<double, double>> out((size_t)C);
-    for (int q = 0; q < C; ++q)
-        out[(size_t)q] = std::make_pair((double)cnt[(size_t)q].nse / cnt[(size_t)q].experiment / (double)(n - r),
-                                        (double)cnt[(size_t)q].nde / cnt[(size_t)q].experiment);
-    if (counters_out) *counters_out = cnt;
     return out;
+}
+
+// The same for a set of candidate codes over GF(q), q = q_mod = 2^p (FHT_DEC): what upstream's ggp search does when it scores every
+// candidate of one pattern with bp_simulation(q_mod, HM, HC, ...) after reset_random() (search_ggp/scenario_based_code_generation.cpp:
+// 692-940).  codes[c] holds the shifts and coefs[c] the coefficients (natural representation, ncols2convert = 0) of candidate c; the
+// matrices are taken as given -- left2right, which upstream's bp_simulation applies to both, is the caller's, as with ldpc_hip_open_gfq.
+// One pair <SER, FER> per code: symbol errors at the information positions per frame and information symbol, and frame errors per
+// frame, each equal to what a frame-by-frame run of ldpc_hip_simulate_gfq (random_messages = 0) gives for that code alone under the
+// same rule.  show_process == 0 is one ldpc_hip_simulate_codes_gfq_stop call; otherwise ldpc_hip_simulate_codes_gfq per batch with the
+// rule replayed on the host.  bp_simulation() itself keeps failing for q_mod > 2: a single GF(q) code is not built in this layer.
+template <class Mat, class Env>
+std::vector<std::pair<double, double>> bp_simulation_codes_gfq_t(int q_mod, std::vector<Mat> const &codes, std::vector<Mat> const &coefs,
+                                                                 int tailbite_length, int max_iterations, int n_frame_errors,
+                                                                 long long n_experiments, double snr, double reference_frame_error,
+                                                                 int show_process, unsigned long long seed, int device = 0,
+                                                                 std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                                 long long max_batch = 65536) {
+    if (codes.empty() || codes.size() != coefs.size()) Env::fail("bp_simulation_codes_gfq: empty code set, or not one coefficient matrix per code");
+    if (first_batch < 1 || max_batch < first_batch) Env::fail("bp_simulation_codes_gfq: bad batch sizes");
+    int q_bits = 0;
+    while ((1 << q_bits) < q_mod) ++q_bits;
+    if (q_mod < 4 || (1 << q_bits) != q_mod) Env::fail("bp_simulation_codes_gfq: q_mod is a power of two, at least 4 (binary sets: bp_simulation_codes)");
+    const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols(), M = tailbite_length;
+    const long long r = (long long)b * M, n = (long long)c * M;
+    std::vector<int16_t> hb((size_t)C * b * c), hc((size_t)C * b * c);
+    for (int q = 0; q < C; ++q) {
+        if (codes[(size_t)q].n_rows() != b || codes[(size_t)q].n_cols() != c || coefs[(size_t)q].n_rows() != b || coefs[(size_t)q].n_cols() != c)
+            Env::fail("bp_simulation_codes_gfq: the codes of a set share one shape");
+        for (int i = 0; i < b; ++i)
+            for (int j = 0; j < c; ++j) {
+                hb[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
+                hc[((size_t)q * b + i) * c + j] = (int16_t)coefs[(size_t)q](i, j);
+            }
+    }
+    ldpc_hip_ctx *ctx = nullptr;
+    if (ldpc_hip_open_codes_gfq(q_bits, b, c, M, hb.data(), hc.data(), C, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());
+    const auto out = run_code_set<Env>(
+        C, n - r, n_frame_errors, n_experiments, snr, reference_frame_error, show_process, first_batch, max_batch,
+        [&](unsigned long long *state) {
+            return ldpc_hip_simulate_codes_gfq_stop(ctx, snr, max_iterations, seed, 0, n_frame_errors, n_experiments, reference_frame_error, first_batch,
+                                                    max_batch, state);
+        },
+        [&](long long first, long long B, unsigned long long *totals, int32_t *info) {
+            return ldpc_hip_simulate_codes_gfq(ctx, snr, max_iterations, seed, first, B, totals, info);
+        },
+        counters_out);
+    ldpc_hip_close(ctx);
+    return out;
+}
+
+inline std::vector<std::pair<double, double>> bp_simulation_codes_gfq(int q_mod, std::vector<Matrix> const &codes, std::vector<Matrix> const &coefs,
+                                                                      int tailbite_length, int max_iterations, int n_frame_errors, int n_experiments,
+                                                                      double snr, double reference_frame_error, int show_process,
+                                                                      unsigned long long seed = 1, int device = 0,
+                                                                      std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                                      long long max_batch = 65536) {
+    return bp_simulation_codes_gfq_t<Matrix, OwnRngEnv>(q_mod, codes, coefs, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr,
+                                                        reference_frame_error, show_process, seed, device, counters_out, first_batch, max_batch);
 }
 
 // the standalone form: ldpc::Matrix, same tail as bp_simulation() plus the Philox seed

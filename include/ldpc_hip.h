@@ -495,6 +495,56 @@ int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured
                                  long long first_frame, int n_frame_errors, long long n_experiments, double reference_frame_error,
                                  long long first_batch, long long max_batch, unsigned long long *state);
 
+/* ---- GF(q) code sets: C candidate codes over GF(q) of one shape x B frames in one launch (csrc/ldpc_gfq_codeset.hpp) ----------------
+ * What upstream's second search driver does (search_ggp/scenario_based_code_generation.cpp:692-940): every candidate comes from one
+ * pattern and differs in the shifts and, for q_mod > 2, in the coefficients; reset_random() before each one gives all of them the same
+ * noise, and bp_simulation(q_mod, HM, HC, ...) scores it with FHT_DEC.  hb [C][rh][nh] and hc [C][rh][nh]: the C candidates one after
+ * the other, with the conventions of ldpc_hip_open_gfq (shifts reduced mod M, -1 = empty circulant, hc is not read there; natural
+ * representation, ncols2convert = 0).  The patterns may differ between the codes.  Results are bit-identical to a context opened with
+ * ldpc_hip_open_gfq on the same pair of matrices, whatever mixture of column weights the set holds.
+ * LDPC_HIP_EUNSUPPORTED, as ldpc_hip_open_gfq per code: a block row of weight < 2 or > 1024, q_bits outside 2 .. 10, a coefficient 0
+ * on a non-empty circulant, M, rh or nh >= 65536; LDPC_HIP_EINVAL: C < 1, a non-positive size, a shift below -1, a coefficient
+ * outside GF(q).  The message names the code and the row or position.  There is no further limit on M, rh or nh: the message state
+ * lives in a workspace in global memory.
+ * The context serves the *_codes_gfq* entry points only (plus ldpc_hip_codes, ldpc_hip_gfq_q, ldpc_hip_gfq_sigma, ldpc_hip_n / _r,
+ * ldpc_hip_edges = the largest edge count of the set, ldpc_hip_kernel_name, the profile calls): the binary *_codes*, the single-code
+ * GF(q), the binary and the multi-device entry points return LDPC_HIP_EINVAL on it, and the *_codes_gfq* entry points return
+ * LDPC_HIP_EINVAL on any other context.  Close with ldpc_hip_close.
+ * Randomly encoded messages are not part of the set path: the all-zero word is a codeword of every candidate, and the encoder's plan
+ * (ldpc_hip_encode_gfq_dev) is decided per code. */
+int ldpc_hip_open_codes_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, const int16_t *hc, int C, int device, ldpc_hip_ctx **out);
+/* The table ldpc_hip_open_codes_gfq uploads, built on the host (no GPU needed; the same checks and return codes), with the sizes-only
+ * mode and the capacity / length contract of ldpc_hip_codes_table_host.  offsets [C] = index of each code's record; a record is
+ * E, cw2 (1 = every block column has weight 2), row_start[rh + 1], col_start[nh + 1], e_col[E], e_circ[E], e_rl[E], ce_edge[E]:
+ * edges in row-major order with their block column, shift and coefficient - 1 (the row of the set's multiplication / division
+ * tables, which hold all q - 1 coefficients), and per block column the edges in ascending row order. */
+int ldpc_hip_codes_gfq_table_host(int q_bits, int rh, int nh, int M, const int16_t *hb, const int16_t *hc, int C, int32_t *offsets,
+                                  int32_t *table, long long capacity, long long *length);
+/* Work item (c, f) decodes frame f of code c as ldpc_hip_decode_gfq_dev does with p_thr = 0.  d_soft: [B][q][N] when shared_soft != 0
+ * (every code decodes the same B received words) or [C][B][q][N]; d_qhard [C][B][N], d_iters [C][B], d_post [C][B][q][N], each
+ * optional (NULL).  maxiter >= 1.  Asynchronous on `stream`.  LDPC_HIP_GFQ_SLOTS=n as in ldpc_hip_decode_gfq_dev, with C * B work
+ * items in place of B frames; C * B <= 2^31 - 1. */
+int ldpc_hip_decode_codes_gfq_dev(ldpc_hip_ctx *ctx, const double *d_soft, int shared_soft, long long B, int maxiter, int16_t *d_qhard,
+                                  int32_t *d_iters, double *d_post, void *stream);
+/* ldpc_hip_count_errors_gfq_dev with d_codeword = NULL per code: d_frame_info [C][B] or NULL, d_counters [C][5] (DEVICE, accumulated). */
+int ldpc_hip_count_errors_codes_gfq_dev(ldpc_hip_ctx *ctx, const int16_t *d_qhard, const int32_t *d_iters, long long B,
+                                        int32_t *d_frame_info, unsigned long long *d_counters, void *stream);
+/* Frames [first_frame, first_frame + B) of every code through channel -> decode -> count on the all-zero word; the symbol
+ * probabilities are drawn ONCE per piece (the noise of ldpc_hip_gfq_channel_dev, keyed by seed, global frame and bit; sigma =
+ * ldpc_hip_gfq_sigma(snr_db), which depends on rh and nh only) and shared by the codes, so counters[c] equals what
+ * ldpc_hip_simulate_gfq(..., random_messages = 0, ...) accumulates from zero for code c alone over the same seed and frame range.
+ * Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or NULL.  B is worked off in pieces of the context's
+ * workspace (LDPC_HIP_GFQ_PIECE=n caps the frames per piece); the result does not depend on the pieces, on LDPC_HIP_GFQ_SLOTS or on
+ * how B is split over calls with consecutive first_frame.  One call at a time per context, on the null stream. */
+int ldpc_hip_simulate_codes_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame, long long B,
+                                unsigned long long *counters, int32_t *frame_info);
+/* ldpc_hip_simulate_codes_stop for a GF(q) set: the same rule per code on the device, the same state [C][4] (nse counts wrong
+ * information SYMBOLS), batch schedule, meaning of frames_decoded and LDPC_HIP_EINVAL cases, over the noise of
+ * ldpc_hip_simulate_codes_gfq from first_frame on. */
+int ldpc_hip_simulate_codes_gfq_stop(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame,
+                                     int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
+                                     long long max_batch, unsigned long long *state);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

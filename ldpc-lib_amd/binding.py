@@ -194,6 +194,12 @@ def load_library():
     lib.ldpc_hip_count_errors_codes_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_codes.argtypes = [vp, f64, i32, i32, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_simulate_codes_stop.argtypes = [vp, f64, i32, i32, f64, u64, i64, i32, i64, f64, i64, i64, vp]
+    lib.ldpc_hip_open_codes_gfq.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_codes_gfq_table_host.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, C.POINTER(i64)]
+    lib.ldpc_hip_decode_codes_gfq_dev.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, vp]
+    lib.ldpc_hip_count_errors_codes_gfq_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    lib.ldpc_hip_simulate_codes_gfq.argtypes = [vp, f64, i32, u64, i64, i64, vp, vp]
+    lib.ldpc_hip_simulate_codes_gfq_stop.argtypes = [vp, f64, i32, u64, i64, i32, i64, f64, i64, i64, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -754,6 +760,133 @@ class LdpcHipCodes:
                                                    int(n_frame_errors), int(n_experiments), float(reference_frame_error), int(first_batch),
                                                    int(max_batch), state.ctypes.data)
         _check(self.lib, rc, "ldpc_hip_simulate_codes_stop")
+        return state
+
+    def profile(self, enable=True):
+        _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")
+
+    def profile_read(self, reset=True):
+        """(total milliseconds, launches) of the decode launches timed with HIP events since the last reset."""
+        ms, n = C.c_double(), C.c_longlong()
+        _check(self.lib, self.lib.ldpc_hip_profile_read(self.h, C.byref(ms), C.byref(n), int(reset)), "ldpc_hip_profile_read")
+        return ms.value, n.value
+
+
+def _gfq_code_stacks(codes_hb, codes_hc):
+    hb, hc = _code_stack(codes_hb), _code_stack(codes_hc)
+    assert hb.shape == hc.shape, "codes_hb and codes_hc: [C, rh, nh] shifts and coefficients of the same codes"
+    return hb, hc
+
+
+def codes_gfq_table(q_bits, codes_hb, codes_hc, M):
+    """The table of a GF(q) code set as ldpc_hip_open_codes_gfq uploads it, built on the host (needs no GPU): (offsets int32 [C], table
+    int32).  Code c owns the record table[offsets[c]:] = E, cw2, row_start[rh + 1], col_start[nh + 1], e_col[E], e_circ[E], e_rl[E]
+    (coefficient - 1), ce_edge[E]."""
+    lib = load_library()
+    hb, hc = _gfq_code_stacks(codes_hb, codes_hc)
+    Cn, rh, nh = hb.shape
+    n = C.c_longlong()
+    _check(lib, lib.ldpc_hip_codes_gfq_table_host(int(q_bits), rh, nh, int(M), hb.ctypes.data, hc.ctypes.data, Cn, None, None, 0, C.byref(n)),
+           "ldpc_hip_codes_gfq_table_host")
+    off = np.empty(Cn, dtype=np.int32)
+    tab = np.empty(n.value, dtype=np.int32)
+    _check(lib, lib.ldpc_hip_codes_gfq_table_host(int(q_bits), rh, nh, int(M), hb.ctypes.data, hc.ctypes.data, Cn, off.ctypes.data, tab.ctypes.data,
+                                                  n.value, None), "ldpc_hip_codes_gfq_table_host")
+    return off, tab
+
+
+class LdpcHipCodesGfq:
+    """C candidate codes over GF(q), q = 2^q_bits, of one shape (codes_hb, codes_hc int16 [C, rh, nh]: shifts and coefficients as
+    LdpcHipGfq takes them, lifting M) on one GPU, decoded C x B frames per launch (ldpc_hip_open_codes_gfq): what upstream's ggp
+    search scores.  Bit-identical to LdpcHipGfq on each pair of matrices."""
+
+    def __init__(self, q_bits, codes_hb, codes_hc, M, device=0):
+        self.lib = load_library()
+        hb, hc = _gfq_code_stacks(codes_hb, codes_hc)
+        self.C, self.rh, self.nh = hb.shape
+        self.M, self.q_bits, self.device = int(M), int(q_bits), int(device)
+        h = C.c_void_p()
+        rc = self.lib.ldpc_hip_open_codes_gfq(self.q_bits, self.rh, self.nh, self.M, hb.ctypes.data, hc.ctypes.data, self.C, self.device, C.byref(h))
+        _check(self.lib, rc, "ldpc_hip_open_codes_gfq")
+        self.h = h
+        self.N = self.lib.ldpc_hip_n(h)
+        self.R = self.lib.ldpc_hip_r(h)
+        self.edges = self.lib.ldpc_hip_edges(h)
+        self.q = self.lib.ldpc_hip_gfq_q(h)
+        self.kernel_name = self.lib.ldpc_hip_kernel_name(h).decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ldpc_hip_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def sigma(self, snr_db):
+        """bp_simulation.cpp:444-445 with punctured_blocks = 0: rh and nh only, common to the set."""
+        return self.lib.ldpc_hip_gfq_sigma(self.h, float(snr_db))
+
+    def decode(self, soft, maxiter, shared=True, want_post=False, stream=None):
+        """soft: torch float64 CUDA tensor, [B, q, N] (shared=True: every code decodes the same received words) or [C, B, q, N]; not
+        modified.  Returns (qhard int16 [C, B, N], iters int32 [C, B], post float64 [C, B, q, N] | None)."""
+        import torch
+        assert soft.is_cuda and soft.dtype == torch.float64 and soft.is_contiguous()
+        assert soft.dim() == (3 if shared else 4) and tuple(soft.shape[-2:]) == (self.q, self.N) and (shared or soft.shape[0] == self.C), tuple(soft.shape)
+        B = soft.shape[-3]
+        qhard = torch.empty((self.C, B, self.N), dtype=torch.int16, device=soft.device)
+        iters = torch.empty((self.C, B), dtype=torch.int32, device=soft.device)
+        post = torch.empty((self.C, B, self.q, self.N), dtype=torch.float64, device=soft.device) if want_post else None
+        rc = self.lib.ldpc_hip_decode_codes_gfq_dev(self.h, soft.data_ptr(), 1 if shared else 0, B, int(maxiter), qhard.data_ptr(), iters.data_ptr(),
+                                                    post.data_ptr() if post is not None else None, _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_decode_codes_gfq_dev")
+        return qhard, iters, post
+
+    def count_errors(self, qhard, iters, counters=None, want_frame_info=False, stream=None):
+        """qhard [C, B, N], iters [C, B] as decode() returns them, against the all-zero word.  Returns (counters int64 CUDA tensor
+        [C, 5] = nse, nde, nue, frames, sum |iters| per code -- `counters` itself, accumulated, when one is passed --, frame_info int32
+        [C, B] | None)."""
+        import torch
+        assert tuple(iters.shape[:1]) == (self.C,) and qhard.is_contiguous() and iters.is_contiguous()
+        assert qhard.dtype == torch.int16 and iters.dtype == torch.int32 and tuple(qhard.shape) == (self.C, iters.shape[1], self.N)
+        B = iters.shape[1]
+        if counters is None:
+            counters = torch.zeros((self.C, 5), dtype=torch.int64, device=iters.device)
+        assert counters.is_cuda and counters.dtype == torch.int64 and tuple(counters.shape) == (self.C, 5) and counters.is_contiguous()
+        info = torch.empty((self.C, B), dtype=torch.int32, device=iters.device) if want_frame_info else None
+        rc = self.lib.ldpc_hip_count_errors_codes_gfq_dev(self.h, qhard.data_ptr(), iters.data_ptr(), B, info.data_ptr() if info is not None else None,
+                                                          counters.data_ptr(), _stream_ptr(stream))
+        _check(self.lib, rc, "ldpc_hip_count_errors_codes_gfq_dev")
+        return counters, info
+
+    def simulate(self, snr_db, maxiter, seed, first_frame, frames, records=False):
+        """Frames [first_frame, first_frame + frames) of every code over the same noise, the all-zero word sent.  Returns counters
+        uint64 [C, 5] (nse, nde, nue, frames, sum |iters| per code: what LdpcHipGfq.simulate(random_messages=False) gives for that
+        code alone), and with records=True also frame_info int32 [C, frames]."""
+        cnt = np.zeros((self.C, 5), dtype=np.uint64)
+        info = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_simulate_codes_gfq(self.h, float(snr_db), int(maxiter), int(seed), int(first_frame), int(frames), cnt.ctypes.data,
+                                                  info.ctypes.data if info is not None else None)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes_gfq")
+        return (cnt, info) if records else cnt
+
+    def simulate_until(self, snr_db, maxiter, seed, n_frame_errors, n_experiments, reference_frame_error, first_frame=0, first_batch=1024,
+                       max_batch=65536):
+        """LdpcHipCodes.simulate_until for a GF(q) set (ldpc_hip_simulate_codes_gfq_stop).  Returns uint64 [C, 4] = experiment, nse,
+        nde, frames_decoded per code; nse counts wrong information symbols."""
+        state = np.zeros((self.C, 4), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_simulate_codes_gfq_stop(self.h, float(snr_db), int(maxiter), int(seed), int(first_frame), int(n_frame_errors),
+                                                       int(n_experiments), float(reference_frame_error), int(first_batch), int(max_batch), state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes_gfq_stop")
         return state
 
     def profile(self, enable=True):

@@ -2,6 +2,13 @@
 // shared-noise Monte-Carlo pass.  Included at the end of ldpc_hip.hip.
 #pragma once
 
+// ldpc_hip_simulate_codes_stop and its GF(q) twin: the per-code state of the stopping rule and the list of the codes still running
+struct codeset_rule_ws {
+    unsigned long long *rule = nullptr;              // [C][4]: experiment, nse, nde, frames_decoded
+    int32_t *running = nullptr, *list = nullptr;     // [C] each
+    int32_t *nactive = nullptr;                      // [1]
+};
+
 struct ldpc_codeset_state {
     int C = 0;
     int ne_max = 0;                    // the largest edge count of a code of the set
@@ -13,15 +20,12 @@ struct ldpc_codeset_state {
     int32_t *w_iters = nullptr, *w_info = nullptr;   // [C][w_frames]
     unsigned long long *w_cnt = nullptr;             // [C][5]
     long long w_frames = 0;
-    // ldpc_hip_simulate_codes_stop: the per-code state of the stopping rule and the list of the codes still running
-    unsigned long long *w_rule = nullptr;            // [C][4]: experiment, nse, nde, frames_decoded
-    int32_t *w_running = nullptr, *w_list = nullptr; // [C] each
-    int32_t *w_nactive = nullptr;                    // [1]
+    codeset_rule_ws stop;                            // ldpc_hip_simulate_codes_stop
 };
 
 void ldpc_codeset_release(ldpc_codeset_state *s) {
     if (!s) return;
-    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt, s->w_rule, s->w_running, s->w_list, s->w_nactive};
+    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt, s->stop.rule, s->stop.running, s->stop.list, s->stop.nactive};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     delete s;
@@ -256,6 +260,47 @@ int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long lo
     return 0;
 }
 
+// The batch schedule and the stopping rule of ldpc_hip_simulate_codes_stop around the launches of one piece: run_piece(first, nb, list,
+// n_active) draws, decodes and counts frames [first, first + nb) of the run for the n_active codes of `list` (DEVICE), leaving their
+// records in w_info [n_active][nb].  The device is the caller's current one; w_cnt [C][5] is cleared; state [C][4] is the HOST result.
+template <class Piece>
+int codeset_stop_loop(size_t C, long long piece, int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
+                      long long max_batch, codeset_rule_ws &w, const int32_t *w_info, unsigned long long *w_cnt, unsigned long long *state, Piece run_piece) {
+    if (!w.rule) {
+        HIP_TRY(hipMalloc(&w.rule, sizeof(unsigned long long) * 4 * C));
+        HIP_TRY(hipMalloc(&w.running, sizeof(int32_t) * C));
+        HIP_TRY(hipMalloc(&w.list, sizeof(int32_t) * C));
+        HIP_TRY(hipMalloc(&w.nactive, sizeof(int32_t)));
+    }
+    std::vector<int32_t> ident(C), ones(C, 1);
+    for (size_t q = 0; q < C; ++q) ident[q] = (int32_t)q;
+    HIP_TRY(hipMemcpy(w.list, ident.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.running, ones.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(w.rule, 0, sizeof(unsigned long long) * 4 * C, nullptr));
+    HIP_TRY(hipMemsetAsync(w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
+    int32_t n_active = (int32_t)C;
+    long long first = 0, batch = first_batch;   // every running code has consumed the same number of frames: `first`
+    while (n_active > 0) {
+        const long long room = n_experiments + 1 - first;
+        const long long B = batch < room ? batch : room;
+        if (B <= 0) break;
+        for (long long done = 0; done < B && n_active > 0; done += piece) {
+            const long long nb = (B - done) < piece ? (B - done) : piece;
+            if (int rc = run_piece(first + done, nb, w.list, n_active)) return rc;
+            const ldpc::CodesetRuleArgs ra{w_info, w.list, w.rule, w.running, nb, n_frame_errors, n_experiments, reference_frame_error};
+            hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, w.running, (int)C, w.list, w.nactive);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&n_active, w.nactive, sizeof(int32_t), hipMemcpyDeviceToHost));   // the one value the host needs per piece
+        }
+        first += B;
+        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+    }
+    HIP_TRY(hipMemcpy(state, w.rule, sizeof(unsigned long long) * 4 * C, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -271,7 +316,7 @@ int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, in
     return codeset_open("ldpc_hip_open_codes_tdmp", LDPC_HIP_TASP_DEC, rh, nh, M, hd, C, device, out);
 }
 
-int ldpc_hip_codes(const ldpc_hip_ctx *c) { return c && c->codes ? c->codes->C : 0; }
+int ldpc_hip_codes(const ldpc_hip_ctx *c);   // ldpc_gfq_codeset_api.hpp: a GF(q) code-set context answers too
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
                               int32_t *d_iters, double *d_soft, void *stream_) {
@@ -332,42 +377,13 @@ int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *c, double snr_db, int punctured_b
     HIP_TRY(hipSetDevice(c->device));
     const long long piece = codeset_piece(c, max_batch < n_experiments + 1 ? max_batch : n_experiments + 1);
     if (int rc = codeset_reserve(c, piece)) return rc;
-    if (!s->w_rule) {
-        HIP_TRY(hipMalloc(&s->w_rule, sizeof(unsigned long long) * 4 * C));
-        HIP_TRY(hipMalloc(&s->w_running, sizeof(int32_t) * C));
-        HIP_TRY(hipMalloc(&s->w_list, sizeof(int32_t) * C));
-        HIP_TRY(hipMalloc(&s->w_nactive, sizeof(int32_t)));
-    }
-    std::vector<int32_t> ident(C), ones(C, 1);
-    for (size_t q = 0; q < C; ++q) ident[q] = (int32_t)q;
-    HIP_TRY(hipMemcpy(s->w_list, ident.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->w_running, ones.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(s->w_rule, 0, sizeof(unsigned long long) * 4 * C, nullptr));
-    HIP_TRY(hipMemsetAsync(s->w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
     codeset_channel_args(c, punctured_blocks, seed, ch);
-    int32_t n_active = (int32_t)C;
-    long long first = 0, batch = first_batch;   // every running code has consumed the same number of frames: `first`
-    while (n_active > 0) {
-        const long long room = n_experiments + 1 - first;
-        const long long B = batch < room ? batch : room;
-        if (B <= 0) break;
-        for (long long done = 0; done < B && n_active > 0; done += piece) {
-            const long long nb = (B - done) < piece ? (B - done) : piece;
-            if (int rc = codeset_channel_launch(c, ch, first_frame + first + done, nb)) return rc;
-            if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, s->w_list, n_active)) return rc;
-            if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, s->w_info, s->w_cnt, nullptr, s->w_list, n_active)) return rc;
-            const ldpc::CodesetRuleArgs ra{s->w_info, s->w_list, s->w_rule, s->w_running, nb, n_frame_errors, n_experiments, reference_frame_error};
-            hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, s->w_running, (int)C, s->w_list, s->w_nactive);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(&n_active, s->w_nactive, sizeof(int32_t), hipMemcpyDeviceToHost));   // the one value the host needs per piece
-        }
-        first += B;
-        if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
-    }
-    HIP_TRY(hipMemcpy(state, s->w_rule, sizeof(unsigned long long) * 4 * C, hipMemcpyDeviceToHost));
-    return 0;
+    return codeset_stop_loop(C, piece, n_frame_errors, n_experiments, reference_frame_error, first_batch, max_batch, s->stop, s->w_info, s->w_cnt, state,
+                             [&](long long first, long long nb, const int32_t *list, int n_active) -> int {
+                                 if (int rc = codeset_channel_launch(c, ch, first_frame + first, nb)) return rc;
+                                 if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, list, n_active)) return rc;
+                                 return codeset_count_launch(c, s->w_hard, s->w_iters, nb, s->w_info, s->w_cnt, nullptr, list, n_active);
+                             });
 }
 
 }  // extern "C"

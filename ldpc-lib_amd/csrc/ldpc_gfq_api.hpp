@@ -181,7 +181,7 @@ int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, cons
     return 0;
 }
 
-int ldpc_hip_gfq_q(const ldpc_hip_ctx *c) { return c && c->gfq ? c->gfq->q : 0; }
+int ldpc_hip_gfq_q(const ldpc_hip_ctx *c);   // ldpc_gfq_codeset_api.hpp: a GF(q) code-set context answers too
 
 int ldpc_hip_gfq_coefficients(const ldpc_hip_ctx *c, int16_t *hc_out) {
     if (!c || !c->gfq || !hc_out) return fail(LDPC_HIP_EINVAL, "ldpc_hip_gfq_coefficients: not a GF(q) context, or null output");

@@ -93,21 +93,22 @@ int gfq_encoder_plan(ldpc_hip_ctx *c) {
     return 0;
 }
 
-int gfq_grid(const ldpc_gfq_state *g, long long items, int per_block) {
+int gfq_grid(int num_cu, long long items, int per_block) {
     long long blocks = (items + per_block - 1) / per_block;
-    const long long cap = (long long)g->num_cu * 32;
+    const long long cap = (long long)num_cu * 32;
     if (blocks > cap) blocks = cap;
     return (int)(blocks < 1 ? 1 : blocks);
 }
+int gfq_grid(const ldpc_gfq_state *g, long long items, int per_block) { return gfq_grid(g->num_cu, items, per_block); }
 
-int gfq_channel_launch(ldpc_hip_ctx *c, const int16_t *d_codeword, const int32_t *d_ok, const double *d_noise, double sigma, uint64_t seed,
+// the channel of a code of length N over GF(2^q_bits); a code-set context (ldpc_gfq_codeset_api.hpp) launches it too
+int gfq_channel_launch(int num_cu, int N, int q_bits, const int16_t *d_codeword, const int32_t *d_ok, const double *d_noise, double sigma, uint64_t seed,
                        long long first_frame, long long B, double *d_soft, hipStream_t stream) {
-    ldpc_gfq_state *g = c->gfq;
     ldpc_gfq::QChanArgs a{};
     a.codeword = d_codeword; a.ok = d_ok; a.noise = d_noise; a.soft = d_soft;
-    a.B = B; a.first_frame = first_frame; a.N = c->N; a.q_bits = g->q_bits; a.sigma = sigma; a.seed = seed;
-    const dim3 grid((unsigned)gfq_grid(g, B * (long long)c->N, 256)), block(256);
-    switch (g->q_bits) {
+    a.B = B; a.first_frame = first_frame; a.N = N; a.q_bits = q_bits; a.sigma = sigma; a.seed = seed;
+    const dim3 grid((unsigned)gfq_grid(num_cu, B * (long long)N, 256)), block(256);
+    switch (q_bits) {
     case 2: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_kernel<2>, grid, block, 0, stream, a); break;
     case 3: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_kernel<3>, grid, block, 0, stream, a); break;
     case 4: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_kernel<4>, grid, block, 0, stream, a); break;
@@ -120,6 +121,10 @@ int gfq_channel_launch(ldpc_hip_ctx *c, const int16_t *d_codeword, const int32_t
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+int gfq_channel_launch(ldpc_hip_ctx *c, const int16_t *d_codeword, const int32_t *d_ok, const double *d_noise, double sigma, uint64_t seed,
+                       long long first_frame, long long B, double *d_soft, hipStream_t stream) {
+    return gfq_channel_launch(c->gfq->num_cu, c->N, c->gfq->q_bits, d_codeword, d_ok, d_noise, sigma, seed, first_frame, B, d_soft, stream);
 }
 
 int gfq_count_launch(ldpc_hip_ctx *c, const int16_t *d_qhard, const int16_t *d_codeword, const int32_t *d_ok, const int32_t *d_iters, long long B,
@@ -173,7 +178,7 @@ int ldpc_hip_gfq_left2right(int16_t *matr, int rh, int nh) {
 int ldpc_hip_gfq_k(const ldpc_hip_ctx *c) { return c && c->gfq && c->nh > c->rh ? (c->nh - c->rh) * c->M : 0; }
 
 double ldpc_hip_gfq_sigma(const ldpc_hip_ctx *c, double snr_db) {
-    if (!c || !c->gfq) return 0.0;
+    if (!c || (!c->gfq && !c->codes_gfq)) return 0.0;
     const double bitrate = (double)(c->nh - c->rh) / c->nh;   // bp_simulation.cpp:444 with punctured_blocks = 0
     return sqrt(pow(10, -snr_db / 10) / 2 / bitrate);          // :445
 }

@@ -31,6 +31,7 @@
 #include "ldpc_encode.hpp"
 #include "ldpc_gfq.hpp"
 #include "ldpc_gfq_chain.hpp"
+#include "ldpc_gfq_codeset.hpp"
 
 namespace {
 
@@ -168,11 +169,14 @@ struct ldpc_gfq_state;                       // FHT_DEC (GF(q)) contexts: ldpc_g
 void ldpc_gfq_release(ldpc_gfq_state *g);
 struct ldpc_codeset_state;                   // code-set contexts (C codes of one shape): ldpc_codeset_api.hpp
 void ldpc_codeset_release(ldpc_codeset_state *s);
+struct ldpc_codeset_gfq_state;               // GF(q) code-set contexts: ldpc_gfq_codeset_api.hpp
+void ldpc_codeset_gfq_release(ldpc_codeset_gfq_state *s);
 
 struct ldpc_hip_ctx {
     int decoder_id = 0, device = 0;
     ldpc_gfq_state *gfq = nullptr;           // set by ldpc_hip_open_gfq: the context decodes with ldpc_hip_decode_gfq_* only
     ldpc_codeset_state *codes = nullptr;     // set by ldpc_hip_open_codes: the context decodes with ldpc_hip_*_codes* only
+    ldpc_codeset_gfq_state *codes_gfq = nullptr;   // set by ldpc_hip_open_codes_gfq: the context serves ldpc_hip_*_codes_gfq* only
     int rh = 0, nh = 0, M = 0, N = 0, R = 0, ne = 0, hard_words = 0;
     // generic (table-driven) kernel geometry
     int F = 1;         // frames per workgroup (M <= 64: floor(64/M))
@@ -287,6 +291,8 @@ int set_device(const ldpc_hip_ctx *c) {
         return fail(LDPC_HIP_EINVAL, "this entry point serves binary codes; a GF(q) context (ldpc_hip_open_gfq) decodes with ldpc_hip_decode_gfq_dev / _host");
     if (c->codes)
         return fail(LDPC_HIP_EINVAL, "this entry point serves one code; a code-set context (ldpc_hip_open_codes) decodes with ldpc_hip_decode_codes_dev / ldpc_hip_simulate_codes");
+    if (c->codes_gfq)
+        return fail(LDPC_HIP_EINVAL, "this entry point serves one binary code; a GF(q) code-set context (ldpc_hip_open_codes_gfq) decodes with ldpc_hip_decode_codes_gfq_dev / ldpc_hip_simulate_codes_gfq");
     HIP_TRY(hipSetDevice(c->device));
     return 0;
 }
@@ -644,6 +650,7 @@ void ldpc_hip_close(ldpc_hip_ctx *c) {
     if (c->d_hd_enc) (void)hipFree(c->d_hd_enc);
     ldpc_gfq_release(c->gfq);
     ldpc_codeset_release(c->codes);
+    ldpc_codeset_gfq_release(c->codes_gfq);
     ldpc_mt::release(c->mt);
     for (auto &ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     delete c;
@@ -1330,3 +1337,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_gfq_api.hpp"
 #include "ldpc_gfq_chain_api.hpp"
 #include "ldpc_codeset_api.hpp"
+#include "ldpc_gfq_codeset_api.hpp"
