@@ -4,7 +4,8 @@
  * draw order as upstream (commons_portable.cpp:138-178, bp_simulation.cpp:512,600-611) -- continued ON THE GPU by default
  * (ldpc_hip_mt_*: the generator's words, libstdc++'s polar method and glibc's log reproduced bit for bit, so only the 8-byte frame
  * records cross PCIe; LDPC_HIP_EXACT_NOISE=host draws on the host instead) -- frames are decoded in GPU batches, and upstream's
- * sequential stopping rule (bp_simulation.cpp:591,820) is replayed over the ordered per-frame results.  On an early stop the
+ * sequential stopping rule (bp_simulation.cpp:591,820) is replayed over the ordered per-frame results (ldpc::replay_stop_rule, the one
+ * replay behind every harness of this header).  On an early stop the
  * generator is rolled back and re-advanced so that it is left exactly where upstream's frame-by-frame loop leaves it (later
  * callers draw from it: main_good_code_search.cpp:316).
  * Result, counters and generator state are identical to upstream's for q_mod == 2, modulation SKIP/QAM4,
@@ -157,6 +158,31 @@ inline bool device_stream_matches_host(ldpc_hip_ctx *ctx) {
 
 struct SimCounters { long long nse = 0, nde = 0, nue = 0, experiment = 0, sum_abs_iters = 0; };
 
+// Upstream's sequential stopping rule (bp_simulation.cpp:591, :805-823) replayed over the ordered results of a batch of B frames, the
+// one place where the harnesses below apply it.  frame(f) gives the record of frame f -- the low 30 bits hold the wrong information
+// bits, bit 30 is set when any bit is wrong -- and its iteration count; on_error() runs at each error frame once it is counted (the
+// show_process line).  used: the frames of the batch the rule consumed; stop: the run ends with the last of them.
+struct StopReplay { long long used; bool stop; };
+template <class Frame, class OnError>
+inline StopReplay replay_stop_rule(SimCounters &k, int n_frame_errors, long long n_experiments, double reference_frame_error, long long B,
+                                   Frame frame, OnError on_error) {
+    const auto running = [&] { return k.nde < n_frame_errors && k.experiment <= n_experiments; };   // :591
+    StopReplay r{0, false};
+    while (!r.stop && r.used < B && running()) {
+        const std::pair<int32_t, int> rec = frame(r.used);
+        ++k.experiment; ++r.used;
+        k.sum_abs_iters += rec.second < 0 ? -rec.second : rec.second;
+        if (rec.first != 0) {                                                                        // :805
+            k.nse += rec.first & ((1 << 30) - 1); ++k.nde;
+            if (rec.second >= 0) ++k.nue;
+            on_error();
+            r.stop = k.nde >= 10 && (double)k.nde / k.experiment > 2.5 * reference_frame_error;      // :820
+        }
+    }
+    r.stop = r.stop || !running();
+    return r;
+}
+
 template <class Mat, class Env>
 std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_length, int max_iterations,
                                           int n_frame_errors, int n_experiments, double snr,
@@ -209,11 +235,16 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
 
     Env::burn_codeword_draws(H, M);  // :512
 
-    long long nse = 0, nue = 0, nde = 0, experiment = 0, sum_abs_iters = 0;
+    SimCounters k;
     std::vector<double> llr, decword;
     std::vector<int32_t> iters;
     long long batch = 64;
-    bool stop = false;
+    bool stop = n_frame_errors <= 0 || n_experiments < 0;                                        // :591 fails before the first frame
+    const auto show = [&] {
+        if (show_process)
+            printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)k.experiment, (int)k.nse, (int)k.nde,
+                   (int)k.nue, (double)k.nse / k.experiment / (n - r), (double)k.nde / k.experiment);
+    };
 
     // Noise on the device (default): the GPUs continue the generator's own stream -- same words, same polar-method attempts, same
     // libm log -- so nothing but the 8-byte frame records crosses PCIe.  LDPC_HIP_EXACT_NOISE=host keeps the draws on the host.
@@ -228,29 +259,18 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
         const long long cap = (max_batch > 65536 * (long long)devices.size()) ? max_batch : 65536 * (long long)devices.size();
         std::vector<int32_t> info;
         batch = 256;
-        while (!stop && nde < n_frame_errors && experiment <= n_experiments) {                  // :591
-            const long long room = (long long)n_experiments + 1 - experiment;
+        while (!stop) {
+            const long long room = (long long)n_experiments + 1 - k.experiment;
             const long long B = batch < room ? batch : room;
             info.resize((size_t)B); iters.resize((size_t)B);
             if (ldpc_hip_mt_get_state_multi(ctx, mt_words, &mt_pos) != 0) Env::fail(ldpc_hip_last_error());   // snapshot (+ the frame count: experiment)
             if (ldpc_hip_mt_frames_multi(ctx, snr, modulation_type, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, B, info.data(),
                                          iters.data()) != 0)
                 Env::fail(ldpc_hip_last_error());
-            long long used = 0;
-            for (long long f = 0; f < B; ++f) {                                                 // ordered replay of :591-823
-                if (!(nde < n_frame_errors && experiment <= n_experiments)) { stop = true; break; }
-                ++experiment; ++used;
-                const int iter = iters[(size_t)f];
-                sum_abs_iters += iter < 0 ? -iter : iter;
-                if (info[(size_t)f] != 0) {                                                      // bit 30: any wrong bit (:805)
-                    nse += info[(size_t)f] & ((1 << 30) - 1); ++nde;
-                    if (iter >= 0) ++nue;
-                    if (show_process)
-                        printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)experiment,
-                               (int)nse, (int)nde, (int)nue, (double)nse / experiment / (n - r), (double)nde / experiment);
-                    if (nde >= 10 && (double)nde / experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
-                }
-            }
+            const StopReplay rp = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B,
+                                                   [&](long long f) { return std::make_pair(info[(size_t)f], (int)iters[(size_t)f]); }, show);
+            stop = rp.stop;
+            const long long used = rp.used, experiment = k.experiment;
             if (used < B) {  // stopped inside the batch: put the generator where the frame-by-frame loop leaves it
                 if (ldpc_hip_mt_set_state_multi(ctx, mt_words, mt_pos) != 0) Env::fail(ldpc_hip_last_error());
                 if (ldpc_hip_mt_set_frame_index_multi(ctx, experiment - used) != 0) Env::fail(ldpc_hip_last_error());   // set_state restarts the count
@@ -262,8 +282,8 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
         if (!mt_import(Env::generator(), mt_words, mt_pos)) Env::fail("bp_simulation: could not hand the generator state back to std::mt19937");
         stop = true;   // the host-noise loop below is skipped
     }
-    while (!device_noise && !stop && nde < n_frame_errors && experiment <= n_experiments) {     // :591
-        const long long room = (long long)n_experiments + 1 - experiment;
+    while (!stop) {
+        const long long room = (long long)n_experiments + 1 - k.experiment;
         const long long B = batch < room ? batch : room;
         llr.resize((size_t)B * n); decword.resize((size_t)B * n); iters.resize((size_t)B);
         const std::mt19937 snapshot = Env::generator();
@@ -281,25 +301,15 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
         if (ldpc_hip_decode_host_multi(ctx, llr.data(), B, max_iterations, DEC_DECISION_HARD, 0.8 /*MS_ALPHA*/, decword.data(),
                                        iters.data(), 0) != 0)
             Env::fail(ldpc_hip_last_error());
-        long long used = 0;
-        for (long long f = 0; f < B; ++f) {                                                     // ordered replay of :591-823
-            if (!(nde < n_frame_errors && experiment <= n_experiments)) { stop = true; break; }
-            ++experiment; ++used;
-            const int iter = iters[(size_t)f];
-            sum_abs_iters += iter < 0 ? -iter : iter;
+        const StopReplay rp = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B, [&](long long f) {
             const double *d = decword.data() + (size_t)f * n;
             int curr_nse = 0, curr_nse_info = 0;                                                 // :735-742
             for (int i = 0; i < n; ++i)
                 if (d[i] != 0.0) { ++curr_nse; if (i >= r) ++curr_nse_info; }
-            if (curr_nse > 0) {                                                                  // :805-823
-                nse += curr_nse_info; ++nde;
-                if (iter >= 0) ++nue;
-                if (show_process)
-                    printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)experiment,
-                           (int)nse, (int)nde, (int)nue, (double)nse / experiment / (n - r), (double)nde / experiment);
-                if (nde >= 10 && (double)nde / experiment > 2.5 * reference_frame_error) { stop = true; break; }
-            }
-        }
+            return std::make_pair((int32_t)(curr_nse_info | (curr_nse > 0 ? 1 << 30 : 0)), (int)iters[(size_t)f]);   // the device's record
+        }, show);
+        stop = rp.stop;
+        const long long used = rp.used;
         if (used < B) {  // stopped inside the batch: leave the generator where the frame-by-frame loop would
             Env::generator() = snapshot;
             for (long long i = 0, cnt = used * n; i < cnt; ++i) (void)Env::gaussian();
@@ -307,8 +317,8 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
         if (batch < max_batch) batch *= 4;
     }
     ldpc_hip_close_multi(ctx);                                                                   // :831
-    if (counters_out) { counters_out->nse = nse; counters_out->nde = nde; counters_out->nue = nue; counters_out->experiment = experiment; counters_out->sum_abs_iters = sum_abs_iters; }
-    return std::make_pair((double)nse / experiment / (n - r), (double)nde / experiment);         // :840
+    if (counters_out) *counters_out = k;
+    return std::make_pair((double)k.nse / k.experiment / (n - r), (double)k.nde / k.experiment); // :840
 }
 
 // the single-device form (device ordinal; LDPC_HIP_DEVICES overrides it)
@@ -351,38 +361,31 @@ std::pair<double, double> bp_simulation_throughput_t(int q_mod, Mat const &H, in
     if (ncw > 0 && codewords && ldpc_hip_multi_set_codewords(m, codewords, ncw) != 0) Env::fail(ldpc_hip_last_error());
     if (ncw > 0 && !codewords && ldpc_hip_multi_set_random_codewords(m, seed, ncw) != 0) Env::fail(ldpc_hip_last_error());   // made on the device
     const int nsh = (int)devices.size();
-    long long nse = 0, nue = 0, nde = 0, experiment = 0, sum_abs_iters = 0, first = 0;
+    SimCounters k;
+    long long first = 0;
     std::vector<int32_t> info, iters;
-    bool stop = false;
+    bool stop = n_frame_errors <= 0 || n_experiments < 0;                                        // :591 fails before the first frame
     long long batch = 1024;   // ramp up like the exact harness: short runs stop after few frames
-    while (!stop && nde < n_frame_errors && experiment <= n_experiments) {                       // :591
-        const long long room = n_experiments + 1 - experiment;
+    while (!stop) {
+        const long long room = n_experiments + 1 - k.experiment;
         long long B = batch * nsh;
         if (B > room) B = room;
         info.resize((size_t)B); iters.resize((size_t)B);
         if (ldpc_hip_frames_multi(m, snr, modulation_type, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, first, B, batch,
                                   info.data(), iters.data(), nullptr, nullptr) != 0)
             Env::fail(ldpc_hip_last_error());
-        for (long long f = 0; f < B; ++f) {                                                      // ordered replay of :591-823
-            if (!(nde < n_frame_errors && experiment <= n_experiments)) { stop = true; break; }
-            ++experiment;
-            const int it = iters[(size_t)f];
-            sum_abs_iters += it < 0 ? -it : it;
-            if (info[(size_t)f] != 0) {                                                          // bit 30: any wrong bit (:805)
-                nse += info[(size_t)f] & ((1 << 30) - 1); ++nde;
-                if (it >= 0) ++nue;
-                if (show_process)
-                    printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)experiment, (int)nse, (int)nde,
-                           (int)nue, (double)nse / experiment / (double)(n - r), (double)nde / experiment);
-                if (nde >= 10 && (double)nde / experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
-            }
-        }
+        stop = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B,
+                                [&](long long f) { return std::make_pair(info[(size_t)f], (int)iters[(size_t)f]); }, [&] {
+                                    if (show_process)
+                                        printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)k.experiment, (int)k.nse,
+                                               (int)k.nde, (int)k.nue, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
+                                }).stop;
         first += B;
         if (batch < batch_per_gpu) batch = batch * 4 < batch_per_gpu ? batch * 4 : batch_per_gpu;
     }
     ldpc_hip_close_multi(m);
-    if (counters_out) { counters_out->nse = nse; counters_out->nde = nde; counters_out->nue = nue; counters_out->experiment = experiment; counters_out->sum_abs_iters = sum_abs_iters; }
-    return std::make_pair((double)nse / experiment / (double)(n - r), (double)nde / experiment);
+    if (counters_out) *counters_out = k;
+    return std::make_pair((double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
 }
 
 // The run of an opened code-set context, binary or GF(q): stop(state [C][4]) is the context's *_stop call (the rule on the device),
@@ -419,19 +422,13 @@ std::vector<std::pair<double, double>> run_code_set(int C, long long info_len, i
             if (!running[(size_t)q]) continue;
             SimCounters &k = cnt[(size_t)q];
             const int32_t *rec = info.data() + (size_t)q * (size_t)B;
-            bool stop = false;
-            for (long long f = 0; f < B; ++f) {                                                  // ordered replay of :591-823
-                if (!(k.nde < n_frame_errors && k.experiment <= n_experiments)) { stop = true; break; }
-                ++k.experiment;
-                if (rec[f] != 0) {                                                               // bit 30: any wrong bit (:805)
-                    k.nse += rec[f] & ((1 << 30) - 1); ++k.nde;
-                    if (show_process)
-                        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse,
-                               (int)k.nde, (double)k.nse / k.experiment / (double)info_len, (double)k.nde / k.experiment);
-                    if (k.nde >= 10 && (double)k.nde / k.experiment > 2.5 * reference_frame_error) { stop = true; break; }   // :820
-                }
-            }
-            if (stop || !(k.nde < n_frame_errors && k.experiment <= n_experiments)) { running[(size_t)q] = 0; --n_running; }
+            const bool stop = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B,
+                                               [&](long long f) { return std::make_pair(rec[f], 0); }, [&] {
+                                                   printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse,
+                                                          (int)k.nde, (double)k.nse / k.experiment / (double)info_len, (double)k.nde / k.experiment);
+                                               }).stop;
+            k.nue = 0;   // the records carry no iteration counts: nue and sum_abs_iters stay 0
+            if (stop) { running[(size_t)q] = 0; --n_running; }
         }
         first += B;
         if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;

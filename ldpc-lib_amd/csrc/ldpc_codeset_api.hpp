@@ -1,5 +1,7 @@
 // Host side of the code-set kernels (ldpc_codeset.hpp): the concatenated graph table, the ldpc_hip_*codes* entry points and the
-// shared-noise Monte-Carlo pass.  Included at the end of ldpc_hip.hip.
+// shared-noise Monte-Carlo pass.  What a binary and a GF(q) code set (ldpc_gfq_codeset_api.hpp) keep and do alike -- the tables, the
+// per-code outputs of a piece, the fixed-length and the stopping-rule loop -- is codeset_common and the functions around it.
+// Included at the end of ldpc_hip.hip.
 #pragma once
 
 // ldpc_hip_simulate_codes_stop and its GF(q) twin: the per-code state of the stopping rule and the list of the codes still running
@@ -9,25 +11,35 @@ struct codeset_rule_ws {
     int32_t *nactive = nullptr;                      // [1]
 };
 
-struct ldpc_codeset_state {
+// what every code-set state holds
+struct codeset_common {
     int C = 0;
     int ne_max = 0;                    // the largest edge count of a code of the set
     std::vector<int32_t> off, tab;     // host copies of the device tables
     int32_t *d_off = nullptr, *d_tab = nullptr;
-    // workspace of ldpc_hip_simulate_codes for w_frames frames per code
-    double *w_llr = nullptr;           // [w_frames][N], shared by the codes
-    uint32_t *w_hard = nullptr;        // [C][w_frames][hard_words]
+    // workspace of the simulate entry points for w_frames frames per code, next to the decoder's own input and decisions
     int32_t *w_iters = nullptr, *w_info = nullptr;   // [C][w_frames]
     unsigned long long *w_cnt = nullptr;             // [C][5]
     long long w_frames = 0;
-    codeset_rule_ws stop;                            // ldpc_hip_simulate_codes_stop
+    codeset_rule_ws stop;                            // the *_stop entry points
 };
+
+struct ldpc_codeset_state : codeset_common {
+    double *w_llr = nullptr;           // [w_frames][N], shared by the codes
+    uint32_t *w_hard = nullptr;        // [C][w_frames][hard_words]
+};
+
+void codeset_common_release(codeset_common &s) {
+    void *dev[] = {s.d_off, s.d_tab, s.w_iters, s.w_info, s.w_cnt, s.stop.rule, s.stop.running, s.stop.list, s.stop.nactive};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+}
 
 void ldpc_codeset_release(ldpc_codeset_state *s) {
     if (!s) return;
-    void *dev[] = {s->d_off, s->d_tab, s->w_llr, s->w_hard, s->w_iters, s->w_info, s->w_cnt, s->stop.rule, s->stop.running, s->stop.list, s->stop.nactive};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
+    if (s->w_llr) (void)hipFree(s->w_llr);
+    if (s->w_hard) (void)hipFree(s->w_hard);
+    codeset_common_release(*s);
     delete s;
 }
 
@@ -102,16 +114,45 @@ int codeset_ctx(const ldpc_hip_ctx *c, const char *who) {
     return 0;
 }
 
+// Workgroups per code of the count kernels: four frames (waves) each, fewer when there are many codes
+int codeset_count_blocks(long long B, int C) {
+    const long long bpc = (B + 3) / 4, cap = 2048 / C > 1 ? 2048 / C : 1;
+    return (int)(bpc > cap ? cap : bpc);
+}
+
 // code_list / n_slots: the codes of the [n_slots][B] inputs (null: all C codes in order), see ldpc_codeset.hpp
 int codeset_count_launch(const ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
                          unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0) {
     const int C = code_list ? n_slots : c->codes->C;
-    long long bpc = (B + 3) / 4;            // workgroups per code: four frames (waves) each, fewer when there are many codes
-    const long long cap = 2048 / C > 1 ? 2048 / C : 1;
-    if (bpc > cap) bpc = cap;
-    ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, code_list, B, (int)bpc, c->hard_words, c->R};
-    hipLaunchKernelGGL(ldpc::count_errors_codes_kernel, dim3((unsigned)(bpc * C)), dim3(256), 0, stream, a);
+    const int bpc = codeset_count_blocks(B, C);
+    ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, code_list, B, bpc, c->hard_words, c->R};
+    hipLaunchKernelGGL(ldpc::count_errors_codes_kernel, dim3((unsigned)((long long)bpc * C)), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The result of a *_table_host entry point: any of length, offsets [C] and table [capacity] may be null
+int codeset_table_out(const char *who, const std::vector<int32_t> &off, const std::vector<int32_t> &tab, int32_t *offsets, int32_t *table,
+                      long long capacity, long long *length) {
+    if (length) *length = (long long)tab.size();
+    if (offsets) std::memcpy(offsets, off.data(), sizeof(int32_t) * off.size());
+    if (table) {
+        if (capacity < (long long)tab.size())
+            return fail(LDPC_HIP_EINVAL, "%s: the table has %lld entries, room for %lld", who, (long long)tab.size(), capacity);
+        std::memcpy(table, tab.data(), sizeof(int32_t) * tab.size());
+    }
+    return 0;
+}
+
+// Takes the built tables into the state and onto the current device, with the counters of the simulate entry points
+int codeset_upload(codeset_common &s, int C, int ne_max, std::vector<int32_t> &off, std::vector<int32_t> &tab) {
+    s.off.swap(off); s.tab.swap(tab);
+    s.C = C; s.ne_max = ne_max;
+    HIP_TRY(hipMalloc(&s.d_off, sizeof(int32_t) * s.off.size()));
+    HIP_TRY(hipMemcpy(s.d_off, s.off.data(), sizeof(int32_t) * s.off.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s.d_tab, sizeof(int32_t) * s.tab.size()));
+    HIP_TRY(hipMemcpy(s.d_tab, s.tab.data(), sizeof(int32_t) * s.tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s.w_cnt, sizeof(unsigned long long) * 5 * (size_t)C));
     return 0;
 }
 
@@ -123,14 +164,7 @@ int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16
                               long long capacity, long long *length) {
     std::vector<int32_t> off, tab;
     if (int rc = codeset_build("ldpc_hip_codes_table_host", decoder_id, rh, nh, M, hd, C, off, tab)) return rc;
-    if (length) *length = (long long)tab.size();
-    if (offsets) std::memcpy(offsets, off.data(), sizeof(int32_t) * off.size());
-    if (table) {
-        if (capacity < (long long)tab.size())
-            return fail(LDPC_HIP_EINVAL, "ldpc_hip_codes_table_host: the table has %lld entries, room for %lld", (long long)tab.size(), capacity);
-        std::memcpy(table, tab.data(), sizeof(int32_t) * tab.size());
-    }
-    return 0;
+    return codeset_table_out("ldpc_hip_codes_table_host", off, tab, offsets, table, capacity, length);
 }
 
 }  // extern "C"
@@ -148,11 +182,9 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
     std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
-    s->off.swap(off); s->tab.swap(tab);
-    s->C = C; s->ne_max = ne_max;
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
-    c->ne = (int)(s->tab.size() - (size_t)C * (rh + 1));   // edges of the whole set
+    c->ne = (int)(tab.size() - (size_t)C * (rh + 1));   // edges of the whole set
     c->hard_words = (c->N + 31) / 32;
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
@@ -161,11 +193,7 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" : "tasp_layered_codes_kernel") +
                      (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&s->d_off, sizeof(int32_t) * s->off.size()));
-    HIP_TRY(hipMemcpy(s->d_off, s->off.data(), sizeof(int32_t) * s->off.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&s->d_tab, sizeof(int32_t) * s->tab.size()));
-    HIP_TRY(hipMemcpy(s->d_tab, s->tab.data(), sizeof(int32_t) * s->tab.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&s->w_cnt, sizeof(unsigned long long) * 5 * (size_t)C));
+    if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
     *out = c.release();
     return 0;
 }
@@ -197,49 +225,49 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     else
         k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
     if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->prof) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
+    ProfTimer timer;
+    if (int rc = timer.begin(c, stream)) return rc;
     void *kargs[] = {&a};
     c->last_launch = c->kernel_name.c_str();
     HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * n_slots)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
     HIP_TRY(hipGetLastError());
-    if (c->prof) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        c->events.emplace_back(ev0, ev1);
-    }
-    return 0;
+    return timer.end();
 }
 
-// Frames per piece of the simulate entry points: at most 65536, the [C][piece] outputs within 1 GiB, LDPC_HIP_CODES_PIECE=n caps it.
-long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
-    const size_t C = (size_t)c->codes->C;
-    const size_t per_frame = C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
-    long long piece = (long long)(((size_t)1 << 30) / per_frame);
+// Frames per piece of the simulate entry points: at most 65536, the buffers of a piece (bytes_per_frame) within 1 GiB, the environment
+// variable `cap_env` = n caps it (read per call).
+long long codeset_piece(size_t bytes_per_frame, const char *cap_env, long long B) {
+    long long piece = (long long)(((size_t)1 << 30) / bytes_per_frame);
     piece = piece > (1 << 16) ? (1 << 16) : (piece < 1 ? 1 : piece);
-    if (const char *e = getenv("LDPC_HIP_CODES_PIECE")) { if (atoll(e) > 0 && atoll(e) < piece) piece = atoll(e); }
+    if (const char *e = getenv(cap_env)) { if (atoll(e) > 0 && atoll(e) < piece) piece = atoll(e); }
     return piece > B ? B : piece;
 }
 
-// The context's workspace for `piece` frames per code (grown, never shrunk).
+long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
+    const size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
+    return codeset_piece(per_frame, "LDPC_HIP_CODES_PIECE", B);
+}
+
+// The workspace for `piece` frames per code (grown, never shrunk): the decoder's input [piece] of in_bytes per frame, shared by the
+// codes, its decisions [C][piece] of out_bytes per frame, and the iteration counts and records [C][piece].
+int codeset_reserve(codeset_common &s, long long piece, void **w_in, size_t in_bytes, void **w_out, size_t out_bytes) {
+    if (piece <= s.w_frames) return 0;
+    const size_t C = (size_t)s.C;
+    void *old[] = {*w_in, *w_out, s.w_iters, s.w_info};
+    for (void *p : old)
+        if (p) (void)hipFree(p);
+    *w_in = nullptr; *w_out = nullptr; s.w_iters = nullptr; s.w_info = nullptr; s.w_frames = 0;
+    HIP_TRY(hipMalloc(w_in, in_bytes * (size_t)piece));
+    HIP_TRY(hipMalloc(w_out, out_bytes * C * (size_t)piece));
+    HIP_TRY(hipMalloc(&s.w_iters, sizeof(int32_t) * C * (size_t)piece));
+    HIP_TRY(hipMalloc(&s.w_info, sizeof(int32_t) * C * (size_t)piece));
+    s.w_frames = piece;
+    return 0;
+}
+
 int codeset_reserve(ldpc_hip_ctx *c, long long piece) {
     ldpc_codeset_state *s = c->codes;
-    const size_t C = (size_t)s->C;
-    if (piece > s->w_frames) {
-        void *old[] = {s->w_llr, s->w_hard, s->w_iters, s->w_info};
-        for (void *p : old)
-            if (p) (void)hipFree(p);
-        s->w_llr = nullptr; s->w_hard = nullptr; s->w_iters = nullptr; s->w_info = nullptr; s->w_frames = 0;
-        HIP_TRY(hipMalloc(&s->w_llr, sizeof(double) * (size_t)piece * c->N));
-        HIP_TRY(hipMalloc(&s->w_hard, sizeof(uint32_t) * C * (size_t)piece * c->hard_words));
-        HIP_TRY(hipMalloc(&s->w_iters, sizeof(int32_t) * C * (size_t)piece));
-        HIP_TRY(hipMalloc(&s->w_info, sizeof(int32_t) * C * (size_t)piece));
-        s->w_frames = piece;
-    }
-    return 0;
+    return codeset_reserve(*s, piece, (void **)&s->w_llr, sizeof(double) * (size_t)c->N, (void **)&s->w_hard, sizeof(uint32_t) * (size_t)c->hard_words);
 }
 
 // The channel of ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word for the simulate entry points: noise keyed by
@@ -260,12 +288,51 @@ int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long lo
     return 0;
 }
 
-// The batch schedule and the stopping rule of ldpc_hip_simulate_codes_stop around the launches of one piece: run_piece(first, nb, list,
+// channel -> set decode on the shared LLRs -> set count, for frames [first_frame, first_frame + nb) and the n_active codes of `list`
+// (null: all)
+int codeset_piece_launch(ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, int maxiter, double alpha, long long first_frame, long long nb, bool want_info,
+                         const int32_t *list, int n_active) {
+    ldpc_codeset_state *s = c->codes;
+    if (int rc = codeset_channel_launch(c, ch, first_frame, nb)) return rc;
+    if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, list, n_active)) return rc;
+    return codeset_count_launch(c, s->w_hard, s->w_iters, nb, want_info ? s->w_info : nullptr, s->w_cnt, nullptr, list, n_active);
+}
+
+// The fixed-length run of the simulate entry points in pieces: run_piece(first, nb) draws, decodes and counts frames [first, first + nb)
+// of the call for all codes, leaving their records in w_info [C][nb] where frame_info is asked for.  The device is the caller's
+// current one; counters [C][5] and frame_info [C][B] (may be null) are the HOST results.
+template <class Piece>
+int codeset_simulate_loop(codeset_common &s, long long piece, long long B, unsigned long long *counters, int32_t *frame_info, Piece run_piece) {
+    const size_t C = (size_t)s.C;
+    HIP_TRY(hipMemsetAsync(s.w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
+    for (long long done = 0; done < B; done += piece) {
+        const long long nb = (B - done) < piece ? (B - done) : piece;
+        if (int rc = run_piece(done, nb)) return rc;
+        if (frame_info)   // [C][nb] on the device -> columns [done, done + nb) of the caller's [C][B]
+            HIP_TRY(hipMemcpy2D(frame_info + done, sizeof(int32_t) * (size_t)B, s.w_info, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(counters, s.w_cnt, sizeof(unsigned long long) * 5 * C, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// What the two *_stop entry points ask of their arguments
+int codeset_stop_args(const char *who, const unsigned long long *state, long long first_frame, long long first_batch, long long max_batch, int maxiter) {
+    if (!state || first_frame < 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
+    if (first_batch < 1 || max_batch < first_batch)
+        return fail(LDPC_HIP_EINVAL, "%s: batches of %lld .. %lld frames; 1 <= first_batch <= max_batch", who, first_batch, max_batch);
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "%s: maxiter must be >= 1 (got %d)", who, maxiter);
+    return 0;
+}
+
+// The batch schedule and the stopping rule of the *_stop entry points around the launches of one piece: run_piece(first, nb, list,
 // n_active) draws, decodes and counts frames [first, first + nb) of the run for the n_active codes of `list` (DEVICE), leaving their
 // records in w_info [n_active][nb].  The device is the caller's current one; w_cnt [C][5] is cleared; state [C][4] is the HOST result.
 template <class Piece>
-int codeset_stop_loop(size_t C, long long piece, int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
-                      long long max_batch, codeset_rule_ws &w, const int32_t *w_info, unsigned long long *w_cnt, unsigned long long *state, Piece run_piece) {
+int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
+                      long long max_batch, unsigned long long *state, Piece run_piece) {
+    const size_t C = (size_t)s.C;
+    codeset_rule_ws &w = s.stop;
     if (!w.rule) {
         HIP_TRY(hipMalloc(&w.rule, sizeof(unsigned long long) * 4 * C));
         HIP_TRY(hipMalloc(&w.running, sizeof(int32_t) * C));
@@ -277,7 +344,7 @@ int codeset_stop_loop(size_t C, long long piece, int n_frame_errors, long long n
     HIP_TRY(hipMemcpy(w.list, ident.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(w.running, ones.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(w.rule, 0, sizeof(unsigned long long) * 4 * C, nullptr));
-    HIP_TRY(hipMemsetAsync(w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
+    HIP_TRY(hipMemsetAsync(s.w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
     int32_t n_active = (int32_t)C;
     long long first = 0, batch = first_batch;   // every running code has consumed the same number of frames: `first`
     while (n_active > 0) {
@@ -287,7 +354,7 @@ int codeset_stop_loop(size_t C, long long piece, int n_frame_errors, long long n
         for (long long done = 0; done < B && n_active > 0; done += piece) {
             const long long nb = (B - done) < piece ? (B - done) : piece;
             if (int rc = run_piece(first + done, nb, w.list, n_active)) return rc;
-            const ldpc::CodesetRuleArgs ra{w_info, w.list, w.rule, w.running, nb, n_frame_errors, n_experiments, reference_frame_error};
+            const ldpc::CodesetRuleArgs ra{s.w_info, w.list, w.rule, w.running, nb, n_frame_errors, n_experiments, reference_frame_error};
             hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, w.running, (int)C, w.list, w.nactive);
@@ -316,8 +383,6 @@ int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, in
     return codeset_open("ldpc_hip_open_codes_tdmp", LDPC_HIP_TASP_DEC, rh, nh, M, hd, C, device, out);
 }
 
-int ldpc_hip_codes(const ldpc_hip_ctx *c);   // ldpc_gfq_codeset_api.hpp: a GF(q) code-set context answers too
-
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
                               int32_t *d_iters, double *d_soft, void *stream_) {
     if (int rc = codeset_ctx(c, "ldpc_hip_decode_codes_dev")) return rc;
@@ -338,51 +403,33 @@ int ldpc_hip_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks
     if (int rc = codeset_ctx(c, "ldpc_hip_simulate_codes")) return rc;
     if (!counters || B < 0 || first_frame < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes: bad argument");
     if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes: maxiter must be >= 1 (got %d)", maxiter);
-    ldpc_codeset_state *s = c->codes;
-    const size_t C = (size_t)s->C;
     ldpc::ChannelArgs ch{};
     if (int rc = awgn_sigma(c, snr_db, 0, punctured_blocks, &ch.sigma)) return rc;   // the common rate (nh - rh) / (nh - punctured_blocks)
     HIP_TRY(hipSetDevice(c->device));
     const long long piece = codeset_piece(c, B);
     if (int rc = codeset_reserve(c, piece)) return rc;
-    HIP_TRY(hipMemsetAsync(s->w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
     codeset_channel_args(c, punctured_blocks, seed, ch);
-    for (long long done = 0; done < B; done += piece) {
-        const long long nb = (B - done) < piece ? (B - done) : piece;
-        if (int rc = codeset_channel_launch(c, ch, first_frame + done, nb)) return rc;
-        if (int rc = ldpc_hip_decode_codes_dev(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr)) return rc;
-        if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, frame_info ? s->w_info : nullptr, s->w_cnt, nullptr)) return rc;
-        if (frame_info)   // [C][nb] on the device -> columns [done, done + nb) of the caller's [C][B]
-            HIP_TRY(hipMemcpy2D(frame_info + done, sizeof(int32_t) * (size_t)B, s->w_info, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
-                                hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(hipMemcpy(counters, s->w_cnt, sizeof(unsigned long long) * 5 * C, hipMemcpyDeviceToHost));
-    return 0;
+    return codeset_simulate_loop(*c->codes, piece, B, counters, frame_info, [&](long long first, long long nb) -> int {
+        return codeset_piece_launch(c, ch, maxiter, alpha, first_frame + first, nb, frame_info != nullptr, nullptr, 0);
+    });
 }
 
 int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed, long long first_frame,
                                  int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
                                  long long max_batch, unsigned long long *state) {
     if (int rc = codeset_ctx(c, "ldpc_hip_simulate_codes_stop")) return rc;
-    if (!state || first_frame < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: bad argument");
-    if (first_batch < 1 || max_batch < first_batch)
-        return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: batches of %lld .. %lld frames; 1 <= first_batch <= max_batch", first_batch, max_batch);
-    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_simulate_codes_stop: maxiter must be >= 1 (got %d)", maxiter);
-    ldpc_codeset_state *s = c->codes;
-    const size_t C = (size_t)s->C;
+    if (int rc = codeset_stop_args("ldpc_hip_simulate_codes_stop", state, first_frame, first_batch, max_batch, maxiter)) return rc;
     ldpc::ChannelArgs ch{};
     if (int rc = awgn_sigma(c, snr_db, 0, punctured_blocks, &ch.sigma)) return rc;   // the common rate (nh - rh) / (nh - punctured_blocks)
-    std::memset(state, 0, sizeof(unsigned long long) * 4 * C);
+    std::memset(state, 0, sizeof(unsigned long long) * 4 * (size_t)c->codes->C);
     if (n_frame_errors <= 0 || n_experiments < 0) return 0;   // :591 fails before the first frame
     HIP_TRY(hipSetDevice(c->device));
     const long long piece = codeset_piece(c, max_batch < n_experiments + 1 ? max_batch : n_experiments + 1);
     if (int rc = codeset_reserve(c, piece)) return rc;
     codeset_channel_args(c, punctured_blocks, seed, ch);
-    return codeset_stop_loop(C, piece, n_frame_errors, n_experiments, reference_frame_error, first_batch, max_batch, s->stop, s->w_info, s->w_cnt, state,
+    return codeset_stop_loop(*c->codes, piece, n_frame_errors, n_experiments, reference_frame_error, first_batch, max_batch, state,
                              [&](long long first, long long nb, const int32_t *list, int n_active) -> int {
-                                 if (int rc = codeset_channel_launch(c, ch, first_frame + first, nb)) return rc;
-                                 if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, list, n_active)) return rc;
-                                 return codeset_count_launch(c, s->w_hard, s->w_iters, nb, s->w_info, s->w_cnt, nullptr, list, n_active);
+                                 return codeset_piece_launch(c, ch, maxiter, alpha, first_frame + first, nb, true, list, n_active);
                              });
 }
 

@@ -1,11 +1,17 @@
 // Host side of FHT_DEC (decoder id 6, ldpc_gfq.hpp): what decod_open(FHT_DEC, q_bits, ...) + decod_init build once per context
-// (decoders.cpp:1104-1161) and the ldpc_hip_*gfq* entry points.  Included at the end of ldpc_hip.hip.
+// (decoders.cpp:1104-1161) and the ldpc_hip_*gfq* entry points.  What a GF(q) code-set context (ldpc_gfq_codeset_api.hpp) builds and
+// launches the same way lives here once: the graph of one code (gfq_graph), the mul | div tables (gfq_tables), the choice of the
+// kernel instance (gfq_choose, gfq_dispatch) and the sizing of the workspace slots (gfq_slots).  Included at the end of ldpc_hip.hip.
 #pragma once
+
+struct GfqKernel {                // the gfq_kernel / gfq_codes_kernel instance a context launches
+    bool spec = false;            // q = 16 / q = 64 instance
+    int ql = 0, lpc = 0;          // its check-node mapping
+};
 
 struct ldpc_gfq_state {
     int q_bits = 0, q = 0, ncoef = 0, cw2 = 0, max_rw = 0;
-    int ql = 0, lpc = 0;          // check-node mapping of the kernel this context launches
-    bool spec = false;            // q = 16 / q = 64 instance
+    GfqKernel kern;
     std::vector<int16_t> hc_after;   // hc as decod_init leaves it (ncols2convert applied)
     int32_t *d_i32 = nullptr;     // row_start | e_col | e_circ | e_rl | col_start | ce_edge
     int16_t *d_i16 = nullptr;     // mul | div
@@ -58,9 +64,116 @@ void gfq_field(int q_bits, std::vector<int> &lg, std::vector<int> &alog) {
     }
 }
 
-template <int QL, int LPC>
-int gfq_launch(const ldpc_gfq::Args &a, int grid, int threads, hipStream_t stream) {
-    hipLaunchKernelGGL((ldpc_gfq::gfq_kernel<QL, LPC>), dim3((unsigned)grid), dim3((unsigned)threads), 0, stream, a);
+// mul | div for the listed coefficients (p2table, decoders.cpp:6673-6750): mul[c][s] = s * coefs[c], div[c][s] = s / coefs[c], both
+// [coefs.size()][q]; the entries of s = 0 stay 0
+std::vector<int16_t> gfq_tables(int q_bits, const std::vector<int> &coefs) {
+    std::vector<int> lg, alog;
+    gfq_field(q_bits, lg, alog);
+    const int q = 1 << q_bits, ncoef = (int)coefs.size(), mod = q - 1;
+    std::vector<int16_t> tab((size_t)2 * ncoef * q, 0);
+    for (int c = 0; c < ncoef; ++c)
+        for (int s = 1; s < q; ++s) {
+            const int x = lg[s], y = lg[coefs[c]];
+            int r = x + y;
+            if (r >= mod) r -= mod;
+            tab[(size_t)c * q + s] = (int16_t)alog[r];
+            r = x - y;
+            if (r < 0) r += mod;
+            tab[(size_t)(ncoef + c) * q + s] = (int16_t)alog[r];
+        }
+    return tab;
+}
+
+// One code's graph as decod_init maps it: rows hold their edges in ascending column order (find_list_of_symbols, decoders.cpp:867-901),
+// columns theirs in ascending row order, cw2 = "every block column has weight 2" (find_column_weight, :837-865).
+struct GfqGraph {
+    std::vector<int32_t> row_start, col_start, e_col, e_circ, e_coef, ce_edge;   // e_coef: the coefficient of the edge, 1 .. q - 1
+    int cw2 = 0, max_rw = 0, E = 0;
+};
+
+// Builds g from the (hb, hc) of one code, with upstream's limits; every refusal starts with `pre`.  in_a_set: the rules a code set
+// reads differently -- it refuses a shift below -1 (a single code takes it as an empty circulant), and it does not read the coefficient
+// under an empty circulant (a single code refuses one >= q there, and names a negative one on a circulant "no coefficient").
+int gfq_graph(const char *pre, bool in_a_set, int rh, int nh, int M, int q, const int16_t *hb, const int16_t *hc, GfqGraph &g) {
+    g.row_start.assign((size_t)rh + 1, 0); g.col_start.assign((size_t)nh + 1, 0);
+    g.e_col.clear(); g.e_circ.clear(); g.e_coef.clear(); g.ce_edge.clear();
+    g.max_rw = 0;
+    for (int j = 0; j < rh; ++j) {
+        for (int k = 0; k < nh; ++k) {
+            const int s = hb[(size_t)j * nh + k], v = hc[(size_t)j * nh + k];
+            if (!in_a_set && v >= q) return fail(LDPC_HIP_EINVAL, "%scoefficient %d at (%d, %d) is not an element of GF(%d)", pre, v, j, k, q);
+            if (in_a_set && s < -1) return fail(LDPC_HIP_EINVAL, "%sshift %d at (%d, %d) is below -1", pre, s, j, k);
+            if (s < 0) continue;
+            if (!in_a_set && v < 0) return fail(LDPC_HIP_EINVAL, "%scirculant (%d, %d) has no coefficient", pre, j, k);
+            if (v < 0 || v >= q) return fail(LDPC_HIP_EINVAL, "%scoefficient %d at (%d, %d) is not an element of GF(%d)", pre, v, j, k, q);
+            if (v == 0)   // upstream files it under index q and then reads its logarithm table one entry past the end (decoders.cpp:884, :6692)
+                return fail(LDPC_HIP_EUNSUPPORTED, "%scoefficient 0 at (%d, %d): upstream's tables are undefined for it", pre, j, k);
+            g.e_col.push_back(k); g.e_circ.push_back(s % M); g.e_coef.push_back(v);
+        }
+        g.row_start[(size_t)j + 1] = (int32_t)g.e_col.size();
+        const int rw = g.row_start[(size_t)j + 1] - g.row_start[(size_t)j];
+        if (rw < 2)   // map_graph reads Sigma_backH[1] / Sigma_forwardH[rw-2] it never set (decoders.cpp:6355-6360)
+            return fail(LDPC_HIP_EUNSUPPORTED, "%sblock row %d has weight %d; upstream's check node needs at least 2", pre, j, rw);
+        if (rw > 1024)
+            return fail(LDPC_HIP_EUNSUPPORTED, "%sblock row %d has weight %d; at most 1024 is supported (upstream's RWMAX, decoders.cpp:73)", pre, j, rw);
+        if (rw > g.max_rw) g.max_rw = rw;
+    }
+    g.E = (int)g.e_col.size();
+    if ((long long)g.E * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "%s%lld edges, at most 2^28 - 1 are supported", pre, (long long)g.E * M);
+    g.cw2 = 1;
+    for (int k = 0; k < nh; ++k) {
+        for (int e = 0; e < g.E; ++e)
+            if (g.e_col[(size_t)e] == k) g.ce_edge.push_back(e);
+        g.col_start[(size_t)k + 1] = (int32_t)g.ce_edge.size();
+        if (g.col_start[(size_t)k + 1] - g.col_start[(size_t)k] != 2) g.cw2 = 0;
+    }
+    return 0;
+}
+
+// q = 16 and q = 64 have their own instances (LDPC_HIP_GFQ_GENERIC=1: the generic ones for them too)
+GfqKernel gfq_choose(int q) {
+    const char *genv = getenv("LDPC_HIP_GFQ_GENERIC");
+    const bool force_generic = genv && atoi(genv) != 0;
+    GfqKernel k;
+    if (!force_generic && q == 16) { k.spec = true; k.ql = 16; k.lpc = 1; }
+    else if (!force_generic && q == 64) { k.spec = true; k.ql = 16; k.lpc = 4; }
+    else { k.ql = q <= 256 ? 4 : q / 64; k.lpc = q / k.ql; }
+    return k;
+}
+
+std::string gfq_kernel_name(const char *kernel, int q, const GfqKernel &k) {
+    char name[64];
+    snprintf(name, sizeof name, "%s<%sq=%d,%dx%d>", kernel, k.spec ? "" : "generic,", q, k.ql, k.lpc);
+    return name;
+}
+
+// launch(QL, LPC) with the template arguments of the chosen instance as std::integral_constants
+template <class Launch>
+void gfq_dispatch(const GfqKernel &k, Launch launch) {
+    using std::integral_constant;
+    if (k.spec && k.lpc == 1) launch(integral_constant<int, 16>(), integral_constant<int, 1>());
+    else if (k.spec) launch(integral_constant<int, 16>(), integral_constant<int, 4>());
+    else if (k.ql == 4) launch(integral_constant<int, 4>(), integral_constant<int, 0>());
+    else if (k.ql == 8) launch(integral_constant<int, 8>(), integral_constant<int, 0>());
+    else launch(integral_constant<int, 16>(), integral_constant<int, 0>());
+}
+
+// One workgroup per slot of the workspace; the work items beyond the slots are worked off inside the launch, slot by slot.  Gives the
+// workgroup size and the slots of a launch over `items` work items, and grows d_ws [ws_slots][stride] to hold them.
+int gfq_slots(int num_cu, int R, int N, int lpc, size_t stride, long long items, char *&d_ws, int &ws_slots, int &threads, int &slots_out) {
+    const long long lanes = std::max((long long)R * lpc, (long long)N);
+    threads = (int)std::min(256LL, std::max(64LL, (lanes + 63) / 64 * 64));
+    long long slots = (long long)num_cu * 1024 / threads;
+    if (const char *e = getenv("LDPC_HIP_GFQ_SLOTS")) { if (atoll(e) > 0) slots = atoll(e); }
+    while (slots > 1 && (size_t)slots * stride > ((size_t)4 << 30)) slots /= 2;
+    if (slots > items) slots = items;
+    if (slots > ws_slots) {
+        if (d_ws) (void)hipFree(d_ws);
+        d_ws = nullptr; ws_slots = 0;
+        HIP_TRY(hipMalloc(&d_ws, (size_t)slots * stride));
+        ws_slots = (int)slots;
+    }
+    slots_out = (int)slots;
     return 0;
 }
 
@@ -82,85 +195,37 @@ int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, cons
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_gfq: device %d of %d", device, ndev);
 
-    // rows: edges in ascending column order; the coefficients in use, ascending (find_list_of_symbols, decoders.cpp:867-901)
-    std::vector<int32_t> row_start(rh + 1, 0), e_col, e_circ, e_coef;
+    GfqGraph gr;
+    if (int rc = gfq_graph("FHT_DEC: ", false, rh, nh, M, q, hb, hc, gr)) return rc;
+    // the tables hold the coefficients in use, ascending (find_list_of_symbols, decoders.cpp:867-901)
     std::vector<char> used(q, 0);
-    int max_rw = 0;
-    for (int j = 0; j < rh; ++j) {
-        for (int k = 0; k < nh; ++k) {
-            const int s = hb[(size_t)j * nh + k], v = hc[(size_t)j * nh + k];
-            if (v >= q) return fail(LDPC_HIP_EINVAL, "FHT_DEC: coefficient %d at (%d, %d) is not an element of GF(%d)", v, j, k, q);
-            if (s < 0) continue;
-            if (v < 0) return fail(LDPC_HIP_EINVAL, "FHT_DEC: circulant (%d, %d) has no coefficient", j, k);
-            if (v == 0)   // upstream files it under index q and then reads its logarithm table one entry past the end (decoders.cpp:884, :6692)
-                return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: coefficient 0 at (%d, %d): upstream's tables are undefined for it", j, k);
-            e_col.push_back(k); e_circ.push_back(s % M); e_coef.push_back(v);
-            used[v] = 1;
-        }
-        row_start[j + 1] = (int32_t)e_col.size();
-        const int rw = row_start[j + 1] - row_start[j];
-        if (rw < 2)   // map_graph reads Sigma_backH[1] / Sigma_forwardH[rw-2] it never set (decoders.cpp:6355-6360)
-            return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: block row %d has weight %d; upstream's check node needs at least 2", j, rw);
-        if (rw > 1024) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: row weight %d, at most 1024 is supported (upstream's RWMAX, decoders.cpp:73)", rw);
-        if (rw > max_rw) max_rw = rw;
-    }
-    const int E = (int)e_col.size();
-    if ((long long)E * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "FHT_DEC: %lld edges, at most 2^28 - 1 are supported", (long long)E * M);
+    for (int v : gr.e_coef) used[v] = 1;
     std::vector<int> coef_index(q, -1), coefs;
     for (int v = 1; v < q; ++v)
         if (used[v]) { coef_index[v] = (int)coefs.size(); coefs.push_back(v); }
-    std::vector<int32_t> e_rl(E);
-    for (int e = 0; e < E; ++e) e_rl[e] = coef_index[e_coef[e]];
-
-    // columns: edges in ascending row order, and upstream's "every block column has weight 2" (find_column_weight, :837-865)
-    std::vector<int32_t> col_start(nh + 1, 0), ce_edge;
-    int cw2 = 1;
-    for (int k = 0; k < nh; ++k) {
-        for (int j = 0; j < rh; ++j)
-            for (int e = row_start[j]; e < row_start[j + 1]; ++e)
-                if (e_col[e] == k) ce_edge.push_back(e);
-        col_start[k + 1] = (int32_t)ce_edge.size();
-        if (col_start[k + 1] - col_start[k] != 2) cw2 = 0;
-    }
-
-    // field and the tables per used coefficient (p2table, :6673-6750): mul[c][s] = s * coef, div[c][s] = s / coef, row 0 stays 0
-    std::vector<int> lg, alog;
-    gfq_field(q_bits, lg, alog);
-    const int ncoef = (int)coefs.size(), mod = q - 1;
-    std::vector<int16_t> tab((size_t)2 * ncoef * q, 0);
-    for (int c = 0; c < ncoef; ++c)
-        for (int s = 1; s < q; ++s) {
-            const int x = lg[s], y = lg[coefs[c]];
-            int r = x + y;
-            if (r >= mod) r -= mod;
-            tab[(size_t)c * q + s] = (int16_t)alog[r];
-            r = x - y;
-            if (r < 0) r += mod;
-            tab[(size_t)(ncoef + c) * q + s] = (int16_t)alog[r];
-        }
+    std::vector<int32_t> e_rl(gr.E);
+    for (int e = 0; e < gr.E; ++e) e_rl[e] = coef_index[gr.e_coef[e]];
+    const int ncoef = (int)coefs.size();
+    const std::vector<int16_t> tab = gfq_tables(q_bits, coefs);
 
     std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
     c->decoder_id = LDPC_HIP_FHT_DEC; c->device = device;
-    c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M; c->ne = E;
+    c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M; c->ne = gr.E;
     c->hard_words = (c->N + 31) / 32;
     ldpc_gfq_state *g = c->gfq = new ldpc_gfq_state();
-    g->q_bits = q_bits; g->q = q; g->ncoef = ncoef; g->cw2 = cw2; g->max_rw = max_rw;
+    g->q_bits = q_bits; g->q = q; g->ncoef = ncoef; g->cw2 = gr.cw2; g->max_rw = gr.max_rw;
     // the matrix decod_init leaves in hc: the first ncols2convert columns go from power to natural representation AFTER the
     // tables were made from the values as given (:1151-1159)
     g->hc_after.assign(hc, hc + (size_t)rh * nh);
     g->hb.assign(hb, hb + (size_t)rh * nh);
+    std::vector<int> lg, alog;
+    gfq_field(q_bits, lg, alog);
     for (int j = 0; j < rh; ++j)
         for (int k = 0; k < ncols2convert; ++k)
             if (g->hc_after[(size_t)j * nh + k] > -1) g->hc_after[(size_t)j * nh + k] = (int16_t)alog[g->hc_after[(size_t)j * nh + k]];
 
-    const char *genv = getenv("LDPC_HIP_GFQ_GENERIC");
-    const bool force_generic = genv && atoi(genv) != 0;
-    if (!force_generic && q == 16) { g->spec = true; g->ql = 16; g->lpc = 1; }
-    else if (!force_generic && q == 64) { g->spec = true; g->ql = 16; g->lpc = 4; }
-    else { g->ql = q <= 256 ? 4 : q / 64; g->lpc = q / g->ql; }
-    char name[64];
-    snprintf(name, sizeof name, "gfq_kernel<%sq=%d,%dx%d>", g->spec ? "" : "generic,", q, g->ql, g->lpc);
-    c->kernel_name = name;
+    g->kern = gfq_choose(q);
+    c->kernel_name = gfq_kernel_name("gfq_kernel", q, g->kern);
     c->last_launch = "";
 
     HIP_TRY(hipSetDevice(device));
@@ -169,9 +234,9 @@ int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, cons
     g->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
     std::vector<int32_t> i32;
     auto put = [&](const std::vector<int32_t> &v) { const size_t at = i32.size(); i32.insert(i32.end(), v.begin(), v.end()); return at; };
-    put(row_start);
-    g->off_e_col = put(e_col); g->off_e_circ = put(e_circ); g->off_e_rl = put(e_rl);
-    g->off_col_start = put(col_start); g->off_ce_edge = put(ce_edge);
+    put(gr.row_start);
+    g->off_e_col = put(gr.e_col); g->off_e_circ = put(gr.e_circ); g->off_e_rl = put(e_rl);
+    g->off_col_start = put(gr.col_start); g->off_ce_edge = put(gr.ce_edge);
     g->off_div = (size_t)ncoef * q;
     HIP_TRY(hipMalloc(&g->d_i32, sizeof(int32_t) * i32.size()));
     HIP_TRY(hipMemcpy(g->d_i32, i32.data(), sizeof(int32_t) * i32.size(), hipMemcpyHostToDevice));
@@ -180,8 +245,6 @@ int ldpc_hip_open_gfq(int q_bits, int rh, int nh, int M, const int16_t *hb, cons
     *out = c.release();
     return 0;
 }
-
-int ldpc_hip_gfq_q(const ldpc_hip_ctx *c);   // ldpc_gfq_codeset_api.hpp: a GF(q) code-set context answers too
 
 int ldpc_hip_gfq_coefficients(const ldpc_hip_ctx *c, int16_t *hc_out) {
     if (!c || !c->gfq || !hc_out) return fail(LDPC_HIP_EINVAL, "ldpc_hip_gfq_coefficients: not a GF(q) context, or null output");
@@ -201,46 +264,25 @@ int ldpc_hip_decode_gfq_dev(ldpc_hip_ctx *c, const double *d_soft, long long B, 
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream = (hipStream_t)stream_;
 
-    // one workgroup per frame slot; a batch beyond the slots is worked off inside the launch, slot by slot
-    const long long items = std::max((long long)c->R * g->lpc, (long long)c->N);
-    const int threads = (int)std::min(256LL, std::max(64LL, (items + 63) / 64 * 64));
     const size_t stride = ldpc_gfq::slot_bytes(c->ne, c->M, c->N, g->q);
-    long long slots = (long long)g->num_cu * 1024 / threads;
-    if (const char *e = getenv("LDPC_HIP_GFQ_SLOTS")) { if (atoll(e) > 0) slots = atoll(e); }
-    while (slots > 1 && (size_t)slots * stride > ((size_t)4 << 30)) slots /= 2;
-    if (slots > B) slots = B;
-    if (slots > g->ws_slots) {
-        if (g->d_ws) (void)hipFree(g->d_ws);
-        g->d_ws = nullptr; g->ws_slots = 0;
-        HIP_TRY(hipMalloc(&g->d_ws, (size_t)slots * stride));
-        g->ws_slots = (int)slots;
-    }
+    int threads = 0, slots = 0;   // one slot per frame in flight
+    if (int rc = gfq_slots(g->num_cu, c->R, c->N, g->kern.lpc, stride, B, g->d_ws, g->ws_slots, threads, slots)) return rc;
     ldpc_gfq::Args a{};
     a.soft = d_soft; a.qhard = d_qhard; a.iters = d_iters; a.post = d_post;
     a.ws = g->d_ws; a.ws_stride = stride; a.B = B; a.maxiter = maxiter;
-    a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.R = c->R; a.E = c->ne; a.q = g->q; a.lpc = g->lpc; a.cw2 = g->cw2;
+    a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.R = c->R; a.E = c->ne; a.q = g->q; a.lpc = g->kern.lpc; a.cw2 = g->cw2;
     a.row_start = g->d_i32; a.e_col = g->d_i32 + g->off_e_col; a.e_circ = g->d_i32 + g->off_e_circ; a.e_rl = g->d_i32 + g->off_e_rl;
     a.col_start = g->d_i32 + g->off_col_start; a.ce_edge = g->d_i32 + g->off_ce_edge;
     a.mul = g->d_i16; a.div = g->d_i16 + g->off_div;
 
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->prof) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
+    ProfTimer timer;
+    if (int rc = timer.begin(c, stream)) return rc;
     c->last_launch = c->kernel_name.c_str();
-    if (g->spec && g->lpc == 1) gfq_launch<16, 1>(a, (int)slots, threads, stream);
-    else if (g->spec) gfq_launch<16, 4>(a, (int)slots, threads, stream);
-    else if (g->ql == 4) gfq_launch<4, 0>(a, (int)slots, threads, stream);
-    else if (g->ql == 8) gfq_launch<8, 0>(a, (int)slots, threads, stream);
-    else gfq_launch<16, 0>(a, (int)slots, threads, stream);
+    gfq_dispatch(g->kern, [&](auto ql, auto lpc) {
+        hipLaunchKernelGGL((ldpc_gfq::gfq_kernel<decltype(ql)::value, decltype(lpc)::value>), dim3((unsigned)slots), dim3((unsigned)threads), 0, stream, a);
+    });
     HIP_TRY(hipGetLastError());
-    if (c->prof) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        c->events.emplace_back(ev0, ev1);
-    }
-    return 0;
+    return timer.end();
 }
 
 int ldpc_hip_decode_gfq_host(ldpc_hip_ctx *c, const double *soft, long long B, int maxiter, double p_thr, int16_t *qhard, int32_t *iters,

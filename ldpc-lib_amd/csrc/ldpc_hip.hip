@@ -324,6 +324,30 @@ int set_lds_limit(const void *kernel, size_t bytes) {
     return 0;
 }
 
+// HIP-event timing of one decode call (ldpc_hip_profile_enable): begin() before its launches; end() after them hands the two events
+// to c->events for ldpc_hip_profile_read.  A return in between destroys them.
+struct ProfTimer {
+    ldpc_hip_ctx *c = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int begin(ldpc_hip_ctx *ctx, hipStream_t s) {
+        if (!ctx->prof) return 0;
+        c = ctx; stream = s;
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+        return 0;
+    }
+    int end() {
+        if (!c) return 0;
+        HIP_TRY(hipEventRecord(ev1, stream));
+        c->events.emplace_back(ev0, ev1);
+        ev0 = ev1 = nullptr;
+        return 0;
+    }
+    ~ProfTimer() { for (hipEvent_t e : {ev0, ev1}) if (e) (void)hipEventDestroy(e); }
+};
+
 // Which code-specialised body serves this decoder / code shape, if any.  `required`: no generic kernel exists.
 struct SpecPlan { const char *body = nullptr; int threads = 0; size_t lds = 0; bool required = false; int frames_per_block = 1; };
 
@@ -691,12 +715,8 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
     hipStream_t stream = (hipStream_t)stream_;
     adopt_jit(c);
 
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->prof) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
+    ProfTimer timer;
+    if (int rc = timer.begin(c, stream)) return rc;
     bool use_spec = c->spec_aot || c->spec_jit;
     bool use_global = c->global_tier;
     const int ims_ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5458, MS_ALPHA_FPP = 4
@@ -865,11 +885,7 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
         }
     }
     HIP_TRY(hipGetLastError());
-    if (c->prof) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        c->events.emplace_back(ev0, ev1);
-    }
-    return 0;
+    return timer.end();
 }
 
 int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter, int decision, double alpha,
