@@ -411,13 +411,42 @@ __device__ __forceinline__ void pack_hard(u32 *dst, const int tid, Pred pred) {
 // see `at` below.  16 896 B at N = 2048: eight frames per CU stay resident (135 168 of 163 840 B).
 constexpr unsigned long kMsM64LdsBytes(unsigned long n) { return sizeof(double) * n + 512; }
 
+// ms_m64_body keeps the decoded check-to-variable values of its first block rows in registers from STATE1 to STATE3 (see
+// there): whole rows in ascending order while their edges fit into `budget`; a row that does not fit, and every row after it,
+// decode twice as before.  A code whose edges all fit keeps all of them.
+template <class C>
+constexpr int ms_m64_keep_rows(int budget) {
+    int edges = 0, rows = 0;
+    while (rows < C::RH && edges + C::RW[rows] <= budget) edges += C::RW[rows++];
+    return rows;
+}
+// The edge budget of the shipped body: 70 edges = block rows 0-9 of the (2048,1024) example code, 253 VGPRs without a spill at two
+// waves per SIMD; the next row (78 edges) spills 11 (profiles/r13_flagship_variants.txt, r13_flagship_isa_histogram.txt).
+constexpr int kMsM64KeepEdges = 70;
+// What the budget has to share the 256 registers with grows with the code: 5 per block row (m1, m2, the record word), 2 per block
+// column in flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row
+// before it uses it).  The example code (16 rows, 24 columns, width 8) leaves room for 70 edges = 140 registers; a code that
+// needs more for the rest gives the difference back, one edge per register (twice what the count asks: the allocator does not
+// pack as tightly as the count).  An edge count alone knows nothing of the number of block rows: codes of 20 and more block rows
+// spill with no edge kept at all, and with this second term they spill no more than that (cross-compiled 20 x 40, 24 x 32 and
+// 30 x 60 protographs: 12, 39 and 40 spilled VGPRs against 12, 40 and 137 before round 13).  Rows of weight 16 need no term of
+// their own: 8 x 32 with every row 16 wide keeps four rows in 232 VGPRs.
+template <class C>
+constexpr int ms_m64_keep_budget() {
+    constexpr int cols = C::NH < 24 ? C::NH : 24;
+    constexpr int others = 5 * C::RH + 2 * cols + 2 * C::WMAX, others_example = 5 * 16 + 2 * 24 + 2 * 8;
+    constexpr int cut = others > others_example ? others - others_example : 0;
+    return kMsM64KeepEdges > cut ? kMsM64KeepEdges - cut : 0;
+}
+
 template <class C>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
+    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
-    const double alpha = a.alpha;
+    const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
     long long fr = blockIdx.x;  // one wave per frame; with a.queue the wave goes on to further frames (uniform: an SGPR pair)
 
     // The image starts one block column (512 B) into the allocation, so a rotation needs no wrap arithmetic: variable
@@ -449,15 +478,34 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     int res = -a.maxiter;
     for (int iter = 0; iter < a.maxiter; ++iter) {
         // The channel LLRs are needed only in STATE2.  Instead of pinning 64 VGPRs for the whole kernel they are
-        // re-read every iteration (16 KiB per frame: L2 / Infinity-Cache hits after the first pass) right here, so the
-        // loads fly under STATE1's ALU work, and the registers are free again during STATE3 where pressure peaks.
+        // re-read every iteration (16 KiB per frame: L2 / Infinity-Cache hits after the first pass), and not before
+        // STATE2 itself: 16 block columns between STATE1 and STATE2, then 8 more at each group of 8 columns, 16 columns
+        // ahead.  At most 24 columns (48 VGPRs) are in flight, and none during STATE1 and STATE3 -- the registers go to
+        // `keep`.  (Until round 13 all 32 columns were loaded here, "under STATE1's ALU work"; the other wave of the SIMD
+        // covers the latency just as well: profiles/r13_flagship_variants.txt, placements (a), (b), (c).)
         double y[NH];
-        int yo = 0;
-        asm volatile("" : "+v"(yo));  // opaque per iteration: the loads must not be hoisted out of the loop again
-        static_for<0, NH>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            y[k] = yrow[yo + k * 64];
-        });
+        auto load_y = [&](auto K0, auto K1) {   // columns [K0, min(K1, NH))
+            int yo = 0;
+            asm volatile("" : "+v"(yo));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
+            static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                y[k] = yrow[yo + k * 64];
+            });
+        };
+        // The decoded c2v value of an edge is needed twice: here in STATE1 (cv, added into the variable) and in STATE3
+        // (x = alpha * cv, taken out of the variable's sum again).  Block rows [0, KR) keep cv in registers instead of
+        // decoding the record a second time: x = keep * |alpha| is ONE v_mul_f64 in place of compare, two selects, bfi and
+        // add, and the row's two products m1 * alpha, m2 * alpha go as well.  The bits are those of the second decode:
+        //   - the second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's sign), cv is
+        //     +-(pos == s ? m2 : m1) with the same sign bit and the same select, both from the same record;
+        //   - m1 and m2 are finite and in [0, 32767]: they start at 0.0 and are fmin / fmax against kMaxVal afterwards, which
+        //     never return a NaN;
+        //   - IEEE multiplication is sign-symmetric: (+-m) * |alpha| and +-(m * |alpha|) are the same bits, zeros and
+        //     denormals included (round-to-nearest does not look at the sign);
+        //   - -ffp-contract=off keeps this product and the subtraction after it apart, as it does for the second decode.
+        // Between STATE1 and STATE3 of a retained row m1[j] and m2[j] are dead, so a retained edge costs 2 registers and a
+        // retained row gives 4 back.
+        double keep[RH][C::WMAX];
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
@@ -474,6 +522,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 constexpr int s = decltype(S)::value;
                 const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
                 const double cv = signed_mag(aa, Wt);
+                if constexpr (j < KR) keep[j][s] = cv;
                 Wt = twice(Wt);
                 double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
                 if constexpr (C::FIRST[j][s]) *p = cv;
@@ -482,8 +531,10 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
         });
         // ---------------- STATE2 (:4670-4685): soft = y + acc*alpha (two roundings)
+        load_y(IC<0>{}, IC<16>{});
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
+            if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
             double *p = own(K);
             const double pr = *p * alpha;
             *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
@@ -498,10 +549,6 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             // opaque: otherwise the compiler keeps STATE1's 112 select masks and shifted sign words alive across the
             // whole iteration to reuse them here (SGPR + VGPR spills to scratch); recomputing costs 3 ops per edge.
             asm volatile("" : "+v"(mt));
-            const u32 pos = mt & 0xffu;
-            u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
-            double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
-            asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
             double r[RW];
@@ -509,12 +556,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 constexpr int s = decltype(S)::value;
                 r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
             });
-            static_for<0, RW>([&](auto S) {
+            // slot s with its old c2v value x taken out: sign word, min1 / min2 / min1 slot -- the same for both kinds of row
+            auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
-                sy ^= hi32(r[s]);
-                const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
-                const double x = signed_mag(aa, Wt);
-                Wt = twice(Wt);
                 const double tt = r[s] - x;              // v2c
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);  // (nS << 1) | sign(tt): slot s lands on bit RW-1-s
                 const double v = fabs(tt);
@@ -528,7 +572,27 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     npos = sel32(npos, (u32)s, c1);
                     nm1 = fmin(v, nm1);
                 }
-            });
+            };
+            if constexpr (j < KR) {
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    sy ^= hi32(r[s]);
+                    step(S, keep[j][s] * alpha_mag);     // STATE1's value: no second decode, see `keep`
+                });
+            } else {
+                const u32 pos = mt & 0xffu;
+                u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
+                double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
+                asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    sy ^= hi32(r[s]);
+                    const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
+                    const double x = signed_mag(aa, Wt);
+                    Wt = twice(Wt);
+                    step(S, x);
+                });
+            }
             failw |= sy;
             m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
             __builtin_amdgcn_sched_barrier(0);
