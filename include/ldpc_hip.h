@@ -451,11 +451,24 @@ int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd
  * (LDPC_HIP_EINVAL; map_bin reads SB[1]), no empty block column, any nh; LDPC_HIP_EUNSUPPORTED when the LDS image of a workgroup,
  * floor(64 / M) * 8 * (nh * M + ne_max * M) + 16 bytes with ne_max the largest number of circulants of a code, exceeds 160 KiB. */
 int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* The same for the integer advanced sum-product decoder (LDPC_HIP_IASP_DEC; isum_prod_gf2_decod_qc_lm, decoders.cpp:3822-4121, imap_bin
+ * :2235-2271), both of its branches: a code whose block columns all hold two circulants takes upstream's own branch, decided per code.
+ * An ordinary code-set context, served by the entry points below (alpha is ignored).  rh and nh are NOT limited (nothing is kept per
+ * block row or column: the 30 x 60, M = 67 shape of upstream's input12L.jsonx fits).  Limits: M <= 512, row weights 2 .. 16 (imap_bin
+ * reads SB[1]), no empty block column, at most 65535 circulants per code (LDPC_HIP_EINVAL); LDPC_HIP_EUNSUPPORTED when the LDS image
+ * of a workgroup, floor(64 / M) * 2 * (ne_max * M + 2 * nh * M) bytes rounded up to 16, + 16, with ne_max the largest number of
+ * circulants of a code, exceeds 160 KiB.
+ * Measured (profiles/r14_codeset_iasp_time.txt; 30 x 60, M = 67, 50 iterations, 1.0 dB, 4096 frames per code): the set is SLOWER than
+ * one ldpc_hip_open context per code on the shape-unlimited tier (JIT off): 621 against 518 ms at 16 codes (0.83x), 9896 against
+ * 8297 ms at 256 (0.84x), 42.7 against 32.5 ms for one code; an unseen code through hiprtc in the foreground costs 36.2 s. */
+int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
-/* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) upload, built on the host (no GPU
- * needed; the same checks and return codes): per code
+/* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
+ * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
  * row_start[rh + 1] (relative to the code's own edge list) followed by its edges (block column << 16) | shift, rows then columns
- * ascending; offsets [C] = index of each code's row_start[0] in the table.  *length = entries of the table; offsets and table may
+ * ascending; offsets [C] = index of each code's row_start[0] in the table.  An IASP_DEC record goes on with cw2 (1: every block
+ * column holds exactly two circulants), col_start[nh + 1] and col_edges (row-major index of the edge in its code << 16) | shift,
+ * columns then rows ascending.  *length = entries of the table; offsets and table may
  * be NULL (sizes only), capacity = room in table. */
 int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                               long long capacity, long long *length);
@@ -471,7 +484,7 @@ int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *ctx, const uint32_t *d_hard, c
 /* Frames [first_frame, first_frame + B) of every code through channel -> decode -> count; the BPSK LLRs are drawn ONCE (the noise of
  * ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word, keyed by seed, global frame and position) and shared by the
  * codes, so counters[c] equals what ldpc_hip_simulate returns for code c alone with the same seed and frame range.  sigma uses the
- * common rate (nh - rh) / (nh - punctured_blocks); punctured positions carry 0.5, or 0.0 for a TDMP set, as in ldpc_hip_awgn_llr_dev.  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
+ * common rate (nh - rh) / (nh - punctured_blocks); punctured positions carry 0.5, or 0.0 for a TDMP or IASP set, as in ldpc_hip_awgn_llr_dev.  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
  * NULL.  B is worked off in pieces of the context's workspace (LDPC_HIP_CODES_PIECE=n caps the frames per piece); the result does
  * not depend on the pieces or on how B is split over calls with consecutive first_frame.
  * The workspace belongs to the context: one ldpc_hip_simulate_codes call at a time per context, on the null stream; callers that

@@ -188,6 +188,7 @@ def load_library():
     lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
     lib.ldpc_hip_open_codes.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_open_codes_tdmp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_open_codes_iasp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_codes.argtypes = [vp]
     lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
@@ -655,7 +656,8 @@ def _code_stack(codes):
 
 def codes_table(decoder_id, codes, M):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
-    int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order."""
+    int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
+    DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
@@ -670,8 +672,8 @@ def codes_table(decoder_id, codes, M):
 
 class LdpcHipCodes:
     """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
-    (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP): what a code search scores.  decoder_id DEC_MS, DEC_LMS or DEC_TASP;
-    bit-identical to LdpcHip on each matrix."""
+    (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP): what a code search scores.
+    decoder_id DEC_MS, DEC_LMS, DEC_TASP or DEC_IASP; bit-identical to LdpcHip on each matrix."""
 
     def __init__(self, decoder_id, codes, M, device=0):
         self.lib = load_library()
@@ -679,11 +681,12 @@ class LdpcHipCodes:
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        if self.decoder_id == DEC_TASP:
-            rc = self.lib.ldpc_hip_open_codes_tdmp(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
+        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp"}.get(self.decoder_id)
+        if own:
+            rc = getattr(self.lib, own)(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         else:
             rc = self.lib.ldpc_hip_open_codes(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
-        _check(self.lib, rc, "ldpc_hip_open_codes_tdmp" if self.decoder_id == DEC_TASP else "ldpc_hip_open_codes")
+        _check(self.lib, rc, own or "ldpc_hip_open_codes")
         self.h = h
         self.N = self.lib.ldpc_hip_n(h)
         self.R = self.lib.ldpc_hip_r(h)

@@ -13,9 +13,9 @@
 //   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N];
 //   * a launch may cover a subset of the codes: code_list[n_active] names the code of every slot blockIdx.x / blocks_per_code (null =
 //     the identity).  The graph table and the per-code LLR slice follow the code, the outputs follow the slot ([n_active][B]...).
-// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel compute (fp64, reference operation order,
-// contraction off); only the frame index and the table base differ (and, for TDMP, where the state lives), so the results are
-// bit-identical to a single-code context.
+// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel compute (fp64,
+// reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp); only the frame index and the table
+// base differ (and, for TDMP and IASP, where the state lives), so the results are bit-identical to a single-code context.
 #pragma once
 
 #include "ldpc_kernels.hpp"
@@ -36,7 +36,7 @@ struct CodesetArgs {
     int blocks_per_code;      // ceil(B / F)
     int C, rh, nh, M, N, F, maxiter, hard_words;
     double alpha;
-    int ne_max;               // tasp_layered_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
+    int ne_max;               // tasp_layered_codes_kernel, iasp_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
 };
 
 // The graph table is read-only for the whole launch and its addresses are wave-uniform: reading it through the constant address
@@ -456,6 +456,169 @@ __global__ void __launch_bounds__(MW ? 512 : 64) tasp_layered_codes_kernel(const
     }
     if (a.soft_out)
         for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = post[(k * M + n) * F + f];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Integer advanced sum-product (decoder 5): isum_prod_gf2_decod_qc_lm (decoders.cpp:3822-4121, imap_bin :2235-2271, icheck_syndrome
+// :3772-3803) on work item (c, w), written as iasp_global_kernel (ldpc_global.hpp) writes it -- the same calls of ldpc_spec::iasp
+// in the same order -- with the state on chip instead of in a workspace:
+//   * table record of a code: row_start[rh+1] | edges[ne] | cw2 | col_start[nh+1] | col_edges[ne], col_edges = (slot << 16) | shift
+//     with rows ascending, slot = the edge's row-major index inside its own code; cw2 = every block column holds two circulants;
+//   * LDS, all u16 and interleaved over the F frames of a packed wave: the per-edge state ST[ne_max][M][F] (ST[e][n] belongs to check
+//     n of edge e's block row), the a-posteriori word so[N][F], the channel word ych[N][F], then the vote flag:
+//     F * 2 * (ne_max * M + 2 * N) bytes, rounded up to 16, + 16 (iasp_codes_words_bytes).  Lanes n and n + 1 of a frame share a dword
+//     when F = 1, frames f and f + 1 of a check otherwise: consecutive lanes read and write consecutive halfwords either way;
+//   * check phase: lane n owns check n of block row j, j in a run-time loop -- nothing of a row outlives it, so rh is unbounded.
+//     P[] and imap_bin's forward products SF[] are VGPRs with static indices (the pass is unrolled RWM times under the wave-uniform
+//     predicate i < rw); the backward product is one register while slot i is finished.  The rows touch disjoint edges;
+//   * variable phase: lane t owns variable t of block column k, k in a run-time loop; the column's edges in a run-time loop (any
+//     column weight), or upstream's own branch for a code whose columns all have weight 2 (the flag is per code, wave-uniform).
+// A converged frame of a packed wave (and a frame beyond B) stores nothing more: its state and outputs stay as they were.
+// ---------------------------------------------------------------------------------------------------------
+__host__ __device__ inline size_t iasp_codes_words_bytes(int F, int M, int N, int ne_max) {   // the u16 arrays in front of the vote flag
+    return ((size_t)F * 2 * ((size_t)ne_max * M + 2 * (size_t)N) + 15) & ~(size_t)15;
+}
+
+template <int RWM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) iasp_codes_kernel(const CodesetArgs s) {
+    namespace I = ldpc_spec::iasp;
+    extern __shared__ double lds[];
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const int M = a.M, F = MW ? 1 : a.F, N = a.N, rh = a.rh, nh = a.nh;             // one frame per multi-wave workgroup
+    const TabPtr rs = tab_ptr(a.row_start);                                         // the code's record; its parts by offset
+    const int ne = rs[rh], MF = M * F;
+    const int ed = rh + 1, cs = ed + ne + 1, ce = cs + nh + 1;                      // edges[], col_start[], col_edges[]
+    const bool cw2 = rs[ed + ne] != 0;
+    uint16_t *const ST = reinterpret_cast<uint16_t *>(lds);
+    uint16_t *const so = ST + s.ne_max * M * F, *const ych = so + N * F;
+    int *const sh_flag = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + iasp_codes_words_bytes(F, M, N, s.ne_max));
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+    auto back = [&](int t, int c) { const int x = t - c; return x < 0 ? x + M : x; };   // the check of variable t on an edge of shift c
+    // where the frame's outputs go, per lane (VGPRs): the scalar registers are the scarce ones in the loops below
+    uint32_t *const hard_fr = a.hard ? a.hard + fr * a.hard_words : nullptr;
+    int32_t *const iters_fr = a.iters ? a.iters + fr : nullptr;
+    double *const soft_fr = a.soft_out ? a.soft_out + fr * N + n : nullptr;
+
+    if (valid) {                                                                    // :3858-3897
+        for (int k = 0; k < nh; ++k) {
+            const uint32_t q = I::q12(I::prior(live ? a.llr[fr * N + k * M + n] : 0.0));
+            for (int c = rs[cs + k]; c < rs[cs + k + 1]; ++c) {                     // state <- rotated Q12 value
+                const uint32_t d = (uint32_t)rs[ce + c];
+                ST[((int)(d >> 16) * M + back(n, (int)(d & 0xffffu))) * F + f] = (uint16_t)q;
+            }
+            so[(k * M + n) * F + f] = ych[(k * M + n) * F + f] = (uint16_t)(q << 4);   // then the words, Q16
+        }
+    }
+    if (MW) __syncthreads();
+
+    auto syndrome_fail = [&]() -> bool {                                            // icheck_syndrome :3772-3803
+        uint32_t failw = 0;
+        for (int j = 0; j < rh; ++j) {
+            const int e0 = rs[j], e1 = rs[j + 1];
+            uint32_t sy = 0;
+            for (int e = e0; e < e1; ++e) {
+                const uint32_t d = (uint32_t)rs[ed + e];
+                sy ^= (uint32_t)so[((int)(d >> 16) * M + rot_idx(n, (int)(d & 0xffffu), M)) * F + f] >> 15;
+            }
+            failw |= sy;
+        }
+        return valid && failw;
+    };
+
+    bool done = !inb;
+    int res = -a.maxiter;
+    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);          // :3899-3906
+    if (!done && !frame_fail) { done = true; res = 0; }                             // a codeword at the input: no iteration, 0
+    for (int steps = 0; steps < a.maxiter;) {
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+        const bool wr = !done && valid;
+        for (int j = 0; j < rh; ++j) {                                              // imap_bin :2235-2271, row weights 2 .. RWM
+            const int e0 = rs[j], rw = rs[j + 1] - e0;
+            int z = (e0 * M + n) * F + f;                                           // slot i of the check: ST[z], z walks up, then down
+            int P[RWM], SF[RWM];
+            int fw = 0;
+#pragma unroll
+            for (int i = 0; i < RWM; ++i) {                                         // forward products; SF[rw - 1] is never read
+                P[i] = 0; SF[i] = 0;
+                if (i < rw) {
+                    P[i] = I::chk_p(ST[z]);
+                    z += MF;
+                    fw = i == 0 ? P[i] : I::i16(I::chk_mul(P[i], fw));
+                    SF[i] = fw;
+                }
+            }
+            int sb = 0;                                                             // backward: SB[i + 1] while slot i is written
+#pragma unroll
+            for (int i = RWM - 1; i >= 0; --i) {
+                if (i < rw) {
+                    uint32_t out;
+                    z -= MF;
+                    if (i == 0) out = I::chk_out(sb);
+                    else if (i == rw - 1) { out = I::chk_out(SF[i - 1]); sb = P[i]; }   // SF[rw - 2]
+                    else { out = I::chk_out(I::chk_mul(SF[i - 1], sb)); sb = I::i16(I::chk_mul(P[i], sb)); }
+                    if (wr) ST[z] = (uint16_t)out;
+                }
+            }
+        }
+        if (MW) __syncthreads();
+        if (cw2) {
+            for (int k = 0; k < nh; ++k) {                                          // :3915-3977
+                const int c0 = rs[cs + k];
+                const uint32_t g0 = (uint32_t)rs[ce + c0], g1 = (uint32_t)rs[ce + c0 + 1];   // rows ascending
+                const int v = (k * M + n) * F + f;
+                const int z0 = ((int)(g0 >> 16) * M + back(n, (int)(g0 & 0xffffu))) * F + f;
+                const int z1 = ((int)(g1 >> 16) * M + back(n, (int)(g1 & 0xffffu))) * F + f;
+                uint32_t sv, d0, d1;
+                I::cw2(ych[v], ST[z0], ST[z1], sv, d0, d1);
+                if (wr) { so[v] = (uint16_t)sv; ST[z0] = (uint16_t)d0; ST[z1] = (uint16_t)d1; }
+            }
+        } else {
+            for (int k = 0; k < nh; ++k) {                                          // :3978-4100
+                const int c0 = rs[cs + k], c1 = rs[cs + k + 1];
+                const int v = (k * M + n) * F + f;
+                const uint32_t y = ych[v];
+                uint32_t P1 = y << 16, P0 = (65536u - y) << 16;
+                for (int c = c0; c < c1; ++c) {                                     // rows ascending
+                    const uint32_t d = (uint32_t)rs[ce + c];
+                    I::col_mul(P1, P0, ST[((int)(d >> 16) * M + back(n, (int)(d & 0xffffu))) * F + f]);
+                }
+                const uint32_t sv = I::col_soft(P1, P0);
+                if (wr) so[v] = (uint16_t)sv;
+                for (int c = c0; c < c1; ++c) {
+                    const uint32_t d = (uint32_t)rs[ce + c];
+                    const int zi = ((int)(d >> 16) * M + back(n, (int)(d & 0xffffu))) * F + f;
+                    const uint32_t nd = I::local_update(sv, ST[zi]);
+                    if (wr) ST[zi] = (uint16_t)nd;
+                }
+            }
+        }
+        if (MW) __syncthreads();
+        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);           // :4104-4113
+        ++steps;
+        if (!done && !frame_fail) { done = true; res = steps; }                     // else -steps = -maxiter at the end
+    }
+    // hard bit = so >> 15, soft output = so / 65536 (imake_output :3805-3820, decision 1)
+    if (!live) return;
+    if (n == 0 && iters_fr) *iters_fr = res;
+    if (hard_fr) {
+        for (int wd = n; wd < a.hard_words; wd += M) {
+            uint32_t bits = 0;
+            for (int b = 0; b < 32; ++b) {
+                const int v = 32 * wd + b;
+                if (v < N) bits |= (uint32_t)(so[v * F + f] >> 15) << b;
+            }
+            hard_fr[wd] = bits;
+        }
+    }
+    if (soft_fr)
+        for (int k = 0; k < nh; ++k) soft_fr[k * M] = (double)so[(k * M + n) * F + f] / 65536.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------

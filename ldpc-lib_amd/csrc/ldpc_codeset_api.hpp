@@ -46,40 +46,44 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
 namespace {
 
 // Dynamic LDS of the code-set kernels.  MS / LMS: the a-posteriori values of F frames + the vote flag.  TDMP: the a-posteriori
-// probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.
+// probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.  IASP: the u16 state ST[ne_max][M], a-posteriori
+// word and channel word of F frames, rounded up to 16 bytes, + the vote flag.
 size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
+    if (decoder_id == LDPC_HIP_IASP_DEC) return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16;
     const size_t per_frame = (size_t)nh * M + (decoder_id == LDPC_HIP_TASP_DEC ? (size_t)ne_max * M : 0);
     return sizeof(double) * per_frame * (size_t)F + 16;
 }
 
 // Checks a code set and builds its table: per code row_start[rh+1] (relative to the code's own edge list) then edges[]
-// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  The one place where
-// the limits of the three set kernels live.
+// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  An IASP record goes on
+// with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and col_edges[]
+// ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  The one place where the limits
+// of the set kernels live.
 int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
                   std::vector<int32_t> &tab, int *ne_max_out = nullptr) {
-    const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
+    const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC, iasp = decoder_id == LDPC_HIP_IASP_DEC;
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
+    if (!iasp && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
     if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
     const int F = M > 64 ? 1 : 64 / M;
-    if (codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)
+    if (!iasp && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP: with the byte count, once ne_max is known
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
     off.clear(); tab.clear();
-    std::vector<char> col_used((size_t)nh);
+    std::vector<int> col_w((size_t)nh);
     int ne_max = 0;
     for (int c = 0; c < C; ++c) {
         const int16_t *h = hd + (size_t)c * rh * nh;
-        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh >= ((size_t)1 << 31))
+        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (iasp ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
             return fail(LDPC_HIP_EINVAL, "%s: the table of %d codes exceeds 2^31 entries", who, C);
         off.push_back((int32_t)tab.size());
         const size_t rs = tab.size();
         tab.resize(rs + (size_t)rh + 1);
-        std::fill(col_used.begin(), col_used.end(), 0);
+        std::fill(col_w.begin(), col_w.end(), 0);
         int ne = 0;
         for (int j = 0; j < rh; ++j) {
             tab[rs + j] = ne;
@@ -89,19 +93,40 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
                 if (v < -1 || v >= M) return fail(LDPC_HIP_EINVAL, "%s: code %d, shift %d at (%d, %d) is outside [-1, %d)", who, c, v, j, k, M);
                 if (v == -1) continue;
                 tab.push_back((int32_t)(((uint32_t)k << 16) | (uint32_t)v));
-                col_used[(size_t)k] = 1;
+                ++col_w[(size_t)k];
                 ++rw; ++ne;
             }
             if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
             if (rw > kRWM) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
             if (tdmp && rw < 2)   // map_bin reads SB[1] (decoders.cpp:2191-2228)
                 return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; TDMP sum-product needs at least 2", who, c, j, rw);
+            if (iasp && rw < 2)   // imap_bin reads SB[1] (decoders.cpp:2235-2271)
+                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; integer advanced sum-product needs at least 2", who, c, j, rw);
         }
         tab[rs + rh] = ne;
         ne_max = ne > ne_max ? ne : ne_max;
         for (int k = 0; k < nh; ++k)
-            if (!col_used[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
+            if (!col_w[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
+        if (iasp) {
+            if (ne > 65535) return fail(LDPC_HIP_EINVAL, "%s: code %d has %d circulants; a column entry names its edge in 16 bits", who, c, ne);
+            bool cw2 = true;   // the rule of ldpc_hip_open, per code
+            for (int k = 0; k < nh; ++k) cw2 = cw2 && col_w[(size_t)k] == 2;
+            tab.push_back(cw2 ? 1 : 0);
+            const size_t cst = tab.size(), ed = rs + (size_t)rh + 1;
+            tab.resize(cst + (size_t)nh + 1 + (size_t)ne);
+            int q = 0;
+            for (int k = 0; k < nh; ++k) { tab[cst + k] = q; q += col_w[(size_t)k]; }
+            tab[cst + nh] = q;
+            std::vector<int> fill(tab.begin() + (long)cst, tab.begin() + (long)cst + nh);
+            for (int e = 0; e < ne; ++e) {   // row-major order: the rows of a column come out ascending
+                const uint32_t d = (uint32_t)tab[ed + (size_t)e];
+                tab[cst + (size_t)nh + 1 + (size_t)fill[d >> 16]++] = (int32_t)(((uint32_t)e << 16) | (d & 0xffffu));
+            }
+        }
     }
+    if (iasp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d circulants x %d checks + 2 x %d variables) halfwords need an LDS image of %zu bytes; the limit is 160 KiB",
+                    who, F, ne_max, M, nh * M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
     if (tdmp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB",
                     who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
@@ -184,13 +209,15 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
-    c->ne = (int)(tab.size() - (size_t)C * (rh + 1));   // edges of the whole set
+    c->ne = decoder_id == LDPC_HIP_IASP_DEC ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
+                                            : (int)(tab.size() - (size_t)C * (rh + 1));
     c->hard_words = (c->N + 31) / 32;
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
     c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max);
-    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" : "tasp_layered_codes_kernel") +
+    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" :
+                                 decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : "tasp_layered_codes_kernel") +
                      (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
@@ -220,6 +247,8 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     const void *k;
     if (c->decoder_id == LDPC_HIP_TASP_DEC)   // alpha is not read
         k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
+    else if (c->decoder_id == LDPC_HIP_IASP_DEC)   // alpha is not read here either
+        k = c->multiwave ? (const void *)ldpc::iasp_codes_kernel<kRWM, true> : (const void *)ldpc::iasp_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_MS_DEC)
         k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
     else
@@ -276,7 +305,7 @@ void codeset_channel_args(const ldpc_hip_ctx *c, int punctured_blocks, uint64_t 
     ch.llr = c->codes->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
     ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
     ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_IASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
 }
 
 int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long long first_frame, long long nb) {
@@ -374,13 +403,17 @@ extern "C" {
 
 int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     if (out) *out = nullptr;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP sets open through ldpc_hip_open_codes_tdmp
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP and IASP sets open through ldpc_hip_open_codes_tdmp / _iasp
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", decoder_id);
     return codeset_open("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     return codeset_open("ldpc_hip_open_codes_tdmp", LDPC_HIP_TASP_DEC, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    return codeset_open("ldpc_hip_open_codes_iasp", LDPC_HIP_IASP_DEC, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
