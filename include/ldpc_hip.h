@@ -462,6 +462,18 @@ int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, in
  * one ldpc_hip_open context per code on the shape-unlimited tier (JIT off): 621 against 518 ms at 16 codes (0.83x), 9896 against
  * 8297 ms at 256 (0.84x), 42.7 against 32.5 ms for one code; an unseen code through hiprtc in the foreground costs 36.2 s. */
 int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* The same for the low-complexity high-efficiency decoder (LDPC_HIP_LCHE_DEC; lche_decod, decoders.cpp:2899-3012, map_bin_llr
+ * :2815-2890, logexp_int :2777-2813): an ordinary code-set context, served by the entry points below (alpha is ignored), kernel
+ * lche_layered_codes_kernel.  rh and nh are NOT limited (nothing is kept per block row or column).  Limits: M <= 512, row weights
+ * 1 .. 16, no empty block row or column, shifts in [-1, M), C >= 1 (LDPC_HIP_EINVAL); LDPC_HIP_EUNSUPPORTED when the LDS image of a
+ * workgroup, floor(64 / M) * 8 * (nh * M + ne_max * M) + 8 * 310 + 16 bytes (the a-posteriori LLRs, the per-edge state, the 96 + 214
+ * table words of logexp_int, the vote flag) with ne_max the largest number of circulants of a code, exceeds 160 KiB.
+ * ldpc_hip_open_codes(LDPC_HIP_LCHE_DEC, ...) stays LDPC_HIP_EINVAL.
+ * Measured (profiles/r15_codeset_lche_time.txt; 50 iterations, 4096 frames per code, wall time against one ldpc_hip_open context per
+ * code on the shape-unlimited tier, JIT off): 16 x 32, M = 64, 1.5 dB: 86.8 against 225.0 ms at 16 codes (2.59x), 1405 against 3660 ms
+ * at 256 (2.61x), 7.9 against 15.4 ms for one code; 30 x 60, M = 67, 2.0 dB: 401 against 572 ms at 16 codes (1.43x), 6434 against
+ * 9315 ms at 256 (1.45x); an unseen 16 x 32 code through hiprtc in the foreground costs 1.05 s. */
+int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
 /* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
  * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
@@ -472,6 +484,10 @@ int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context 
  * be NULL (sizes only), capacity = room in table. */
 int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                               long long capacity, long long *length);
+/* The table ldpc_hip_open_codes_lche uploads, with its checks and return codes: per code row_start[rh + 1] followed by its edges, the
+ * record of MS_DEC.  (ldpc_hip_codes_table_host(LDPC_HIP_LCHE_DEC, ...) stays LDPC_HIP_EINVAL.) */
+int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
+                                   long long *length);
 /* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
  * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
  * maxiter >= 1.  Asynchronous on `stream`. */
@@ -484,7 +500,7 @@ int ldpc_hip_count_errors_codes_dev(ldpc_hip_ctx *ctx, const uint32_t *d_hard, c
 /* Frames [first_frame, first_frame + B) of every code through channel -> decode -> count; the BPSK LLRs are drawn ONCE (the noise of
  * ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word, keyed by seed, global frame and position) and shared by the
  * codes, so counters[c] equals what ldpc_hip_simulate returns for code c alone with the same seed and frame range.  sigma uses the
- * common rate (nh - rh) / (nh - punctured_blocks); punctured positions carry 0.5, or 0.0 for a TDMP or IASP set, as in ldpc_hip_awgn_llr_dev.  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
+ * common rate (nh - rh) / (nh - punctured_blocks); punctured positions carry 0.5, or 0.0 for a TDMP, IASP or LCHE set, as in ldpc_hip_awgn_llr_dev.  Synchronous; counters [C][5] (HOST, overwritten), frame_info [C][B] (HOST) or
  * NULL.  B is worked off in pieces of the context's workspace (LDPC_HIP_CODES_PIECE=n caps the frames per piece); the result does
  * not depend on the pieces or on how B is split over calls with consecutive first_frame.
  * The workspace belongs to the context: one ldpc_hip_simulate_codes call at a time per context, on the null stream; callers that

@@ -189,6 +189,8 @@ def load_library():
     lib.ldpc_hip_open_codes.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_open_codes_tdmp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_open_codes_iasp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_open_codes_lche.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_codes_table_lche_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
     lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
@@ -657,23 +659,30 @@ def _code_stack(codes):
 def codes_table(decoder_id, codes, M):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
-    DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order."""
+    DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order.  DEC_LCHE: the record of
+    DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host)."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
     n = C.c_longlong()
-    _check(lib, lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, None, None, 0, C.byref(n)), "ldpc_hip_codes_table_host")
+    if int(decoder_id) == DEC_LCHE:
+        who = "ldpc_hip_codes_table_lche_host"
+        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_lche_host(rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
+    else:
+        who = "ldpc_hip_codes_table_host"
+        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
+    _check(lib, call(None, None, 0, C.byref(n)), who)
     off = np.empty(Cn, dtype=np.int32)
     tab = np.empty(n.value, dtype=np.int32)
-    _check(lib, lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off.ctypes.data, tab.ctypes.data, n.value, None),
-           "ldpc_hip_codes_table_host")
+    _check(lib, call(off.ctypes.data, tab.ctypes.data, n.value, None), who)
     return off, tab
 
 
 class LdpcHipCodes:
     """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
-    (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP): what a code search scores.
-    decoder_id DEC_MS, DEC_LMS, DEC_TASP or DEC_IASP; bit-identical to LdpcHip on each matrix."""
+    (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP, ldpc_hip_open_codes_lche for
+    DEC_LCHE): what a code search scores.  decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP or DEC_LCHE; bit-identical to LdpcHip on
+    each matrix."""
 
     def __init__(self, decoder_id, codes, M, device=0):
         self.lib = load_library()
@@ -681,7 +690,7 @@ class LdpcHipCodes:
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp"}.get(self.decoder_id)
+        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp", DEC_LCHE: "ldpc_hip_open_codes_lche"}.get(self.decoder_id)
         if own:
             rc = getattr(self.lib, own)(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         else:

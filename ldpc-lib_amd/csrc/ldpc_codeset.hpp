@@ -13,13 +13,14 @@
 //   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N];
 //   * a launch may cover a subset of the codes: code_list[n_active] names the code of every slot blockIdx.x / blocks_per_code (null =
 //     the identity).  The graph table and the per-code LLR slice follow the code, the outputs follow the slot ([n_active][B]...).
-// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel compute (fp64,
-// reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp); only the frame index and the table
-// base differ (and, for TDMP and IASP, where the state lives), so the results are bit-identical to a single-code context.
+// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel / lche_global_kernel
+// compute (fp64, reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp; LCHE: ldpc_spec::lche);
+// only the frame index and the table base differ (and, for TDMP, IASP and LCHE, where the state lives), so the results are
+// bit-identical to a single-code context.
 #pragma once
 
 #include "ldpc_kernels.hpp"
-#include "ldpc_spec.hpp"   // exp_glibc
+#include "ldpc_spec.hpp"   // exp_glibc, iasp, lche
 
 namespace ldpc {
 
@@ -36,7 +37,7 @@ struct CodesetArgs {
     int blocks_per_code;      // ceil(B / F)
     int C, rh, nh, M, N, F, maxiter, hard_words;
     double alpha;
-    int ne_max;               // tasp_layered_codes_kernel, iasp_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
+    int ne_max;               // tasp_layered_codes_kernel, iasp_codes_kernel, lche_layered_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
 };
 
 // The graph table is read-only for the whole launch and its addresses are wave-uniform: reading it through the constant address
@@ -619,6 +620,157 @@ __global__ void __launch_bounds__(MW ? 512 : 64) iasp_codes_kernel(const Codeset
     }
     if (soft_fr)
         for (int k = 0; k < nh; ++k) soft_fr[k * M] = (double)so[(k * M + n) * F + f] / 65536.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Low-complexity high-efficiency decoder (decoder 9): lche_decod (decoders.cpp:2899-3012, map_bin_llr :2815-2890, logexp_int
+// :2777-2813, check_syndrome :793-814 on L < 0) on work item (c, w), written as lche_global_kernel (ldpc_global.hpp) writes it -- the
+// same statements in the same order through ldpc_spec::lche::logexp -- with the state on chip instead of in a workspace:
+//   * LDS: the a-posteriori LLRs L[N][F], then the per-edge state Z[ne_max][M][F] (e = edge index inside the frame's own code;
+//     Z[e][n] is only ever touched by lane n), then the 96 + 214 table words of logexp (divergent indices, copied in at the start as
+//     lche_body does), then the vote flag: F * 8 * (N + ne_max * M) + 8 * (kTabWords + kStepWords) bytes (lche_codes_image_bytes) + 16;
+//   * one lane owns one check of the current layer, the block rows in a run-time loop: nothing of a row outlives it, so rh is
+//     unbounded.  u[] and p[] are VGPRs with static indices (the passes are unrolled RWM times under a predicate on the wave-uniform
+//     row weight).  lche_global_kernel forms u = L - Z and p = logexp(|u|) again in its second pass; L and Z of the check's edges are
+//     unchanged until the check itself writes them (a row's edges lie in distinct block columns and the checks of a layer touch
+//     disjoint variables), so the second evaluation has the first one's operands and gives its bits: keeping the values changes no
+//     result and saves one of the three logexp per edge and layer.  All of a row's L values are read before the first is written;
+//   * a logexp is a chain of dependent compares, exponent arithmetic and two LDS lookups, and nothing hides its latency but the
+//     row's other edges: both passes work on groups of G = 4 edges in one basic block, as in the TDMP kernel (the predicate is per
+//     group; slots beyond the row's end recompute its last edge, add nothing to the parity or the sum and store nowhere).
+// A converged frame of a packed wave (and a frame beyond B) stores nothing more: its state and outputs stay as they were.  A lane that
+// must not store aims at the spare word behind the vote flag, which nothing reads.
+// ---------------------------------------------------------------------------------------------------------
+__host__ __device__ inline size_t lche_codes_image_bytes(int F, int M, int N, int ne_max) {   // L, Z and the tables, in front of the vote flag
+    return (size_t)F * 8 * ((size_t)N + (size_t)ne_max * M) + 8 * (size_t)(ldpc_spec::lche::kTabWords + ldpc_spec::lche::kStepWords);
+}
+
+template <int RWM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) lche_layered_codes_kernel(const CodesetArgs s) {
+    namespace E = ldpc_spec::lche;
+    extern __shared__ double lds[];
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
+    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
+    double *const L = lds, *const Z = lds + (size_t)N * F;
+    double *const tab = Z + (size_t)s.ne_max * M * F;
+    const double *const T = tab, *const S = tab + E::kTabWords;
+    int *const sh_flag = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + lche_codes_image_bytes(F, M, N, s.ne_max));
+    const int spare = s.ne_max * M * F + E::kTabWords + E::kStepWords + 1;          // index into Z of the second half of the flag's 16 bytes
+    constexpr int G = 4;                                                            // edges of a row worked on side by side
+    static_assert(RWM % G == 0, "lche_layered_codes_kernel: whole groups");
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+    const int ne = rs[rh];
+
+    for (int i = threadIdx.x; i < E::kTabWords + E::kStepWords; i += (int)blockDim.x)
+        tab[i] = i < E::kTabWords ? E::kLcheTab[i] : E::kLcheStep[i - E::kTabWords];
+    if (valid) {
+        for (int k = 0; k < nh; ++k) L[(k * M + n) * F + f] = live ? a.llr[fr * N + k * M + n] : 0.0;   // :2923-2924, the input as it is
+        for (int e = 0; e < ne; ++e) Z[(e * M + n) * F + f] = 0.0;                  // :2919-2921
+    }
+    __syncthreads();
+
+    auto syndrome_fail = [&]() -> bool {                                            // check_syndrome :793-814 on L < 0
+        uint32_t failw = 0;
+        for (int j = 0; j < rh; ++j) {
+            const int e0 = rs[j], e1 = rs[j + 1];
+            uint32_t sy = 0;
+            for (int e = e0; e < e1; ++e) {
+                const uint32_t d = (uint32_t)ed[e];
+                const int k = d >> 16, c = d & 0xffffu;
+                sy ^= (uint32_t)(L[(k * M + rot_idx(n, c, M)) * F + f] < 0);
+            }
+            failw |= sy;
+        }
+        return valid && failw;
+    };
+
+    bool done = !inb;
+    int res = -a.maxiter;
+    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);          // :2928-2937
+    if (!done && !frame_fail) { done = true; res = 0; }                             // a codeword at the input: no iteration, 0
+    for (int steps = 0; steps < a.maxiter;) {
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+        const bool wr = !done && valid;
+        for (int j = 0; j < rh; ++j) {                                              // layers in sequence (:2946)
+            const int e0 = rs[j], rw = rs[j + 1] - e0;
+            double u[RWM], p[RWM];
+#pragma unroll
+            for (int i = 0; i < RWM; ++i) { u[i] = 0.0; p[i] = 0.0; }
+            bool par = false;
+            double sum = 0.0;
+#pragma unroll
+            for (int g0 = 0; g0 < RWM; g0 += G) {                                   // map_bin_llr :2836-2855
+                if (g0 < rw) {
+#pragma unroll
+                    for (int q = 0; q < G; ++q) {                                   // G independent chains; slots beyond the row repeat its last edge
+                        const int i = g0 + q < rw ? g0 + q : rw - 1;
+                        const uint32_t d = (uint32_t)ed[e0 + i];
+                        const int k = d >> 16, c = d & 0xffffu;
+                        const double uu = L[(k * M + rot_idx(n, c, M)) * F + f] - Z[((e0 + i) * M + n) * F + f];
+                        u[g0 + q] = uu;
+                        p[g0 + q] = E::logexp(uu < 0.0 ? -uu : uu, T, S);
+                    }
+#pragma unroll
+                    for (int q = 0; q < G; ++q) {                                   // parity and sum in edge order, over the row's own edges
+                        const bool in_row = g0 + q < rw;
+                        par ^= in_row && u[g0 + q] < 0;
+                        sum = in_row ? sum + p[g0 + q] : sum;
+                    }
+                }
+            }
+#pragma unroll
+            for (int g0 = 0; g0 < RWM; g0 += G) {                                   // :2857-2863, :2974-2988
+                if (g0 < rw) {
+                    double cv[G];
+                    int zi[G], li[G];
+#pragma unroll
+                    for (int q = 0; q < G; ++q) {                                   // where the group's results go, settled before the chains
+                        const int i = g0 + q;
+                        const bool ok = wr && i < rw;
+                        const int ii = i < rw ? i : rw - 1;
+                        const uint32_t d = (uint32_t)ed[e0 + ii];
+                        const int k = d >> 16, c = d & 0xffffu;
+                        zi[q] = ok ? ((e0 + ii) * M + n) * F + f : spare;
+                        li[q] = ok ? (k * M + rot_idx(n, c, M)) * F + f : N * F + spare;
+                    }
+#pragma unroll
+                    for (int q = 0; q < G; ++q) {
+                        const double av = E::logexp(p[g0 + q] - sum, T, S);
+                        cv[q] = ((u[g0 + q] < 0) != par) ? av : -av;
+                    }
+#pragma unroll
+                    for (int q = 0; q < G; ++q) { L[li[q]] = cv[q] + u[g0 + q]; Z[zi[q]] = cv[q]; }
+                }
+            }
+            if (MW) __syncthreads();
+        }
+        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);           // :2995-3001 (the value after the last layer)
+        ++steps;
+        if (!done && !frame_fail) { done = true; res = steps; }                     // else -steps = -maxiter at the end
+    }
+    // glob_outputs: decword[k] = L[k] < 0 (:3005-3006), the final L as the soft output
+    if (!live) return;
+    if (n == 0 && a.iters) a.iters[fr] = res;
+    if (a.hard) {
+        for (int wd = n; wd < a.hard_words; wd += M) {
+            uint32_t bits = 0;
+            for (int b = 0; b < 32; ++b) {
+                const int v = 32 * wd + b;
+                if (v < N) bits |= (uint32_t)(L[v * F + f] < 0) << b;
+            }
+            a.hard[fr * a.hard_words + wd] = bits;
+        }
+    }
+    if (a.soft_out)
+        for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = L[(k * M + n) * F + f];
 }
 
 // ---------------------------------------------------------------------------------------------------------

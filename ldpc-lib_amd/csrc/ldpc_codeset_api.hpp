@@ -47,9 +47,11 @@ namespace {
 
 // Dynamic LDS of the code-set kernels.  MS / LMS: the a-posteriori values of F frames + the vote flag.  TDMP: the a-posteriori
 // probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.  IASP: the u16 state ST[ne_max][M], a-posteriori
-// word and channel word of F frames, rounded up to 16 bytes, + the vote flag.
+// word and channel word of F frames, rounded up to 16 bytes, + the vote flag.  LCHE: the a-posteriori LLRs and the per-edge state
+// Z[ne_max][M] of F frames, the tables of logexp, + the vote flag.
 size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
     if (decoder_id == LDPC_HIP_IASP_DEC) return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16;
+    if (decoder_id == LDPC_HIP_LCHE_DEC) return ldpc::lche_codes_image_bytes(F, M, nh * M, ne_max) + 16;
     const size_t per_frame = (size_t)nh * M + (decoder_id == LDPC_HIP_TASP_DEC ? (size_t)ne_max * M : 0);
     return sizeof(double) * per_frame * (size_t)F + 16;
 }
@@ -58,20 +60,22 @@ size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
 // ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  An IASP record goes on
 // with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and col_edges[]
 // ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  The one place where the limits
-// of the set kernels live.
+// of the set kernels live.  lche_route: the caller is one of the LCHE entry points (ldpc_hip_open_codes_lche,
+// ldpc_hip_codes_table_lche_host); decoder 9 through any other route is refused like the ids no set kernel serves.
 int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
-                  std::vector<int32_t> &tab, int *ne_max_out = nullptr) {
+                  std::vector<int32_t> &tab, int *ne_max_out = nullptr, bool lche_route = false) {
     const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC, iasp = decoder_id == LDPC_HIP_IASP_DEC;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
+    const bool lche = decoder_id == LDPC_HIP_LCHE_DEC && lche_route;
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), and with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host", who, decoder_id);
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (!iasp && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
+    if (!iasp && !lche && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
     if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
     const int F = M > 64 ? 1 : 64 / M;
-    if (!iasp && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP: with the byte count, once ne_max is known
+    if (!iasp && !lche && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE: with the byte count, once ne_max is known
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
     off.clear(); tab.clear();
     std::vector<int> col_w((size_t)nh);
@@ -129,6 +133,9 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
                     who, F, ne_max, M, nh * M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
     if (tdmp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB",
+                    who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
+    if (lche && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori LLRs + %d circulants x %d checks) and the tables of logexp need an LDS image of %zu bytes; the limit is 160 KiB",
                     who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
     if (ne_max_out) *ne_max_out = ne_max;
     return 0;
@@ -192,6 +199,13 @@ int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16
     return codeset_table_out("ldpc_hip_codes_table_host", off, tab, offsets, table, capacity, length);
 }
 
+int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
+                                   long long *length) {
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build("ldpc_hip_codes_table_lche_host", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, off, tab, nullptr, true)) return rc;
+    return codeset_table_out("ldpc_hip_codes_table_lche_host", off, tab, offsets, table, capacity, length);
+}
+
 }  // extern "C"
 
 namespace {
@@ -201,7 +215,7 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
     int ne_max = 0;
-    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max)) return rc;
+    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id == LDPC_HIP_LCHE_DEC)) return rc;   // only ldpc_hip_open_codes_lche passes 9
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
@@ -217,7 +231,8 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
     c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max);
     c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" :
-                                 decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : "tasp_layered_codes_kernel") +
+                                 decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : decoder_id == LDPC_HIP_LCHE_DEC ? "lche_layered_codes_kernel" :
+                                 "tasp_layered_codes_kernel") +
                      (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
@@ -249,6 +264,8 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
         k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_IASP_DEC)   // alpha is not read here either
         k = c->multiwave ? (const void *)ldpc::iasp_codes_kernel<kRWM, true> : (const void *)ldpc::iasp_codes_kernel<kRWM, false>;
+    else if (c->decoder_id == LDPC_HIP_LCHE_DEC)   // nor here
+        k = c->multiwave ? (const void *)ldpc::lche_layered_codes_kernel<kRWM, true> : (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_MS_DEC)
         k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
     else
@@ -305,7 +322,7 @@ void codeset_channel_args(const ldpc_hip_ctx *c, int punctured_blocks, uint64_t 
     ch.llr = c->codes->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
     ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
     ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_IASP_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
 }
 
 int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long long first_frame, long long nb) {
@@ -403,7 +420,7 @@ extern "C" {
 
 int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     if (out) *out = nullptr;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP and IASP sets open through ldpc_hip_open_codes_tdmp / _iasp
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP, IASP and LCHE sets open through ldpc_hip_open_codes_tdmp / _iasp / _lche
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", decoder_id);
     return codeset_open("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, device, out);
 }
@@ -414,6 +431,10 @@ int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, in
 
 int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     return codeset_open("ldpc_hip_open_codes_iasp", LDPC_HIP_IASP_DEC, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    return codeset_open("ldpc_hip_open_codes_lche", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
