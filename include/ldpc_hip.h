@@ -128,7 +128,8 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *ctx, const double *d_llr, long long B, int
 int ldpc_hip_set_bp_chain(ldpc_hip_ctx *ctx, int on, int reset_carry);
 
 /* Integer min-sum only: the quantiser arguments of imin_sum_decod_qc_lm (decoders.h:300; defaults MS_THR 1.4,
- * MS_QBITS 6, MS_DBITS 8 of decoders.h:46-48).  `alpha` of the decode calls gives ialpha = (int)(alpha*16). */
+ * MS_QBITS 6, MS_DBITS 8 of decoders.h:46-48).  `alpha` of the decode calls gives ialpha = (int)(alpha*16).  Also on a code-set
+ * context of ldpc_hip_open_codes_ims, for its next call. */
 int ldpc_hip_set_ims_params(ldpc_hip_ctx *ctx, double thr, int qbits, int dbits);
 
 /* Same with HOST pointers, laid out exactly like upstream's per-frame arrays (PCIe-inclusive, synchronous):
@@ -474,6 +475,26 @@ int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, in
  * at 256 (2.61x), 7.9 against 15.4 ms for one code; 30 x 60, M = 67, 2.0 dB: 401 against 572 ms at 16 codes (1.43x), 6434 against
  * 9315 ms at 256 (1.45x); an unseen 16 x 32 code through hiprtc in the foreground costs 1.05 s. */
 int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* The same for integer min-sum (LDPC_HIP_IMS_DEC; imin_sum_decod_qc_lm, decoders.cpp:5430-5690): an ordinary code-set context, served
+ * by the entry points below, kernel ims_flood_codes_kernel.  `alpha` IS read: ialpha = (int)(alpha * 16).  ldpc_hip_set_ims_params on
+ * the set context selects thr, qbits and dbits for the next call (defaults 1.4, 6, 8; the same ranges).  d_soft receives the integer
+ * a-posteriori value as a double.  Bit-identical to one ldpc_hip_open(LDPC_HIP_IMS_DEC) context per code.
+ * The input stage of this decoder does not depend on the code: the energy scale sqrt(N / sum y^2) (a sequential sum whose rounding is
+ * part of the result) and the quantised channel word are computed ONCE per received word (ims_coef_kernel, ims_quantise_kernel) into
+ * the context's workspace -- once per frame for shared LLRs, however many codes decode it -- and every code reads 2 bytes per
+ * variable.  That workspace belongs to the context: a set context serves ONE stream at a time (a second ldpc_hip_decode_codes_dev on
+ * another stream would overwrite the words the first is still reading).
+ * rh and nh are NOT limited (the whole state of a frame is in LDS).  Limits: M <= 512, row weights 1 .. 16, no empty block row or
+ * column, shifts in [-1, M), C >= 1 (LDPC_HIP_EINVAL); LDPC_HIP_EUNSUPPORTED when the LDS image of a workgroup,
+ * floor(64 / M) * (4 * nh * M + 8 * rh * M) bytes rounded up to 16, + 16 (per frame an int16 a-posteriori value and an int16 channel
+ * value per variable and an 8-byte record per check; the vote flag), exceeds 160 KiB: 16 x 32 at M = 512 fits (131 088 bytes),
+ * 20 x 40 at M = 512 does not (163 856).  ldpc_hip_open_codes(LDPC_HIP_IMS_DEC, ...) stays LDPC_HIP_EINVAL.
+ * Measured (profiles/r16_codeset_ims_time.txt; 50 iterations, 4096 frames per code, wall time against one ldpc_hip_open context per
+ * code, JIT off): 16 x 32, M = 64, 2.0 dB, against ims_flood_kernel: 29.7 against 50.3 ms at 16 codes (1.69x), 453 against 844 ms at
+ * 256 (1.86x); the lone shipped matrix runs its ahead-of-time int8 instance and is 4.4x faster than the set (0.80 against 3.53 ms);
+ * 30 x 60, M = 67, 3.0 dB, against ims_global_kernel: 127.5 against 270.0 ms at 16 codes (2.12x), 2007 against 4272 ms at 256 (2.13x),
+ * 10.3 against 16.1 ms for one code. */
+int ldpc_hip_open_codes_ims(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
 /* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
  * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
@@ -488,9 +509,15 @@ int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16
  * record of MS_DEC.  (ldpc_hip_codes_table_host(LDPC_HIP_LCHE_DEC, ...) stays LDPC_HIP_EINVAL.) */
 int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
                                    long long *length);
+/* The table ldpc_hip_open_codes_ims uploads, with its checks and return codes (no GPU needed): the record of MS_DEC, per code
+ * row_start[rh + 1] followed by its edges (block column << 16) | shift in row-major order.
+ * (ldpc_hip_codes_table_host(LDPC_HIP_IMS_DEC, ...) stays LDPC_HIP_EINVAL.) */
+int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
+                                  long long *length);
 /* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
  * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
- * maxiter >= 1.  Asynchronous on `stream`. */
+ * maxiter >= 1.  Asynchronous on `stream`.  An IMS set (ldpc_hip_open_codes_ims) quantises into the context's workspace first: one
+ * stream at a time per context. */
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *ctx, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha,
                               uint32_t *d_hard, int32_t *d_iters, double *d_soft, void *stream);
 /* ldpc_hip_count_errors_dev per code, against the all-zero codeword: d_frame_info [C][B] or NULL (same encoding, bit 30 = any

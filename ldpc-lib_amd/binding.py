@@ -191,6 +191,8 @@ def load_library():
     lib.ldpc_hip_open_codes_iasp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_open_codes_lche.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_codes_table_lche_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
+    lib.ldpc_hip_open_codes_ims.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_codes_table_ims_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
     lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
@@ -660,14 +662,15 @@ def codes_table(decoder_id, codes, M):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
     DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order.  DEC_LCHE: the record of
-    DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host)."""
+    DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host); DEC_IMS: the same record under integer min-sum's limits
+    (ldpc_hip_codes_table_ims_host)."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
     n = C.c_longlong()
-    if int(decoder_id) == DEC_LCHE:
-        who = "ldpc_hip_codes_table_lche_host"
-        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_lche_host(rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
+    if int(decoder_id) in (DEC_LCHE, DEC_IMS):
+        who = "ldpc_hip_codes_table_lche_host" if int(decoder_id) == DEC_LCHE else "ldpc_hip_codes_table_ims_host"
+        call = lambda off, tab, cap, length: getattr(lib, who)(rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
     else:
         who = "ldpc_hip_codes_table_host"
         call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
@@ -681,8 +684,8 @@ def codes_table(decoder_id, codes, M):
 class LdpcHipCodes:
     """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
     (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP, ldpc_hip_open_codes_lche for
-    DEC_LCHE): what a code search scores.  decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP or DEC_LCHE; bit-identical to LdpcHip on
-    each matrix."""
+    DEC_LCHE, ldpc_hip_open_codes_ims for DEC_IMS): what a code search scores.  decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP,
+    DEC_LCHE or DEC_IMS; bit-identical to LdpcHip on each matrix."""
 
     def __init__(self, decoder_id, codes, M, device=0):
         self.lib = load_library()
@@ -690,7 +693,8 @@ class LdpcHipCodes:
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp", DEC_LCHE: "ldpc_hip_open_codes_lche"}.get(self.decoder_id)
+        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp", DEC_LCHE: "ldpc_hip_open_codes_lche",
+               DEC_IMS: "ldpc_hip_open_codes_ims"}.get(self.decoder_id)
         if own:
             rc = getattr(self.lib, own)(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         else:
@@ -773,6 +777,11 @@ class LdpcHipCodes:
                                                    int(max_batch), state.ctypes.data)
         _check(self.lib, rc, "ldpc_hip_simulate_codes_stop")
         return state
+
+    def set_ims_params(self, thr=1.4, qbits=6, dbits=8):
+        """A DEC_IMS set: the quantiser arguments of imin_sum_decod_qc_lm for the next call (defaults MS_THR, MS_QBITS, MS_DBITS of
+        decoders.h:46-48), as LdpcHip.set_ims_params."""
+        _check(self.lib, self.lib.ldpc_hip_set_ims_params(self.h, float(thr), int(qbits), int(dbits)), "ldpc_hip_set_ims_params")
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")

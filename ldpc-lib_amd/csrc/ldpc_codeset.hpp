@@ -13,10 +13,10 @@
 //   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N];
 //   * a launch may cover a subset of the codes: code_list[n_active] names the code of every slot blockIdx.x / blocks_per_code (null =
 //     the identity).  The graph table and the per-code LLR slice follow the code, the outputs follow the slot ([n_active][B]...).
-// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel / lche_global_kernel
-// compute (fp64, reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp; LCHE: ldpc_spec::lche);
-// only the frame index and the table base differ (and, for TDMP, IASP and LCHE, where the state lives), so the results are
-// bit-identical to a single-code context.
+// The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel / lche_global_kernel /
+// ims_flood_kernel compute (fp64, reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp; LCHE:
+// ldpc_spec::lche; IMS: integers behind a quantiser that runs once per received word); only the frame index and the table base differ
+// (and, for TDMP, IASP, LCHE and IMS, where the state lives), so the results are bit-identical to a single-code context.
 #pragma once
 
 #include "ldpc_kernels.hpp"
@@ -771,6 +771,168 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lche_layered_codes_kernel(const
     }
     if (a.soft_out)
         for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = L[(k * M + n) * F + f];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Integer min-sum (decoder 4): imin_sum_decod_qc_lm (decoders.cpp:5430-5690) on work item (c, w), ims_flood_kernel's arithmetic
+// (ldpc_kernels.hpp) in two parts.
+//
+// The input stage does not depend on the code: coef = sqrt(N / sum y^2) (ims_coef_kernel, ldpc_frontend.hpp: the sum is sequential
+// and its rounding is part of the result) and the quantised channel word are functions of the received word alone.
+// ims_flood_kernel lets every lane walk the N LLRs of its frame; over shared LLRs that would be repeated per code.  Here
+// ims_quantise_kernel writes the int16 word once per received word ([B][N], or [C][B][N] for per-code LLRs) and every code reads
+// 2 bytes per variable instead of 8.
+//
+// ims_flood_codes_kernel keeps the whole state of a frame in LDS, so neither rh nor nh is bounded:
+//   * rec[R][F], R = rh * M: per check one 8-byte record {u16 m1, u16 m2, u32 meta}, meta = the 16 edge-sign bits | pos << kRowBits as
+//     in ims_flood_kernel's registers; rec[(j * M + n) * F + f] is only ever touched by lane n of frame f;
+//   * soft[N][F] int16: the accumulator of STATE1, then the a-posteriori value;
+//   * iy[N][F] int16: the quantised channel word, loaded once; iy[(k * M + n) * F + f] is only read by lane n;
+//   * F * (4 * N + 8 * R) bytes, rounded up to 16 (ims_codes_image_bytes), then the vote flag's 16.
+// Stored values never leave [-max_data, max_data] (max_data <= 16383; |iy| <= max_quant <= 16383, m1, m2 in [0, max_data]): halfwords
+// hold them exactly; sums and scaled magnitudes are 32-bit registers.  STATE1 adds the block rows in ascending order and saturates
+// after every add, as the reference does (saturating adds do not commute).
+// A converged frame of a packed wave (and a frame beyond B) stores nothing more: its state and outputs stay as they were.
+// ---------------------------------------------------------------------------------------------------------
+struct ImsQuantArgs {
+    const double *llr;   // [frames][N]
+    const double *coef;  // [frames] from ims_coef_kernel
+    int16_t *q;          // [frames][N]
+    long long total;     // frames * N
+    int N;
+    double thr;
+    int max_quant;
+};
+
+// ims_flood_kernel's quantiser (decoders.cpp:5483-5500): magnitude, scale, clamp, round, sign -- in that order
+__device__ __forceinline__ int ims_quantise(double val, double coef, double thr, int max_quant) {
+    int sign = 0;
+    if (val < 0) { val = -val; sign = 1; }
+    val *= coef;
+    if (val > thr) val = thr;
+    const int ival = (int)(short)floor(val * max_quant / thr + 0.5);
+    return sign ? -ival : ival;
+}
+
+__global__ void __launch_bounds__(256) ims_quantise_kernel(const ImsQuantArgs a) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.total; i += (long long)gridDim.x * blockDim.x)
+        a.q[i] = (int16_t)ims_quantise(a.llr[i], a.coef[i / a.N], a.thr, a.max_quant);
+}
+
+struct ImsCodesArgs {
+    const int16_t *q;    // the quantised channel words, laid out like CodesetArgs::llr
+    int max_data;        // (1 << (dbits - 1)) - 1, decoders.cpp:5445
+    int ialpha;          // (int)(alpha * 16), :5458
+};
+
+__host__ __device__ inline size_t ims_codes_image_bytes(int F, int N, int R) {   // rec, soft and iy, in front of the vote flag
+    return ((size_t)F * (4 * (size_t)N + 8 * (size_t)R) + 15) & ~(size_t)15;
+}
+
+template <bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const CodesetArgs s, const ImsCodesArgs q) {
+    extern __shared__ double lds[];
+    int w;
+    const DecArgs a = codeset_view(s, w);
+    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
+    const int M = a.M, F = MW ? 1 : a.F, N = a.N, rh = a.rh, nh = a.nh, R = rh * M;
+    uint2 *const rec = reinterpret_cast<uint2 *>(lds);
+    int16_t *const soft = reinterpret_cast<int16_t *>(rec + (size_t)R * F), *const iy = soft + (size_t)N * F;
+    int *const sh_flag = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + ims_codes_image_bytes(F, N, R));
+    const int max_data = q.max_data, ialpha = q.ialpha;
+    int n, f;
+    const bool valid = lane_map<MW>(F, M, n, f);
+    const unsigned long long per = MW ? 0ull : slot_mask(F);
+    const long long fr = (long long)w * F + f;
+    const bool inb = fr < a.B;
+    const bool live = valid && inb;
+    auto sat = [&](int x) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); };  // limit_val :4308
+
+    if (valid) {
+        const int16_t *const qf = q.q + (a.llr - s.llr) + (inb ? fr : 0) * (long long)N;   // the code's slice, as for the LLRs
+        for (int k = 0; k < nh; ++k) iy[(k * M + n) * F + f] = live ? qf[k * M + n] : (int16_t)0;
+        for (int j = 0; j < rh; ++j) rec[(j * M + n) * F + f] = make_uint2(0u, 0u);        // :5462-5470
+    }
+
+    bool done = !inb;
+    int res = -a.maxiter;
+    for (int iter = 0; iter < a.maxiter; ++iter) {
+        const bool wr = !done && valid;
+        if (wr)
+            for (int k = 0; k < nh; ++k) soft[(k * M + n) * F + f] = 0;
+        if (MW) __syncthreads();
+        for (int j = 0; j < rh; ++j) {   // STATE1 :5540-5576
+            const int e0 = rs[j], rw = rs[j + 1] - e0;
+            const uint2 rc = rec[(j * M + n) * F + f];
+            const uint32_t mt = rc.y;
+            const uint32_t par = __popc(mt & 0xffffu) & 1u;
+            const uint32_t pos = mt >> kRowBits;
+            const int c1 = ((int)(rc.x & 0xffffu) * ialpha) >> 4, c2 = ((int)(rc.x >> 16) * ialpha) >> 4;
+            for (int idx = 0; idx < rw; ++idx) {
+                const uint32_t d = (uint32_t)ed[e0 + idx];
+                const int k = d >> 16, c = d & 0xffffu;
+                const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                const int tmp = (pos == (uint32_t)idx) ? c2 : c1;
+                const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
+                if (wr) soft[addr] = (int16_t)sat((int)soft[addr] + cv);
+            }
+            if (MW) __syncthreads();     // the next block row adds into the same variables
+        }
+        if (wr) {                        // STATE2 :5579-5604
+            for (int k = 0; k < nh; ++k) {
+                const int o = (k * M + n) * F + f;
+                soft[o] = (int16_t)sat((int)iy[o] + (int)soft[o]);
+            }
+        }
+        if (MW) __syncthreads();
+        uint32_t failw = 0;
+        for (int j = 0; j < rh; ++j) {   // STATE3 :5610-5678
+            const int e0 = rs[j], rw = rs[j + 1] - e0;
+            const int ri = (j * M + n) * F + f;
+            const uint2 rc = rec[ri];
+            const uint32_t mt = rc.y;
+            const uint32_t par = __popc(mt & 0xffffu) & 1u;
+            const uint32_t pos = mt >> kRowBits;
+            const int c1 = ((int)(rc.x & 0xffffu) * ialpha) >> 4, c2 = ((int)(rc.x >> 16) * ialpha) >> 4;
+            int nm1 = max_data, nm2 = max_data;
+            uint32_t npos = 0, nS = 0, sy = 0;
+            for (int idx = 0; idx < rw; ++idx) {
+                const uint32_t d = (uint32_t)ed[e0 + idx];
+                const int k = d >> 16, c = d & 0xffffu;
+                const int r = soft[(k * M + rot_idx(n, c, M)) * F + f];
+                sy ^= (uint32_t)r;
+                const int val = (pos == (uint32_t)idx) ? c2 : c1;
+                const int t = (((mt >> idx) ^ par) & 1u) ? -val : val;
+                const int msg = r - t;
+                nS |= ((uint32_t)msg >> 31) << idx;
+                int v = msg < 0 ? -msg : msg;
+                v = v > max_data ? max_data : v;
+                if (v < nm1) { npos = idx; nm2 = nm1; nm1 = v; }
+                else if (v < nm2) nm2 = v;
+            }
+            failw |= sy;
+            if (wr) rec[ri] = make_uint2((uint32_t)nm1 | ((uint32_t)nm2 << 16), nS | (npos << kRowBits));
+        }
+        const bool fail = valid && (failw >> 31);
+        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
+        if (!done && !frame_fail) { done = true; res = iter + 1; }  // :5684-5689
+        if (MW) { if (done) break; }
+        else if (__all(done)) break;
+    }
+    if (!live) return;
+    if (n == 0 && a.iters) a.iters[fr] = res;
+    if (a.hard) {
+        for (int wd = n; wd < a.hard_words; wd += M) {
+            uint32_t bits = 0;
+            for (int b = 0; b < 32; ++b) {
+                const int v = 32 * wd + b;
+                if (v < N) bits |= ((uint32_t)(int)soft[v * F + f] >> 31) << b;
+            }
+            a.hard[fr * a.hard_words + wd] = bits;
+        }
+    }
+    if (a.soft_out)
+        for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = (double)soft[(k * M + n) * F + f];
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -27,6 +27,10 @@ struct codeset_common {
 struct ldpc_codeset_state : codeset_common {
     double *w_llr = nullptr;           // [w_frames][N], shared by the codes
     uint32_t *w_hard = nullptr;        // [C][w_frames][hard_words]
+    // an IMS set: the quantiser's results for the received words of one decode launch (grown on demand, never shrunk)
+    double *w_coef = nullptr;          // [w_q_frames]
+    int16_t *w_q = nullptr;            // [w_q_frames][N]
+    long long w_q_frames = 0;
 };
 
 void codeset_common_release(codeset_common &s) {
@@ -39,6 +43,8 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
     if (!s) return;
     if (s->w_llr) (void)hipFree(s->w_llr);
     if (s->w_hard) (void)hipFree(s->w_hard);
+    if (s->w_coef) (void)hipFree(s->w_coef);
+    if (s->w_q) (void)hipFree(s->w_q);
     codeset_common_release(*s);
     delete s;
 }
@@ -48,8 +54,10 @@ namespace {
 // Dynamic LDS of the code-set kernels.  MS / LMS: the a-posteriori values of F frames + the vote flag.  TDMP: the a-posteriori
 // probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.  IASP: the u16 state ST[ne_max][M], a-posteriori
 // word and channel word of F frames, rounded up to 16 bytes, + the vote flag.  LCHE: the a-posteriori LLRs and the per-edge state
-// Z[ne_max][M] of F frames, the tables of logexp, + the vote flag.
-size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
+// Z[ne_max][M] of F frames, the tables of logexp, + the vote flag.  IMS: per frame an int16 a-posteriori value and an int16 channel
+// value per variable and an 8-byte record per check, F * (4 * N + 8 * R) bytes rounded up to 16, + the vote flag.
+size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max, int rh = 0) {
+    if (decoder_id == LDPC_HIP_IMS_DEC) return ldpc::ims_codes_image_bytes(F, nh * M, rh * M) + 16;
     if (decoder_id == LDPC_HIP_IASP_DEC) return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16;
     if (decoder_id == LDPC_HIP_LCHE_DEC) return ldpc::lche_codes_image_bytes(F, M, nh * M, ne_max) + 16;
     const size_t per_frame = (size_t)nh * M + (decoder_id == LDPC_HIP_TASP_DEC ? (size_t)ne_max * M : 0);
@@ -60,22 +68,27 @@ size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max) {
 // ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  An IASP record goes on
 // with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and col_edges[]
 // ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  The one place where the limits
-// of the set kernels live.  lche_route: the caller is one of the LCHE entry points (ldpc_hip_open_codes_lche,
-// ldpc_hip_codes_table_lche_host); decoder 9 through any other route is refused like the ids no set kernel serves.
+// of the set kernels live.  own_route: the decoder whose own entry points the caller is one of (ldpc_hip_open_codes_lche,
+// ldpc_hip_codes_table_lche_host: 9; ldpc_hip_open_codes_ims, ldpc_hip_codes_table_ims_host: 4), or 0; decoders 4 and 9 through any
+// other route are refused like the ids no set kernel serves.
 int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
-                  std::vector<int32_t> &tab, int *ne_max_out = nullptr, bool lche_route = false) {
+                  std::vector<int32_t> &tab, int *ne_max_out = nullptr, int own_route = 0) {
     const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC, iasp = decoder_id == LDPC_HIP_IASP_DEC;
-    const bool lche = decoder_id == LDPC_HIP_LCHE_DEC && lche_route;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), and with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host", who, decoder_id);
+    const bool lche = decoder_id == LDPC_HIP_LCHE_DEC && own_route == LDPC_HIP_LCHE_DEC;
+    const bool ims = decoder_id == LDPC_HIP_IMS_DEC && own_route == LDPC_HIP_IMS_DEC;
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche && !ims)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host and with IMS_DEC (4) through ldpc_hip_open_codes_ims / ldpc_hip_codes_table_ims_host", who, decoder_id);
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (!iasp && !lche && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
+    if (!iasp && !lche && !ims && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
     if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
     const int F = M > 64 ? 1 : 64 / M;
-    if (!iasp && !lche && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE: with the byte count, once ne_max is known
+    if (ims && codeset_lds_bytes(decoder_id, nh, M, F, 0, rh) > 160 * 1024)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (4 x %d variables + 8 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB",
+                    who, F, nh * M, rh * M, codeset_lds_bytes(decoder_id, nh, M, F, 0, rh));
+    if (!iasp && !lche && !ims && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE: with the byte count, once ne_max is known
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
     off.clear(); tab.clear();
     std::vector<int> col_w((size_t)nh);
@@ -202,8 +215,15 @@ int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16
 int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
                                    long long *length) {
     std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_codes_table_lche_host", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, off, tab, nullptr, true)) return rc;
+    if (int rc = codeset_build("ldpc_hip_codes_table_lche_host", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, off, tab, nullptr, LDPC_HIP_LCHE_DEC)) return rc;
     return codeset_table_out("ldpc_hip_codes_table_lche_host", off, tab, offsets, table, capacity, length);
+}
+
+int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
+                                  long long *length) {
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build("ldpc_hip_codes_table_ims_host", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, off, tab, nullptr, LDPC_HIP_IMS_DEC)) return rc;
+    return codeset_table_out("ldpc_hip_codes_table_ims_host", off, tab, offsets, table, capacity, length);
 }
 
 }  // extern "C"
@@ -215,7 +235,7 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
     int ne_max = 0;
-    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id == LDPC_HIP_LCHE_DEC)) return rc;   // only ldpc_hip_open_codes_lche passes 9
+    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id)) return rc;   // only ldpc_hip_open_codes_lche passes 9, only ldpc_hip_open_codes_ims 4
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
@@ -229,14 +249,38 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
-    c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max);
+    c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max, rh);
     c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" :
                                  decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : decoder_id == LDPC_HIP_LCHE_DEC ? "lche_layered_codes_kernel" :
-                                 "tasp_layered_codes_kernel") +
+                                 decoder_id == LDPC_HIP_IMS_DEC ? "ims_flood_codes_kernel" : "tasp_layered_codes_kernel") +
                      (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
     *out = c.release();
+    return 0;
+}
+
+// An IMS set: the quantiser over the `frames` received words of a decode launch, into the context's workspace, on `stream`.
+// ims_coef_kernel's sequential energy sum, then one coalesced stream fp64 -> int16.
+int codeset_ims_quantise(ldpc_hip_ctx *c, const double *d_llr, long long frames, hipStream_t stream) {
+    ldpc_codeset_state *s = c->codes;
+    if (frames > s->w_q_frames) {
+        if (s->w_coef) (void)hipFree(s->w_coef);
+        if (s->w_q) (void)hipFree(s->w_q);
+        s->w_coef = nullptr; s->w_q = nullptr; s->w_q_frames = 0;
+        HIP_TRY(hipMalloc(&s->w_coef, sizeof(double) * (size_t)frames));
+        HIP_TRY(hipMalloc(&s->w_q, sizeof(int16_t) * (size_t)frames * (size_t)c->N));
+        s->w_q_frames = frames;
+    }
+    if ((frames + 63) / 64 > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %lld received words are more than one launch takes", frames);
+    ldpc::ImsCoefArgs ca{d_llr, s->w_coef, frames, c->N};
+    hipLaunchKernelGGL(ldpc::ims_coef_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, stream, ca);
+    HIP_TRY(hipGetLastError());
+    ldpc::ImsQuantArgs qa{d_llr, s->w_coef, s->w_q, frames * (long long)c->N, c->N, c->ims_thr, (1 << (c->ims_qbits - 1)) - 1};
+    long long blocks = (qa.total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL(ldpc::ims_quantise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qa);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -266,6 +310,8 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
         k = c->multiwave ? (const void *)ldpc::iasp_codes_kernel<kRWM, true> : (const void *)ldpc::iasp_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_LCHE_DEC)   // nor here
         k = c->multiwave ? (const void *)ldpc::lche_layered_codes_kernel<kRWM, true> : (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>;
+    else if (c->decoder_id == LDPC_HIP_IMS_DEC)    // alpha is read: ialpha below
+        k = c->multiwave ? (const void *)ldpc::ims_flood_codes_kernel<true> : (const void *)ldpc::ims_flood_codes_kernel<false>;
     else if (c->decoder_id == LDPC_HIP_MS_DEC)
         k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
     else
@@ -273,7 +319,12 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
     ProfTimer timer;
     if (int rc = timer.begin(c, stream)) return rc;
-    void *kargs[] = {&a};
+    ldpc::ImsCodesArgs ia{};   // the second argument of ims_flood_codes_kernel; the other kernels take the first alone
+    if (c->decoder_id == LDPC_HIP_IMS_DEC) {   // once per received word: B of them when the codes share the LLRs, C * B otherwise
+        if (int rc = codeset_ims_quantise(c, d_llr, shared_llr ? B : B * (long long)s->C, stream)) return rc;
+        ia.q = s->w_q; ia.max_data = (1 << (c->ims_dbits - 1)) - 1; ia.ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5445, :5458
+    }
+    void *kargs[] = {&a, &ia};
     c->last_launch = c->kernel_name.c_str();
     HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * n_slots)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
     HIP_TRY(hipGetLastError());
@@ -290,7 +341,8 @@ long long codeset_piece(size_t bytes_per_frame, const char *cap_env, long long B
 }
 
 long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
-    const size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
+    size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
+    if (c->decoder_id == LDPC_HIP_IMS_DEC) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
     return codeset_piece(per_frame, "LDPC_HIP_CODES_PIECE", B);
 }
 
@@ -420,7 +472,7 @@ extern "C" {
 
 int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     if (out) *out = nullptr;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP, IASP and LCHE sets open through ldpc_hip_open_codes_tdmp / _iasp / _lche
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC)   // TDMP, IASP, LCHE and IMS sets open through ldpc_hip_open_codes_tdmp / _iasp / _lche / _ims
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes: decoder id %d; a code set decodes with MS_DEC (3) or LMS_DEC (8)", decoder_id);
     return codeset_open("ldpc_hip_open_codes", decoder_id, rh, nh, M, hd, C, device, out);
 }
@@ -435,6 +487,10 @@ int ldpc_hip_open_codes_iasp(int rh, int nh, int M, const int16_t *hd, int C, in
 
 int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     return codeset_open("ldpc_hip_open_codes_lche", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_ims(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    return codeset_open("ldpc_hip_open_codes_ims", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
