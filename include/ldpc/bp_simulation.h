@@ -449,7 +449,7 @@ std::vector<std::pair<double, double>> run_code_set(int C, long long info_len, i
 // sequential stopping rule (:591, :805-823) is replayed per code over its ordered records, and a code that has stopped ignores the
 // records of later batches.  With show_process == 0 the whole run is one ldpc_hip_simulate_codes_stop call instead: the same rule on
 // the device, every launch over the codes still running, no records on the host; the results are the same integers.  decoder_type: MS_DEC, LMS_DEC, TASP_DEC (7, ldpc_hip_open_codes_tdmp),
-// IASP_DEC (5, ldpc_hip_open_codes_iasp), LCHE_DEC (9, ldpc_hip_open_codes_lche) or IMS_DEC (4, ldpc_hip_open_codes_ims).  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// IASP_DEC (5, ldpc_hip_open_codes_iasp), LCHE_DEC (9, ldpc_hip_open_codes_lche), IMS_DEC (4, ldpc_hip_open_codes_ims), SP_DEC or ASP_DEC (1, 2, ldpc_hip_open_codes_sp).  counters_out: nse, nde and experiment per code (the [C][B] records carry
 // no iteration counts, so nue and sum_abs_iters stay 0).
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
@@ -475,6 +475,8 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
          : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
          : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
          : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC
+             ? ldpc_hip_open_codes_sp(decoder_type, b, c, M, hd.data(), C, device, &ctx)
                                              : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
         Env::fail(ldpc_hip_last_error());
     const auto out = run_code_set<Env>(

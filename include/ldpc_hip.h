@@ -495,6 +495,33 @@ int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, in
  * 30 x 60, M = 67, 3.0 dB, against ims_global_kernel: 127.5 against 270.0 ms at 16 codes (2.12x), 2007 against 4272 ms at 256 (2.13x),
  * 10.3 against 16.1 ms for one code. */
 int ldpc_hip_open_codes_ims(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* The same for the two flooding sum-product decoders: decoder_id LDPC_HIP_SP_DEC (sum_prod_decod_qc_lm, decoders.cpp:1923-2185,
+ * likelihood ratios) or LDPC_HIP_ASP_DEC (sum_prod_gf2_decod_qc_lm, decoders.cpp:2324-2581, probabilities); any other id is
+ * LDPC_HIP_EINVAL.  An ordinary code-set context, served by the entry points below, kernels sp_flood_codes_kernel and
+ * asp_flood_codes_kernel.  `alpha` is ignored.  Bit-identical to one ldpc_hip_open context per code; an ASP code whose block columns
+ * all hold exactly two circulants takes upstream's own branch (:2431-2480, unclamped), per code.
+ * rh and nh are NOT limited, and SP does not limit the row weight either (a row of weight 1 is legal).  Limits: M <= 512, for ASP row
+ * weights 2 .. 16, no empty block row or column, shifts in [-1, M), at most 65535 circulants per code, C >= 1 (LDPC_HIP_EINVAL).
+ * LDS: the whole state of a frame, and no a-posteriori array.  Per frame, with ne_max the largest circulant count of a code of the set:
+ *   SP : 8 * (ne_max * M + N + R) + 4 * ceil(N / 32) bytes (per-edge messages, channel likelihood ratios, check products, hard bits),
+ *   ASP: 8 * (ne_max * M + N) + 4 * ceil(N / 32) bytes (per-edge state, channel probabilities, hard bits).
+ * LDPC_HIP_EUNSUPPORTED only when ONE frame does not fit, that is when its image rounded up to 16, + 16, exceeds 160 KiB (the message
+ * carries the byte count): 16 x 32 with 112 circulants at M = 126 fits (161 808 bytes for SP, 145 680 for ASP), at M = 128 SP does
+ * not (164 368).  Launch shape, a function of the shape alone: L = 64 lanes (M <= 64; F = min(floor(64 / M), what fits 160 KiB) frames
+ * side by side) or 64 * ceil(M / 64) lanes (F = 1) serve one block row or column at a time, and a workgroup of
+ * min(1024 / L, nh) such groups deals the block columns and rows of its frames over its waves.
+ * d_soft: SP forms it again from the LDS image at the end (the operands and order of `soft *= A`); ASP stores it every iteration.
+ * ldpc_hip_open_codes(1 | 2, ...) and ldpc_hip_codes_table_host(1 | 2, ...) stay LDPC_HIP_EINVAL.  Gallager BP (id 0) has no set
+ * route: its frames are not independent.
+ * Measured (profiles/r17_codeset_sp_time.txt; 4096 frames per code, wall time against one ldpc_hip_open context per code, JIT off).
+ * SP, 16 x 32, M = 64, 50 iterations, 2.0 dB, against sp_flood_kernel (LDS-resident): 61.0 against 65.4 ms at 16 codes (1.07x), 1000
+ * against 1095 ms at 256 (1.09x), and for ONE code the set is SLOWER than its single-code context: 5.12 against 4.73 ms (0.92x).
+ * SP against sp_global_kernel: 16 x 32, M = 126, 15 iterations, 1.7 dB: 92.5 against 251.0 ms at 16 codes (2.71x), 1467 against 3999 ms
+ * at 256 (2.73x), 6.2 against 16.0 ms for one code; 30 x 60, M = 67, 50 iterations, 2.0 dB: 284.5 against 622.6 ms (2.19x), 4675 against
+ * 10216 ms (2.19x), 19.9 against 39.6 ms.  ASP against asp_global_kernel: M = 64: 36.3 against 111.7 ms at 16 codes (3.07x), 590 against
+ * 1839 ms at 256 (3.12x), 3.1 against 8.1 ms for one code; M = 126: 64.9 against 315.6 ms (4.86x), 1025 against 5048 ms (4.92x), 4.6
+ * against 20.9 ms; 30 x 60: 178.4 against 574.4 ms (3.22x), 2920 against 9446 ms (3.24x), 12.8 against 36.4 ms. */
+int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
 /* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
  * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
@@ -514,6 +541,12 @@ int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int
  * (ldpc_hip_codes_table_host(LDPC_HIP_IMS_DEC, ...) stays LDPC_HIP_EINVAL.) */
 int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
                                   long long *length);
+/* The table ldpc_hip_open_codes_sp uploads, with its checks and return codes (no GPU needed): for both decoders the record of
+ * LDPC_HIP_IASP_DEC, per code row_start[rh + 1], the edges (block column << 16) | shift in row-major order, cw2 (1 when every block
+ * column holds exactly two circulants; ASP reads it, SP ignores it), col_start[nh + 1] and col_edges (row-major edge index << 16) |
+ * shift, columns then rows ascending.  (ldpc_hip_codes_table_host(1 | 2, ...) stays LDPC_HIP_EINVAL.) */
+int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                 long long capacity, long long *length);
 /* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
  * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
  * maxiter >= 1.  Asynchronous on `stream`.  An IMS set (ldpc_hip_open_codes_ims) quantises into the context's workspace first: one

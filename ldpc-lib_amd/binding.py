@@ -193,6 +193,8 @@ def load_library():
     lib.ldpc_hip_codes_table_lche_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_open_codes_ims.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_codes_table_ims_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
+    lib.ldpc_hip_open_codes_sp.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+    lib.ldpc_hip_codes_table_sp_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
     lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
@@ -663,7 +665,8 @@ def codes_table(decoder_id, codes, M):
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
     DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order.  DEC_LCHE: the record of
     DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host); DEC_IMS: the same record under integer min-sum's limits
-    (ldpc_hip_codes_table_ims_host)."""
+    (ldpc_hip_codes_table_ims_host); DEC_SP, DEC_ASP: the record of DEC_IASP under the limits of the flooding sum-product set kernels
+    (ldpc_hip_codes_table_sp_host)."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
@@ -671,6 +674,9 @@ def codes_table(decoder_id, codes, M):
     if int(decoder_id) in (DEC_LCHE, DEC_IMS):
         who = "ldpc_hip_codes_table_lche_host" if int(decoder_id) == DEC_LCHE else "ldpc_hip_codes_table_ims_host"
         call = lambda off, tab, cap, length: getattr(lib, who)(rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
+    elif int(decoder_id) in (DEC_SP, DEC_ASP):
+        who = "ldpc_hip_codes_table_sp_host"
+        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_sp_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
     else:
         who = "ldpc_hip_codes_table_host"
         call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
@@ -684,8 +690,8 @@ def codes_table(decoder_id, codes, M):
 class LdpcHipCodes:
     """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
     (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP, ldpc_hip_open_codes_lche for
-    DEC_LCHE, ldpc_hip_open_codes_ims for DEC_IMS): what a code search scores.  decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP,
-    DEC_LCHE or DEC_IMS; bit-identical to LdpcHip on each matrix."""
+    DEC_LCHE, ldpc_hip_open_codes_ims for DEC_IMS, ldpc_hip_open_codes_sp for DEC_SP and DEC_ASP): what a code search scores.
+    decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP, DEC_LCHE, DEC_IMS, DEC_SP or DEC_ASP; bit-identical to LdpcHip on each matrix."""
 
     def __init__(self, decoder_id, codes, M, device=0):
         self.lib = load_library()
@@ -695,7 +701,10 @@ class LdpcHipCodes:
         h = C.c_void_p()
         own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp", DEC_LCHE: "ldpc_hip_open_codes_lche",
                DEC_IMS: "ldpc_hip_open_codes_ims"}.get(self.decoder_id)
-        if own:
+        if self.decoder_id in (DEC_SP, DEC_ASP):
+            own = "ldpc_hip_open_codes_sp"
+            rc = self.lib.ldpc_hip_open_codes_sp(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
+        elif own:
             rc = getattr(self.lib, own)(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         else:
             rc = self.lib.ldpc_hip_open_codes(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))

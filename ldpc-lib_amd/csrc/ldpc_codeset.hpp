@@ -17,6 +17,7 @@
 // ims_flood_kernel compute (fp64, reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp; LCHE:
 // ldpc_spec::lche; IMS: integers behind a quantiser that runs once per received word); only the frame index and the table base differ
 // (and, for TDMP, IASP, LCHE and IMS, where the state lives), so the results are bit-identical to a single-code context.
+// The two flooding sum-product decoders (ids 1 and 2) deal a frame over several waves and live in ldpc_codeset_sp.hpp.
 #pragma once
 
 #include "ldpc_kernels.hpp"

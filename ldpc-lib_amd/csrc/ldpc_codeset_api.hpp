@@ -55,8 +55,12 @@ namespace {
 // probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.  IASP: the u16 state ST[ne_max][M], a-posteriori
 // word and channel word of F frames, rounded up to 16 bytes, + the vote flag.  LCHE: the a-posteriori LLRs and the per-edge state
 // Z[ne_max][M] of F frames, the tables of logexp, + the vote flag.  IMS: per frame an int16 a-posteriori value and an int16 channel
-// value per variable and an 8-byte record per check, F * (4 * N + 8 * R) bytes rounded up to 16, + the vote flag.
+// value per variable and an 8-byte record per check, F * (4 * N + 8 * R) bytes rounded up to 16, + the vote flag.  SP / ASP: the
+// images of ldpc_codeset_sp.hpp, F * (8 * (ne_max * M + N + R) + 4 * ceil(N / 32)) bytes (ASP: without the R check products) rounded
+// up to 16, + the vote flags.
 size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max, int rh = 0) {
+    if (decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_ASP_DEC)
+        return ldpc::sp_codes_image_bytes(decoder_id == LDPC_HIP_ASP_DEC, F, nh * M, rh * M, M, ne_max) + 16;
     if (decoder_id == LDPC_HIP_IMS_DEC) return ldpc::ims_codes_image_bytes(F, nh * M, rh * M) + 16;
     if (decoder_id == LDPC_HIP_IASP_DEC) return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16;
     if (decoder_id == LDPC_HIP_LCHE_DEC) return ldpc::lche_codes_image_bytes(F, M, nh * M, ne_max) + 16;
@@ -70,32 +74,36 @@ size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max, int r
 // ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  The one place where the limits
 // of the set kernels live.  own_route: the decoder whose own entry points the caller is one of (ldpc_hip_open_codes_lche,
 // ldpc_hip_codes_table_lche_host: 9; ldpc_hip_open_codes_ims, ldpc_hip_codes_table_ims_host: 4), or 0; decoders 4 and 9 through any
-// other route are refused like the ids no set kernel serves.
+// other route are refused like the ids no set kernel serves.  ldpc_hip_open_codes_sp / ldpc_hip_codes_table_sp_host pass 1 or 2 as
+// both: the IASP record under the limits of the two flooding sum-product kernels.
 int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
                   std::vector<int32_t> &tab, int *ne_max_out = nullptr, int own_route = 0) {
     const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC, iasp = decoder_id == LDPC_HIP_IASP_DEC;
     const bool lche = decoder_id == LDPC_HIP_LCHE_DEC && own_route == LDPC_HIP_LCHE_DEC;
     const bool ims = decoder_id == LDPC_HIP_IMS_DEC && own_route == LDPC_HIP_IMS_DEC;
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche && !ims)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host and with IMS_DEC (4) through ldpc_hip_open_codes_ims / ldpc_hip_codes_table_ims_host", who, decoder_id);
+    const bool sp = decoder_id == LDPC_HIP_SP_DEC && own_route == LDPC_HIP_SP_DEC, asp = decoder_id == LDPC_HIP_ASP_DEC && own_route == LDPC_HIP_ASP_DEC;
+    const bool flood = sp || asp;      // the state of a frame is in LDS and dealt over the waves of a workgroup: rh and nh are not limited
+    const bool cols = iasp || flood;   // the record goes on with cw2 and the column-major edges
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche && !ims && !flood)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host and with IMS_DEC (4) through ldpc_hip_open_codes_ims / ldpc_hip_codes_table_ims_host, and with SP_DEC (1) or ASP_DEC (2) through ldpc_hip_open_codes_sp / ldpc_hip_codes_table_sp_host", who, decoder_id);
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (!iasp && !lche && !ims && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
+    if (!iasp && !lche && !ims && !flood && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
     if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
     const int F = M > 64 ? 1 : 64 / M;
     if (ims && codeset_lds_bytes(decoder_id, nh, M, F, 0, rh) > 160 * 1024)
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (4 x %d variables + 8 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB",
                     who, F, nh * M, rh * M, codeset_lds_bytes(decoder_id, nh, M, F, 0, rh));
-    if (!iasp && !lche && !ims && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE: with the byte count, once ne_max is known
+    if (!iasp && !lche && !ims && !flood && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE, SP, ASP: with the byte count, once ne_max is known
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
     off.clear(); tab.clear();
     std::vector<int> col_w((size_t)nh);
     int ne_max = 0;
     for (int c = 0; c < C; ++c) {
         const int16_t *h = hd + (size_t)c * rh * nh;
-        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (iasp ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
+        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (cols ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
             return fail(LDPC_HIP_EINVAL, "%s: the table of %d codes exceeds 2^31 entries", who, C);
         off.push_back((int32_t)tab.size());
         const size_t rs = tab.size();
@@ -114,9 +122,11 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
                 ++rw; ++ne;
             }
             if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
-            if (rw > kRWM) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
+            if (rw > kRWM && !sp) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
             if (tdmp && rw < 2)   // map_bin reads SB[1] (decoders.cpp:2191-2228)
                 return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; TDMP sum-product needs at least 2", who, c, j, rw);
+            if (asp && rw < 2)    // map_bin reads SB[1] as well
+                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; advanced sum-product needs at least 2", who, c, j, rw);
             if (iasp && rw < 2)   // imap_bin reads SB[1] (decoders.cpp:2235-2271)
                 return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; integer advanced sum-product needs at least 2", who, c, j, rw);
         }
@@ -124,7 +134,7 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
         ne_max = ne > ne_max ? ne : ne_max;
         for (int k = 0; k < nh; ++k)
             if (!col_w[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
-        if (iasp) {
+        if (cols) {
             if (ne > 65535) return fail(LDPC_HIP_EINVAL, "%s: code %d has %d circulants; a column entry names its edge in 16 bits", who, c, ne);
             bool cw2 = true;   // the rule of ldpc_hip_open, per code
             for (int k = 0; k < nh; ++k) cw2 = cw2 && col_w[(size_t)k] == 2;
@@ -141,6 +151,9 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
             }
         }
     }
+    if (flood && codeset_lds_bytes(decoder_id, nh, M, 1, ne_max, rh) > 160 * 1024)   // ONE frame does not fit; fewer frames share a workgroup otherwise
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: one frame's image, 8 x (%d circulants x %d + %d variables%s) + 4 x %d bytes, rounded up to 16, + 16 is %zu bytes; the limit is 160 KiB",
+                    who, ne_max, M, nh * M, sp ? " + the checks" : "", (nh * M + 31) / 32, codeset_lds_bytes(decoder_id, nh, M, 1, ne_max, rh));
     if (iasp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
         return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d circulants x %d checks + 2 x %d variables) halfwords need an LDS image of %zu bytes; the limit is 160 KiB",
                     who, F, ne_max, M, nh * M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
@@ -226,6 +239,15 @@ int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int 
     return codeset_table_out("ldpc_hip_codes_table_ims_host", off, tab, offsets, table, capacity, length);
 }
 
+int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                 long long capacity, long long *length) {
+    if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_codes_table_sp_host: decoder id %d; SP_DEC (1) or ASP_DEC (2)", decoder_id);
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build("ldpc_hip_codes_table_sp_host", decoder_id, rh, nh, M, hd, C, off, tab, nullptr, decoder_id)) return rc;
+    return codeset_table_out("ldpc_hip_codes_table_sp_host", off, tab, offsets, table, capacity, length);
+}
+
 }  // extern "C"
 
 namespace {
@@ -235,7 +257,7 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
     int ne_max = 0;
-    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id)) return rc;   // only ldpc_hip_open_codes_lche passes 9, only ldpc_hip_open_codes_ims 4
+    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id)) return rc;   // only ldpc_hip_open_codes_lche passes 9, only ldpc_hip_open_codes_ims 4, only ldpc_hip_open_codes_sp 1 or 2
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
@@ -243,16 +265,22 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
-    c->ne = decoder_id == LDPC_HIP_IASP_DEC ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
+    const bool flood = decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_ASP_DEC;
+    c->ne = decoder_id == LDPC_HIP_IASP_DEC || flood ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
                                             : (int)(tab.size() - (size_t)C * (rh + 1));
     c->hard_words = (c->N + 31) / 32;
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
+    if (flood) {   // ldpc_codeset_sp.hpp: fewer frames when their images do not fit, several groups of lanes per frame
+        c->F = ldpc::sp_codes_frames(decoder_id == LDPC_HIP_ASP_DEC, c->N, c->R, M, ne_max);
+        c->threads = ldpc::sp_codes_groups(M, nh) * ldpc::sp_codes_lanes(M);
+    }
     c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max, rh);
     c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" :
                                  decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : decoder_id == LDPC_HIP_LCHE_DEC ? "lche_layered_codes_kernel" :
-                                 decoder_id == LDPC_HIP_IMS_DEC ? "ims_flood_codes_kernel" : "tasp_layered_codes_kernel") +
+                                 decoder_id == LDPC_HIP_IMS_DEC ? "ims_flood_codes_kernel" : decoder_id == LDPC_HIP_SP_DEC ? "sp_flood_codes_kernel" :
+                                 decoder_id == LDPC_HIP_ASP_DEC ? "asp_flood_codes_kernel" : "tasp_layered_codes_kernel") +
                      (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
@@ -312,6 +340,10 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
         k = c->multiwave ? (const void *)ldpc::lche_layered_codes_kernel<kRWM, true> : (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_IMS_DEC)    // alpha is read: ialpha below
         k = c->multiwave ? (const void *)ldpc::ims_flood_codes_kernel<true> : (const void *)ldpc::ims_flood_codes_kernel<false>;
+    else if (c->decoder_id == LDPC_HIP_SP_DEC)     // alpha is not read
+        k = c->multiwave ? (const void *)ldpc::sp_flood_codes_kernel<true> : (const void *)ldpc::sp_flood_codes_kernel<false>;
+    else if (c->decoder_id == LDPC_HIP_ASP_DEC)    // nor here
+        k = c->multiwave ? (const void *)ldpc::asp_flood_codes_kernel<kRWM, true> : (const void *)ldpc::asp_flood_codes_kernel<kRWM, false>;
     else if (c->decoder_id == LDPC_HIP_MS_DEC)
         k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
     else
@@ -374,7 +406,8 @@ void codeset_channel_args(const ldpc_hip_ctx *c, int punctured_blocks, uint64_t 
     ch.llr = c->codes->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
     ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
     ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+    ch.punct_val = c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC ||
+                   c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
 }
 
 int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long long first_frame, long long nb) {
@@ -491,6 +524,13 @@ int ldpc_hip_open_codes_lche(int rh, int nh, int M, const int16_t *hd, int C, in
 
 int ldpc_hip_open_codes_ims(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
     return codeset_open("ldpc_hip_open_codes_ims", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes_sp: decoder id %d; SP_DEC (1) or ASP_DEC (2)", decoder_id);
+    return codeset_open("ldpc_hip_open_codes_sp", decoder_id, rh, nh, M, hd, C, device, out);
 }
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,

@@ -23,6 +23,7 @@
 #include "ldpc_jit.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_codeset.hpp"
+#include "ldpc_codeset_sp.hpp"
 #include "ldpc_global.hpp"
 #include "ldpc_ms_fast.hpp"
 #include "ldpc_aot.hpp"   // ldpc_spec.hpp, code_appendix_c_m64.hpp + the declarations of the aot/*.hip kernels
