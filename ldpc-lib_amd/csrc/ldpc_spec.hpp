@@ -421,16 +421,19 @@ constexpr int ms_m64_keep_rows(int budget) {
     return rows;
 }
 // The edge budget of the shipped body: 70 edges = block rows 0-9 of the (2048,1024) example code, 253 VGPRs without a spill at two
-// waves per SIMD; the next row (78 edges) spills 11 (profiles/r13_flagship_variants.txt, r13_flagship_isa_histogram.txt).
+// waves per SIMD; the next row (78 edges) spills 12 (profiles/r18_flagship_isa_histogram.txt; chosen in round 13,
+// profiles/r13_flagship_variants.txt).
 constexpr int kMsM64KeepEdges = 70;
 // What the budget has to share the 256 registers with grows with the code: 5 per block row (m1, m2, the record word), 2 per block
 // column in flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row
 // before it uses it).  The example code (16 rows, 24 columns, width 8) leaves room for 70 edges = 140 registers; a code that
 // needs more for the rest gives the difference back, one edge per register (twice what the count asks: the allocator does not
-// pack as tightly as the count).  An edge count alone knows nothing of the number of block rows: codes of 20 and more block rows
-// spill with no edge kept at all, and with this second term they spill no more than that (cross-compiled 20 x 40, 24 x 32 and
-// 30 x 60 protographs: 12, 39 and 40 spilled VGPRs against 12, 40 and 137 before round 13).  Rows of weight 16 need no term of
-// their own: 8 x 32 with every row 16 wide keeps four rows in 232 VGPRs.
+// pack as tightly as the count).  An edge count alone knows nothing of the number of block rows: when the rule was made (round
+// 13) codes of 20 and more block rows spilled with no edge kept at all, and with this second term no more than that.  Since
+// round 18 the syndrome words of the block rows are no longer live to the end of STATE3, and cross-compiled 12 x 32, 20 x 40,
+// 24 x 32 and 30 x 60 protographs spill nothing under this rule (16, 11, 41 and 40 VGPRs before;
+// profiles/r18_flagship_isa_histogram.txt).  Rows of weight 16 need no term of their own: 8 x 32 with every row 16 wide keeps
+// four rows in 232 VGPRs.
 template <class C>
 constexpr int ms_m64_keep_budget() {
     constexpr int cols = C::NH < 24 ? C::NH : 24;
@@ -593,7 +596,12 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     step(S, x);
                 });
             }
+            // Only bit 31 of the syndrome word is ever looked at.  Opaque here, the row's word is folded into failw now and
+            // both stay 32 bits wide.  Left to itself the compiler xors whole doubles (a second chain over the LOW words of
+            // the soft values: 96 v_xor_b32 per iteration), ors the rows' words as 64-bit values, keeps all RH of them live
+            // to the end of STATE3 and ends the loop in a 64-bit compare (profiles/r18_flagship_isa_histogram.txt).
             failw |= sy;
+            asm volatile("" : "+v"(failw));
             m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
             __builtin_amdgcn_sched_barrier(0);
         });

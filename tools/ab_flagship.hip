@@ -2,9 +2,9 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r13_flagship_variants.txt (round 6's variants -- the image 512 B into the allocation, slot 0 of STATE3 folded --
-// are in profiles/r06_flagship_variants.txt, round 2's in profiles/r02_flagship_variants.txt; all of them are part of every body
-// here).
+// Results: profiles/r18_flagship_variants.txt (round 13's variants -- where the channel LLRs are loaded, how many edges are kept from
+// STATE1 to STATE3 -- are in profiles/r13_flagship_variants.txt, round 6's in profiles/r06_flagship_variants.txt, round 2's in
+// profiles/r02_flagship_variants.txt; all of them are part of every body here).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,14 +22,15 @@
 
 namespace ldpc_spec {
 
-// ---- the baseline: ms_m64_body as it was before round 13, word for word (only the name differs)
+// ---- the baseline: ms_m64_body as it was before round 18, word for word (only the name differs)
 template <class C>
 __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
+    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
-    const double alpha = a.alpha;
+    const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
     long long fr = blockIdx.x;  // one wave per frame; with a.queue the wave goes on to further frames (uniform: an SGPR pair)
 
     // The image starts one block column (512 B) into the allocation, so a rotation needs no wrap arithmetic: variable
@@ -61,15 +62,34 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
     int res = -a.maxiter;
     for (int iter = 0; iter < a.maxiter; ++iter) {
         // The channel LLRs are needed only in STATE2.  Instead of pinning 64 VGPRs for the whole kernel they are
-        // re-read every iteration (16 KiB per frame: L2 / Infinity-Cache hits after the first pass) right here, so the
-        // loads fly under STATE1's ALU work, and the registers are free again during STATE3 where pressure peaks.
+        // re-read every iteration (16 KiB per frame: L2 / Infinity-Cache hits after the first pass), and not before
+        // STATE2 itself: 16 block columns between STATE1 and STATE2, then 8 more at each group of 8 columns, 16 columns
+        // ahead.  At most 24 columns (48 VGPRs) are in flight, and none during STATE1 and STATE3 -- the registers go to
+        // `keep`.  (Until round 13 all 32 columns were loaded here, "under STATE1's ALU work"; the other wave of the SIMD
+        // covers the latency just as well: profiles/r13_flagship_variants.txt, placements (a), (b), (c).)
         double y[NH];
-        int yo = 0;
-        asm volatile("" : "+v"(yo));  // opaque per iteration: the loads must not be hoisted out of the loop again
-        static_for<0, NH>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            y[k] = yrow[yo + k * 64];
-        });
+        auto load_y = [&](auto K0, auto K1) {   // columns [K0, min(K1, NH))
+            int yo = 0;
+            asm volatile("" : "+v"(yo));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
+            static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                y[k] = yrow[yo + k * 64];
+            });
+        };
+        // The decoded c2v value of an edge is needed twice: here in STATE1 (cv, added into the variable) and in STATE3
+        // (x = alpha * cv, taken out of the variable's sum again).  Block rows [0, KR) keep cv in registers instead of
+        // decoding the record a second time: x = keep * |alpha| is ONE v_mul_f64 in place of compare, two selects, bfi and
+        // add, and the row's two products m1 * alpha, m2 * alpha go as well.  The bits are those of the second decode:
+        //   - the second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's sign), cv is
+        //     +-(pos == s ? m2 : m1) with the same sign bit and the same select, both from the same record;
+        //   - m1 and m2 are finite and in [0, 32767]: they start at 0.0 and are fmin / fmax against kMaxVal afterwards, which
+        //     never return a NaN;
+        //   - IEEE multiplication is sign-symmetric: (+-m) * |alpha| and +-(m * |alpha|) are the same bits, zeros and
+        //     denormals included (round-to-nearest does not look at the sign);
+        //   - -ffp-contract=off keeps this product and the subtraction after it apart, as it does for the second decode.
+        // Between STATE1 and STATE3 of a retained row m1[j] and m2[j] are dead, so a retained edge costs 2 registers and a
+        // retained row gives 4 back.
+        double keep[RH][C::WMAX];
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
@@ -86,6 +106,7 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
                 constexpr int s = decltype(S)::value;
                 const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
                 const double cv = signed_mag(aa, Wt);
+                if constexpr (j < KR) keep[j][s] = cv;
                 Wt = twice(Wt);
                 double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
                 if constexpr (C::FIRST[j][s]) *p = cv;
@@ -94,8 +115,10 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
         });
         // ---------------- STATE2 (:4670-4685): soft = y + acc*alpha (two roundings)
+        load_y(IC<0>{}, IC<16>{});
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
+            if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
             double *p = own(K);
             const double pr = *p * alpha;
             *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
@@ -110,10 +133,6 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
             // opaque: otherwise the compiler keeps STATE1's 112 select masks and shifted sign words alive across the
             // whole iteration to reuse them here (SGPR + VGPR spills to scratch); recomputing costs 3 ops per edge.
             asm volatile("" : "+v"(mt));
-            const u32 pos = mt & 0xffu;
-            u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
-            double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
-            asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
             double r[RW];
@@ -121,12 +140,9 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
                 constexpr int s = decltype(S)::value;
                 r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
             });
-            static_for<0, RW>([&](auto S) {
+            // slot s with its old c2v value x taken out: sign word, min1 / min2 / min1 slot -- the same for both kinds of row
+            auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
-                sy ^= hi32(r[s]);
-                const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
-                const double x = signed_mag(aa, Wt);
-                Wt = twice(Wt);
                 const double tt = r[s] - x;              // v2c
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);  // (nS << 1) | sign(tt): slot s lands on bit RW-1-s
                 const double v = fabs(tt);
@@ -140,7 +156,27 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
                     npos = sel32(npos, (u32)s, c1);
                     nm1 = fmin(v, nm1);
                 }
-            });
+            };
+            if constexpr (j < KR) {
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    sy ^= hi32(r[s]);
+                    step(S, keep[j][s] * alpha_mag);     // STATE1's value: no second decode, see `keep`
+                });
+            } else {
+                const u32 pos = mt & 0xffu;
+                u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
+                double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
+                asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    sy ^= hi32(r[s]);
+                    const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
+                    const double x = signed_mag(aa, Wt);
+                    Wt = twice(Wt);
+                    step(S, x);
+                });
+            }
             failw |= sy;
             m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
             __builtin_amdgcn_sched_barrier(0);
@@ -173,18 +209,44 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
   }
 }
 
-// ---- round 13: the decoded c2v values of the first block rows stay in registers from STATE1 to STATE3 (see ms_m64_body in
-// ldpc_spec.hpp for the argument why x = keep * |alpha| has the bits of the second decode).
-//   BUDGET  whole block rows are retained in ascending order while their edges fit into BUDGET (0: none, the parent's arithmetic)
-//   YP      where the channel LLRs y[] are loaded (their 2 NH VGPRs are what limits BUDGET):
-//           0  at the top of the iteration, under STATE1's ALU work (the parent's place)
-//           1  all NH loads between STATE1 and STATE2
-//           2  16 columns between STATE1 and STATE2, then 8 more at each group of 8 columns of STATE2, 16 columns ahead
-template <class C, int BUDGET, int YP>
-__device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
+// The lane mask ~0 << SH as ONE scalar shift of -1 by an inline constant, where it is used (variant C).  As C++ constants the ~40
+// distinct wrap masks of a body are hoisted out of its loops; beside the lane masks of a carried row they no longer fit the SGPRs
+// and come back through v_readlane, a vector instruction per use.  `tie` as in sel32_tied: the shift is neither hoisted nor shared
+// between two states.
+template <int SH>
+__device__ __forceinline__ mask64 lanes_from(u32 tie) {
+    static_assert(SH > 0 && SH < 64, "lanes_from: shift out of range");
+    mask64 m;
+    asm("s_lshl_b64 %0, -1, %1" : "=s"(m) : "i"(SH), "v"(tie) : "scc");
+    return m;
+}
+
+// ---- round 18: the variants, separable.
+//   A32     the syndrome word of a row and `failw` stay 32 bits wide (one opaque asm after `failw |= sy`), a row's word is folded
+//           into failw at the row's end.  Shipped.
+//   CARRY   block rows [0, KR) hold their decoded c2v values from STATE3 of one iteration to STATE3 of the next and have no
+//           record (m1, m2, meta); false: they are decoded from the record in STATE1 and kept to STATE3 (round 13, the parent).
+//           Not shipped: fewer vector instructions, no faster (profiles/r18_flagship_variants.txt).
+//   BUDGET  whole block rows are kept in ascending order while their edges fit into BUDGET
+//   SMASK   the wrap mask of a rotated address is one scalar shift where it is used (lanes_from), not a hoisted constant.  Not
+//           shipped.
+// Why a carried value has the bits of the record's decode, cv = +-(s == pos ? m2 : m1):
+//   - the position.  The record's slot is npos = the last slot s >= 1 whose c1 = (v < nm1) held, or 0 (npos starts at 0, lanes_lt
+//     is false on NaN).  A carried row keeps its c1 lane masks and forms  E[s] = c1[s] & ~(c1[s+1] | ... | c1[RW-1])  on the scalar
+//     unit, in descending slot order and in place; slot 0 is the min1 slot where no c1 held.  The same c1, so the same slot in
+//     every lane, ties (strict <: the earlier slot stays) and NaN included;
+//   - the magnitudes.  nm1 and nm2 are what the record would hold as m1 and m2, and the decode's select between them is the one
+//     made here, with E[s] in place of pos == s;
+//   - the sign.  W is the word the record would hold in meta's upper bits -- the signs of the v2c, row parity folded in, slot s on
+//     bit 31 - s -- shifted by the same twice() per slot;
+//   - the start.  The all-zero record of a new frame decodes to +0.0 on every edge (signed_mag(0.0, 0)): keep starts at +0.0,
+//     per frame;
+//   - x = keep * |alpha| in STATE3: as in the parent (see `keep` in ms_m64_body).
+template <class C, bool A32, bool CARRY, int BUDGET, bool SMASK>
+__device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = ms_m64_keep_rows<C>(BUDGET);   // block rows [0, KR) are retained
+    constexpr int KR = ms_m64_keep_rows<C>(BUDGET);   // block rows [0, KR) are kept
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -194,6 +256,7 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
         constexpr int c = decltype(S)::value, k = decltype(K)::value;
         static_assert(c >= 0 && c < 64 && k * 512 + c * 8 < 65536, "shift / block column out of range");
         if constexpr (c == 0) return lds_at(hi + (u32)(k * 512));
+        else if constexpr (SMASK) return lds_at(sel32(hi, lo, lanes_from<64 - c>(tie)) + (u32)(k * 512 + c * 8));
         else return lds_at(sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8));
     };
     auto own = [&](auto K) -> double * { return lds_at(hi + (u32)(decltype(K)::value * 512)); };
@@ -203,17 +266,16 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
 
     double m1[RH], m2[RH];
     u32 meta[RH];
+    double keep[RH][C::WMAX];   // !CARRY: written in STATE1 before it is read in STATE3, so nothing is carried
     static_for<0, RH>([&](auto J) {
         constexpr int j = decltype(J)::value;
-        m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u;
+        if constexpr (CARRY && j < KR) static_for<0, C::RW[j]>([&](auto S) { keep[j][decltype(S)::value] = 0.0; });
+        else { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }
     });
 
     int res = -a.maxiter;
     for (int iter = 0; iter < a.maxiter; ++iter) {
         double y[NH];
-        double keep[RH][C::WMAX];
-        // columns [K0, K1) of y; the offset is opaque at the place of the call, so the loads are neither hoisted out of the
-        // iteration loop nor moved up to an earlier place
         auto load_y = [&](auto K0, auto K1) {
             int yo = 0;
             asm volatile("" : "+v"(yo));
@@ -222,32 +284,42 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
                 y[k] = yrow[yo + k * 64];
             });
         };
-        if constexpr (YP == 0) load_y(IC<0>{}, IC<NH>{});
         // ---------------- STATE1
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            u32 mt = meta[j];
-            asm volatile("" : "+v"(mt));
-            const u32 pos = mt & 0xffu;
-            u32 Wt = mt;
-            static_for<0, C::RW[j]>([&](auto S) {
-                constexpr int s = decltype(S)::value;
-                const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
-                const double cv = signed_mag(aa, Wt);
-                if constexpr (j < KR) keep[j][s] = cv;
-                Wt = twice(Wt);
-                double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                if constexpr (C::FIRST[j][s]) *p = cv;
-                else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            });
+            if constexpr (CARRY && j < KR) {
+                u32 tie;
+                asm volatile("" : "=v"(tie));
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    const double cv = keep[j][s];
+                    double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                    if constexpr (C::FIRST[j][s]) *p = cv;
+                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                });
+            } else {
+                u32 mt = meta[j];
+                asm volatile("" : "+v"(mt));
+                const u32 pos = mt & 0xffu;
+                u32 Wt = mt;
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
+                    const double cv = signed_mag(aa, Wt);
+                    if constexpr (j < KR) keep[j][s] = cv;
+                    Wt = twice(Wt);
+                    double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                    if constexpr (C::FIRST[j][s]) *p = cv;
+                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                });
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (YP == 1) load_y(IC<0>{}, IC<NH>{});
-        if constexpr (YP == 2) load_y(IC<0>{}, IC<16>{});
         // ---------------- STATE2
+        load_y(IC<0>{}, IC<16>{});
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            if constexpr (YP == 2 && k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
+            if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
             double *p = own(K);
             const double pr = *p * alpha;
             *p = (y[k] + 0.0) + pr;
@@ -258,16 +330,18 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
             constexpr int RW = C::RW[j];
-            u32 mt = meta[j];
-            asm volatile("" : "+v"(mt));
+            constexpr bool carried = CARRY && j < KR;
+            u32 mt;
+            if constexpr (carried) asm volatile("" : "=v"(mt));
+            else { mt = meta[j]; asm volatile("" : "+v"(mt)); }
             double nm1 = kMaxVal, nm2 = kMaxVal;
             u32 npos = 0, nS = 0, sy = 0;
+            mask64 lt[RW];   // carried rows: c1 of slot s
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
                 r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
             });
-            // the search for min1 / min2 / the min1 slot and the sign word, the same for both kinds of row
             auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
                 const double tt = r[s] - x;
@@ -278,7 +352,8 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
                 } else {
                     const mask64 c1 = lanes_lt(v, nm1);
                     nm2 = fmin(fmax(v, nm1), nm2);
-                    npos = sel32(npos, (u32)s, c1);
+                    if constexpr (carried) lt[s] = c1;
+                    else npos = sel32(npos, (u32)s, c1);
                     nm1 = fmin(v, nm1);
                 }
             };
@@ -303,7 +378,27 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
                 });
             }
             failw |= sy;
-            m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
+            if constexpr (A32) asm volatile("" : "+v"(failw));
+            u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);
+            if constexpr (carried) {
+                mask64 later = 0ull;
+                static_for<1, RW>([&](auto I) {
+                    constexpr int s = RW - decltype(I)::value;
+                    const mask64 c1 = lt[s];
+                    lt[s] = c1 & ~later;
+                    later |= c1;
+                });
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    double aa;
+                    if constexpr (s == 0) aa = sel64(nm2, nm1, later);
+                    else aa = sel64(nm1, nm2, lt[s]);
+                    keep[j][s] = signed_mag(aa, W);
+                    W = twice(W);
+                });
+            } else {
+                m1[j] = nm1; m2[j] = nm2; meta[j] = W | npos;
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
         if (__ballot((failw >> 31) != 0) == 0ull) { res = iter + 1; break; }
@@ -336,18 +431,17 @@ __device__ __forceinline__ void ms_m64_body_x(const SpecArgs &a) {
 
 using ldpc_spec::SpecArgs;
 typedef ldpc_spec::CodeAppendixCM64 Code;
-#define VARIANT(name, budget, yp) \
-    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_x<Code, budget, yp>(a); }
+#define VARIANT(name, a32, carry, budget, smask) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_y<Code, a32, carry, budget, smask>(a); }
 extern "C" __global__ void __launch_bounds__(64, 2) k_parent(const SpecArgs a) { ldpc_spec::ms_m64_body_parent<Code>(a); }
-VARIANT(k_a26, 26, 0)
-VARIANT(k_a41, 41, 0)
-VARIANT(k_a47, 47, 0)
-VARIANT(k_b41, 41, 1)
-VARIANT(k_b47, 47, 1)
-VARIANT(k_b54, 54, 1)
-VARIANT(k_c54, 54, 2)
-VARIANT(k_c62, 62, 2)
-VARIANT(k_c70, 70, 2)
+VARIANT(k_r13, false, false, 70, false)
+VARIANT(k_a, true, false, 70, false)
+VARIANT(k_ab62, true, true, 62, false)
+VARIANT(k_ab70, true, true, 70, false)
+VARIANT(k_ab78, true, true, 78, false)
+VARIANT(k_ac, true, false, 70, true)
+VARIANT(k_abc70, true, true, 70, true)
+VARIANT(k_abc78, true, true, 78, true)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 
 struct Variant { const void *kern; const char *name; size_t lds; };
@@ -359,16 +453,15 @@ int main(int argc, char **argv) {
     const int N = 2048;
     const size_t L = ldpc_spec::kMsM64LdsBytes(N);
     const Variant var[] = {
-        {(const void *)k_parent, "baseline: the body before round 13 (parent)", L},
-        {(const void *)k_a26, "y at the top (a), rows 0-3 retained (26 edges)", L},
-        {(const void *)k_a41, "y at the top (a), rows 0-5 retained (41 edges)", L},
-        {(const void *)k_a47, "y at the top (a), rows 0-6 retained (47 edges)", L},
-        {(const void *)k_b41, "y before STATE2 (b), rows 0-5 retained (41 edges)", L},
-        {(const void *)k_b47, "y before STATE2 (b), rows 0-6 retained (47 edges)", L},
-        {(const void *)k_b54, "y before STATE2 (b), rows 0-7 retained (54 edges)", L},
-        {(const void *)k_c54, "y in STATE2 by 8, 16 ahead (c), rows 0-7 retained (54 edges)", L},
-        {(const void *)k_c62, "y in STATE2 by 8, 16 ahead (c), rows 0-8 retained (62 edges)", L},
-        {(const void *)k_c70, "y in STATE2 by 8, 16 ahead (c), rows 0-9 retained (70 edges)", L},
+        {(const void *)k_parent, "baseline: the body before round 18 (parent)", L},
+        {(const void *)k_r13, "switches off, 70 edges (must equal the baseline)", L},
+        {(const void *)k_a, "A: 32-bit syndrome word, 70 edges kept STATE1 to STATE3", L},
+        {(const void *)k_ab62, "A + B, rows 0-8 carried (62 edges)", L},
+        {(const void *)k_ab70, "A + B, rows 0-9 carried (70 edges)", L},
+        {(const void *)k_ab78, "A + B, rows 0-10 carried (78 edges)", L},
+        {(const void *)k_ac, "A + C: scalar-shift wrap masks, 70 edges kept STATE1 to STATE3", L},
+        {(const void *)k_abc70, "A + B + C, rows 0-9 carried (70 edges)", L},
+        {(const void *)k_abc78, "A + B + C, rows 0-10 carried (78 edges)", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
     };
     constexpr int NV = sizeof var / sizeof var[0];
