@@ -186,17 +186,10 @@ def load_library():
     lib.ldpc_hip_gfq_channel_dev.argtypes = [vp, vp, vp, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_count_errors_gfq_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
-    lib.ldpc_hip_open_codes.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_open_codes_tdmp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_open_codes_iasp.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_open_codes_lche.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_codes_table_lche_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
-    lib.ldpc_hip_open_codes_ims.argtypes = [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_codes_table_ims_host.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
-    lib.ldpc_hip_open_codes_sp.argtypes = [i32, i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
-    lib.ldpc_hip_codes_table_sp_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
+    for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, *_CODES_ROUTE.values()):
+        getattr(lib, open_codes).argtypes = [i32] * open_id + [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
+        getattr(lib, codes_table_host).argtypes = [i32] * table_id + [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
-    lib.ldpc_hip_codes_table_host.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_dev.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp]
     lib.ldpc_hip_count_errors_codes_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_codes.argtypes = [vp, f64, i32, i32, f64, u64, i64, i64, vp, vp]
@@ -660,6 +653,19 @@ def _code_stack(codes):
     return codes
 
 
+# The entry points of a code set by decoder id: (open, whether it takes the id as its first argument, table, whether that one does).
+# Any other id goes to the generic pair, which refuses it.
+_CODES_GENERIC = ("ldpc_hip_open_codes", True, "ldpc_hip_codes_table_host", True)
+_CODES_ROUTE = {
+    DEC_SP: ("ldpc_hip_open_codes_sp", True, "ldpc_hip_codes_table_sp_host", True),
+    DEC_ASP: ("ldpc_hip_open_codes_sp", True, "ldpc_hip_codes_table_sp_host", True),
+    DEC_IMS: ("ldpc_hip_open_codes_ims", False, "ldpc_hip_codes_table_ims_host", False),
+    DEC_IASP: ("ldpc_hip_open_codes_iasp", False, "ldpc_hip_codes_table_host", True),
+    DEC_TASP: ("ldpc_hip_open_codes_tdmp", False, "ldpc_hip_codes_table_host", True),
+    DEC_LCHE: ("ldpc_hip_open_codes_lche", False, "ldpc_hip_codes_table_lche_host", False),
+}
+
+
 def codes_table(decoder_id, codes, M):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
@@ -671,15 +677,9 @@ def codes_table(decoder_id, codes, M):
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
     n = C.c_longlong()
-    if int(decoder_id) in (DEC_LCHE, DEC_IMS):
-        who = "ldpc_hip_codes_table_lche_host" if int(decoder_id) == DEC_LCHE else "ldpc_hip_codes_table_ims_host"
-        call = lambda off, tab, cap, length: getattr(lib, who)(rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
-    elif int(decoder_id) in (DEC_SP, DEC_ASP):
-        who = "ldpc_hip_codes_table_sp_host"
-        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_sp_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
-    else:
-        who = "ldpc_hip_codes_table_host"
-        call = lambda off, tab, cap, length: lib.ldpc_hip_codes_table_host(int(decoder_id), rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
+    _, _, who, takes_id = _CODES_ROUTE.get(int(decoder_id), _CODES_GENERIC)
+    head = (int(decoder_id),) if takes_id else ()
+    call = lambda off, tab, cap, length: getattr(lib, who)(*head, rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
     _check(lib, call(None, None, 0, C.byref(n)), who)
     off = np.empty(Cn, dtype=np.int32)
     tab = np.empty(n.value, dtype=np.int32)
@@ -688,9 +688,8 @@ def codes_table(decoder_id, codes, M):
 
 
 class LdpcHipCodes:
-    """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch
-    (ldpc_hip_open_codes; ldpc_hip_open_codes_tdmp for DEC_TASP, ldpc_hip_open_codes_iasp for DEC_IASP, ldpc_hip_open_codes_lche for
-    DEC_LCHE, ldpc_hip_open_codes_ims for DEC_IMS, ldpc_hip_open_codes_sp for DEC_SP and DEC_ASP): what a code search scores.
+    """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch (ldpc_hip_open_codes
+    or the decoder's own open entry point, _CODES_ROUTE): what a code search scores.
     decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP, DEC_LCHE, DEC_IMS, DEC_SP or DEC_ASP; bit-identical to LdpcHip on each matrix."""
 
     def __init__(self, decoder_id, codes, M, device=0):
@@ -699,16 +698,10 @@ class LdpcHipCodes:
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        own = {DEC_TASP: "ldpc_hip_open_codes_tdmp", DEC_IASP: "ldpc_hip_open_codes_iasp", DEC_LCHE: "ldpc_hip_open_codes_lche",
-               DEC_IMS: "ldpc_hip_open_codes_ims"}.get(self.decoder_id)
-        if self.decoder_id in (DEC_SP, DEC_ASP):
-            own = "ldpc_hip_open_codes_sp"
-            rc = self.lib.ldpc_hip_open_codes_sp(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
-        elif own:
-            rc = getattr(self.lib, own)(self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
-        else:
-            rc = self.lib.ldpc_hip_open_codes(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
-        _check(self.lib, rc, own or "ldpc_hip_open_codes")
+        who, takes_id, _, _ = _CODES_ROUTE.get(self.decoder_id, _CODES_GENERIC)
+        head = (self.decoder_id,) if takes_id else ()
+        rc = getattr(self.lib, who)(*head, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
+        _check(self.lib, rc, who)
         self.h = h
         self.N = self.lib.ldpc_hip_n(h)
         self.R = self.lib.ldpc_hip_r(h)

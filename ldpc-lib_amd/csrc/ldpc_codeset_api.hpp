@@ -51,59 +51,98 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
 
 namespace {
 
-// Dynamic LDS of the code-set kernels.  MS / LMS: the a-posteriori values of F frames + the vote flag.  TDMP: the a-posteriori
-// probabilities and the per-edge state Z[ne_max][M] of F frames + the vote flag.  IASP: the u16 state ST[ne_max][M], a-posteriori
-// word and channel word of F frames, rounded up to 16 bytes, + the vote flag.  LCHE: the a-posteriori LLRs and the per-edge state
-// Z[ne_max][M] of F frames, the tables of logexp, + the vote flag.  IMS: per frame an int16 a-posteriori value and an int16 channel
-// value per variable and an 8-byte record per check, F * (4 * N + 8 * R) bytes rounded up to 16, + the vote flag.  SP / ASP: the
-// images of ldpc_codeset_sp.hpp, F * (8 * (ne_max * M + N + R) + 4 * ceil(N / 32)) bytes (ASP: without the R check products) rounded
-// up to 16, + the vote flags.
-size_t codeset_lds_bytes(int decoder_id, int nh, int M, int F, int ne_max, int rh = 0) {
-    if (decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_ASP_DEC)
-        return ldpc::sp_codes_image_bytes(decoder_id == LDPC_HIP_ASP_DEC, F, nh * M, rh * M, M, ne_max) + 16;
-    if (decoder_id == LDPC_HIP_IMS_DEC) return ldpc::ims_codes_image_bytes(F, nh * M, rh * M) + 16;
-    if (decoder_id == LDPC_HIP_IASP_DEC) return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16;
-    if (decoder_id == LDPC_HIP_LCHE_DEC) return ldpc::lche_codes_image_bytes(F, M, nh * M, ne_max) + 16;
-    const size_t per_frame = (size_t)nh * M + (decoder_id == LDPC_HIP_TASP_DEC ? (size_t)ne_max * M : 0);
-    return sizeof(double) * per_frame * (size_t)F + 16;
+// Dynamic LDS of the code-set kernels for F frames per workgroup: the image that the kernel's header describes (ldpc_codeset.hpp,
+// ldpc_codeset_sp.hpp) + 16 for the vote flags.  MS / LMS: the a-posteriori values alone; TDMP: the per-edge state Z[ne_max][M] next to them.
+size_t codeset_lds_apost(int F, int, int nh, int M, int) { return sizeof(double) * ((size_t)nh * M) * (size_t)F + 16; }
+size_t codeset_lds_tdmp(int F, int, int nh, int M, int ne_max) { return sizeof(double) * ((size_t)nh * M + (size_t)ne_max * M) * (size_t)F + 16; }
+size_t codeset_lds_iasp(int F, int, int nh, int M, int ne_max) { return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16; }
+size_t codeset_lds_lche(int F, int, int nh, int M, int ne_max) { return ldpc::lche_codes_image_bytes(F, M, nh * M, ne_max) + 16; }
+size_t codeset_lds_ims(int F, int rh, int nh, int M, int) { return ldpc::ims_codes_image_bytes(F, nh * M, rh * M) + 16; }
+size_t codeset_lds_sp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(false, F, nh * M, rh * M, M, ne_max) + 16; }
+size_t codeset_lds_asp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(true, F, nh * M, rh * M, M, ne_max) + 16; }
+
+enum codeset_lds_text { LDS_NONE, LDS_LENGTH, LDS_IMS, LDS_IASP, LDS_TDMP, LDS_LCHE, LDS_FLOOD };   // the refusals of codeset_lds_refusal
+
+enum : unsigned {
+    CS_COLS = 1,     // the record goes on with cw2, col_start and col_edges, and a column entry names its edge in 16 bits
+    CS_FLOOD = 2,    // a frame's state is in LDS and dealt over the waves of a workgroup (ldpc_codeset_sp.hpp): frames and threads are
+                     // sp_codes_frames and sp_codes_groups x sp_codes_lanes, and a set is refused only when ONE frame's image does not fit
+    CS_CHECKS = 4,   // that image holds the R check products
+    CS_QUANT = 8,    // the kernel reads the quantiser's int16 words through a second argument (ImsCodesArgs)
+};
+
+// What a set decoder is on the host: the one place where the limits of the set kernels live
+struct codeset_kind {
+    int id;
+    const char *kernel;                // kernel_name, "<multiwave>" appended when M > 64
+    const void *wave, *multiwave;      // its instance for M <= 64 and the one for M > 64
+    int rh_max, nh_max, rw_max;        // block rows and block columns (the kernel holds them, or their channel LLRs, in registers) and row weight; 0: any
+    const char *min_rw2;               // row weight at least 2 (map_bin and imap_bin read SB[1], decoders.cpp:2191-2271), under this name; null: 1 is legal
+    unsigned is;                       // CS_*
+    size_t (*lds)(int F, int rh, int nh, int M, int ne_max);
+    codeset_lds_text early, late;      // the image is checked before the table is built (with ne_max = 0) and once ne_max is known
+};
+
+const codeset_kind codeset_kinds[] = {
+    {LDPC_HIP_SP_DEC, "sp_flood_codes_kernel", (const void *)ldpc::sp_flood_codes_kernel<false>, (const void *)ldpc::sp_flood_codes_kernel<true>,
+     0, 0, 0, nullptr, CS_COLS | CS_FLOOD | CS_CHECKS, codeset_lds_sp, LDS_NONE, LDS_FLOOD},
+    {LDPC_HIP_ASP_DEC, "asp_flood_codes_kernel", (const void *)ldpc::asp_flood_codes_kernel<kRWM, false>, (const void *)ldpc::asp_flood_codes_kernel<kRWM, true>,
+     0, 0, kRWM, "advanced sum-product", CS_COLS | CS_FLOOD, codeset_lds_asp, LDS_NONE, LDS_FLOOD},
+    {LDPC_HIP_MS_DEC, "ms_flood_codes_kernel", (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>, (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true>,
+     kRHM, kNHM, kRWM, nullptr, 0, codeset_lds_apost, LDS_LENGTH, LDS_NONE},
+    {LDPC_HIP_IMS_DEC, "ims_flood_codes_kernel", (const void *)ldpc::ims_flood_codes_kernel<false>, (const void *)ldpc::ims_flood_codes_kernel<true>,
+     0, 0, kRWM, nullptr, CS_QUANT, codeset_lds_ims, LDS_IMS, LDS_NONE},
+    {LDPC_HIP_IASP_DEC, "iasp_codes_kernel", (const void *)ldpc::iasp_codes_kernel<kRWM, false>, (const void *)ldpc::iasp_codes_kernel<kRWM, true>,
+     0, 0, kRWM, "integer advanced sum-product", CS_COLS, codeset_lds_iasp, LDS_NONE, LDS_IASP},
+    {LDPC_HIP_TASP_DEC, "tasp_layered_codes_kernel", (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>, (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true>,
+     kRHM, 0, kRWM, "TDMP sum-product", 0, codeset_lds_tdmp, LDS_LENGTH, LDS_TDMP},
+    {LDPC_HIP_LMS_DEC, "lms_layered_codes_kernel", (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>, (const void *)ldpc::lms_layered_codes_kernel<kRHM, true>,
+     kRHM, 0, kRWM, nullptr, 0, codeset_lds_apost, LDS_LENGTH, LDS_NONE},
+    {LDPC_HIP_LCHE_DEC, "lche_layered_codes_kernel", (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>, (const void *)ldpc::lche_layered_codes_kernel<kRWM, true>,
+     0, 0, kRWM, nullptr, 0, codeset_lds_lche, LDS_NONE, LDS_LCHE},
+};
+
+// The entry points come here with an id that their route serves
+const codeset_kind *codeset_find(int decoder_id) {
+    for (const codeset_kind &k : codeset_kinds)
+        if (k.id == decoder_id) return &k;
+    return nullptr;
 }
 
-// Checks a code set and builds its table: per code row_start[rh+1] (relative to the code's own edge list) then edges[]
-// ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  An IASP record goes on
-// with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and col_edges[]
-// ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  The one place where the limits
-// of the set kernels live.  own_route: the decoder whose own entry points the caller is one of (ldpc_hip_open_codes_lche,
-// ldpc_hip_codes_table_lche_host: 9; ldpc_hip_open_codes_ims, ldpc_hip_codes_table_ims_host: 4), or 0; decoders 4 and 9 through any
-// other route are refused like the ids no set kernel serves.  ldpc_hip_open_codes_sp / ldpc_hip_codes_table_sp_host pass 1 or 2 as
-// both: the IASP record under the limits of the two flooding sum-product kernels.
-int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
-                  std::vector<int32_t> &tab, int *ne_max_out = nullptr, int own_route = 0) {
-    const bool tdmp = decoder_id == LDPC_HIP_TASP_DEC, iasp = decoder_id == LDPC_HIP_IASP_DEC;
-    const bool lche = decoder_id == LDPC_HIP_LCHE_DEC && own_route == LDPC_HIP_LCHE_DEC;
-    const bool ims = decoder_id == LDPC_HIP_IMS_DEC && own_route == LDPC_HIP_IMS_DEC;
-    const bool sp = decoder_id == LDPC_HIP_SP_DEC && own_route == LDPC_HIP_SP_DEC, asp = decoder_id == LDPC_HIP_ASP_DEC && own_route == LDPC_HIP_ASP_DEC;
-    const bool flood = sp || asp;      // the state of a frame is in LDS and dealt over the waves of a workgroup: rh and nh are not limited
-    const bool cols = iasp || flood;   // the record goes on with cw2 and the column-major edges
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && !tdmp && !iasp && !lche && !ims && !flood)
-        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host and with IMS_DEC (4) through ldpc_hip_open_codes_ims / ldpc_hip_codes_table_ims_host, and with SP_DEC (1) or ASP_DEC (2) through ldpc_hip_open_codes_sp / ldpc_hip_codes_table_sp_host", who, decoder_id);
+// An image beyond 160 KiB, in the words of its kernel
+int codeset_lds_refusal(const codeset_kind &k, codeset_lds_text text, const char *who, int F, int rh, int nh, int M, int ne_max) {
+    const int N = nh * M;
+    const size_t bytes = k.lds(F, rh, nh, M, ne_max);
+    switch (text) {
+    case LDS_LENGTH: return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, N, F);
+    case LDS_IMS: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (4 x %d variables + 8 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, rh * M, bytes);
+    case LDS_IASP: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d circulants x %d checks + 2 x %d variables) halfwords need an LDS image of %zu bytes; the limit is 160 KiB", who, F, ne_max, M, N, bytes);
+    case LDS_TDMP: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, ne_max, M, bytes);
+    case LDS_LCHE: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori LLRs + %d circulants x %d checks) and the tables of logexp need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, ne_max, M, bytes);
+    default: return fail(LDPC_HIP_EUNSUPPORTED, "%s: one frame's image, 8 x (%d circulants x %d + %d variables%s) + 4 x %d bytes, rounded up to 16, + 16 is %zu bytes; the limit is 160 KiB", who, ne_max, M, N, k.is & CS_CHECKS ? " + the checks" : "", (N + 31) / 32, bytes);
+    }
+}
+
+// Checks a code set against the limits of its kernel and builds its table: per code row_start[rh+1] (relative to the code's own edge
+// list) then edges[] ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  A
+// CS_COLS record goes on with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and
+// col_edges[] ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).
+int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
+                  std::vector<int32_t> &tab, int *ne_max_out = nullptr) {
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
     if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
-    if (!iasp && !lche && !ims && !flood && rh > kRHM) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kRHM);
-    if (decoder_id == LDPC_HIP_MS_DEC && nh > kNHM)
-        return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kNHM);
-    const int F = M > 64 ? 1 : 64 / M;
-    if (ims && codeset_lds_bytes(decoder_id, nh, M, F, 0, rh) > 160 * 1024)
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (4 x %d variables + 8 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB",
-                    who, F, nh * M, rh * M, codeset_lds_bytes(decoder_id, nh, M, F, 0, rh));
-    if (!iasp && !lche && !ims && !flood && codeset_lds_bytes(decoder_id, nh, M, F, 0) > 160 * 1024)   // IASP, LCHE, SP, ASP: with the byte count, once ne_max is known
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length %d x %d frames per wave does not fit the 160 KiB LDS image", who, nh * M, F);
+    if (kind.rh_max && rh > kind.rh_max) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kind.rh_max);
+    if (kind.nh_max && nh > kind.nh_max)
+        return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kind.nh_max);
+    const int F = kind.is & CS_FLOOD ? 1 : M > 64 ? 1 : 64 / M;   // the frames whose images have to fit
+    if (kind.early && kind.lds(F, rh, nh, M, 0) > 160 * 1024) return codeset_lds_refusal(kind, kind.early, who, F, rh, nh, M, 0);
     off.clear(); tab.clear();
     std::vector<int> col_w((size_t)nh);
     int ne_max = 0;
     for (int c = 0; c < C; ++c) {
         const int16_t *h = hd + (size_t)c * rh * nh;
-        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (cols ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
+        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (kind.is & CS_COLS ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
             return fail(LDPC_HIP_EINVAL, "%s: the table of %d codes exceeds 2^31 entries", who, C);
         off.push_back((int32_t)tab.size());
         const size_t rs = tab.size();
@@ -122,19 +161,15 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
                 ++rw; ++ne;
             }
             if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
-            if (rw > kRWM && !sp) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kRWM);
-            if (tdmp && rw < 2)   // map_bin reads SB[1] (decoders.cpp:2191-2228)
-                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; TDMP sum-product needs at least 2", who, c, j, rw);
-            if (asp && rw < 2)    // map_bin reads SB[1] as well
-                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; advanced sum-product needs at least 2", who, c, j, rw);
-            if (iasp && rw < 2)   // imap_bin reads SB[1] (decoders.cpp:2235-2271)
-                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; integer advanced sum-product needs at least 2", who, c, j, rw);
+            if (kind.rw_max && rw > kind.rw_max) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kind.rw_max);
+            if (kind.min_rw2 && rw < 2)
+                return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; %s needs at least 2", who, c, j, rw, kind.min_rw2);
         }
         tab[rs + rh] = ne;
         ne_max = ne > ne_max ? ne : ne_max;
         for (int k = 0; k < nh; ++k)
             if (!col_w[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
-        if (cols) {
+        if (kind.is & CS_COLS) {
             if (ne > 65535) return fail(LDPC_HIP_EINVAL, "%s: code %d has %d circulants; a column entry names its edge in 16 bits", who, c, ne);
             bool cw2 = true;   // the rule of ldpc_hip_open, per code
             for (int k = 0; k < nh; ++k) cw2 = cw2 && col_w[(size_t)k] == 2;
@@ -151,18 +186,7 @@ int codeset_build(const char *who, int decoder_id, int rh, int nh, int M, const 
             }
         }
     }
-    if (flood && codeset_lds_bytes(decoder_id, nh, M, 1, ne_max, rh) > 160 * 1024)   // ONE frame does not fit; fewer frames share a workgroup otherwise
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: one frame's image, 8 x (%d circulants x %d + %d variables%s) + 4 x %d bytes, rounded up to 16, + 16 is %zu bytes; the limit is 160 KiB",
-                    who, ne_max, M, nh * M, sp ? " + the checks" : "", (nh * M + 31) / 32, codeset_lds_bytes(decoder_id, nh, M, 1, ne_max, rh));
-    if (iasp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d circulants x %d checks + 2 x %d variables) halfwords need an LDS image of %zu bytes; the limit is 160 KiB",
-                    who, F, ne_max, M, nh * M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
-    if (tdmp && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB",
-                    who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
-    if (lche && codeset_lds_bytes(decoder_id, nh, M, F, ne_max) > 160 * 1024)
-        return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori LLRs + %d circulants x %d checks) and the tables of logexp need an LDS image of %zu bytes; the limit is 160 KiB",
-                    who, F, nh * M, ne_max, M, codeset_lds_bytes(decoder_id, nh, M, F, ne_max));
+    if (kind.late && kind.lds(F, rh, nh, M, ne_max) > 160 * 1024) return codeset_lds_refusal(kind, kind.late, who, F, rh, nh, M, ne_max);
     if (ne_max_out) *ne_max_out = ne_max;
     return 0;
 }
@@ -214,38 +238,39 @@ int codeset_upload(codeset_common &s, int C, int ne_max, std::vector<int32_t> &o
     return 0;
 }
 
+int codeset_table_host(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                       long long capacity, long long *length) {
+    std::vector<int32_t> off, tab;
+    if (int rc = codeset_build(who, *codeset_find(decoder_id), rh, nh, M, hd, C, off, tab)) return rc;
+    return codeset_table_out(who, off, tab, offsets, table, capacity, length);
+}
+
 }  // namespace
 
 extern "C" {
 
 int ldpc_hip_codes_table_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                               long long capacity, long long *length) {
-    std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_codes_table_host", decoder_id, rh, nh, M, hd, C, off, tab)) return rc;
-    return codeset_table_out("ldpc_hip_codes_table_host", off, tab, offsets, table, capacity, length);
+    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_IASP_DEC && decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_LMS_DEC)
+        return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; a code set decodes with MS_DEC (3), IASP_DEC (5), TASP_DEC (7) or LMS_DEC (8), with LCHE_DEC (9) through ldpc_hip_open_codes_lche / ldpc_hip_codes_table_lche_host and with IMS_DEC (4) through ldpc_hip_open_codes_ims / ldpc_hip_codes_table_ims_host, and with SP_DEC (1) or ASP_DEC (2) through ldpc_hip_open_codes_sp / ldpc_hip_codes_table_sp_host", "ldpc_hip_codes_table_host", decoder_id);
+    return codeset_table_host("ldpc_hip_codes_table_host", decoder_id, rh, nh, M, hd, C, offsets, table, capacity, length);
 }
 
 int ldpc_hip_codes_table_lche_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
                                    long long *length) {
-    std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_codes_table_lche_host", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, off, tab, nullptr, LDPC_HIP_LCHE_DEC)) return rc;
-    return codeset_table_out("ldpc_hip_codes_table_lche_host", off, tab, offsets, table, capacity, length);
+    return codeset_table_host("ldpc_hip_codes_table_lche_host", LDPC_HIP_LCHE_DEC, rh, nh, M, hd, C, offsets, table, capacity, length);
 }
 
 int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table, long long capacity,
                                   long long *length) {
-    std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_codes_table_ims_host", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, off, tab, nullptr, LDPC_HIP_IMS_DEC)) return rc;
-    return codeset_table_out("ldpc_hip_codes_table_ims_host", off, tab, offsets, table, capacity, length);
+    return codeset_table_host("ldpc_hip_codes_table_ims_host", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, offsets, table, capacity, length);
 }
 
 int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                                  long long capacity, long long *length) {
     if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_codes_table_sp_host: decoder id %d; SP_DEC (1) or ASP_DEC (2)", decoder_id);
-    std::vector<int32_t> off, tab;
-    if (int rc = codeset_build("ldpc_hip_codes_table_sp_host", decoder_id, rh, nh, M, hd, C, off, tab, nullptr, decoder_id)) return rc;
-    return codeset_table_out("ldpc_hip_codes_table_sp_host", off, tab, offsets, table, capacity, length);
+    return codeset_table_host("ldpc_hip_codes_table_sp_host", decoder_id, rh, nh, M, hd, C, offsets, table, capacity, length);
 }
 
 }  // extern "C"
@@ -257,7 +282,8 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
     int ne_max = 0;
-    if (int rc = codeset_build(who, decoder_id, rh, nh, M, hd, C, off, tab, &ne_max, decoder_id)) return rc;   // only ldpc_hip_open_codes_lche passes 9, only ldpc_hip_open_codes_ims 4, only ldpc_hip_open_codes_sp 1 or 2
+    const codeset_kind &kind = *codeset_find(decoder_id);
+    if (int rc = codeset_build(who, kind, rh, nh, M, hd, C, off, tab, &ne_max)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
@@ -265,23 +291,18 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
-    const bool flood = decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_ASP_DEC;
-    c->ne = decoder_id == LDPC_HIP_IASP_DEC || flood ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
-                                            : (int)(tab.size() - (size_t)C * (rh + 1));
+    c->ne = kind.is & CS_COLS ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
+                              : (int)(tab.size() - (size_t)C * (rh + 1));
     c->hard_words = (c->N + 31) / 32;
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
     c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
-    if (flood) {   // ldpc_codeset_sp.hpp: fewer frames when their images do not fit, several groups of lanes per frame
-        c->F = ldpc::sp_codes_frames(decoder_id == LDPC_HIP_ASP_DEC, c->N, c->R, M, ne_max);
+    if (kind.is & CS_FLOOD) {   // fewer frames when their images do not fit, several groups of lanes per frame
+        c->F = ldpc::sp_codes_frames(!(kind.is & CS_CHECKS), c->N, c->R, M, ne_max);
         c->threads = ldpc::sp_codes_groups(M, nh) * ldpc::sp_codes_lanes(M);
     }
-    c->lds_bytes = codeset_lds_bytes(decoder_id, nh, M, c->F, ne_max, rh);
-    c->kernel_name = std::string(decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_codes_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_layered_codes_kernel" :
-                                 decoder_id == LDPC_HIP_IASP_DEC ? "iasp_codes_kernel" : decoder_id == LDPC_HIP_LCHE_DEC ? "lche_layered_codes_kernel" :
-                                 decoder_id == LDPC_HIP_IMS_DEC ? "ims_flood_codes_kernel" : decoder_id == LDPC_HIP_SP_DEC ? "sp_flood_codes_kernel" :
-                                 decoder_id == LDPC_HIP_ASP_DEC ? "asp_flood_codes_kernel" : "tasp_layered_codes_kernel") +
-                     (c->multiwave ? "<multiwave>" : "");
+    c->lds_bytes = kind.lds(c->F, rh, nh, M, ne_max);
+    c->kernel_name = std::string(kind.kernel) + (c->multiwave ? "<multiwave>" : "");
     HIP_TRY(hipSetDevice(device));
     if (int rc = codeset_upload(*s, C, ne_max, off, tab)) return rc;
     *out = c.release();
@@ -331,28 +352,13 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
     a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
     a.alpha = alpha; a.ne_max = s->ne_max;
-    const void *k;
-    if (c->decoder_id == LDPC_HIP_TASP_DEC)   // alpha is not read
-        k = c->multiwave ? (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true> : (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>;
-    else if (c->decoder_id == LDPC_HIP_IASP_DEC)   // alpha is not read here either
-        k = c->multiwave ? (const void *)ldpc::iasp_codes_kernel<kRWM, true> : (const void *)ldpc::iasp_codes_kernel<kRWM, false>;
-    else if (c->decoder_id == LDPC_HIP_LCHE_DEC)   // nor here
-        k = c->multiwave ? (const void *)ldpc::lche_layered_codes_kernel<kRWM, true> : (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>;
-    else if (c->decoder_id == LDPC_HIP_IMS_DEC)    // alpha is read: ialpha below
-        k = c->multiwave ? (const void *)ldpc::ims_flood_codes_kernel<true> : (const void *)ldpc::ims_flood_codes_kernel<false>;
-    else if (c->decoder_id == LDPC_HIP_SP_DEC)     // alpha is not read
-        k = c->multiwave ? (const void *)ldpc::sp_flood_codes_kernel<true> : (const void *)ldpc::sp_flood_codes_kernel<false>;
-    else if (c->decoder_id == LDPC_HIP_ASP_DEC)    // nor here
-        k = c->multiwave ? (const void *)ldpc::asp_flood_codes_kernel<kRWM, true> : (const void *)ldpc::asp_flood_codes_kernel<kRWM, false>;
-    else if (c->decoder_id == LDPC_HIP_MS_DEC)
-        k = c->multiwave ? (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_codes_kernel<kRHM, kNHM, false>;
-    else
-        k = c->multiwave ? (const void *)ldpc::lms_layered_codes_kernel<kRHM, true> : (const void *)ldpc::lms_layered_codes_kernel<kRHM, false>;
+    const codeset_kind &kind = *codeset_find(c->decoder_id);
+    const void *k = c->multiwave ? kind.multiwave : kind.wave;
     if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
     ProfTimer timer;
     if (int rc = timer.begin(c, stream)) return rc;
-    ldpc::ImsCodesArgs ia{};   // the second argument of ims_flood_codes_kernel; the other kernels take the first alone
-    if (c->decoder_id == LDPC_HIP_IMS_DEC) {   // once per received word: B of them when the codes share the LLRs, C * B otherwise
+    ldpc::ImsCodesArgs ia{};   // the second argument of a CS_QUANT kernel; the others take the first alone
+    if (kind.is & CS_QUANT) {   // once per received word: B of them when the codes share the LLRs, C * B otherwise
         if (int rc = codeset_ims_quantise(c, d_llr, shared_llr ? B : B * (long long)s->C, stream)) return rc;
         ia.q = s->w_q; ia.max_data = (1 << (c->ims_dbits - 1)) - 1; ia.ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5445, :5458
     }
@@ -374,7 +380,7 @@ long long codeset_piece(size_t bytes_per_frame, const char *cap_env, long long B
 
 long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
     size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
-    if (c->decoder_id == LDPC_HIP_IMS_DEC) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
+    if (codeset_find(c->decoder_id)->is & CS_QUANT) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
     return codeset_piece(per_frame, "LDPC_HIP_CODES_PIECE", B);
 }
 
@@ -406,8 +412,7 @@ void codeset_channel_args(const ldpc_hip_ctx *c, int punctured_blocks, uint64_t 
     ch.llr = c->codes->w_llr; ch.N = c->N; ch.T = 26.0; ch.seed = seed;
     ch.tx = nullptr; ch.ncw = 1; ch.ntx = c->N; ch.scatter = nullptr;
     ch.punct_start = c->N - c->M * punctured_blocks;
-    ch.punct_val = c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC ||
-                   c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC ? 0.0 : 0.5;   // the rule of ldpc_hip_awgn_llr_dev (bp_simulation.cpp:700, out_type :451-466)
+    ch.punct_val = punctured_llr(c->decoder_id);
 }
 
 int codeset_channel_launch(const ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, long long first_frame, long long nb) {

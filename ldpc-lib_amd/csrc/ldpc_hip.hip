@@ -943,6 +943,12 @@ int ldpc_hip_set_bp_chain(ldpc_hip_ctx *c, int on, int reset_carry) {
     return 0;
 }
 
+// What the channel writes at a punctured position for this decoder (bp_simulation.cpp:700 (sic), out_type :451-466)
+static double punctured_llr(int decoder_id) {
+    return (decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_TASP_DEC || decoder_id == LDPC_HIP_ASP_DEC ||
+            decoder_id == LDPC_HIP_IASP_DEC || decoder_id == LDPC_HIP_LCHE_DEC) ? 0.0 : 0.5;
+}
+
 static int awgn_sigma(const ldpc_hip_ctx *c, double snr_db, int modulation_type, int punctured_blocks, double *sigma) {
     const int b = c->rh, cc = c->nh;
     if (punctured_blocks < 0 || punctured_blocks >= cc) return fail(LDPC_HIP_EINVAL, "punctured_blocks=%d", punctured_blocks);
@@ -1142,8 +1148,7 @@ int ldpc_hip_channel_llr_dev(ldpc_hip_ctx *c, double snr_db, int modulation_type
     a.tx = c->ncw > 0 ? c->d_tx : nullptr; a.ncw = c->ncw > 0 ? c->ncw : 1; a.ntx = c->chain_ntx;
     a.scatter = c->d_scatter;
     a.punct_start = c->N - c->M * punctured_blocks;
-    a.punct_val = (c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC ||
-                   c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC) ? 0.0 : 0.5;  // :700 (sic), out_type :451-466
+    a.punct_val = punctured_llr(c->decoder_id);
     const int m = modulation_type <= 1 ? 2 : 2 * modulation_type;
     const long long total = B * (long long)((c->N + m - 1) / m);
     long long blocks = (total + 255) / 256;

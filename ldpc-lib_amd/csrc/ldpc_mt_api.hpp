@@ -233,8 +233,7 @@ int mt_frame_proto(ldpc_hip_ctx *c, double snr_db, int modulation_type, int punc
     a.tx = c->ncw > 0 ? c->d_tx : nullptr; a.ncw = c->ncw > 0 ? c->ncw : 1; a.ntx = c->chain_ntx;
     a.scatter = c->d_scatter;
     a.punct_start = c->N - c->M * punctured_blocks;
-    a.punct_val = (c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC ||
-                   c->decoder_id == LDPC_HIP_IASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC) ? 0.0 : 0.5;  // :700 (sic)
+    a.punct_val = punctured_llr(c->decoder_id);
     return 0;
 }
 
