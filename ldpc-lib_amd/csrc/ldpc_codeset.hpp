@@ -18,6 +18,12 @@
 // ldpc_spec::lche; IMS: integers behind a quantiser that runs once per received word); only the frame index and the table base differ
 // (and, for TDMP, IASP, LCHE and IMS, where the state lives), so the results are bit-identical to a single-code context.
 // The two flooding sum-product decoders (ids 1 and 2) deal a frame over several waves and live in ldpc_codeset_sp.hpp.
+// Structure: the min-sum, layered min-sum, IASP and integer min-sum set kernels are codeset_view, their own state and arithmetic, and the
+// pieces that ldpc_kernels.hpp holds once for every frame-resident kernel -- frame_lane, edge_idx, row_syndrome, stop_vote / stop_all,
+// frame_outputs.  The flooding min-sum kernel is nothing but the view and ms_flood_body.  Where a shared piece cost registers or time its
+// kernel kept its own: iasp_codes_kernel writes its outputs itself (the reason stands in the kernel), lms_layered_codes_kernel has its own
+// syndrome and edge decode, and tasp_layered_codes_kernel and lche_layered_codes_kernel use none of the pieces: with them they were 0.7 % and
+// 1.0 - 1.5 % slower (profiles/kernel_refactor_time.txt).
 #pragma once
 
 #include "ldpc_kernels.hpp"
@@ -71,109 +77,10 @@ __device__ __forceinline__ DecArgs codeset_view(const CodesetArgs &s, int &w) {
 // ---------------------------------------------------------------------------------------------------------
 template <int RHM, int NHM, bool MW>
 __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_codes_kernel(const CodesetArgs s) {
-    extern __shared__ double lds[];  // [N][F] soft / acc, then one flag word
+    extern __shared__ double lds[];
     int w;
     const DecArgs a = codeset_view(s, w);
-    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
-    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
-    int *const sh_flag = (int *)(lds + (size_t)N * F);
-    const double alpha = a.alpha;
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)w * F + f;   // frame of THIS code
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
-
-    double y[NHM];
-#pragma unroll
-    for (int k = 0; k < NHM; ++k) y[k] = (k < nh && live) ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
-
-    double m1[RHM], m2[RHM];
-    uint32_t meta[RHM];
-#pragma unroll
-    for (int j = 0; j < RHM; ++j) { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }
-
-    bool done = !inb;
-    int res = -a.maxiter;
-
-    for (int iter = 0; iter < a.maxiter; ++iter) {
-        const bool wr = !done && valid;
-        // ---- STATE1
-        if (wr) {
-#pragma unroll
-            for (int k = 0; k < NHM; ++k) if (k < nh) lds[(k * M + n) * F + f] = 0.0;
-        }
-        if (MW) __syncthreads();
-#pragma unroll
-        for (int j = 0; j < RHM; ++j) {
-            if (j < rh) {
-                const int e0 = rs[j], rw = rs[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = (uint32_t)ed[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
-                    const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                    if (wr) lds[addr] = lds[addr] + cv;
-                }
-                if (MW) __syncthreads();
-            }
-        }
-        // ---- STATE2: multiply, then add -- two roundings (no FMA)
-        if (wr) {
-#pragma unroll
-            for (int k = 0; k < NHM; ++k) {
-                if (k < nh) {
-                    const int o = (k * M + n) * F + f;
-                    const double p = lds[o] * alpha;
-                    lds[o] = y[k] + p;
-                }
-            }
-        }
-        if (MW) __syncthreads();
-        // ---- STATE3
-        uint32_t failw = 0;
-#pragma unroll
-        for (int j = 0; j < RHM; ++j) {
-            if (j < rh) {
-                const int e0 = rs[j], rw = rs[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                const double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
-                double nm1 = kMaxVal, nm2 = kMaxVal;
-                uint32_t npos = 0, nS = 0, sy = 0;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = (uint32_t)ed[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
-                    const double r = lds[addr];
-                    sy ^= hi32(r);
-                    const double aa = (pos == (uint32_t)idx) ? a2 : a1;
-                    const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                    const double t = r - x;
-                    nS |= (hi32(t) >> 31) << idx;
-                    const double v = fmin(fabs(t), kMaxVal);
-                    const bool c1 = v < nm1;
-                    nm2 = fmin(fmax(v, nm1), nm2);
-                    npos = c1 ? (uint32_t)idx : npos;
-                    nm1 = fmin(v, nm1);
-                }
-                failw |= sy;
-                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
-            }
-        }
-        const bool fail = valid && (failw >> 31);
-        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
-        if (!done && !frame_fail) { done = true; res = iter + 1; }
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
-    }
-    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
+    ms_flood_body<RHM, NHM, MW>(a, lds, w, tab_ptr(a.row_start), tab_ptr(a.edges));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -193,16 +100,13 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const 
     const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
     int *const sh_flag = (int *)(lds + (size_t)N * F);
     const double beta = 0.4;
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)w * F + f;
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, w);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
 
     if (valid) {
         for (int k = 0; k < nh; ++k)
-            lds[(k * M + n) * F + f] = live ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
+            lds[(k * M + n) * F + f] = l.live ? a.llr[l.fr * N + k * M + n] + 0.0 : 0.0;
     }
     double m1[RHM], m2[RHM];
     uint32_t meta[RHM];
@@ -225,15 +129,12 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const 
         return valid && (failw >> 31);
     };
 
-    bool done = !inb;
-    int res = -a.maxiter;
-    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);
-    if (!done && !frame_fail) { done = true; res = 1; }
-    const bool at_entry = done && inb;   // no layer ran: upstream's soft[] is y itself, -0.0 included
+    FrameStop st = stop_init(l, a.maxiter);
+    stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, 1);
+    const bool at_entry = st.done && l.inb;   // no layer ran: upstream's soft[] is y itself, -0.0 included
     for (int iter = 0; iter < a.maxiter; ++iter) {
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
-        const bool wr = !done && valid;
+        if (stop_all<MW>(st)) break;
+        const bool wr = !st.done && valid;
 #pragma unroll
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
@@ -272,16 +173,15 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const 
                     const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
                     if (wr) lds[addr] = t + cv;
                 }
-                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
                 if (MW) __syncthreads();
             }
         }
-        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);
-        if (!done && !frame_fail) { done = true; res = iter + 1; }
+        stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, iter + 1);
     }
-    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
-    if (live && at_entry && a.soft_out)
-        for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = a.llr[fr * N + k * M + n];
+    write_outputs(a, lds, l, st.res);
+    if (l.live && at_entry && a.soft_out)
+        for (int k = 0; k < a.nh; ++k) a.soft_out[l.fr * N + k * M + n] = a.llr[l.fr * N + k * M + n];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -495,21 +395,20 @@ __global__ void __launch_bounds__(MW ? 512 : 64) iasp_codes_kernel(const Codeset
     uint16_t *const ST = reinterpret_cast<uint16_t *>(lds);
     uint16_t *const so = ST + s.ne_max * M * F, *const ych = so + N * F;
     int *const sh_flag = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + iasp_codes_words_bytes(F, M, N, s.ne_max));
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)w * F + f;
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, w);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
     auto back = [&](int t, int c) { const int x = t - c; return x < 0 ? x + M : x; };   // the check of variable t on an edge of shift c
-    // where the frame's outputs go, per lane (VGPRs): the scalar registers are the scarce ones in the loops below
-    uint32_t *const hard_fr = a.hard ? a.hard + fr * a.hard_words : nullptr;
-    int32_t *const iters_fr = a.iters ? a.iters + fr : nullptr;
-    double *const soft_fr = a.soft_out ? a.soft_out + fr * N + n : nullptr;
+    // where the frame's outputs go, per lane (VGPRs): the scalar registers are the scarce ones in the loops below.  That is why this
+    // kernel writes its outputs itself: frame_outputs forms these addresses at the end, from values that stay in scalar registers
+    // through the iteration loop, and the kernel then spills scalar registers, which it does not do this way.
+    uint32_t *const hard_fr = a.hard ? a.hard + l.fr * a.hard_words : nullptr;
+    int32_t *const iters_fr = a.iters ? a.iters + l.fr : nullptr;
+    double *const soft_fr = a.soft_out ? a.soft_out + l.fr * N + n : nullptr;
 
     if (valid) {                                                                    // :3858-3897
         for (int k = 0; k < nh; ++k) {
-            const uint32_t q = I::q12(I::prior(live ? a.llr[fr * N + k * M + n] : 0.0));
+            const uint32_t q = I::q12(I::prior(l.live ? a.llr[l.fr * N + k * M + n] : 0.0));
             for (int c = rs[cs + k]; c < rs[cs + k + 1]; ++c) {                     // state <- rotated Q12 value
                 const uint32_t d = (uint32_t)rs[ce + c];
                 ST[((int)(d >> 16) * M + back(n, (int)(d & 0xffffu))) * F + f] = (uint16_t)q;
@@ -520,27 +419,14 @@ __global__ void __launch_bounds__(MW ? 512 : 64) iasp_codes_kernel(const Codeset
     if (MW) __syncthreads();
 
     auto syndrome_fail = [&]() -> bool {                                            // icheck_syndrome :3772-3803
-        uint32_t failw = 0;
-        for (int j = 0; j < rh; ++j) {
-            const int e0 = rs[j], e1 = rs[j + 1];
-            uint32_t sy = 0;
-            for (int e = e0; e < e1; ++e) {
-                const uint32_t d = (uint32_t)rs[ed + e];
-                sy ^= (uint32_t)so[((int)(d >> 16) * M + rot_idx(n, (int)(d & 0xffffu), M)) * F + f] >> 15;
-            }
-            failw |= sy;
-        }
-        return valid && failw;
+        return valid && row_syndrome(rs, rs + ed, rh, l, M, F, [=](int i) { return (uint32_t)so[i] >> 15; }) != 0;
     };
 
-    bool done = !inb;
-    int res = -a.maxiter;
-    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);          // :3899-3906
-    if (!done && !frame_fail) { done = true; res = 0; }                             // a codeword at the input: no iteration, 0
+    FrameStop st = stop_init(l, a.maxiter);
+    stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, 0);                           // :3899-3906; a codeword at the input: no iteration, 0
     for (int steps = 0; steps < a.maxiter;) {
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
-        const bool wr = !done && valid;
+        if (stop_all<MW>(st)) break;
+        const bool wr = !st.done && valid;
         for (int j = 0; j < rh; ++j) {                                              // imap_bin :2235-2271, row weights 2 .. RWM
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             int z = (e0 * M + n) * F + f;                                           // slot i of the check: ST[z], z walks up, then down
@@ -602,13 +488,12 @@ __global__ void __launch_bounds__(MW ? 512 : 64) iasp_codes_kernel(const Codeset
             }
         }
         if (MW) __syncthreads();
-        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);           // :4104-4113
-        ++steps;
-        if (!done && !frame_fail) { done = true; res = steps; }                     // else -steps = -maxiter at the end
+        ++steps;                                                                    // a frame that never passes keeps -steps = -maxiter
+        stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, steps);                   // :4104-4113
     }
     // hard bit = so >> 15, soft output = so / 65536 (imake_output :3805-3820, decision 1)
-    if (!live) return;
-    if (n == 0 && iters_fr) *iters_fr = res;
+    if (!l.live) return;
+    if (n == 0 && iters_fr) *iters_fr = st.res;
     if (hard_fr) {
         for (int wd = n; wd < a.hard_words; wd += M) {
             uint32_t bits = 0;
@@ -841,24 +726,20 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
     int16_t *const soft = reinterpret_cast<int16_t *>(rec + (size_t)R * F), *const iy = soft + (size_t)N * F;
     int *const sh_flag = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + ims_codes_image_bytes(F, N, R));
     const int max_data = q.max_data, ialpha = q.ialpha;
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)w * F + f;
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, w);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
     auto sat = [&](int x) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); };  // limit_val :4308
 
     if (valid) {
-        const int16_t *const qf = q.q + (a.llr - s.llr) + (inb ? fr : 0) * (long long)N;   // the code's slice, as for the LLRs
-        for (int k = 0; k < nh; ++k) iy[(k * M + n) * F + f] = live ? qf[k * M + n] : (int16_t)0;
+        const int16_t *const qf = q.q + (a.llr - s.llr) + (l.inb ? l.fr : 0) * (long long)N;   // the code's slice, as for the LLRs
+        for (int k = 0; k < nh; ++k) iy[(k * M + n) * F + f] = l.live ? qf[k * M + n] : (int16_t)0;
         for (int j = 0; j < rh; ++j) rec[(j * M + n) * F + f] = make_uint2(0u, 0u);        // :5462-5470
     }
 
-    bool done = !inb;
-    int res = -a.maxiter;
+    FrameStop st = stop_init(l, a.maxiter);
     for (int iter = 0; iter < a.maxiter; ++iter) {
-        const bool wr = !done && valid;
+        const bool wr = !st.done && valid;
         if (wr)
             for (int k = 0; k < nh; ++k) soft[(k * M + n) * F + f] = 0;
         if (MW) __syncthreads();
@@ -870,9 +751,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
             const uint32_t pos = mt >> kRowBits;
             const int c1 = ((int)(rc.x & 0xffffu) * ialpha) >> 4, c2 = ((int)(rc.x >> 16) * ialpha) >> 4;
             for (int idx = 0; idx < rw; ++idx) {
-                const uint32_t d = (uint32_t)ed[e0 + idx];
-                const int k = d >> 16, c = d & 0xffffu;
-                const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
                 const int tmp = (pos == (uint32_t)idx) ? c2 : c1;
                 const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
                 if (wr) soft[addr] = (int16_t)sat((int)soft[addr] + cv);
@@ -898,9 +777,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
             int nm1 = max_data, nm2 = max_data;
             uint32_t npos = 0, nS = 0, sy = 0;
             for (int idx = 0; idx < rw; ++idx) {
-                const uint32_t d = (uint32_t)ed[e0 + idx];
-                const int k = d >> 16, c = d & 0xffffu;
-                const int r = soft[(k * M + rot_idx(n, c, M)) * F + f];
+                const int r = soft[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
                 sy ^= (uint32_t)r;
                 const int val = (pos == (uint32_t)idx) ? c2 : c1;
                 const int t = (((mt >> idx) ^ par) & 1u) ? -val : val;
@@ -914,26 +791,10 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
             failw |= sy;
             if (wr) rec[ri] = make_uint2((uint32_t)nm1 | ((uint32_t)nm2 << 16), nS | (npos << kRowBits));
         }
-        const bool fail = valid && (failw >> 31);
-        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
-        if (!done && !frame_fail) { done = true; res = iter + 1; }  // :5684-5689
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
+        stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :5684-5689
+        if (stop_all<MW>(st)) break;
     }
-    if (!live) return;
-    if (n == 0 && a.iters) a.iters[fr] = res;
-    if (a.hard) {
-        for (int wd = n; wd < a.hard_words; wd += M) {
-            uint32_t bits = 0;
-            for (int b = 0; b < 32; ++b) {
-                const int v = 32 * wd + b;
-                if (v < N) bits |= ((uint32_t)(int)soft[v * F + f] >> 31) << b;
-            }
-            a.hard[fr * a.hard_words + wd] = bits;
-        }
-    }
-    if (a.soft_out)
-        for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = (double)soft[(k * M + n) * F + f];
+    frame_outputs(a, F, l, st.res, [=](int i) { return (uint32_t)(int)soft[i] >> 31; }, [=](int i) { return (double)soft[i]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -22,6 +22,14 @@
 // -0.0 (and NaN); inputs are canonicalised (y + 0.0) on load, after which no intermediate of the algorithms
 // can be -0.0 (x - y is -0.0 only for x = -0.0, y = +0.0; x + y only for x = y = -0.0), and the sign of a
 // zero never influences a non-zero value or a comparison.  Inputs must be finite.
+//
+// What every frame-resident kernel does the same way is written once, here, for this file and for the code-set
+// kernels of ldpc_codeset.hpp: who a lane is (Lane, frame_lane), the LDS index behind an edge (edge_idx), the
+// per-row syndrome (row_syndrome), the stop bookkeeping (FrameStop, stop_vote, stop_all) and the frame's
+// outputs (frame_outputs).  What differs between decoders -- the word whose bit decides, the result a clean
+// vote stores, the conversion of the soft value -- arrives as a functor or a value.  The functors capture their
+// LDS pointer by value ([=]): captured by reference it sits in a stack slot until the functor is inlined, and the
+// register allocation of the whole kernel moves (profiles/kernel_refactor_resources.txt).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,9 +84,54 @@ __device__ __forceinline__ unsigned long long slot_mask(int F) {
     return per;
 }
 
+// Who a lane is in work item w (the w-th wave or workgroup of a code's frames): lane_map's (n, f, valid), the lane
+// mask of frame slot 0, the frame, whether the frame exists (uniform per frame, and per workgroup when MW) and
+// whether the lane has a frame and a row of it to store for.
+// The kernels copy n, f and valid into locals, so that their arithmetic lines read as they always did, and read the
+// rest (fr, inb, live) through the struct.
+struct Lane {
+    int n, f;
+    bool valid;
+    unsigned long long per;
+    long long fr;
+    bool inb, live;
+};
+
+template <bool MW>
+__device__ __forceinline__ Lane frame_lane(int F, int M, long long B, int w) {
+    Lane l;
+    l.valid = lane_map<MW>(F, M, l.n, l.f);
+    l.per = MW ? 0ull : slot_mask(F);
+    l.fr = (long long)w * F + l.f;
+    l.inb = l.fr < B;
+    l.live = l.valid && l.inb;
+    return l;
+}
+
 __device__ __forceinline__ int rot_idx(int n, int c, int M) {
     int t = n + c;
     return t >= M ? t - M : t;
+}
+
+// The LDS index of the variable that check n reaches over edge d = (block column << 16) | shift
+__device__ __forceinline__ int edge_idx(uint32_t d, int n, int M, int F, int f) {
+    const int k = d >> 16, c = d & 0xffffu;
+    return (k * M + rot_idx(n, c, M)) * F + f;
+}
+
+// check_syndrome's double loop (decoders.cpp:793-814) for the lane's check of every block row: the OR over the
+// block rows of the XOR over the row's variables of word(LDS index).  The caller picks the deciding bit of the
+// result and masks it with the lane's validity.
+template <class RowStart, class Edges, class Word>
+__device__ __forceinline__ uint32_t row_syndrome(RowStart rs, Edges ed, int rh, const Lane &l, int M, int F, Word word) {
+    uint32_t failw = 0;
+    for (int j = 0; j < rh; ++j) {
+        const int e0 = rs[j], e1 = rs[j + 1];
+        uint32_t sy = 0;
+        for (int e = e0; e < e1; ++e) sy ^= word(edge_idx((uint32_t)ed[e], l.n, M, F, l.f));
+        failw |= sy;
+    }
+    return failw;
 }
 
 // "Does any check of MY frame fail?"  fail/valid are per lane.  Returns a per-lane bool (uniform per frame).
@@ -100,32 +153,50 @@ __device__ __forceinline__ bool frame_vote(bool fail, int F, int f, unsigned lon
     }
 }
 
-// Pack the hard decisions of a frame from the sign bits of the LDS-resident soft values and write the
-// frame's outputs.  Called by all lanes of the frame.
+// Stop bookkeeping, per FRAME: every lane of a frame (valid or not) carries the same values.  A frame beyond B is
+// done from the start; res stays -maxiter for a frame that the iteration loop leaves unconverged.
+struct FrameStop {
+    bool done;
+    int res;
+};
+
+__device__ __forceinline__ FrameStop stop_init(const Lane &l, int maxiter) { return FrameStop{!l.inb, -maxiter}; }
+
+// Vote on the lanes' failing checks; a running frame without one stops with the result res_clean.
 template <bool MW>
-__device__ __forceinline__ void write_outputs(const DecArgs &a, const double *lds, long long fr, int n, int f,
-                                               bool live, int res, double thr_is_one) {
-    const int M = a.M, F = a.F, N = a.N;
-    if (!live) return;
-    if (n == 0 && a.iters) a.iters[fr] = res;
+__device__ __forceinline__ void stop_vote(FrameStop &st, bool fail, const Lane &l, int F, int *sh_flag, int res_clean) {
+    const bool frame_fail = frame_vote<MW>(fail, F, l.f, l.per, sh_flag);
+    if (!st.done && !frame_fail) { st.done = true; st.res = res_clean; }
+}
+
+// all frames of this wave (MW: the frame of this workgroup) are done
+template <bool MW>
+__device__ __forceinline__ bool stop_all(const FrameStop &st) { return MW ? st.done : __all(st.done); }
+
+// The outputs of a frame, called by all its lanes: the iteration result, the hard decisions hard(LDS index of the
+// variable) packed 32 to a word, and the soft values soft(LDS index).
+template <class Hard, class Soft>
+__device__ __forceinline__ void frame_outputs(const DecArgs &a, int F, const Lane &l, int res, Hard hard, Soft soft) {
+    const int M = a.M, N = a.N;
+    if (!l.live) return;
+    if (l.n == 0 && a.iters) a.iters[l.fr] = res;
     if (a.hard) {
-        for (int w = n; w < a.hard_words; w += M) {
+        for (int wd = l.n; wd < a.hard_words; wd += M) {
             uint32_t bits = 0;
             for (int b = 0; b < 32; ++b) {
-                const int v = 32 * w + b;
-                if (v < N) {
-                    const double s = lds[v * F + f];
-                    // MS/LMS: soft < 0 (sign bit, soft is never -0.0); SP: soft < 1.0
-                    const uint32_t bit = thr_is_one != 0.0 ? (uint32_t)(s < 1.0) : (hi32(s) >> 31);
-                    bits |= bit << b;
-                }
+                const int v = 32 * wd + b;
+                if (v < N) bits |= (uint32_t)hard(v * F + l.f) << b;
             }
-            a.hard[fr * a.hard_words + w] = bits;
+            a.hard[l.fr * a.hard_words + wd] = bits;
         }
     }
-    if (a.soft_out) {
-        for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = lds[(k * M + n) * F + f];
-    }
+    if (a.soft_out)
+        for (int k = 0; k < a.nh; ++k) a.soft_out[l.fr * N + k * M + l.n] = soft((k * M + l.n) * F + l.f);
+}
+
+// MS / LMS: hard bit = soft < 0 (the sign bit; soft is never -0.0), soft output = the LDS-resident value
+__device__ __forceinline__ void write_outputs(const DecArgs &a, const double *lds, const Lane &l, int res) {
+    frame_outputs(a, a.F, l, res, [=](int i) { return hi32(lds[i]) >> 31; }, [=](int i) { return lds[i]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -136,34 +207,33 @@ __device__ __forceinline__ void write_outputs(const DecArgs &a, const double *ld
 //                 STATE3  new records per check row from v2c = soft - alpha*c2v_old ; syndrome = xor of signs
 // Algorithmic state traffic that the CPU code moves through memory every iteration (4.25*E + 30*R + 8.125*N
 // bytes at 4-byte LLR width) stays in VGPRs/LDS here.
+//
+// The body serves ms_flood_kernel (work item blockIdx.x, the graph through plain global pointers) and
+// ms_flood_codes_kernel (ldpc_codeset.hpp: work item w of a code, the graph through the constant address space).
 // ---------------------------------------------------------------------------------------------------------
-template <int RHM, int NHM, bool MW>
-__global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a) {
-    extern __shared__ double lds[];  // [N][F] soft / acc, then one flag word (kept behind, so the base stays aligned)
+template <int RHM, int NHM, bool MW, class RowStart, class Edges>
+__device__ __forceinline__ void ms_flood_body(const DecArgs &a, double *lds, int w, RowStart rs, Edges ed) {
+    // lds: [N][F] soft / acc, then one flag word (kept behind, so the base stays aligned)
     const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
     int *const sh_flag = (int *)(lds + (size_t)N * F);
     const double alpha = a.alpha;
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)blockIdx.x * F + f;
-    const bool inb = fr < a.B;          // uniform per frame (and per workgroup when MW)
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, w);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
 
     double y[NHM];
 #pragma unroll
-    for (int k = 0; k < NHM; ++k) y[k] = (k < nh && live) ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
+    for (int k = 0; k < NHM; ++k) y[k] = (k < nh && l.live) ? a.llr[l.fr * N + k * M + n] + 0.0 : 0.0;
 
     double m1[RHM], m2[RHM];
     uint32_t meta[RHM];  // [15:0] v2c sign bit of the row's idx-th edge, [23:16] idx of the min1 edge
 #pragma unroll
     for (int j = 0; j < RHM; ++j) { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }  // :4579-4596
 
-    bool done = !inb;   // per FRAME: every lane of a frame (valid or not) carries the same value
-    int res = -a.maxiter;
+    FrameStop st = stop_init(l, a.maxiter);
 
     for (int iter = 0; iter < a.maxiter; ++iter) {
-        const bool wr = !done && valid;  // this lane may store
+        const bool wr = !st.done && valid;  // this lane may store
         // ---- STATE1 (:4633-4667)
         if (wr) {
 #pragma unroll
@@ -173,14 +243,12 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a
 #pragma unroll
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
-                const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
                 const uint32_t mt = meta[j];
                 const uint32_t par = __popc(mt & 0xffffu) & 1u;  // row sign = xor of the row's edge signs
                 const uint32_t pos = mt >> kRowBits;
                 for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = a.edges[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                    const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
                     const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
                     const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
                     if (wr) lds[addr] = lds[addr] + cv;
@@ -205,7 +273,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a
 #pragma unroll
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
-                const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
                 const uint32_t mt = meta[j];
                 const uint32_t par = __popc(mt & 0xffffu) & 1u;
                 const uint32_t pos = mt >> kRowBits;
@@ -213,10 +281,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a
                 double nm1 = kMaxVal, nm2 = kMaxVal;
                 uint32_t npos = 0, nS = 0, sy = 0;
                 for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = a.edges[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
-                    const double r = lds[addr];
+                    const double r = lds[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
                     sy ^= hi32(r);
                     const double aa = (pos == (uint32_t)idx) ? a2 : a1;
                     const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
@@ -229,16 +294,19 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a
                     nm1 = fmin(v, nm1);
                 }
                 failw |= sy;
-                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
             }
         }
-        const bool fail = valid && (failw >> 31);
-        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
-        if (!done && !frame_fail) { done = true; res = iter + 1; }  // :4761-4766
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
+        stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :4761-4766
+        if (stop_all<MW>(st)) break;
     }
-    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
+    write_outputs(a, lds, l, st.res);
+}
+
+template <int RHM, int NHM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a) {
+    extern __shared__ double lds[];
+    ms_flood_body<RHM, NHM, MW>(a, lds, blockIdx.x, a.row_start, a.edges);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -253,16 +321,13 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
     const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
     int *const sh_flag = (int *)(lds + (size_t)N * F);
     const double beta = 0.4;  // :5163 (the alpha/beta arguments are dead upstream)
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)blockIdx.x * F + f;
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, blockIdx.x);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
 
     if (valid) {
         for (int k = 0; k < nh; ++k)  // :5088 soft = y
-            lds[(k * M + n) * F + f] = live ? a.llr[fr * N + k * M + n] + 0.0 : 0.0;
+            lds[(k * M + n) * F + f] = l.live ? a.llr[l.fr * N + k * M + n] + 0.0 : 0.0;
     }
     double m1[RHM], m2[RHM];
     uint32_t meta[RHM];
@@ -286,15 +351,12 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
         return valid && (failw >> 31);
     };
 
-    bool done = !inb;
-    int res = -a.maxiter;                                              // :5424 when the loop runs dry
-    bool frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);  // :5111-5115
-    if (!done && !frame_fail) { done = true; res = 1; }                // :5119 at iter 0 -> returns 0+1
-    const bool at_entry = done && inb;                                 // no layer ran: upstream's soft[] is y itself, -0.0 included
+    FrameStop st = stop_init(l, a.maxiter);                            // res: :5424 when the loop runs dry
+    stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, 1);              // :5111-5115; :5119 at iter 0 -> returns 0+1
+    const bool at_entry = st.done && l.inb;                            // no layer ran: upstream's soft[] is y itself, -0.0 included
     for (int iter = 0; iter < a.maxiter; ++iter) {
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
-        const bool wr = !done && valid;
+        if (stop_all<MW>(st)) break;
+        const bool wr = !st.done && valid;
 #pragma unroll
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
@@ -335,16 +397,15 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
                         if (wr) lds[addr[idx]] = tv[idx] + cv;
                     }
                 }
-                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
                 if (MW) __syncthreads();  // the next layer reads what this one wrote
             }
         }
-        frame_fail = frame_vote<MW>(syndrome_fail(), F, f, per, sh_flag);  // :5281-5284
-        if (!done && !frame_fail) { done = true; res = iter + 1; }          // :5287, returns iter+1
+        stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, iter + 1);   // :5281-5284; :5287, returns iter+1
     }
-    write_outputs<MW>(a, lds, fr, n, f, live, res, 0.0);
-    if (live && at_entry && a.soft_out)
-        for (int k = 0; k < a.nh; ++k) a.soft_out[fr * N + k * M + n] = a.llr[fr * N + k * M + n];
+    write_outputs(a, lds, l, st.res);
+    if (l.live && at_entry && a.soft_out)
+        for (int k = 0; k < a.nh; ++k) a.soft_out[l.fr * N + k * M + n] = a.llr[l.fr * N + k * M + n];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -366,12 +427,9 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
     const int max_data = (1 << (a.ims_dbits - 1)) - 1;   // :5445
     const int max_quant = (1 << (a.ims_qbits - 1)) - 1;  // :5446
     const int ialpha = (int)(a.alpha * (1 << 4));         // :5458 MS_ALPHA_FPP = 4
-    int n, f;
-    const bool valid = lane_map<MW>(F, M, n, f);
-    const unsigned long long per = MW ? 0ull : slot_mask(F);
-    const long long fr = (long long)blockIdx.x * F + f;
-    const bool inb = fr < a.B;
-    const bool live = valid && inb;
+    const Lane l = frame_lane<MW>(F, M, a.B, blockIdx.x);
+    const int n = l.n, f = l.f;
+    const bool valid = l.valid;
     auto sat = [&](int x) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); };  // limit_val :4308
 
     // :5472-5500 energy-normalised quantiser.  Every lane of a frame walks the frame's LLRs in index order (same
@@ -379,13 +437,13 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
     int iy[NHM];
     {
         double en = 0;
-        const double *yf = a.llr + (inb ? fr : 0) * (long long)N;
+        const double *yf = a.llr + (l.inb ? l.fr : 0) * (long long)N;
         for (int i = 0; i < N; ++i) { const double v = yf[i]; en += v * v; }
         const double coef = sqrt((double)N / en);
 #pragma unroll
         for (int k = 0; k < NHM; ++k) {
             iy[k] = 0;
-            if (k < nh && live) {
+            if (k < nh && l.live) {
                 double val = yf[k * M + n];
                 int sign = 0;
                 if (val < 0) { val = -val; sign = 1; }
@@ -401,10 +459,9 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
 #pragma unroll
     for (int j = 0; j < RHM; ++j) { m1[j] = 0; m2[j] = 0; meta[j] = 0u; }
 
-    bool done = !inb;
-    int res = -a.maxiter;
+    FrameStop st = stop_init(l, a.maxiter);
     for (int iter = 0; iter < a.maxiter; ++iter) {
-        const bool wr = !done && valid;
+        const bool wr = !st.done && valid;
         if (wr) {
 #pragma unroll
             for (int k = 0; k < NHM; ++k) if (k < nh) lds[(k * M + n) * F + f] = 0;
@@ -418,9 +475,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
                 const uint32_t par = __popc(mt & 0xffffu) & 1u;
                 const uint32_t pos = mt >> kRowBits;
                 for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = a.edges[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
+                    const int addr = edge_idx(a.edges[e0 + idx], n, M, F, f);
                     int tmp = (pos == (uint32_t)idx) ? m2[j] : m1[j];
                     tmp = (tmp * ialpha) >> 4;
                     const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
@@ -450,9 +505,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
                 int nm1 = max_data, nm2 = max_data;
                 uint32_t npos = 0, nS = 0, sy = 0;
                 for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = a.edges[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int r = lds[(k * M + rot_idx(n, c, M)) * F + f];
+                    const int r = lds[edge_idx(a.edges[e0 + idx], n, M, F, f)];
                     sy ^= (uint32_t)r;
                     const int aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
                     const int val = (aa * ialpha) >> 4;
@@ -465,29 +518,13 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
                     else if (v < nm2) nm2 = v;
                 }
                 failw |= sy;
-                if (!done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
             }
         }
-        const bool fail = valid && (failw >> 31);
-        const bool frame_fail = frame_vote<MW>(fail, F, f, per, sh_flag);
-        if (!done && !frame_fail) { done = true; res = iter + 1; }  // :5684-5689
-        if (MW) { if (done) break; }
-        else if (__all(done)) break;
+        stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :5684-5689
+        if (stop_all<MW>(st)) break;
     }
-    if (!live) return;
-    if (n == 0 && a.iters) a.iters[fr] = res;
-    if (a.hard) {
-        for (int w = n; w < a.hard_words; w += M) {
-            uint32_t bits = 0;
-            for (int b = 0; b < 32; ++b) {
-                const int v = 32 * w + b;
-                if (v < N) bits |= ((uint32_t)lds[v * F + f] >> 31) << b;
-            }
-            a.hard[fr * a.hard_words + w] = bits;
-        }
-    }
-    if (a.soft_out)
-        for (int k = 0; k < nh; ++k) a.soft_out[fr * N + k * M + n] = (double)lds[(k * M + n) * F + f];
+    frame_outputs(a, F, l, st.res, [=](int i) { return (uint32_t)lds[i] >> 31; }, [=](int i) { return (double)lds[i]; });
 }
 
 }  // namespace ldpc
