@@ -411,29 +411,78 @@ __device__ __forceinline__ void pack_hard(u32 *dst, const int tid, Pred pred) {
 // see `at` below.  16 896 B at N = 2048: eight frames per CU stay resident (135 168 of 163 840 B).
 constexpr unsigned long kMsM64LdsBytes(unsigned long n) { return sizeof(double) * n + 512; }
 
+// A block column of ms_m64_body is LOCAL when it has an edge, every one of its edges has shift 0 and its first and last block row
+// are at most kMsM64LocalSpan apart: variable `lane` of such a column exchanges values with check `lane` of its rows and with
+// nothing else, so its sum never has to leave the lane (see STATE3 there).  The dual diagonal of a parity part is the usual case
+// (span 1).  The span is capped because the column's soft value, and the decoded values of its later edges, stay in registers
+// from its first block row to its last; a column over the cap takes the way through LDS like any rotated one.
+constexpr int kMsM64LocalSpan = 3;
+template <class C>
+constexpr int ms_m64_slot_of(int j, int k) {   // slot of block column k in block row j, or -1
+    for (int s = 0; s < C::RW[j]; ++s)
+        if (C::COL[j][s] == k) return s;
+    return -1;
+}
+template <class C>
+constexpr int ms_m64_first_row(int k) {        // first block row with an edge in block column k, or -1
+    for (int j = 0; j < C::RH; ++j)
+        if (ms_m64_slot_of<C>(j, k) >= 0) return j;
+    return -1;
+}
+template <class C>
+constexpr int ms_m64_last_row(int k) {
+    for (int j = C::RH - 1; j >= 0; --j)
+        if (ms_m64_slot_of<C>(j, k) >= 0) return j;
+    return -1;
+}
+template <class C>
+constexpr bool ms_m64_local_col(int k) {
+    for (int j = 0; j < C::RH; ++j) {
+        const int s = ms_m64_slot_of<C>(j, k);
+        if (s >= 0 && C::SH[j][s] != 0) return false;
+    }
+    return ms_m64_first_row<C>(k) >= 0 && ms_m64_last_row<C>(k) - ms_m64_first_row<C>(k) <= kMsM64LocalSpan;
+}
+template <class C>
+constexpr int ms_m64_local_starts(int j) {     // local columns whose first block row is j (0 for j past the last row)
+    int n = 0;
+    for (int s = 0; j < C::RH && s < C::RW[j]; ++s)
+        n += ms_m64_local_col<C>(C::COL[j][s]) && ms_m64_first_row<C>(C::COL[j][s]) == j ? 1 : 0;
+    return n;
+}
+template <class C>
+constexpr int ms_m64_row_edges(int j) {        // edges of block row j that go through LDS: those of columns that are not local
+    int n = 0;
+    for (int s = 0; s < C::RW[j]; ++s) n += ms_m64_local_col<C>(C::COL[j][s]) ? 0 : 1;
+    return n;
+}
+
 // ms_m64_body keeps the decoded check-to-variable values of its first block rows in registers from STATE1 to STATE3 (see
 // there): whole rows in ascending order while their edges fit into `budget`; a row that does not fit, and every row after it,
-// decode twice as before.  A code whose edges all fit keeps all of them.
+// decode twice as before.  A code whose edges all fit keeps all of them.  Edges of local columns are not counted: STATE1 does
+// not decode them.
 template <class C>
 constexpr int ms_m64_keep_rows(int budget) {
     int edges = 0, rows = 0;
-    while (rows < C::RH && edges + C::RW[rows] <= budget) edges += C::RW[rows++];
+    while (rows < C::RH && edges + ms_m64_row_edges<C>(rows) <= budget) edges += ms_m64_row_edges<C>(rows++);
     return rows;
 }
-// The edge budget of the shipped body: 70 edges = block rows 0-9 of the (2048,1024) example code, 253 VGPRs without a spill at two
-// waves per SIMD; the next row (78 edges) spills 12 (profiles/r18_flagship_isa_histogram.txt; chosen in round 13,
+// The edge budget of the shipped body: 57 edges that go through LDS = block rows 0-10 of the (2048,1024) example code, 251 VGPRs
+// without a spill at two waves per SIMD; the next row (61 edges) spills 4 (profiles/r19_flagship_isa_histogram.txt).  Until round
+// 19 the edges of the dual diagonal were kept too and the budget was 70 edges of any kind = block rows 0-9 (chosen in round 13,
 // profiles/r13_flagship_variants.txt).
-constexpr int kMsM64KeepEdges = 70;
+constexpr int kMsM64KeepEdges = 57;
 // What the budget has to share the 256 registers with grows with the code: 5 per block row (m1, m2, the record word), 2 per block
 // column in flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row
-// before it uses it).  The example code (16 rows, 24 columns, width 8) leaves room for 70 edges = 140 registers; a code that
+// before it uses it).  The example code (16 rows, 24 columns, width 8) leaves room for 57 edges = 114 registers; a code that
 // needs more for the rest gives the difference back, one edge per register (twice what the count asks: the allocator does not
 // pack as tightly as the count).  An edge count alone knows nothing of the number of block rows: when the rule was made (round
 // 13) codes of 20 and more block rows spilled with no edge kept at all, and with this second term no more than that.  Since
 // round 18 the syndrome words of the block rows are no longer live to the end of STATE3, and cross-compiled 12 x 32, 20 x 40,
 // 24 x 32 and 30 x 60 protographs spill nothing under this rule (16, 11, 41 and 40 VGPRs before;
 // profiles/r18_flagship_isa_histogram.txt).  Rows of weight 16 need no term of their own: 8 x 32 with every row 16 wide keeps
-// four rows in 232 VGPRs.
+// four rows in 232 VGPRs.  Round 19 (local columns, 57 edges) left the second term as it is: the same protographs and the hiprtc
+// instances of the GPU tests spill nothing and need up to 28 VGPRs fewer than before, none more (profiles/r19_flagship_isa_histogram.txt).
 template <class C>
 constexpr int ms_m64_keep_budget() {
     constexpr int cols = C::NH < 24 ? C::NH : 24;
@@ -459,7 +508,8 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // shift 0 is `hi` itself.  (Before: add, and, add-the-LDS-base -- three VOP2 -- per rotated edge and state, a copy + an add per
     // block row.)  The ~40 distinct rotated addresses must still not be hoisted out of the iteration loop into long-lived VGPRs
     // (that costs more in spills than the select it saves): `tie`, see sel32_tied.
-    const u32 lo = lds_addr(lds) + (u32)lane * 8u, hi = lo + 512u;
+    const u32 lane8 = (u32)lane * 8u;
+    const u32 lo = lds_addr(lds) + lane8, hi = lo + 512u;
     auto at = [&](u32 tie, auto S, auto K) -> double * {
         constexpr int c = decltype(S)::value, k = decltype(K)::value;
         static_assert(c >= 0 && c < 64 && k * 512 + c * 8 < 65536, "shift / block column out of range");
@@ -467,9 +517,14 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         else return lds_at(sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8));
     };
     auto own = [&](auto K) -> double * { return lds_at(hi + (u32)(decltype(K)::value * 512)); };   // this lane's variable of block column k
+    // A block column that is local (ms_m64_local_col) is not read or added to in LDS inside the iteration: STATE1 and STATE2 skip
+    // it, STATE3 forms its soft value in a register at the column's first block row, see there.
 
   while (fr < a.nframes) {   // one pass without a queue
     const double *const yrow = a.llr + fr * N + lane;  // this frame's channel LLRs, variable (k, lane) at yrow[64 k]
+    // The same values as a buffer, for the local columns: resource and column offset are scalars, the lane's offset is lane8, so
+    // a load costs no address arithmetic on the vector unit (a 64-bit address per block row did: 3 instructions per column).
+    const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
 
     double m1[RH], m2[RH];
     u32 meta[RH];  // [31:32-RW] sign of the c2v on slot s (own v2c sign xor row parity) on bit 31-s, ready to use; [7:0] slot of the min1 edge
@@ -492,8 +547,25 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             asm volatile("" : "+v"(yo));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
             static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
                 constexpr int k = decltype(K)::value;
-                y[k] = yrow[yo + k * 64];
+                if constexpr (!ms_m64_local_col<C>(k)) y[k] = yrow[yo + k * 64];
             });
+        };
+        // The channel values of the local columns whose first block row is JN: STATE3 loads them one block row ahead.
+        double yl[NH], soft_l[NH];
+        auto load_yl = [&](auto JN) {
+            constexpr int jn = decltype(JN)::value;
+            if constexpr (ms_m64_local_starts<C>(jn) > 0) {
+                u32 so = 0;
+                asm volatile("" : "+s"(so));   // opaque where it stands, as yo above, but on the scalar side
+                static_for<0, C::RW[jn]>([&](auto S) {
+                    constexpr int k = C::COL[jn][decltype(S)::value];
+                    if constexpr (ms_m64_local_col<C>(k) && ms_m64_first_row<C>(k) == jn) {
+                        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
+                        yl[k] = mk(v.y, v.x);
+                    }
+                });
+            }
         };
         // The decoded c2v value of an edge is needed twice: here in STATE1 (cv, added into the variable) and in STATE3
         // (x = alpha * cv, taken out of the variable's sum again).  Block rows [0, KR) keep cv in registers instead of
@@ -506,8 +578,8 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         //   - IEEE multiplication is sign-symmetric: (+-m) * |alpha| and +-(m * |alpha|) are the same bits, zeros and
         //     denormals included (round-to-nearest does not look at the sign);
         //   - -ffp-contract=off keeps this product and the subtraction after it apart, as it does for the second decode.
-        // Between STATE1 and STATE3 of a retained row m1[j] and m2[j] are dead, so a retained edge costs 2 registers and a
-        // retained row gives 4 back.
+        // An edge of a local column is not decoded here at all (no LDS operation, no keep entry); STATE3 decodes it at the
+        // column's first block row and puts the value into keep[j][s] for the edge's own row, kept row or not.
         double keep[RH][C::WMAX];
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
@@ -523,13 +595,17 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
             static_for<0, C::RW[j]>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
-                const double cv = signed_mag(aa, Wt);
-                if constexpr (j < KR) keep[j][s] = cv;
-                Wt = twice(Wt);
-                double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                if constexpr (C::FIRST[j][s]) *p = cv;
-                else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
+                    Wt = twice(Wt);   // the slot's bit of the sign word is passed over
+                } else {
+                    const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
+                    const double cv = signed_mag(aa, Wt);
+                    if constexpr (j < KR) keep[j][s] = cv;
+                    Wt = twice(Wt);
+                    double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                    if constexpr (C::FIRST[j][s]) *p = cv;
+                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             });
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
         });
@@ -538,11 +614,14 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
             if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
-            double *p = own(K);
-            const double pr = *p * alpha;
-            *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            if constexpr (!ms_m64_local_col<C>(k)) {
+                double *p = own(K);
+                const double pr = *p * alpha;
+                *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            }
             if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // 8 columns in flight, not 32 (VGPR budget)
         });
+        load_yl(IC<0>{});
         // ---------------- STATE3 (:4690-4755)
         u32 failw = 0;
         static_for<0, RH>([&](auto J) {
@@ -552,12 +631,44 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             // opaque: otherwise the compiler keeps STATE1's 112 select masks and shifted sign words alive across the
             // whole iteration to reuse them here (SGPR + VGPR spills to scratch); recomputing costs 3 ops per edge.
             asm volatile("" : "+v"(mt));
+            load_yl(IC<j + 1>{});
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                constexpr int k = C::COL[j][s];
+                if constexpr (!ms_m64_local_col<C>(k)) {
+                    r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<k>{});
+                } else {
+                    // A local column: variable `lane` meets check `lane` in every one of its rows.  At its FIRST block row the
+                    // column's STATE1 and STATE2 happen here, in registers: the old c2v values of all its edges are decoded from
+                    // the records of their rows -- this row's and later ones, which STATE3 has not reached, so they still hold
+                    // the previous iteration -- and added in ascending block-row order, the first one taken as it is (what the
+                    // FIRST store and the ds_add_f64 did); then the same product and sum as STATE2, three roundings in all.
+                    // Every decoded value goes into keep[][] of its own row, where x = keep * |alpha| takes it out again (the
+                    // bits of the second decode, see `keep`); the soft value stays in soft_l until the column's last row.  It
+                    // is also written to the image once, for the outputs: the loop can end after any iteration.
+                    if constexpr (ms_m64_first_row<C>(k) == j) {
+                        double acc = 0.0;
+                        static_for<j, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
+                            constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
+                            if constexpr (ss >= 0) {
+                                const u32 m = jj == j ? mt : meta[jj];
+                                const double aa = sel64(m1[jj], m2[jj], lanes_eq(m & 0xffu, (u32)ss));
+                                // slot ss of the sign word sits on bit 31 - ss
+                                const double cv = signed_mag(aa, ss == 0 ? m : ss == 1 ? twice(m) : m << ss);
+                                keep[jj][ss] = cv;
+                                if constexpr (jj == j) acc = cv;
+                                else acc = acc + cv;
+                            }
+                        });
+                        const double pr = acc * alpha;
+                        soft_l[k] = (yl[k] + 0.0) + pr;
+                        *own(IC<k>{}) = soft_l[k];
+                    }
+                    r[s] = soft_l[k];
+                }
             });
             // slot s with its old c2v value x taken out: sign word, min1 / min2 / min1 slot -- the same for both kinds of row
             auto step = [&](auto S, double x) {
@@ -590,10 +701,15 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 static_for<0, RW>([&](auto S) {
                     constexpr int s = decltype(S)::value;
                     sy ^= hi32(r[s]);
-                    const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
-                    const double x = signed_mag(aa, Wt);
-                    Wt = twice(Wt);
-                    step(S, x);
+                    if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
+                        Wt = twice(Wt);
+                        step(S, keep[j][s] * alpha_mag);     // decoded at the column's first block row
+                    } else {
+                        const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
+                        const double x = signed_mag(aa, Wt);
+                        Wt = twice(Wt);
+                        step(S, x);
+                    }
                 });
             }
             // Only bit 31 of the syndrome word is ever looked at.  Opaque here, the row's word is folded into failw now and

@@ -2,7 +2,8 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r18_flagship_variants.txt (round 13's variants -- where the channel LLRs are loaded, how many edges are kept from
+// Results: profiles/r19_flagship_variants.txt (round 18's variants -- the 32-bit syndrome word, carried c2v values, scalar wrap masks -- are in
+// profiles/r18_flagship_variants.txt and still switches of ms_m64_body_y here; round 13's variants -- where the channel LLRs are loaded, how many edges are kept from
 // STATE1 to STATE3 -- are in profiles/r13_flagship_variants.txt, round 6's in profiles/r06_flagship_variants.txt, round 2's in
 // profiles/r02_flagship_variants.txt; all of them are part of every body here).
 #include <hip/hip_runtime.h>
@@ -22,12 +23,28 @@
 
 namespace ldpc_spec {
 
-// ---- the baseline: ms_m64_body as it was before round 18, word for word (only the name differs)
+// ---- round 18's edge budget: every edge of a block row counts, 70 edges (ldpc_spec.hpp counts the edges of local block columns no
+// longer: ms_m64_keep_rows, kMsM64KeepEdges)
+template <class C>
+constexpr int keep_rows_r18(int budget) {
+    int edges = 0, rows = 0;
+    while (rows < C::RH && edges + C::RW[rows] <= budget) edges += C::RW[rows++];
+    return rows;
+}
+template <class C>
+constexpr int keep_budget_r18() {
+    constexpr int cols = C::NH < 24 ? C::NH : 24;
+    constexpr int others = 5 * C::RH + 2 * cols + 2 * C::WMAX, others_example = 5 * 16 + 2 * 24 + 2 * 8;
+    constexpr int cut = others > others_example ? others - others_example : 0;
+    return 70 > cut ? 70 - cut : 0;
+}
+
+// ---- the baseline: ms_m64_body as it was before round 19, word for word (only the name and the two functions above differ)
 template <class C>
 __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
+    constexpr int KR = keep_rows_r18<C>(keep_budget_r18<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -177,7 +194,12 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
                     step(S, x);
                 });
             }
+            // Only bit 31 of the syndrome word is ever looked at.  Opaque here, the row's word is folded into failw now and
+            // both stay 32 bits wide.  Left to itself the compiler xors whole doubles (a second chain over the LOW words of
+            // the soft values: 96 v_xor_b32 per iteration), ors the rows' words as 64-bit values, keeps all RH of them live
+            // to the end of STATE3 and ends the loop in a 64-bit compare (profiles/r18_flagship_isa_histogram.txt).
             failw |= sy;
+            asm volatile("" : "+v"(failw));
             m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -242,27 +264,50 @@ __device__ __forceinline__ mask64 lanes_from(u32 tie) {
 //   - the start.  The all-zero record of a new frame decodes to +0.0 on every edge (signed_mag(0.0, 0)): keep starts at +0.0,
 //     per frame;
 //   - x = keep * |alpha| in STATE3: as in the parent (see `keep` in ms_m64_body).
-template <class C, bool A32, bool CARRY, int BUDGET, bool SMASK>
+__device__ __forceinline__ double buf_f64(__amdgpu_buffer_rsrc_t rsrc, u32 voffset, u32 soffset) {
+    typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voffset, (int)soffset, 0);
+    return mk(v.y, v.x);
+}
+template <class C, bool LOCAL>
+constexpr bool local_col_y(int k) { return LOCAL && ms_m64_local_col<C>(k); }
+template <class C, bool LOCAL>
+constexpr int keep_rows_y(int budget) { return LOCAL ? ms_m64_keep_rows<C>(budget) : keep_rows_r18<C>(budget); }
+
+// ---- round 19, on top of the switches of round 18 (above):
+//   LOCAL   local block columns (ldpc_spec.hpp: ms_m64_local_col) stay out of LDS: STATE1 and STATE2 skip them, STATE3 forms the
+//           soft value at the column's first block row from the records of its rows; BUDGET then counts the other edges only.
+//   PLAIN   the image reads of STATE2 and STATE3 go through a volatile LDS pointer: ds_read_b64 each, no ds_read2st64_b64.
+template <class C, bool A32, bool CARRY, int BUDGET, bool SMASK, bool LOCAL = false, bool PLAIN = false>
 __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = ms_m64_keep_rows<C>(BUDGET);   // block rows [0, KR) are kept
+    constexpr int KR = keep_rows_y<C, LOCAL>(BUDGET);   // block rows [0, KR) are kept
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
     long long fr = blockIdx.x;
-    const u32 lo = lds_addr(lds) + (u32)lane * 8u, hi = lo + 512u;
-    auto at = [&](u32 tie, auto S, auto K) -> double * {
+    const u32 lane8 = (u32)lane * 8u;
+    const u32 lo = lds_addr(lds) + lane8, hi = lo + 512u;
+    auto at_addr = [&](u32 tie, auto S, auto K) -> u32 {
         constexpr int c = decltype(S)::value, k = decltype(K)::value;
         static_assert(c >= 0 && c < 64 && k * 512 + c * 8 < 65536, "shift / block column out of range");
-        if constexpr (c == 0) return lds_at(hi + (u32)(k * 512));
-        else if constexpr (SMASK) return lds_at(sel32(hi, lo, lanes_from<64 - c>(tie)) + (u32)(k * 512 + c * 8));
-        else return lds_at(sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8));
+        if constexpr (c == 0) return hi + (u32)(k * 512);
+        else if constexpr (SMASK) return sel32(hi, lo, lanes_from<64 - c>(tie)) + (u32)(k * 512 + c * 8);
+        else return sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8);
     };
+    auto at = [&](u32 tie, auto S, auto K) -> double * { return lds_at(at_addr(tie, S, K)); };
     auto own = [&](auto K) -> double * { return lds_at(hi + (u32)(decltype(K)::value * 512)); };
+    auto image = [&](u32 addr) -> double {
+        if constexpr (PLAIN) return *(volatile lds_f64 *)(unsigned long)addr;
+        else return *lds_at(addr);
+    };
 
   while (fr < a.nframes) {
     const double *const yrow = a.llr + fr * N + lane;
+    // this frame's channel LLRs as a buffer: a local column is loaded at lane8 + 512 k with no vector address arithmetic (the
+    // resource and the column's offset are scalars)
+    const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
 
     double m1[RH], m2[RH];
     u32 meta[RH];
@@ -281,8 +326,22 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
             asm volatile("" : "+v"(yo));
             static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
                 constexpr int k = decltype(K)::value;
-                y[k] = yrow[yo + k * 64];
+                if constexpr (!local_col_y<C, LOCAL>(k)) y[k] = yrow[yo + k * 64];
             });
+        };
+        // channel values of the local columns whose first block row is JN
+        double yl[NH], soft_l[NH];
+        auto load_yl = [&](auto JN) {
+            constexpr int jn = decltype(JN)::value;
+            if constexpr (LOCAL && ms_m64_local_starts<C>(jn) > 0) {
+                u32 so = 0;
+                asm volatile("" : "+s"(so));   // opaque where it stands, on the scalar side: no vector instruction
+                static_for<0, C::RW[jn]>([&](auto S) {
+                    constexpr int k = C::COL[jn][decltype(S)::value];
+                    if constexpr (local_col_y<C, LOCAL>(k) && ms_m64_first_row<C>(k) == jn)
+                        yl[k] = buf_f64(ybuf, lane8, so + (u32)(k * 512));
+                });
+            }
         };
         // ---------------- STATE1
         static_for<0, RH>([&](auto J) {
@@ -292,10 +351,12 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
                 asm volatile("" : "=v"(tie));
                 static_for<0, C::RW[j]>([&](auto S) {
                     constexpr int s = decltype(S)::value;
-                    const double cv = keep[j][s];
-                    double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                    if constexpr (C::FIRST[j][s]) *p = cv;
-                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if constexpr (!local_col_y<C, LOCAL>(C::COL[j][s])) {
+                        const double cv = keep[j][s];
+                        double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                        if constexpr (C::FIRST[j][s]) *p = cv;
+                        else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                 });
             } else {
                 u32 mt = meta[j];
@@ -304,13 +365,17 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
                 u32 Wt = mt;
                 static_for<0, C::RW[j]>([&](auto S) {
                     constexpr int s = decltype(S)::value;
-                    const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
-                    const double cv = signed_mag(aa, Wt);
-                    if constexpr (j < KR) keep[j][s] = cv;
-                    Wt = twice(Wt);
-                    double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                    if constexpr (C::FIRST[j][s]) *p = cv;
-                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if constexpr (local_col_y<C, LOCAL>(C::COL[j][s])) {
+                        Wt = twice(Wt);
+                    } else {
+                        const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
+                        const double cv = signed_mag(aa, Wt);
+                        if constexpr (j < KR) keep[j][s] = cv;
+                        Wt = twice(Wt);
+                        double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                        if constexpr (C::FIRST[j][s]) *p = cv;
+                        else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                 });
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -320,11 +385,14 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
             if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
-            double *p = own(K);
-            const double pr = *p * alpha;
-            *p = (y[k] + 0.0) + pr;
+            if constexpr (!local_col_y<C, LOCAL>(k)) {
+                double *p = own(K);
+                const double pr = image(hi + (u32)(k * 512)) * alpha;
+                *p = (y[k] + 0.0) + pr;
+            }
             if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);
         });
+        load_yl(IC<0>{});
         // ---------------- STATE3
         u32 failw = 0;
         static_for<0, RH>([&](auto J) {
@@ -334,13 +402,43 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
             u32 mt;
             if constexpr (carried) asm volatile("" : "=v"(mt));
             else { mt = meta[j]; asm volatile("" : "+v"(mt)); }
+            load_yl(IC<j + 1>{});
             double nm1 = kMaxVal, nm2 = kMaxVal;
             u32 npos = 0, nS = 0, sy = 0;
             mask64 lt[RW];   // carried rows: c1 of slot s
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                constexpr int k = C::COL[j][s];
+                if constexpr (!local_col_y<C, LOCAL>(k)) {
+                    r[s] = image(at_addr(mt, IC<C::SH[j][s]>{}, IC<k>{}));
+                } else {
+                    if constexpr (ms_m64_first_row<C>(k) == j) {
+                        // the column's sum, in ascending block-row order, from the OLD records of its rows (this row's and later
+                        // ones: STATE3 has not reached them); the first value as it is, like the FIRST store
+                        double acc = 0.0;
+                        static_for<j, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
+                            constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
+                            if constexpr (ss >= 0) {
+                                double cv;
+                                if constexpr (CARRY && jj < KR) {
+                                    cv = keep[jj][ss];
+                                } else {
+                                    const u32 m = jj == j ? mt : meta[jj];
+                                    const double aa = sel64(m1[jj], m2[jj], lanes_eq(m & 0xffu, (u32)ss));
+                                    cv = signed_mag(aa, ss == 0 ? m : ss == 1 ? twice(m) : m << ss);   // slot ss of the sign word sits on bit 31 - ss
+                                    keep[jj][ss] = cv;
+                                }
+                                if constexpr (jj == j) acc = cv;
+                                else acc = acc + cv;
+                            }
+                        });
+                        const double pr = acc * alpha;
+                        soft_l[k] = (yl[k] + 0.0) + pr;
+                        *own(IC<k>{}) = soft_l[k];   // for the outputs: the loop can end after any iteration
+                    }
+                    r[s] = soft_l[k];
+                }
             });
             auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
@@ -371,10 +469,15 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
                 static_for<0, RW>([&](auto S) {
                     constexpr int s = decltype(S)::value;
                     sy ^= hi32(r[s]);
-                    const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
-                    const double x = signed_mag(aa, Wt);
-                    Wt = twice(Wt);
-                    step(S, x);
+                    if constexpr (local_col_y<C, LOCAL>(C::COL[j][s])) {
+                        Wt = twice(Wt);
+                        step(S, keep[j][s] * alpha_mag);
+                    } else {
+                        const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
+                        const double x = signed_mag(aa, Wt);
+                        Wt = twice(Wt);
+                        step(S, x);
+                    }
                 });
             }
             failw |= sy;
@@ -431,17 +534,21 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
 
 using ldpc_spec::SpecArgs;
 typedef ldpc_spec::CodeAppendixCM64 Code;
-#define VARIANT(name, a32, carry, budget, smask) \
-    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_y<Code, a32, carry, budget, smask>(a); }
+#define VARIANT(name, ...) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_y<Code, __VA_ARGS__>(a); }
 extern "C" __global__ void __launch_bounds__(64, 2) k_parent(const SpecArgs a) { ldpc_spec::ms_m64_body_parent<Code>(a); }
-VARIANT(k_r13, false, false, 70, false)
-VARIANT(k_a, true, false, 70, false)
-VARIANT(k_ab62, true, true, 62, false)
-VARIANT(k_ab70, true, true, 70, false)
-VARIANT(k_ab78, true, true, 78, false)
-VARIANT(k_ac, true, false, 70, true)
-VARIANT(k_abc70, true, true, 70, true)
-VARIANT(k_abc78, true, true, 78, true)
+//               A32   CARRY budget SMASK LOCAL PLAIN
+VARIANT(k_off,   true, false, 70, false)
+VARIANT(k_c78,   true, true, 78, false)
+VARIANT(k_l50,   true, false, 50, false, true, false)
+VARIANT(k_l57,   true, false, 57, false, true, false)
+VARIANT(k_lc57,  true, true, 57, false, true, false)
+VARIANT(k_lc61,  true, true, 61, false, true, false)
+VARIANT(k_p,     true, false, 70, false, false, true)
+VARIANT(k_lp50,  true, false, 50, false, true, true)
+VARIANT(k_lp57,  true, false, 57, false, true, true)
+VARIANT(k_lpc57, true, true, 57, false, true, true)
+VARIANT(k_lpc61, true, true, 61, false, true, true)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 
 struct Variant { const void *kern; const char *name; size_t lds; };
@@ -453,15 +560,18 @@ int main(int argc, char **argv) {
     const int N = 2048;
     const size_t L = ldpc_spec::kMsM64LdsBytes(N);
     const Variant var[] = {
-        {(const void *)k_parent, "baseline: the body before round 18 (parent)", L},
-        {(const void *)k_r13, "switches off, 70 edges (must equal the baseline)", L},
-        {(const void *)k_a, "A: 32-bit syndrome word, 70 edges kept STATE1 to STATE3", L},
-        {(const void *)k_ab62, "A + B, rows 0-8 carried (62 edges)", L},
-        {(const void *)k_ab70, "A + B, rows 0-9 carried (70 edges)", L},
-        {(const void *)k_ab78, "A + B, rows 0-10 carried (78 edges)", L},
-        {(const void *)k_ac, "A + C: scalar-shift wrap masks, 70 edges kept STATE1 to STATE3", L},
-        {(const void *)k_abc70, "A + B + C, rows 0-9 carried (70 edges)", L},
-        {(const void *)k_abc78, "A + B + C, rows 0-10 carried (78 edges)", L},
+        {(const void *)k_parent, "baseline: the body before round 19 (parent)", L},
+        {(const void *)k_off, "round 19's switches off, 70 edges (must equal the baseline)", L},
+        {(const void *)k_c78, "carried rows 0-10 (round 18's B, 78 edges)", L},
+        {(const void *)k_l50, "A: local columns, rows 0-9 kept (50 edges)", L},
+        {(const void *)k_l57, "A: local columns, rows 0-10 kept (57 edges)", L},
+        {(const void *)k_lc57, "A + carried rows 0-10 (57 edges)", L},
+        {(const void *)k_lc61, "A + carried rows 0-11 (61 edges)", L},
+        {(const void *)k_p, "B: plain 64-bit image reads, 70 edges", L},
+        {(const void *)k_lp50, "A + B, rows 0-9 kept (50 edges)", L},
+        {(const void *)k_lp57, "A + B, rows 0-10 kept (57 edges)", L},
+        {(const void *)k_lpc57, "A + B + carried rows 0-10 (57 edges)", L},
+        {(const void *)k_lpc61, "A + B + carried rows 0-11 (61 edges)", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
     };
     constexpr int NV = sizeof var / sizeof var[0];
