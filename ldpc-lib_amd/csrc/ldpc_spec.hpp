@@ -88,6 +88,7 @@ constexpr double kMaxVal = 32767.0;  // decoders.cpp:4299-4301
 typedef unsigned long long mask64;
 __device__ __forceinline__ mask64 lanes_eq(u32 a, u32 b) { return __builtin_amdgcn_uicmp(a, b, 32 /*ICMP_EQ*/); }
 __device__ __forceinline__ mask64 lanes_lt(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 4 /*FCMP_OLT*/); }
+__device__ __forceinline__ mask64 lanes_oeq(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 1 /*FCMP_OEQ*/); }
 __device__ __forceinline__ u32 sel32(u32 if0, u32 if1, mask64 m) {
     u32 d;
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(if0), "v"(if1), "s"(m));
@@ -457,45 +458,44 @@ constexpr int ms_m64_row_edges(int j) {        // edges of block row j that go t
     return n;
 }
 
-// ms_m64_body keeps the decoded check-to-variable values of its first block rows in registers from STATE1 to STATE3 (see
-// there): whole rows in ascending order while their edges fit into `budget`; a row that does not fit, and every row after it,
-// decode twice as before.  A code whose edges all fit keeps all of them.  Edges of local columns are not counted: STATE1 does
-// not decode them.
+// ms_m64_body CARRIES the decoded check-to-variable values of its first block rows in registers from STATE3 of one iteration to
+// STATE3 of the next (see `keep` there): whole rows in ascending order while they fit; a row that does not fit, and every row after
+// it, hands a record (m1, m2, sign word + slot) to the next iteration and decodes it twice, as before.  What a carried row costs:
+// 2 VGPRs per edge that goes through LDS, for the WHOLE iteration -- STATE2 with its channel values in flight included -- less the 5
+// VGPRs of the record it no longer has.  Edges of local columns are not counted: they live from the column's first block row to
+// its last only, in carried rows and in the others.  `budget` is in registers.
 template <class C>
 constexpr int ms_m64_keep_rows(int budget) {
     int edges = 0, rows = 0;
-    while (rows < C::RH && edges + ms_m64_row_edges<C>(rows) <= budget) edges += ms_m64_row_edges<C>(rows++);
+    while (rows < C::RH && 2 * (edges + ms_m64_row_edges<C>(rows)) - 5 * (rows + 1) <= budget) edges += ms_m64_row_edges<C>(rows++);
     return rows;
 }
-// The edge budget of the shipped body: 57 edges that go through LDS = block rows 0-10 of the (2048,1024) example code, 251 VGPRs
-// without a spill at two waves per SIMD; the next row (61 edges) spills 4 (profiles/r19_flagship_isa_histogram.txt).  Until round
-// 19 the edges of the dual diagonal were kept too and the budget was 70 edges of any kind = block rows 0-9 (chosen in round 13,
-// profiles/r13_flagship_variants.txt).
-constexpr int kMsM64KeepEdges = 57;
-// What the budget has to share the 256 registers with grows with the code: 5 per block row (m1, m2, the record word), 2 per block
-// column in flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row
-// before it uses it).  The example code (16 rows, 24 columns, width 8) leaves room for 57 edges = 114 registers; a code that
-// needs more for the rest gives the difference back, one edge per register (twice what the count asks: the allocator does not
-// pack as tightly as the count).  An edge count alone knows nothing of the number of block rows: when the rule was made (round
-// 13) codes of 20 and more block rows spilled with no edge kept at all, and with this second term no more than that.  Since
-// round 18 the syndrome words of the block rows are no longer live to the end of STATE3, and cross-compiled 12 x 32, 20 x 40,
-// 24 x 32 and 30 x 60 protographs spill nothing under this rule (16, 11, 41 and 40 VGPRs before;
-// profiles/r18_flagship_isa_histogram.txt).  Rows of weight 16 need no term of their own: 8 x 32 with every row 16 wide keeps
-// four rows in 232 VGPRs.  Round 19 (local columns, 57 edges) left the second term as it is: the same protographs and the hiprtc
-// instances of the GPU tests spill nothing and need up to 28 VGPRs fewer than before, none more (profiles/r19_flagship_isa_histogram.txt).
+// The budget of the shipped body: 68 edges that go through LDS in 13 rows = block rows 0-12 of the (2048,1024) example code, 255
+// VGPRs without a spill at two waves per SIMD; the next row (71 edges) spills 4.  Measured at 57, 61 and 68 edges: every row more
+// is faster (profiles/r20_flagship_variants.txt).  (Round 19 kept 57 edges from STATE1 to STATE3 only, round 13 70 edges of any
+// kind: profiles/r19_flagship_isa_histogram.txt, profiles/r13_flagship_variants.txt.)
+constexpr int kMsM64KeepEdges = 68, kMsM64KeepRowsOfExample = 13;
+// What the carried rows share the 256 registers with grows with the code: 5 per block row with a record, 2 per block column in
+// flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row before it
+// uses it).  The example code (16 rows, 24 columns, width 8) leaves 2 * 68 - 5 * 13 = 71 registers to the carried rows on top of
+// that; a code that needs more for the rest gives the difference back, register for register.  A code of 30 block rows is left
+// with nothing and carries no row: such codes run as they did before any value was kept.  Checked by cross-compiling: the shipped
+// instance, every hiprtc instance of the GPU tests and five synthetic protographs (8 x 32 with rows 16 wide to 30 x 60) spill no
+// VGPR and use no scratch under this rule (profiles/r20_flagship_isa_histogram.txt).
 template <class C>
 constexpr int ms_m64_keep_budget() {
     constexpr int cols = C::NH < 24 ? C::NH : 24;
     constexpr int others = 5 * C::RH + 2 * cols + 2 * C::WMAX, others_example = 5 * 16 + 2 * 24 + 2 * 8;
     constexpr int cut = others > others_example ? others - others_example : 0;
-    return kMsM64KeepEdges > cut ? kMsM64KeepEdges - cut : 0;
+    constexpr int regs = 2 * kMsM64KeepEdges - 5 * kMsM64KeepRowsOfExample;
+    return regs > cut ? regs - cut : 0;
 }
 
 template <class C>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
+    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) carry their decoded c2v values, see `keep`
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -526,11 +526,19 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // a load costs no address arithmetic on the vector unit (a 64-bit address per block row did: 3 instructions per column).
     const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
 
+    // What a block row hands from STATE3 of one iteration to the next iteration, in one of two forms:
+    //   rows [KR, RH)  a RECORD: m1, m2 and a word with the signs and the slot of the smallest magnitude, decoded edge by edge in
+    //                  STATE1 and again in STATE3;
+    //   rows [0, KR)   the decoded c2v values themselves, CARRIED in keep[j][s]: no record, no decode (see `keep` below).
     double m1[RH], m2[RH];
     u32 meta[RH];  // [31:32-RW] sign of the c2v on slot s (own v2c sign xor row parity) on bit 31-s, ready to use; [7:0] slot of the min1 edge
+    double keep[RH][C::WMAX];
     static_for<0, RH>([&](auto J) {
         constexpr int j = decltype(J)::value;
-        m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u;   // :4579-4596
+        // per frame: nothing survives into the wave's next frame of a persistent launch.  The all-zero record decodes to +0.0 on
+        // every edge (signed_mag(0.0, 0)), so a carried row starts at +0.0.
+        m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u;   // :4579-4596 (of a carried row only meta is ever read: a 0, see STATE3)
+        if constexpr (j < KR) static_for<0, C::RW[j]>([&](auto S) { keep[j][decltype(S)::value] = 0.0; });
     });
 
     int res = -a.maxiter;
@@ -567,46 +575,70 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 });
             }
         };
-        // The decoded c2v value of an edge is needed twice: here in STATE1 (cv, added into the variable) and in STATE3
-        // (x = alpha * cv, taken out of the variable's sum again).  Block rows [0, KR) keep cv in registers instead of
-        // decoding the record a second time: x = keep * |alpha| is ONE v_mul_f64 in place of compare, two selects, bfi and
-        // add, and the row's two products m1 * alpha, m2 * alpha go as well.  The bits are those of the second decode:
-        //   - the second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's sign), cv is
-        //     +-(pos == s ? m2 : m1) with the same sign bit and the same select, both from the same record;
-        //   - m1 and m2 are finite and in [0, 32767]: they start at 0.0 and are fmin / fmax against kMaxVal afterwards, which
-        //     never return a NaN;
-        //   - IEEE multiplication is sign-symmetric: (+-m) * |alpha| and +-(m * |alpha|) are the same bits, zeros and
-        //     denormals included (round-to-nearest does not look at the sign);
-        //   - -ffp-contract=off keeps this product and the subtraction after it apart, as it does for the second decode.
-        // An edge of a local column is not decoded here at all (no LDS operation, no keep entry); STATE3 decodes it at the
-        // column's first block row and puts the value into keep[j][s] for the edge's own row, kept row or not.
-        double keep[RH][C::WMAX];
+        // The decoded c2v value of an edge, cv = +-(s == pos ? m2 : m1), is needed twice: in STATE1 (added into the variable) and
+        // in STATE3 (x = alpha * cv, taken out of the variable's sum again).  STATE3 of the iteration before had everything cv is
+        // made of in registers.  Block rows [0, KR) therefore form cv there, once, and CARRY it in keep[j][s] to the next
+        // STATE3: STATE1 scatters keep as it is, x = keep * |alpha| is ONE v_mul_f64, and the row has no record.  That takes out
+        // both decodes of the row (compare, two selects, bfi, add per edge and state) and the two products m1 * alpha, m2 * alpha.
+        // The row does not even track the slot of its smallest magnitude: after its min loop slot s takes nm2 where
+        // |tt[s]| == nm1 and nm1 elsewhere, one v_cmp_eq_f64 in front of the two selects instead of v_cmp_lt_f64 + a select of
+        // npos per slot inside the loop.  The bits are those of the record's decode:
+        //   - the magnitude.  (nm1, nm2) are the two smallest of the multiset {K, K, v_0 .. v_RW-1}, K = kMaxVal, v_s = |tt[s]|
+        //     (fmin / fmax drop NaNs; fabs leaves no -0.0, so equal values are equal bits).  (v_s == nm1 ? nm2 : nm1) and
+        //     (s == npos ? nm2 : nm1) can differ in two ways only.  v_s == nm1 and s != npos: the multiset holds nm1 twice, so
+        //     nm2 == nm1 bit for bit and the choice does not matter.  s == npos and v_s != nm1: a slot whose c1 = (v < nm1) held
+        //     last would be npos and equal nm1, so no c1 ever held, npos is its start value 0 and v_0 is a NaN or above K:
+        //     nm1 == nm2 == K.  NaN, +-inf, v >= K, ties of any order and denormals all fall under these cases
+        //     (tests/test_ms_m64_eqslot_cpu.py is the argument as executable text);
+        //   - the sign.  W is the word the record would hold in meta's upper bits, shifted by the same twice() per slot;
+        //   - x = keep * |alpha|.  The second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's
+        //     sign); nm1 and nm2 are finite and in [0, 32767]; IEEE multiplication is sign-symmetric, so (+-m) * |alpha| and
+        //     +-(m * |alpha|) are the same bits, zeros and denormals included; -ffp-contract=off keeps this product and the
+        //     subtraction after it apart, as it does for the second decode.
+        // A carried edge costs 2 VGPRs for the whole iteration, STATE2 with its channel values in flight included, and a carried
+        // row gives back the 5 of its record: ms_m64_keep_budget.  Two tiers only: a row past KR decodes its record twice.
+        // An edge of a LOCAL column is not scattered in STATE1 at all (no LDS operation).  STATE3 at the column's first block row
+        // takes the carried value of a row below KR as it is, decodes the record of a row past KR and puts that value into
+        // keep[j][s] for the edge's own row (within the iteration only).
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            u32 mt = meta[j];
-            // A volatile asm is ordered with the LDS operations around it, and everything this block row computes
-            // depends on its output: the row's ALU work therefore stays between the previous row's LDS operations
-            // and its own (otherwise instruction selection emits all 112 c2v computations first and spills them).
-            asm volatile("" : "+v"(mt));
-            const u32 pos = mt & 0xffu;
-            // sign of the c2v on slot s = (own v2c sign) xor (row sign); slot s sits on bit RW-1-s of the row word.
-            // Wt carries slot 0 on bit 31; every further slot is one full-rate add (Wt += Wt) instead of a shift.
-            u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
-            static_for<0, C::RW[j]>([&](auto S) {
-                constexpr int s = decltype(S)::value;
-                if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
-                    Wt = twice(Wt);   // the slot's bit of the sign word is passed over
-                } else {
-                    const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
-                    const double cv = signed_mag(aa, Wt);
-                    if constexpr (j < KR) keep[j][s] = cv;
-                    Wt = twice(Wt);
-                    double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                    if constexpr (C::FIRST[j][s]) *p = cv;
-                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            });
+            if constexpr (j < KR) {
+                u32 tie;
+                asm volatile("" : "=v"(tie));   // ties the rotated addresses to this row, as mt does below; its value is not used
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    if constexpr (!ms_m64_local_col<C>(C::COL[j][s])) {
+                        const double cv = keep[j][s];
+                        double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                        if constexpr (C::FIRST[j][s]) *p = cv;
+                        else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                });
+            } else {
+                u32 mt = meta[j];
+                // A volatile asm is ordered with the LDS operations around it, and everything this block row computes
+                // depends on its output: the row's ALU work therefore stays between the previous row's LDS operations
+                // and its own (otherwise instruction selection emits all 112 c2v computations first and spills them).
+                asm volatile("" : "+v"(mt));
+                const u32 pos = mt & 0xffu;
+                // sign of the c2v on slot s = (own v2c sign) xor (row sign); slot s sits on bit RW-1-s of the row word.
+                // Wt carries slot 0 on bit 31; every further slot is one full-rate add (Wt += Wt) instead of a shift.
+                u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
+                        Wt = twice(Wt);   // the slot's bit of the sign word is passed over
+                    } else {
+                        const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
+                        const double cv = signed_mag(aa, Wt);
+                        Wt = twice(Wt);
+                        double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                        if constexpr (C::FIRST[j][s]) *p = cv;
+                        else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                });
+            }
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
         });
         // ---------------- STATE2 (:4670-4685): soft = y + acc*alpha (two roundings)
@@ -627,6 +659,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
             constexpr int RW = C::RW[j];
+            // A carried row has no record: its word stays 0 and is a tie for the addresses only (one v_mov_b32 per row).  The read
+            // stands without a condition on purpose: under `if constexpr (j >= KR)`, or with an output-only asm for the carried
+            // rows, a 30 x 60 protograph that carries no row at all spilled 282 VGPRs (profiles/r20_flagship_isa_histogram.txt).
             u32 mt = meta[j];
             // opaque: otherwise the compiler keeps STATE1's 112 select masks and shifted sign words alive across the
             // whole iteration to reuse them here (SGPR + VGPR spills to scratch); recomputing costs 3 ops per edge.
@@ -634,7 +669,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             load_yl(IC<j + 1>{});
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
-            double r[RW];
+            double r[RW], tt_[RW];                  // tt_: the v2c values of a carried row, until its new c2v values are formed
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
                 constexpr int k = C::COL[j][s];
@@ -642,23 +677,25 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<k>{});
                 } else {
                     // A local column: variable `lane` meets check `lane` in every one of its rows.  At its FIRST block row the
-                    // column's STATE1 and STATE2 happen here, in registers: the old c2v values of all its edges are decoded from
-                    // the records of their rows -- this row's and later ones, which STATE3 has not reached, so they still hold
-                    // the previous iteration -- and added in ascending block-row order, the first one taken as it is (what the
-                    // FIRST store and the ds_add_f64 did); then the same product and sum as STATE2, three roundings in all.
-                    // Every decoded value goes into keep[][] of its own row, where x = keep * |alpha| takes it out again (the
-                    // bits of the second decode, see `keep`); the soft value stays in soft_l until the column's last row.  It
-                    // is also written to the image once, for the outputs: the loop can end after any iteration.
+                    // column's STATE1 and STATE2 happen here, in registers: the old c2v values of all its edges -- this row's and
+                    // later ones, which STATE3 has not reached, so they still hold the previous iteration -- are taken from keep
+                    // (carried rows) or decoded from the records of their rows, and added in ascending block-row order, the first
+                    // one taken as it is (what the FIRST store and the ds_add_f64 did); then the same product and sum as STATE2,
+                    // three roundings in all.  A decoded value goes into keep[][] of its own row, where x = keep * |alpha| takes
+                    // it out again (the bits of the second decode, see `keep`); the soft value stays in soft_l until the column's
+                    // last row.  It is also written to the image once, for the outputs: the loop can end after any iteration.
                     if constexpr (ms_m64_first_row<C>(k) == j) {
                         double acc = 0.0;
                         static_for<j, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
                             constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
                             if constexpr (ss >= 0) {
-                                const u32 m = jj == j ? mt : meta[jj];
-                                const double aa = sel64(m1[jj], m2[jj], lanes_eq(m & 0xffu, (u32)ss));
-                                // slot ss of the sign word sits on bit 31 - ss
-                                const double cv = signed_mag(aa, ss == 0 ? m : ss == 1 ? twice(m) : m << ss);
-                                keep[jj][ss] = cv;
+                                if constexpr (jj >= KR) {
+                                    const u32 m = jj == j ? mt : meta[jj];
+                                    const double aa = sel64(m1[jj], m2[jj], lanes_eq(m & 0xffu, (u32)ss));
+                                    // slot ss of the sign word sits on bit 31 - ss
+                                    keep[jj][ss] = signed_mag(aa, ss == 0 ? m : ss == 1 ? twice(m) : m << ss);
+                                }
+                                const double cv = keep[jj][ss];
                                 if constexpr (jj == j) acc = cv;
                                 else acc = acc + cv;
                             }
@@ -670,16 +707,20 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     r[s] = soft_l[k];
                 }
             });
-            // slot s with its old c2v value x taken out: sign word, min1 / min2 / min1 slot -- the same for both kinds of row
+            // slot s with its old c2v value x taken out: sign word, min1 / min2, and for a row with a record the min1 slot
             auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
                 const double tt = r[s] - x;              // v2c
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);  // (nS << 1) | sign(tt): slot s lands on bit RW-1-s
                 const double v = fabs(tt);
+                if constexpr (j < KR) tt_[s] = tt;
                 if constexpr (s == 0) {
                     // from nm1 = nm2 = K, npos = 0 the general step gives nm2 = min(max(v, K), K) = K and npos = sel(0, 0) = 0 for
                     // every v (NaN included): only nm1 moves.  The compiler does not see that; 16 x (max, min, cmp, select) fewer.
                     nm1 = fmin(v, kMaxVal);
+                } else if constexpr (j < KR) {
+                    nm2 = fmin(fmax(v, nm1), nm2);       // a carried row needs no slot, see `keep`
+                    nm1 = fmin(v, nm1);
                 } else {
                     const mask64 c1 = lanes_lt(v, nm1);  // strict: the first minimum keeps the position
                     nm2 = fmin(fmax(v, nm1), nm2);       // = c1 ? nm1 : min(v, nm2)
@@ -691,7 +732,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 static_for<0, RW>([&](auto S) {
                     constexpr int s = decltype(S)::value;
                     sy ^= hi32(r[s]);
-                    step(S, keep[j][s] * alpha_mag);     // STATE1's value: no second decode, see `keep`
+                    step(S, keep[j][s] * alpha_mag);     // the carried value: no decode, see `keep`
                 });
             } else {
                 const u32 pos = mt & 0xffu;
@@ -718,7 +759,16 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             // to the end of STATE3 and ends the loop in a 64-bit compare (profiles/r18_flagship_isa_histogram.txt).
             failw |= sy;
             asm volatile("" : "+v"(failw));
-            m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
+            if constexpr (j < KR) {
+                u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);   // slot s on bit 31 - s, row parity folded in
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    keep[j][s] = signed_mag(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
+                    W = twice(W);
+                });
+            } else {
+                m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
         if (__ballot((failw >> 31) != 0) == 0ull) { res = iter + 1; break; }  // :4761-4766

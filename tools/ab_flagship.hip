@@ -2,7 +2,8 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r19_flagship_variants.txt (round 18's variants -- the 32-bit syndrome word, carried c2v values, scalar wrap masks -- are in
+// Results: profiles/r20_flagship_variants.txt (round 19's variants -- local block columns, plain 64-bit image reads -- are in
+// profiles/r19_flagship_variants.txt and still switches of ms_m64_body_y here; round 18's variants -- the 32-bit syndrome word, carried c2v values, scalar wrap masks -- are in
 // profiles/r18_flagship_variants.txt and still switches of ms_m64_body_y here; round 13's variants -- where the channel LLRs are loaded, how many edges are kept from
 // STATE1 to STATE3 -- are in profiles/r13_flagship_variants.txt, round 6's in profiles/r06_flagship_variants.txt, round 2's in
 // profiles/r02_flagship_variants.txt; all of them are part of every body here).
@@ -39,12 +40,29 @@ constexpr int keep_budget_r18() {
     return 70 > cut ? 70 - cut : 0;
 }
 
-// ---- the baseline: ms_m64_body as it was before round 19, word for word (only the name and the two functions above differ)
+// ---- whole block rows in ascending order while their edges that go through LDS fit into `budget` (round 19's ms_m64_keep_rows; the
+// header's counts registers since round 20)
+template <class C>
+constexpr int keep_rows_r19(int budget) {
+    int edges = 0, rows = 0;
+    while (rows < C::RH && edges + ms_m64_row_edges<C>(rows) <= budget) edges += ms_m64_row_edges<C>(rows++);
+    return rows;
+}
+// ---- round 19's edge budget: 57 edges that go through LDS, kept from STATE1 to STATE3 (ldpc_spec.hpp has the rule of round 20 now)
+template <class C>
+constexpr int keep_budget_r19() {
+    constexpr int cols = C::NH < 24 ? C::NH : 24;
+    constexpr int others = 5 * C::RH + 2 * cols + 2 * C::WMAX, others_example = 5 * 16 + 2 * 24 + 2 * 8;
+    constexpr int cut = others > others_example ? others - others_example : 0;
+    return 57 > cut ? 57 - cut : 0;
+}
+
+// ---- the baseline: ms_m64_body as round 19 shipped it, word for word (only the name and the two budget functions above differ)
 template <class C>
 __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = keep_rows_r18<C>(keep_budget_r18<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
+    constexpr int KR = keep_rows_r19<C>(keep_budget_r19<C>());   // block rows [0, KR) keep their decoded c2v values, see STATE1
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -57,7 +75,8 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
     // shift 0 is `hi` itself.  (Before: add, and, add-the-LDS-base -- three VOP2 -- per rotated edge and state, a copy + an add per
     // block row.)  The ~40 distinct rotated addresses must still not be hoisted out of the iteration loop into long-lived VGPRs
     // (that costs more in spills than the select it saves): `tie`, see sel32_tied.
-    const u32 lo = lds_addr(lds) + (u32)lane * 8u, hi = lo + 512u;
+    const u32 lane8 = (u32)lane * 8u;
+    const u32 lo = lds_addr(lds) + lane8, hi = lo + 512u;
     auto at = [&](u32 tie, auto S, auto K) -> double * {
         constexpr int c = decltype(S)::value, k = decltype(K)::value;
         static_assert(c >= 0 && c < 64 && k * 512 + c * 8 < 65536, "shift / block column out of range");
@@ -65,9 +84,14 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
         else return lds_at(sel32_tied(hi, lo, ~0ull << (64 - c), tie) + (u32)(k * 512 + c * 8));
     };
     auto own = [&](auto K) -> double * { return lds_at(hi + (u32)(decltype(K)::value * 512)); };   // this lane's variable of block column k
+    // A block column that is local (ms_m64_local_col) is not read or added to in LDS inside the iteration: STATE1 and STATE2 skip
+    // it, STATE3 forms its soft value in a register at the column's first block row, see there.
 
   while (fr < a.nframes) {   // one pass without a queue
     const double *const yrow = a.llr + fr * N + lane;  // this frame's channel LLRs, variable (k, lane) at yrow[64 k]
+    // The same values as a buffer, for the local columns: resource and column offset are scalars, the lane's offset is lane8, so
+    // a load costs no address arithmetic on the vector unit (a 64-bit address per block row did: 3 instructions per column).
+    const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
 
     double m1[RH], m2[RH];
     u32 meta[RH];  // [31:32-RW] sign of the c2v on slot s (own v2c sign xor row parity) on bit 31-s, ready to use; [7:0] slot of the min1 edge
@@ -90,8 +114,25 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
             asm volatile("" : "+v"(yo));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
             static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
                 constexpr int k = decltype(K)::value;
-                y[k] = yrow[yo + k * 64];
+                if constexpr (!ms_m64_local_col<C>(k)) y[k] = yrow[yo + k * 64];
             });
+        };
+        // The channel values of the local columns whose first block row is JN: STATE3 loads them one block row ahead.
+        double yl[NH], soft_l[NH];
+        auto load_yl = [&](auto JN) {
+            constexpr int jn = decltype(JN)::value;
+            if constexpr (ms_m64_local_starts<C>(jn) > 0) {
+                u32 so = 0;
+                asm volatile("" : "+s"(so));   // opaque where it stands, as yo above, but on the scalar side
+                static_for<0, C::RW[jn]>([&](auto S) {
+                    constexpr int k = C::COL[jn][decltype(S)::value];
+                    if constexpr (ms_m64_local_col<C>(k) && ms_m64_first_row<C>(k) == jn) {
+                        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
+                        yl[k] = mk(v.y, v.x);
+                    }
+                });
+            }
         };
         // The decoded c2v value of an edge is needed twice: here in STATE1 (cv, added into the variable) and in STATE3
         // (x = alpha * cv, taken out of the variable's sum again).  Block rows [0, KR) keep cv in registers instead of
@@ -104,8 +145,8 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
         //   - IEEE multiplication is sign-symmetric: (+-m) * |alpha| and +-(m * |alpha|) are the same bits, zeros and
         //     denormals included (round-to-nearest does not look at the sign);
         //   - -ffp-contract=off keeps this product and the subtraction after it apart, as it does for the second decode.
-        // Between STATE1 and STATE3 of a retained row m1[j] and m2[j] are dead, so a retained edge costs 2 registers and a
-        // retained row gives 4 back.
+        // An edge of a local column is not decoded here at all (no LDS operation, no keep entry); STATE3 decodes it at the
+        // column's first block row and puts the value into keep[j][s] for the edge's own row, kept row or not.
         double keep[RH][C::WMAX];
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
@@ -121,13 +162,17 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
             u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
             static_for<0, C::RW[j]>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
-                const double cv = signed_mag(aa, Wt);
-                if constexpr (j < KR) keep[j][s] = cv;
-                Wt = twice(Wt);
-                double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
-                if constexpr (C::FIRST[j][s]) *p = cv;
-                else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
+                    Wt = twice(Wt);   // the slot's bit of the sign word is passed over
+                } else {
+                    const double aa = sel64(m1[j], m2[j], lanes_eq(pos, (u32)s));
+                    const double cv = signed_mag(aa, Wt);
+                    if constexpr (j < KR) keep[j][s] = cv;
+                    Wt = twice(Wt);
+                    double *p = at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                    if constexpr (C::FIRST[j][s]) *p = cv;
+                    else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             });
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
         });
@@ -136,11 +181,14 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
             if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
-            double *p = own(K);
-            const double pr = *p * alpha;
-            *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            if constexpr (!ms_m64_local_col<C>(k)) {
+                double *p = own(K);
+                const double pr = *p * alpha;
+                *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            }
             if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // 8 columns in flight, not 32 (VGPR budget)
         });
+        load_yl(IC<0>{});
         // ---------------- STATE3 (:4690-4755)
         u32 failw = 0;
         static_for<0, RH>([&](auto J) {
@@ -150,12 +198,44 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
             // opaque: otherwise the compiler keeps STATE1's 112 select masks and shifted sign words alive across the
             // whole iteration to reuse them here (SGPR + VGPR spills to scratch); recomputing costs 3 ops per edge.
             asm volatile("" : "+v"(mt));
+            load_yl(IC<j + 1>{});
             double nm1 = kMaxVal, nm2 = kMaxVal;    // start value == the MAX_VAL clamp of :4730
             u32 npos = 0, nS = 0, sy = 0;
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                constexpr int k = C::COL[j][s];
+                if constexpr (!ms_m64_local_col<C>(k)) {
+                    r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<k>{});
+                } else {
+                    // A local column: variable `lane` meets check `lane` in every one of its rows.  At its FIRST block row the
+                    // column's STATE1 and STATE2 happen here, in registers: the old c2v values of all its edges are decoded from
+                    // the records of their rows -- this row's and later ones, which STATE3 has not reached, so they still hold
+                    // the previous iteration -- and added in ascending block-row order, the first one taken as it is (what the
+                    // FIRST store and the ds_add_f64 did); then the same product and sum as STATE2, three roundings in all.
+                    // Every decoded value goes into keep[][] of its own row, where x = keep * |alpha| takes it out again (the
+                    // bits of the second decode, see `keep`); the soft value stays in soft_l until the column's last row.  It
+                    // is also written to the image once, for the outputs: the loop can end after any iteration.
+                    if constexpr (ms_m64_first_row<C>(k) == j) {
+                        double acc = 0.0;
+                        static_for<j, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
+                            constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
+                            if constexpr (ss >= 0) {
+                                const u32 m = jj == j ? mt : meta[jj];
+                                const double aa = sel64(m1[jj], m2[jj], lanes_eq(m & 0xffu, (u32)ss));
+                                // slot ss of the sign word sits on bit 31 - ss
+                                const double cv = signed_mag(aa, ss == 0 ? m : ss == 1 ? twice(m) : m << ss);
+                                keep[jj][ss] = cv;
+                                if constexpr (jj == j) acc = cv;
+                                else acc = acc + cv;
+                            }
+                        });
+                        const double pr = acc * alpha;
+                        soft_l[k] = (yl[k] + 0.0) + pr;
+                        *own(IC<k>{}) = soft_l[k];
+                    }
+                    r[s] = soft_l[k];
+                }
             });
             // slot s with its old c2v value x taken out: sign word, min1 / min2 / min1 slot -- the same for both kinds of row
             auto step = [&](auto S, double x) {
@@ -188,10 +268,15 @@ __device__ __forceinline__ void ms_m64_body_parent(const SpecArgs &a) {
                 static_for<0, RW>([&](auto S) {
                     constexpr int s = decltype(S)::value;
                     sy ^= hi32(r[s]);
-                    const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
-                    const double x = signed_mag(aa, Wt);
-                    Wt = twice(Wt);
-                    step(S, x);
+                    if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
+                        Wt = twice(Wt);
+                        step(S, keep[j][s] * alpha_mag);     // decoded at the column's first block row
+                    } else {
+                        const double aa = sel64(a1, a2, lanes_eq(pos, (u32)s));
+                        const double x = signed_mag(aa, Wt);
+                        Wt = twice(Wt);
+                        step(S, x);
+                    }
                 });
             }
             // Only bit 31 of the syndrome word is ever looked at.  Opaque here, the row's word is folded into failw now and
@@ -254,9 +339,17 @@ __device__ __forceinline__ mask64 lanes_from(u32 tie) {
 //           shipped.
 // Why a carried value has the bits of the record's decode, cv = +-(s == pos ? m2 : m1):
 //   - the position.  The record's slot is npos = the last slot s >= 1 whose c1 = (v < nm1) held, or 0 (npos starts at 0, lanes_lt
-//     is false on NaN).  A carried row keeps its c1 lane masks and forms  E[s] = c1[s] & ~(c1[s+1] | ... | c1[RW-1])  on the scalar
-//     unit, in descending slot order and in place; slot 0 is the min1 slot where no c1 held.  The same c1, so the same slot in
-//     every lane, ties (strict <: the earlier slot stays) and NaN included;
+//     is false on NaN).  The mask-chain variant (round 18, !EQ) rebuilds exactly that slot from the c1 lane masks on the scalar
+//     unit.  EQ needs no slot: while v_s = |tt[s]| of the row is in registers,  (v_s == nm1) ? nm2 : nm1  has the bits of
+//     (s == npos) ? nm2 : nm1.  (nm1, nm2) are the two smallest of the multiset {K, K, v_0 .. v_RW-1}, K = kMaxVal: fmin / fmax
+//     drop NaNs, and v = fabs(tt) is never -0.0, so == on the values is == on the bits.  Where the two selects disagree:
+//       v_s == nm1 and s != npos:  the multiset holds nm1 twice (slot s and slot npos, or slot s and a K), so nm2 == nm1 bit for
+//                                  bit and either choice is the same value;
+//       s == npos and v_s != nm1:  nm1 came from no slot's c1 (a slot whose c1 held last would be npos and equal nm1), so npos is
+//                                  its start value 0, nm1 did not come from v_0 either (v_0 is NaN or > K), and no slot was
+//                                  below K: nm1 == nm2 == K.
+//     NaN, +-inf, v > K, v == K, ties of any order and denormals are all inside these cases (tests/test_ms_m64_eqslot_cpu.py walks
+//     them);
 //   - the magnitudes.  nm1 and nm2 are what the record would hold as m1 and m2, and the decode's select between them is the one
 //     made here, with E[s] in place of pos == s;
 //   - the sign.  W is the word the record would hold in meta's upper bits -- the signs of the v2c, row parity folded in, slot s on
@@ -272,14 +365,23 @@ __device__ __forceinline__ double buf_f64(__amdgpu_buffer_rsrc_t rsrc, u32 voffs
 template <class C, bool LOCAL>
 constexpr bool local_col_y(int k) { return LOCAL && ms_m64_local_col<C>(k); }
 template <class C, bool LOCAL>
-constexpr int keep_rows_y(int budget) { return LOCAL ? ms_m64_keep_rows<C>(budget) : keep_rows_r18<C>(budget); }
+constexpr int keep_rows_y(int budget) { return LOCAL ? keep_rows_r19<C>(budget) : keep_rows_r18<C>(budget); }
 
 // ---- round 19, on top of the switches of round 18 (above):
 //   LOCAL   local block columns (ldpc_spec.hpp: ms_m64_local_col) stay out of LDS: STATE1 and STATE2 skip them, STATE3 forms the
 //           soft value at the column's first block row from the records of its rows; BUDGET then counts the other edges only.
 //   PLAIN   the image reads of STATE2 and STATE3 go through a volatile LDS pointer: ds_read_b64 each, no ds_read2st64_b64.
-template <class C, bool A32, bool CARRY, int BUDGET, bool SMASK, bool LOCAL = false, bool PLAIN = false>
+// ---- round 20:
+//   EQ      (with CARRY) a carried row does not track the min1 slot at all: it keeps the v2c values tt[s] of the row, and after the
+//           row's loop slot s takes nm2 where |tt[s]| == nm1 and nm1 elsewhere.  No c1 masks, no scalar mask chain.  Shipped, 68 edges.
+//   INTER   (with CARRY) STATE1 of a carried row is a run of LDS stores / atomics with no vector work between them.  With INTER the
+//           records of the rows past KR are decoded in the scheduling regions of the carried rows (row j decodes the record rows
+//           KR + j, KR + j + KR, ...), so their selects can issue between those atomics; the LDS operations themselves stay where
+//           they are, in ascending block-row order.  Not shipped: no faster (profiles/r20_flagship_variants.txt).
+template <class C, bool A32, bool CARRY, int BUDGET, bool SMASK, bool LOCAL = false, bool PLAIN = false, bool EQ = false, bool INTER = false>
 __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
+    static_assert(!EQ || CARRY, "EQ is a way to carry rows");
+    static_assert(!INTER || CARRY, "INTER spreads the record rows' decode over the carried rows");
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
     constexpr int KR = keep_rows_y<C, LOCAL>(BUDGET);   // block rows [0, KR) are kept
@@ -344,6 +446,7 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
             }
         };
         // ---------------- STATE1
+        double pre[RH][C::WMAX];   // INTER: the decoded values of the record rows, formed beside the carried rows' LDS operations
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
             if constexpr (CARRY && j < KR) {
@@ -356,6 +459,30 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
                         double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
                         if constexpr (C::FIRST[j][s]) *p = cv;
                         else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                });
+                if constexpr (INTER) static_for<KR, RH>([&](auto JR) {
+                    constexpr int jr = decltype(JR)::value;
+                    if constexpr ((jr - KR) % KR == j) {
+                        const u32 mt = meta[jr], pos = mt & 0xffu;
+                        u32 Wt = mt;
+                        static_for<0, C::RW[jr]>([&](auto S) {
+                            constexpr int s = decltype(S)::value;
+                            if constexpr (!local_col_y<C, LOCAL>(C::COL[jr][s]))
+                                pre[jr][s] = signed_mag(sel64(m1[jr], m2[jr], lanes_eq(pos, (u32)s)), Wt);
+                            Wt = twice(Wt);
+                        });
+                    }
+                });
+            } else if constexpr (INTER && KR > 0) {
+                u32 tie;
+                asm volatile("" : "=v"(tie));
+                static_for<0, C::RW[j]>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    if constexpr (!local_col_y<C, LOCAL>(C::COL[j][s])) {
+                        double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
+                        if constexpr (C::FIRST[j][s]) *p = pre[j][s];
+                        else __hip_atomic_fetch_add(p, pre[j][s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 });
             } else {
@@ -405,7 +532,8 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
             load_yl(IC<j + 1>{});
             double nm1 = kMaxVal, nm2 = kMaxVal;
             u32 npos = 0, nS = 0, sy = 0;
-            mask64 lt[RW];   // carried rows: c1 of slot s
+            mask64 lt[RW];   // carried rows, mask chain: c1 of slot s
+            double tt_[RW];  // carried rows, EQ: the v2c value of slot s
             double r[RW];
             static_for<0, RW>([&](auto S) {
                 constexpr int s = decltype(S)::value;
@@ -445,8 +573,12 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
                 const double tt = r[s] - x;
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);
                 const double v = fabs(tt);
+                if constexpr (carried && EQ) tt_[s] = tt;
                 if constexpr (s == 0) {
                     nm1 = fmin(v, kMaxVal);
+                } else if constexpr (carried && EQ) {
+                    nm2 = fmin(fmax(v, nm1), nm2);
+                    nm1 = fmin(v, nm1);
                 } else {
                     const mask64 c1 = lanes_lt(v, nm1);
                     nm2 = fmin(fmax(v, nm1), nm2);
@@ -483,7 +615,13 @@ __device__ __forceinline__ void ms_m64_body_y(const SpecArgs &a) {
             failw |= sy;
             if constexpr (A32) asm volatile("" : "+v"(failw));
             u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);
-            if constexpr (carried) {
+            if constexpr (carried && EQ) {
+                static_for<0, RW>([&](auto S) {
+                    constexpr int s = decltype(S)::value;
+                    keep[j][s] = signed_mag(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
+                    W = twice(W);
+                });
+            } else if constexpr (carried) {
                 mask64 later = 0ull;
                 static_for<1, RW>([&](auto I) {
                     constexpr int s = RW - decltype(I)::value;
@@ -537,18 +675,14 @@ typedef ldpc_spec::CodeAppendixCM64 Code;
 #define VARIANT(name, ...) \
     extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_y<Code, __VA_ARGS__>(a); }
 extern "C" __global__ void __launch_bounds__(64, 2) k_parent(const SpecArgs a) { ldpc_spec::ms_m64_body_parent<Code>(a); }
-//               A32   CARRY budget SMASK LOCAL PLAIN
-VARIANT(k_off,   true, false, 70, false)
-VARIANT(k_c78,   true, true, 78, false)
-VARIANT(k_l50,   true, false, 50, false, true, false)
+//               A32   CARRY budget SMASK LOCAL PLAIN  EQ    INTER
 VARIANT(k_l57,   true, false, 57, false, true, false)
-VARIANT(k_lc57,  true, true, 57, false, true, false)
 VARIANT(k_lc61,  true, true, 61, false, true, false)
-VARIANT(k_p,     true, false, 70, false, false, true)
-VARIANT(k_lp50,  true, false, 50, false, true, true)
-VARIANT(k_lp57,  true, false, 57, false, true, true)
-VARIANT(k_lpc57, true, true, 57, false, true, true)
-VARIANT(k_lpc61, true, true, 61, false, true, true)
+VARIANT(k_le57,  true, true, 57, false, true, false, true)
+VARIANT(k_le61,  true, true, 61, false, true, false, true)
+VARIANT(k_le68,  true, true, 68, false, true, false, true)
+VARIANT(k_lei61, true, true, 61, false, true, false, true, true)
+VARIANT(k_lei68, true, true, 68, false, true, false, true, true)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 
 struct Variant { const void *kern; const char *name; size_t lds; };
@@ -560,18 +694,14 @@ int main(int argc, char **argv) {
     const int N = 2048;
     const size_t L = ldpc_spec::kMsM64LdsBytes(N);
     const Variant var[] = {
-        {(const void *)k_parent, "baseline: the body before round 19 (parent)", L},
-        {(const void *)k_off, "round 19's switches off, 70 edges (must equal the baseline)", L},
-        {(const void *)k_c78, "carried rows 0-10 (round 18's B, 78 edges)", L},
-        {(const void *)k_l50, "A: local columns, rows 0-9 kept (50 edges)", L},
-        {(const void *)k_l57, "A: local columns, rows 0-10 kept (57 edges)", L},
-        {(const void *)k_lc57, "A + carried rows 0-10 (57 edges)", L},
-        {(const void *)k_lc61, "A + carried rows 0-11 (61 edges)", L},
-        {(const void *)k_p, "B: plain 64-bit image reads, 70 edges", L},
-        {(const void *)k_lp50, "A + B, rows 0-9 kept (50 edges)", L},
-        {(const void *)k_lp57, "A + B, rows 0-10 kept (57 edges)", L},
-        {(const void *)k_lpc57, "A + B + carried rows 0-10 (57 edges)", L},
-        {(const void *)k_lpc61, "A + B + carried rows 0-11 (61 edges)", L},
+        {(const void *)k_parent, "baseline: the body round 19 shipped (rows 0-10 kept, 57 edges)", L},
+        {(const void *)k_l57, "round 20's switches off, 57 edges (must equal the baseline)", L},
+        {(const void *)k_lc61, "carried, mask chain, rows 0-11 (61 edges)", L},
+        {(const void *)k_le57, "carried, equality, rows 0-10 (57 edges)", L},
+        {(const void *)k_le61, "carried, equality, rows 0-11 (61 edges)", L},
+        {(const void *)k_le68, "carried, equality, rows 0-12 (68 edges)", L},
+        {(const void *)k_lei61, "carried, equality, 61 edges, record decode interleaved", L},
+        {(const void *)k_lei68, "carried, equality, 68 edges, record decode interleaved", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
     };
     constexpr int NV = sizeof var / sizeof var[0];
