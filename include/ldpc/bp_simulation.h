@@ -19,6 +19,8 @@
  *   ldpc::bp_simulation_t<Mat, Env>()  generic over the matrix type (needs n_rows(), n_cols(), operator()(i,j))
  *                                      and over the environment that owns the generator (see RngEnv below);
  *   ldpc::bp_simulation()              standalone: ldpc::Matrix + the library's own generator (ldpc::reset_random).
+ *   ldpc::bp_simulation_codes_exact()  a set of candidate codes of one shape in exact-replay mode: the stream of the reset generator
+ *                                      drawn once and decoded by every candidate in one launch per batch (_t: generic as above).
  * The drop-in definition of upstream's exact `bp_simulation(int, matrix<int> const&, matrix<int>&, ...)` symbol is
  * csrc/compat/bp_simulation_dropin.cpp (compiled inside the upstream tree).
  */
@@ -138,8 +140,12 @@ inline bool mt_import(std::mt19937 &g, const uint32_t w[624], int pos) {
 // Once per process: does the device-side stream reproduce THIS host's std::mt19937 + std::normal_distribution (libstdc++'s polar
 // method, this libm's log / sqrt)?  4096 samples from a scratch generator, compared bit for bit.  If not -- another standard
 // library, a libm whose log differs in the last place -- the harness keeps drawing on the host, so exact replay stays exact.
-inline bool device_stream_matches_host(ldpc_hip_ctx *ctx) {
+inline std::atomic<int> &device_stream_verdict() {   // -1: not checked yet in this process
     static std::atomic<int> verdict(-1);   // concurrent first calls both run the check and store the same answer
+    return verdict;
+}
+inline bool device_stream_matches_host(ldpc_hip_ctx *ctx) {
+    std::atomic<int> &verdict = device_stream_verdict();
     if (verdict.load() >= 0) return verdict.load() == 1;
     std::mt19937 probe(20240611u);
     uint32_t w[624];
@@ -442,6 +448,33 @@ std::vector<std::pair<double, double>> run_code_set(int C, long long info_len, i
 }
 
 
+// What the code-set harnesses below ask of their arguments, and the set's context: one shape, MODULATION_SKIP, permutation_type 0,
+// opened through the entry point of its decoder.
+template <class Mat, class Env>
+ldpc_hip_ctx *open_code_set(std::vector<Mat> const &codes, int M, int decoder_type, int modulation_type, int permutation_type, long long first_batch,
+                            long long max_batch, int device) {
+    if (codes.empty()) Env::fail("bp_simulation_codes: empty code set");
+    if (modulation_type != MODULATION_SKIP_) Env::fail("bp_simulation_codes: only MODULATION_SKIP (BPSK) is built for code sets");
+    if (permutation_type != 0) Env::fail("bp_simulation_codes: only permutation_type 0 is built for code sets");
+    if (first_batch < 1 || max_batch < first_batch) Env::fail("bp_simulation_codes: bad batch sizes");
+    const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols();
+    std::vector<int16_t> hd((size_t)C * b * c);
+    for (int q = 0; q < C; ++q) {
+        if (codes[(size_t)q].n_rows() != b || codes[(size_t)q].n_cols() != c) Env::fail("bp_simulation_codes: the codes of a set share one shape");
+        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
+    }
+    ldpc_hip_ctx *ctx = nullptr;
+    if ((decoder_type == LDPC_HIP_TASP_DEC   ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC
+             ? ldpc_hip_open_codes_sp(decoder_type, b, c, M, hd.data(), C, device, &ctx)
+                                             : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
+        Env::fail(ldpc_hip_last_error());
+    return ctx;
+}
+
 // A set of candidate codes of one shape over the SAME noise, in throughput mode: what a code search does when it calls
 // reset_random() before every candidate.  One pair <BER, FER> per code, each equal to what bp_simulation_throughput_t returns for
 // that matrix alone with the same seed on one GPU (modulation SKIP, permutation_type 0, the all-zero codeword).  Every batch is
@@ -459,26 +492,9 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
                                                              unsigned long long seed, int device = 0,
                                                              std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
                                                              long long max_batch = 65536) {
-    if (codes.empty()) Env::fail("bp_simulation_codes: empty code set");
-    if (modulation_type != MODULATION_SKIP_) Env::fail("bp_simulation_codes: only MODULATION_SKIP (BPSK) is built for code sets");
-    if (permutation_type != 0) Env::fail("bp_simulation_codes: only permutation_type 0 is built for code sets");
-    if (first_batch < 1 || max_batch < first_batch) Env::fail("bp_simulation_codes: bad batch sizes");
+    ldpc_hip_ctx *ctx = open_code_set<Mat, Env>(codes, tailbite_length, decoder_type, modulation_type, permutation_type, first_batch, max_batch, device);
     const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols(), M = tailbite_length;
     const long long r = (long long)b * M, n = (long long)c * M;
-    std::vector<int16_t> hd((size_t)C * b * c);
-    for (int q = 0; q < C; ++q) {
-        if (codes[(size_t)q].n_rows() != b || codes[(size_t)q].n_cols() != c) Env::fail("bp_simulation_codes: the codes of a set share one shape");
-        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
-    }
-    ldpc_hip_ctx *ctx = nullptr;
-    if ((decoder_type == LDPC_HIP_TASP_DEC   ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC
-             ? ldpc_hip_open_codes_sp(decoder_type, b, c, M, hd.data(), C, device, &ctx)
-                                             : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
-        Env::fail(ldpc_hip_last_error());
     const auto out = run_code_set<Env>(
         C, n - r, n_frame_errors, n_experiments, snr, reference_frame_error, show_process, first_batch, max_batch,
         [&](unsigned long long *state) {
@@ -491,6 +507,153 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
         counters_out);
     ldpc_hip_close(ctx);
     return out;
+}
+
+// A set of candidate codes of one shape in EXACT-REPLAY mode: what `for (candidate) { reset_random(); bp_simulation(...); }` computes
+// (search_ggp/scenario_based_code_generation.cpp:851, main_simulation.cpp:483/492, ldpc_sim.cpp:148), with the noise of upstream's
+// own stream drawn once per batch and decoded by all codes in one launch.  Call it where the loop would call reset_random() for its
+// first candidate: Env::generator() is the generator every candidate starts from.  One pair <BER, FER> per code, and in counters_out
+// the whole SimCounters; each equals what bp_simulation_t returns for that matrix from the same generator state (modulation SKIP,
+// permutation_type 0).  show_process == 0: one ldpc_hip_mt_simulate_codes_stop call, the rule on the device.  Otherwise
+// ldpc_hip_mt_simulate_codes per batch with the records of all codes, the rule replayed per code on the host and a line per error
+// frame.  LDPC_HIP_EXACT_NOISE=host, or a host whose stream the device does not reproduce (device_stream_matches_host), draws the
+// LLRs on the host as bp_simulation_t does and decodes them with ldpc_hip_frames_codes_host.
+// Afterwards Env::generator() holds the state after the last frame code `leave_at` consumed (-1: the last code, what the loop
+// above leaves behind).
+// NOT covered: a caller that goes on with the stream from one SNR to the next per candidate WITHOUT a reset
+// (main_good_code_search.cpp:316-338).  There the candidates' streams part after the first SNR, because each code stops at a
+// frame of its own, and there is no shared noise left to draw once; such a caller stays with bp_simulation_t per candidate.
+template <class Mat, class Env>
+std::vector<std::pair<double, double>> bp_simulation_codes_exact_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
+                                                                   int n_frame_errors, long long n_experiments, double snr,
+                                                                   double reference_frame_error, int decoder_type, int modulation_type,
+                                                                   int permutation_type, int punctured_blocks, int show_process, int device = 0,
+                                                                   std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                                   long long max_batch = 65536, int leave_at = -1) {
+    ldpc_hip_ctx *ctx = open_code_set<Mat, Env>(codes, tailbite_length, decoder_type, modulation_type, permutation_type, first_batch, max_batch, device);
+    const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols(), M = tailbite_length;
+    const long long r = (long long)b * M, n = (long long)c * M;
+    if (leave_at < -1 || leave_at >= C) Env::fail("bp_simulation_codes_exact: leave_at names no code of the set");
+    const int leave = leave_at < 0 ? C - 1 : leave_at;
+    if (punctured_blocks < 0 || punctured_blocks >= c) Env::fail("bp_simulation_codes_exact: punctured_blocks outside [0, nh)");
+
+    Env::burn_codeword_draws(codes[0], M);   // :512, the count depends on the shape only
+    uint32_t words[624];
+    int pos = 0;
+    const bool exported = mt_export(Env::generator(), words, pos);
+    const char *noise_env = getenv("LDPC_HIP_EXACT_NOISE");
+    bool device_noise = exported && !(noise_env && std::string(noise_env) == "host");
+    if (device_noise && device_stream_verdict().load() < 0) {   // once per process, on a single-code context: the probe draws plain samples
+        std::vector<int16_t> hd((size_t)b * c);
+        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[(size_t)i * c + j] = (int16_t)codes[0](i, j);
+        ldpc_hip_ctx *probe = nullptr;
+        const int jit_before = ldpc_hip_set_jit_mode_thread(0);   // the probe decodes nothing
+        const int open_rc = ldpc_hip_open(decoder_type, b, c, M, hd.data(), device, &probe);
+        (void)ldpc_hip_set_jit_mode_thread(jit_before);
+        if (open_rc != 0) Env::fail(ldpc_hip_last_error());
+        (void)device_stream_matches_host(probe);
+        ldpc_hip_close(probe);
+    }
+    device_noise = device_noise && device_stream_verdict().load() == 1;
+
+    std::vector<SimCounters> cnt((size_t)C);
+    const bool nothing = n_frame_errors <= 0 || n_experiments < 0;   // :591 fails before the first frame
+    const auto line = [&](int q) {
+        const SimCounters &k = cnt[(size_t)q];
+        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse, (int)k.nde,
+               (int)k.nue, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
+    };
+    // The per-batch run of both noise sources: frames(B, totals, info, iters) gives the records of the next B frames for all codes
+    const auto batches = [&](auto frames) {
+        std::vector<char> running((size_t)C, 1);
+        std::vector<unsigned long long> totals((size_t)C * 5);
+        std::vector<int32_t> info, iters;
+        int n_running = nothing ? 0 : C;
+        long long first = 0, batch = first_batch;
+        while (n_running > 0) {   // every running code has replayed the same number of frames so far: `first`
+            const long long room = n_experiments + 1 - first;
+            const long long B = batch < room ? batch : room;
+            if (B <= 0) break;
+            info.resize((size_t)C * (size_t)B); iters.resize((size_t)C * (size_t)B);
+            frames(B, totals.data(), info.data(), iters.data());
+            for (int q = 0; q < C; ++q) {
+                if (!running[(size_t)q]) continue;
+                const int32_t *rec = info.data() + (size_t)q * (size_t)B, *it = iters.data() + (size_t)q * (size_t)B;
+                if (replay_stop_rule(cnt[(size_t)q], n_frame_errors, n_experiments, reference_frame_error, B,
+                                     [&](long long f) { return std::make_pair(rec[f], (int)it[f]); }, [&] { if (show_process) line(q); }).stop) {
+                    running[(size_t)q] = 0; --n_running;
+                }
+            }
+            first += B;
+            if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+        }
+    };
+
+    if (device_noise) {
+        if (ldpc_hip_mt_set_state_codes(ctx, words, pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!show_process) {   // nothing to print per error frame: the rule runs on the device
+            std::vector<unsigned long long> state((size_t)C * 6);
+            if (ldpc_hip_mt_simulate_codes_stop(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, n_frame_errors, n_experiments,
+                                                reference_frame_error, first_batch, max_batch, state.data()) != 0)
+                Env::fail(ldpc_hip_last_error());
+            for (int q = 0; q < C; ++q) {
+                const unsigned long long *s = state.data() + (size_t)q * 6;
+                SimCounters &k = cnt[(size_t)q];
+                k.experiment = (long long)s[0]; k.nse = (long long)s[1]; k.nde = (long long)s[2]; k.nue = (long long)s[3];
+                k.sum_abs_iters = (long long)s[4];
+            }
+        } else {
+            batches([&](long long B, unsigned long long *totals, int32_t *info, int32_t *iters) {
+                if (ldpc_hip_mt_simulate_codes(ctx, snr, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, B, totals, info, iters) != 0)
+                    Env::fail(ldpc_hip_last_error());
+            });
+            if (ldpc_hip_mt_set_state_codes(ctx, words, pos) != 0) Env::fail(ldpc_hip_last_error());   // back to the state at entry
+        }
+        // the generator where upstream's loop leaves it for code `leave`
+        if (ldpc_hip_mt_advance_codes(ctx, snr, punctured_blocks, cnt[(size_t)leave].experiment) != 0) Env::fail(ldpc_hip_last_error());
+        if (ldpc_hip_mt_get_state_codes(ctx, words, &pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!mt_import(Env::generator(), words, pos)) Env::fail("bp_simulation_codes_exact: could not hand the generator state back to std::mt19937");
+    } else {
+        const std::mt19937 entry = Env::generator();
+        const int out_type = decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC || decoder_type == LDPC_HIP_IASP_DEC ||
+                             decoder_type == LDPC_HIP_TASP_DEC || decoder_type == LDPC_HIP_LCHE_DEC;                    // :451-466
+        const double bitrate = (double)(c - b) / (c - punctured_blocks);                                               // :444
+        const double sg = std::sqrt(std::pow(10, -snr / 10) / 2 / bitrate);                                            // :445
+        std::vector<double> llr;
+        batches([&](long long B, unsigned long long *totals, int32_t *info, int32_t *iters) {
+            llr.resize((size_t)B * (size_t)n);
+            for (long long f = 0; f < B; ++f) {
+                double *y = llr.data() + (size_t)f * (size_t)n;
+                for (long long i = 0; i < n; ++i) y[i] = -2.0 * (sg * Env::gaussian() + 2.0 * 0.0 - 1.0) / (sg * sg);   // :601-611, codeword == 0
+                for (long long i = n - (long long)M * punctured_blocks; i < n; ++i) y[i] = out_type == 1 ? 0 : 0.5;     // :700-709
+            }
+            if (ldpc_hip_frames_codes_host(ctx, llr.data(), B, max_iterations, 0.8 /*MS_ALPHA*/, totals, info, iters) != 0)
+                Env::fail(ldpc_hip_last_error());
+        });
+        Env::generator() = entry;
+        for (long long i = 0, draws = cnt[(size_t)leave].experiment * n; i < draws; ++i) (void)Env::gaussian();
+    }
+    ldpc_hip_close(ctx);
+    std::vector<std::pair<double, double>> out((size_t)C);
+    for (int q = 0; q < C; ++q)
+        out[(size_t)q] = std::make_pair((double)cnt[(size_t)q].nse / cnt[(size_t)q].experiment / (double)(n - r),   // :840
+                                        (double)cnt[(size_t)q].nde / cnt[(size_t)q].experiment);
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+// the standalone form: ldpc::Matrix and the library's own generator
+inline std::vector<std::pair<double, double>> bp_simulation_codes_exact(std::vector<Matrix> const &codes, int tailbite_length, int max_iterations,
+                                                                        int n_frame_errors, int n_experiments, double snr,
+                                                                        double reference_frame_error, int decoder_type, int modulation_type,
+                                                                        int permutation_type, int permutation_block, int permutation_inter,
+                                                                        int punctured_blocks, int show_process, int device = 0,
+                                                                        std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                                        long long max_batch = 65536, int leave_at = -1) {
+    (void)permutation_block; (void)permutation_inter;   // permutation_type 0 only
+    return bp_simulation_codes_exact_t<Matrix, OwnRngEnv>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr,
+                                                          reference_frame_error, decoder_type, modulation_type, permutation_type, punctured_blocks,
+                                                          show_process, device, counters_out, first_batch, max_batch, leave_at);
 }
 
 // The same for a set of candidate codes over GF(q), q = q_mod = 2^p (FHT_DEC): what upstream's ggp search does when it scores every

@@ -583,6 +583,41 @@ int ldpc_hip_simulate_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_bloc
 int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, uint64_t seed,
                                  long long first_frame, int n_frame_errors, long long n_experiments, double reference_frame_error,
                                  long long first_batch, long long max_batch, unsigned long long *state);
+/* EXACT REPLAY on a binary code set: the noise is upstream's own std::mt19937 / polar-method stream (ldpc_hip_mt_*), drawn ONCE per
+ * piece into the set's [piece][N] LLRs and decoded by every code -- what a search computes that calls reset_random() before each
+ * candidate (search_ggp/scenario_based_code_generation.cpp:851, main_simulation.cpp:483/492, ldpc_sim.cpp:148), one launch per piece
+ * instead of one context and one run per candidate.  The channel is the one ldpc_hip_mt_frames builds for a single context with
+ * modulation_type 0: the all-zero word, the identity interleaver, sigma of the common rate (nh - rh) / (nh - punctured_blocks),
+ * punctured positions at 0.5, or 0.0 for an SP, ASP, TDMP, IASP or LCHE set.  QAM4, interleavers and codewords are not part of the
+ * set path.  Results per code are bit-identical to ldpc_hip_mt_frames on a context opened with that matrix, from the same state.
+ * These five serve binary code-set contexts only: LDPC_HIP_EINVAL on a single-code, a GF(q) and a GF(q)-set context, as the
+ * single-code ldpc_hip_mt_* stay LDPC_HIP_EINVAL on a set.  LDPC_HIP_EINVAL without ldpc_hip_mt_set_state_codes before;
+ * LDPC_HIP_EUNSUPPORTED for a frame longer than one generation round.  Synchronous, one call at a time per context, null stream.
+ * ldpc_hip_mt_set_state_codes / _get_state_codes: as ldpc_hip_mt_set_state / _get_state.
+ * ldpc_hip_mt_advance_codes: draws the next `frames` frames and drops them.
+ * ldpc_hip_mt_simulate_codes: the next B frames of the stream for all C codes; counters [C][5] (HOST, overwritten) as
+ * ldpc_hip_simulate_codes; frame_info [C][B] and iters [C][B] (HOST, each may be NULL) are the ordered records, so a host replay of
+ * the stopping rule has nue and sum |iters| too.  The generator is B frames further on afterwards.  Pieces: LDPC_HIP_CODES_PIECE.
+ * ldpc_hip_mt_simulate_codes_stop: ldpc_hip_simulate_codes_stop over that stream, with the same batch schedule and pieces; the rule
+ * on the device keeps upstream's whole SimCounters: state [C][6] (HOST, overwritten) = experiment, nse, nde, nue, sum |iters|,
+ * frames_decoded per code (nue: error frames with iters >= 0; both over the frames the code consumes).  n_frame_errors <= 0 or
+ * n_experiments < 0: no frame is drawn, state is zero.  The codes stop at different frames, so the call puts the generator and its
+ * frame index BACK to the state at entry; ldpc_hip_mt_advance_codes(ctx, snr_db, punctured_blocks, state[c][0]) then leaves it
+ * where upstream's loop leaves it for code c. */
+/* The same records from LLRs the CALLER drew (a host whose std::mt19937 / libm stream the device does not reproduce keeps the draws
+ * on the host): llr [B][N] (HOST) is uploaded piece by piece into the set's workspace and every code decodes it
+ * (ldpc_hip_decode_codes_dev with shared_llr = 1, then ldpc_hip_count_errors_codes_dev); counters, frame_info and iters as
+ * ldpc_hip_mt_simulate_codes.  Needs no generator state.  Binary code-set contexts only. */
+int ldpc_hip_frames_codes_host(ldpc_hip_ctx *ctx, const double *llr, long long B, int maxiter, double alpha, unsigned long long *counters,
+                               int32_t *frame_info, int32_t *iters);
+int ldpc_hip_mt_set_state_codes(ldpc_hip_ctx *ctx, const uint32_t state[624], int pos);
+int ldpc_hip_mt_get_state_codes(ldpc_hip_ctx *ctx, uint32_t state[624], int *pos);
+int ldpc_hip_mt_advance_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, long long frames);
+int ldpc_hip_mt_simulate_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, long long B,
+                               unsigned long long *counters, int32_t *frame_info, int32_t *iters);
+int ldpc_hip_mt_simulate_codes_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, int n_frame_errors,
+                                    long long n_experiments, double reference_frame_error, long long first_batch, long long max_batch,
+                                    unsigned long long *state);
 
 /* ---- GF(q) code sets: C candidate codes over GF(q) of one shape x B frames in one launch (csrc/ldpc_gfq_codeset.hpp) ----------------
  * What upstream's second search driver does (search_ggp/scenario_based_code_generation.cpp:692-940): every candidate comes from one

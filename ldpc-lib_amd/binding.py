@@ -194,6 +194,12 @@ def load_library():
     lib.ldpc_hip_count_errors_codes_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_codes.argtypes = [vp, f64, i32, i32, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_simulate_codes_stop.argtypes = [vp, f64, i32, i32, f64, u64, i64, i32, i64, f64, i64, i64, vp]
+    lib.ldpc_hip_frames_codes_host.argtypes = [vp, vp, i64, i32, f64, vp, vp, vp]
+    lib.ldpc_hip_mt_set_state_codes.argtypes = [vp, vp, i32]
+    lib.ldpc_hip_mt_get_state_codes.argtypes = [vp, vp, C.POINTER(i32)]
+    lib.ldpc_hip_mt_advance_codes.argtypes = [vp, f64, i32, i64]
+    lib.ldpc_hip_mt_simulate_codes.argtypes = [vp, f64, i32, i32, f64, i64, vp, vp, vp]
+    lib.ldpc_hip_mt_simulate_codes_stop.argtypes = [vp, f64, i32, i32, f64, i32, i64, f64, i64, i64, vp]
     lib.ldpc_hip_open_codes_gfq.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_codes_gfq_table_host.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_gfq_dev.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, vp]
@@ -778,6 +784,47 @@ class LdpcHipCodes:
                                                    int(n_frame_errors), int(n_experiments), float(reference_frame_error), int(first_batch),
                                                    int(max_batch), state.ctypes.data)
         _check(self.lib, rc, "ldpc_hip_simulate_codes_stop")
+        return state
+
+    # ---- exact replay: upstream's own mt19937 / normal_distribution stream, drawn once per piece and shared by the codes ----------
+    def mt_set_state(self, state, pos):
+        """state: 624 uint32 words + index of the next word, as LdpcHip.mt_set_state."""
+        st = np.ascontiguousarray(state, dtype=np.uint32)
+        assert st.shape == (624,)
+        _check(self.lib, self.lib.ldpc_hip_mt_set_state_codes(self.h, st.ctypes.data, int(pos)), "ldpc_hip_mt_set_state_codes")
+
+    def mt_get_state(self):
+        st = np.empty(624, dtype=np.uint32)
+        pos = C.c_int()
+        _check(self.lib, self.lib.ldpc_hip_mt_get_state_codes(self.h, st.ctypes.data, C.byref(pos)), "ldpc_hip_mt_get_state_codes")
+        return st, pos.value
+
+    def mt_advance(self, snr_db, frames, punctured_blocks=0):
+        """Draws the next `frames` frames of the stream and drops them."""
+        _check(self.lib, self.lib.ldpc_hip_mt_advance_codes(self.h, float(snr_db), int(punctured_blocks), int(frames)), "ldpc_hip_mt_advance_codes")
+
+    def mt_simulate(self, snr_db, maxiter, frames, punctured_blocks=0, alpha=0.8, records=False):
+        """The next `frames` frames of the stream for every code.  Returns counters uint64 [C, 5] (nse, nde, nue, frames, sum |iters| per
+        code), and with records=True also frame_info and iters int32 [C, frames]: per code what LdpcHip.mt_frames gives for that matrix
+        from the same generator state."""
+        cnt = np.zeros((self.C, 5), dtype=np.uint64)
+        info = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        its = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_mt_simulate_codes(self.h, float(snr_db), int(punctured_blocks), int(maxiter), float(alpha), int(frames), cnt.ctypes.data,
+                                                 info.ctypes.data if records else None, its.ctypes.data if records else None)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes")
+        return (cnt, info, its) if records else cnt
+
+    def mt_simulate_until(self, snr_db, maxiter, n_frame_errors, n_experiments, reference_frame_error, first_batch=1024, max_batch=65536,
+                          punctured_blocks=0, alpha=0.8):
+        """simulate_until over the exact-replay stream (ldpc_hip_mt_simulate_codes_stop).  Returns uint64 [C, 6] = experiment, nse, nde,
+        nue, sum |iters|, frames_decoded per code: upstream's SimCounters for that matrix after reset_random().  The generator is back
+        at its state at entry afterwards; mt_advance(snr_db, state[c, 0]) takes it to the end of code c's run."""
+        state = np.zeros((self.C, 6), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_mt_simulate_codes_stop(self.h, float(snr_db), int(punctured_blocks), int(maxiter), float(alpha), int(n_frame_errors),
+                                                      int(n_experiments), float(reference_frame_error), int(first_batch), int(max_batch),
+                                                      state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_stop")
         return state
 
     def set_ims_params(self, thr=1.4, qbits=6, dbits=8):

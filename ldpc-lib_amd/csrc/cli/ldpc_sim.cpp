@@ -9,6 +9,9 @@
 //
 //   --throughput   device-side noise (counter-based Philox, not upstream's mt19937 stream): 10^6-10^7 frames/s per GPU; every
 //                  modulation_type 0..4 and permutation_type 0..4; upstream's stopping rule frame by frame over the ordered records
+//   --code-sets    exact mode only: codes that agree in shape, _decoder_type, _lifting, _punctured_blocks, _iterations and _SNRs are
+//                  scored as ONE set per SNR (ldpc::bp_simulation_codes_exact: the noise of the reset generator drawn once, all codes
+//                  of the group in one launch); the result file is the one without the flag except for `time`
 //   --device N     GPU ordinal;  --devices 0,1,2,3 | all   shard the frames over several GPUs (RCCL all-reduce of the counters)
 #include <chrono>
 #include <cmath>
@@ -44,16 +47,51 @@ void reduce_shifts(ldpc::Matrix &H, int M) {
 
 struct Pair { double ber, fer; };
 
+// --code-sets: what decides whether two codes of the scenario can share a set
+struct SetKey {
+    int decoder_type, lifting, punctured_blocks, iterations;
+    std::vector<double> snrs;
+    bool operator==(const SetKey &o) const {
+        return decoder_type == o.decoder_type && lifting == o.lifting && punctured_blocks == o.punctured_blocks && iterations == o.iterations &&
+               snrs == o.snrs;
+    }
+};
+struct SetGroup {
+    SetKey key;
+    std::vector<size_t> members;        // indices into the scenario's `results`
+    std::vector<ldpc::Matrix> codes;    // shifts already reduced
+};
+struct SetResult { std::vector<Pair> per_snr; double secs = 0; };
+
+// does a set context take these codes?  The host-side table builders apply the checks of the open entry points without a GPU.
+bool set_takes(const SetGroup &g, int rows, int columns) {
+    const int C = (int)g.codes.size(), dec = g.key.decoder_type, M = g.key.lifting;
+    std::vector<int16_t> hd((size_t)C * rows * columns);
+    for (int q = 0; q < C; ++q)
+        for (int i = 0; i < rows * columns; ++i) hd[(size_t)q * rows * columns + i] = (int16_t)g.codes[(size_t)q].v[(size_t)i];
+    long long len = 0;
+    switch (dec) {
+    case LDPC_HIP_MS_DEC: case LDPC_HIP_LMS_DEC: case LDPC_HIP_TASP_DEC: case LDPC_HIP_IASP_DEC:
+        return ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+    case LDPC_HIP_LCHE_DEC: return ldpc_hip_codes_table_lche_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+    case LDPC_HIP_IMS_DEC: return ldpc_hip_codes_table_ims_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+    case LDPC_HIP_SP_DEC: case LDPC_HIP_ASP_DEC:
+        return ldpc_hip_codes_table_sp_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+    default: return false;   // BP_DEC and anything else: one code at a time
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool throughput = false;
+    bool throughput = false, code_sets = false;
     int random_codewords = 0;   // --throughput only: transmit this many random codewords encoded on the device instead of the all-zero word
     int device = 0;
     std::string devices_arg;
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--throughput")) throughput = true;
+        else if (!strcmp(argv[i], "--code-sets")) code_sets = true;
         else if (!strcmp(argv[i], "--random-codewords") && i + 1 < argc) random_codewords = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices_arg = argv[++i];
@@ -80,7 +118,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (pos.size() != 3 || pos[0] != "simulation")
-        die("usage: ldpc_sim simulation <scenario file name> <result file name> [--throughput [--random-codewords N]] [--device N | --devices 0,1,.. | --devices all]\n"
+        die("usage: ldpc_sim simulation <scenario file name> <result file name> [--throughput [--random-codewords N]] [--code-sets] [--device N | --devices 0,1,.. | --devices all]\n"
             "       ldpc_sim jsonx <in.jsonx> <out.jsonx>        re-emit in canonical form\n"
             "       ldpc_sim jsonx-get <in.jsonx> <path/to/field>  print one value (falls back to 'defaults' records)");
 
@@ -108,6 +146,49 @@ int main(int argc, char **argv) {
         jsonx::Value out;
         out.set("settings", scenario.select("settings"));
         jsonx::Value &results = out.set("results", jsonx::Value::array());
+
+        // --code-sets: the groups are scored first, each SNR of a group in one bp_simulation_codes_exact call after reset_random(); the
+        // loop below then takes a grouped code's numbers from here and runs every other code as it always did
+        std::vector<SetResult> from_set(codes.items.size());
+        if (code_sets && !throughput && modulation_type == 0 && permutation_type == 0) {
+            std::vector<SetGroup> groups;
+            int rows0 = -1, columns0 = -1;
+            for (size_t code_idx = 0; code_idx < codes.items.size(); ++code_idx) {
+                const jsonx::Value &code = codes.items[code_idx];
+                if ((code.has("_q_mod") ? (int)code.select("_q_mod").as_int() : 2) > 2) continue;
+                if (code.select("_marking").as_string() != "skip") break;   // the loop below dies there: nothing behind it is simulated
+                int r = 0, c = 0;
+                const std::vector<int> cells = code.select("code").as_int_matrix(r, c);
+                if (rows0 == -1) { rows0 = r; columns0 = c; }
+                else if (rows0 != r || columns0 != c) continue;
+                SetKey key{(int)code.select("_decoder_type").as_int(), (int)code.select("_lifting").as_int(),
+                           (int)code.select("_punctured_blocks").as_int(), (int)code.select("_iterations").as_int(), code.select("_SNRs").as_doubles()};
+                ldpc::Matrix H(r, c);
+                H.v = cells;
+                reduce_shifts(H, key.lifting);
+                size_t g = 0;
+                while (g < groups.size() && !(groups[g].key == key)) ++g;
+                if (g == groups.size()) { groups.emplace_back(); groups[g].key = key; }
+                groups[g].members.push_back(code_idx);
+                groups[g].codes.push_back(H);
+            }
+            for (const SetGroup &g : groups) {
+                if (g.members.size() < 2 || g.key.punctured_blocks < 0 || g.key.punctured_blocks >= columns0 || !set_takes(g, rows0, columns0)) continue;
+                const auto t0 = std::chrono::steady_clock::now();
+                for (size_t m : g.members) from_set[m].per_snr.resize(g.key.snrs.size());
+                for (size_t s = 0; s < g.key.snrs.size(); ++s) {
+                    printf("set of %zu codes from code #%zu on, SNR = %6.3f\n", g.members.size(), g.members[0], g.key.snrs[s]);
+                    ldpc::initial_random_seed = seed;
+                    ldpc::reset_random();                                                                                     // :483 all codes are tested with same noise
+                    const std::vector<std::pair<double, double>> p = ldpc::bp_simulation_codes_exact(
+                        g.codes, g.key.lifting, g.key.iterations, num_frame_errors, (int)num_experiments, g.key.snrs[s], error_rate_threshold,
+                        g.key.decoder_type, modulation_type, permutation_type, permutation_block, permutation_inter, g.key.punctured_blocks, 0, devices[0]);
+                    for (size_t q = 0; q < g.members.size(); ++q) from_set[g.members[q]].per_snr[s] = {p[q].first, p[q].second};
+                }
+                const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                for (size_t m : g.members) from_set[m].secs = secs / (double)g.members.size();
+            }
+        }
 
         int rows = -1, columns = -1;
         for (size_t code_idx = 0; code_idx < codes.items.size(); ++code_idx) {
@@ -137,7 +218,9 @@ int main(int argc, char **argv) {
                 printf("code #%zu, original matrix is being processed, SNR = %6.3f\n", code_idx, snrs[s]);
                 esn0[s] = snrs[s] + 10.0 * std::log10(2.0 * bitrate);                                                        // :481
                 Pair res;
-                if (throughput) {
+                if (!from_set[code_idx].per_snr.empty()) {
+                    res = from_set[code_idx].per_snr[s];
+                } else if (throughput) {
                     const std::pair<double, double> p = ldpc::bp_simulation_throughput_t<ldpc::Matrix, ldpc::OwnRngEnv>(
                         2, H, lifting, iterations, num_frame_errors, num_experiments, snrs[s], error_rate_threshold, decoder_type, modulation_type,
                         permutation_type, permutation_block, permutation_inter, punctured_blocks, 0, (unsigned long long)seed, devices, nullptr, 65536, nullptr,
@@ -156,7 +239,8 @@ int main(int argc, char **argv) {
                 if (res.ber < 0 || res.fer < 0) res = {1.0, 1.0};                                                            // :527-531
                 ber[s] = res.ber; fer[s] = res.fer;
             }
-            const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            const double secs = from_set[code_idx].per_snr.empty() ? std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                                                                   : from_set[code_idx].secs;
 
             printf("        |     FER     |     BER\n");
             for (size_t s = 0; s < snrs.size(); ++s) printf("%7.3f | %10.8f  | %10.8f\n", snrs[s], fer[s], ber[s]);

@@ -74,6 +74,31 @@ extern "C" int ldpc_bp_simulation_exact(int rh, int nh, const int *H, int M, int
                                          decoder_type, modulation_type, 0, 128, 1, punctured_blocks, seed, device, out, rng_next);
 }
 
+// A code set in exact-replay mode (ldpc::bp_simulation_codes_exact): codes [C][rh][nh] row-major; seeds the generator as above, once
+// for the whole set.  out [C][7] as above per code; *rng_next = next raw mt19937 output after the run of code leave_at (-1: the last).
+extern "C" int ldpc_bp_simulation_codes_exact(int C, int rh, int nh, const int *codes, int M, int max_iterations, int n_frame_errors,
+                                              int n_experiments, double snr, double reference_frame_error, int decoder_type,
+                                              int punctured_blocks, int show_process, unsigned seed, int device, long long first_batch,
+                                              long long max_batch, int leave_at, double *out, unsigned *rng_next) {
+    std::vector<ldpc::Matrix> set((size_t)C, ldpc::Matrix(rh, nh));
+    for (int q = 0; q < C; ++q)
+        for (int i = 0; i < rh * nh; ++i) set[(size_t)q].v[(size_t)i] = codes[(size_t)q * rh * nh + i];
+    ldpc::initial_random_seed = (int)seed;
+    ldpc::reset_random();
+    std::vector<ldpc::SimCounters> cnt;
+    const std::vector<std::pair<double, double>> res = ldpc::bp_simulation_codes_exact(
+        set, M, max_iterations, n_frame_errors, n_experiments, snr, reference_frame_error, decoder_type, 0, 0, 128, 1, punctured_blocks,
+        show_process, device, &cnt, first_batch, max_batch, leave_at);
+    for (int q = 0; q < C; ++q) {
+        double *o = out + (size_t)q * 7;
+        const ldpc::SimCounters &k = cnt[(size_t)q];
+        o[0] = res[(size_t)q].first; o[1] = res[(size_t)q].second; o[2] = (double)k.nse; o[3] = (double)k.nde; o[4] = (double)k.nue;
+        o[5] = (double)k.experiment; o[6] = (double)k.sum_abs_iters;
+    }
+    if (rng_next) *rng_next = (unsigned)ldpc::random_generator()();
+    return 0;
+}
+
 // Throughput mode (device-side noise, frames sharded over `devices`, upstream's sequential stopping rule on the ordered records).
 // devices == NULL: LDPC_HIP_DEVICES or device 0.  codewords: [ncw][nh*M] 0/1 bytes or NULL (all-zero codeword).
 extern "C" int ldpc_bp_simulation_throughput(int rh, int nh, const int *H, int M, int max_iterations, int n_frame_errors,

@@ -875,19 +875,32 @@ struct CodesetRuleArgs {
     double reference_frame_error;
 };
 
-__global__ void __launch_bounds__(64) stop_rule_codes_kernel(const CodesetRuleArgs a) {
+struct CodesetRuleFullArgs : CodesetRuleArgs {   // state is [C][6]
+    const int32_t *iters;          // [n_active][B]
+};
+
+// FULL: the whole SimCounters of an exact replay.  The state is [C][6] = experiment, nse, nde, nue, sum |iters|, frames_decoded, and
+// the slot's iteration counts iters [n_active][B] are read next to its records: nue counts the error frames with iters >= 0
+// (:809-810) and sum |iters| every frame (:799), both over exactly the frames that reach the state (`take`), with the ballot and the
+// 64-bit sum of nse.  !FULL is the rule of the Philox entry points, state [C][4], and reads no iteration count.
+template <bool FULL>
+__global__ void __launch_bounds__(64) stop_rule_codes_kernel(const std::conditional_t<FULL, CodesetRuleFullArgs, CodesetRuleArgs> a) {
+    constexpr int kWords = FULL ? 6 : 4;
     const int lane = threadIdx.x;
     const int code = tab_ptr(a.code_list)[blockIdx.x];
     const int32_t *const rec = a.frame_info + (long long)blockIdx.x * a.B;
-    unsigned long long *const st = a.state + 4 * (size_t)code;
+    unsigned long long *const st = a.state + kWords * (size_t)code;
     long long experiment = (long long)st[0], nde = (long long)st[2];
     unsigned long long nse = st[1];
+    unsigned long long nue = 0, sit = 0;   // FULL: what this piece adds
     const double thr = 2.5 * a.reference_frame_error;
     const unsigned long long below = (1ull << lane) - 1;
     bool stopped = false;
     for (long long base = 0; base < a.B && !stopped; base += 64) {
         const bool act = base + lane < a.B;
         const int32_t r = act ? rec[base + lane] : 0;
+        int32_t it = 0;
+        if constexpr (FULL) it = act ? a.iters[(long long)blockIdx.x * a.B + base + lane] : 0;
         const bool err = r != 0;                                                     // bit 30: any wrong bit (:805)
         const unsigned long long em = __ballot(err);
         const long long d0 = nde + __popcll(em & below);                             // nde and experiment before this lane's frame
@@ -912,10 +925,19 @@ __global__ void __launch_bounds__(64) stop_rule_codes_kernel(const CodesetRuleAr
             for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
             nse += s;
         }
+        if (FULL) {
+            nue += (unsigned long long)__popcll(__ballot(err && it >= 0) & take);
+            unsigned long long s = lane < n ? (unsigned long long)(it < 0 ? -(long long)it : (long long)it) : 0ull;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            sit += s;
+        }
     }
     if (!(nde < a.n_frame_errors && experiment <= a.n_experiments)) stopped = true;   // :591 fails before the next frame
     if (lane == 0) {
-        st[0] = (unsigned long long)experiment; st[1] = nse; st[2] = (unsigned long long)nde; st[3] += (unsigned long long)a.B;
+        st[0] = (unsigned long long)experiment; st[1] = nse; st[2] = (unsigned long long)nde;
+        if (FULL) { st[3] += nue; st[4] += sit; }
+        st[kWords - 1] += (unsigned long long)a.B;
         if (stopped) a.running[code] = 0;
     }
 }

@@ -6,7 +6,7 @@
 
 // ldpc_hip_simulate_codes_stop and its GF(q) twin: the per-code state of the stopping rule and the list of the codes still running
 struct codeset_rule_ws {
-    unsigned long long *rule = nullptr;              // [C][4]: experiment, nse, nde, frames_decoded
+    unsigned long long *rule = nullptr;              // [C][4]: experiment, nse, nde, frames_decoded; the exact-replay run: [C][6] (room for 6)
     int32_t *running = nullptr, *list = nullptr;     // [C] each
     int32_t *nactive = nullptr;                      // [1]
 };
@@ -464,13 +464,14 @@ int codeset_stop_args(const char *who, const unsigned long long *state, long lon
 // The batch schedule and the stopping rule of the *_stop entry points around the launches of one piece: run_piece(first, nb, list,
 // n_active) draws, decodes and counts frames [first, first + nb) of the run for the n_active codes of `list` (DEVICE), leaving their
 // records in w_info [n_active][nb].  The device is the caller's current one; w_cnt [C][5] is cleared; state [C][4] is the HOST result.
+// full: the rule of an exact replay (stop_rule_codes_kernel<true>), which reads w_iters [n_active][nb] too; state is [C][6].
 template <class Piece>
 int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
-                      long long max_batch, unsigned long long *state, Piece run_piece) {
-    const size_t C = (size_t)s.C;
+                      long long max_batch, unsigned long long *state, Piece run_piece, bool full = false) {
+    const size_t C = (size_t)s.C, words = full ? 6 : 4;
     codeset_rule_ws &w = s.stop;
     if (!w.rule) {
-        HIP_TRY(hipMalloc(&w.rule, sizeof(unsigned long long) * 4 * C));
+        HIP_TRY(hipMalloc(&w.rule, sizeof(unsigned long long) * 6 * C));
         HIP_TRY(hipMalloc(&w.running, sizeof(int32_t) * C));
         HIP_TRY(hipMalloc(&w.list, sizeof(int32_t) * C));
         HIP_TRY(hipMalloc(&w.nactive, sizeof(int32_t)));
@@ -479,7 +480,7 @@ int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, lo
     for (size_t q = 0; q < C; ++q) ident[q] = (int32_t)q;
     HIP_TRY(hipMemcpy(w.list, ident.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(w.running, ones.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(w.rule, 0, sizeof(unsigned long long) * 4 * C, nullptr));
+    HIP_TRY(hipMemsetAsync(w.rule, 0, sizeof(unsigned long long) * words * C, nullptr));
     HIP_TRY(hipMemsetAsync(s.w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
     int32_t n_active = (int32_t)C;
     long long first = 0, batch = first_batch;   // every running code has consumed the same number of frames: `first`
@@ -491,7 +492,9 @@ int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, lo
             const long long nb = (B - done) < piece ? (B - done) : piece;
             if (int rc = run_piece(first + done, nb, w.list, n_active)) return rc;
             const ldpc::CodesetRuleArgs ra{s.w_info, w.list, w.rule, w.running, nb, n_frame_errors, n_experiments, reference_frame_error};
-            hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
+            const ldpc::CodesetRuleFullArgs fa{ra, s.w_iters};
+            if (full) hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel<true>, dim3((unsigned)n_active), dim3(64), 0, nullptr, fa);
+            else hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel<false>, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, w.running, (int)C, w.list, w.nactive);
             HIP_TRY(hipGetLastError());
@@ -500,7 +503,7 @@ int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, lo
         first += B;
         if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
     }
-    HIP_TRY(hipMemcpy(state, w.rule, sizeof(unsigned long long) * 4 * C, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(state, w.rule, sizeof(unsigned long long) * words * C, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -586,6 +589,134 @@ int ldpc_hip_simulate_codes_stop(ldpc_hip_ctx *c, double snr_db, int punctured_b
                              [&](long long first, long long nb, const int32_t *list, int n_active) -> int {
                                  return codeset_piece_launch(c, ch, maxiter, alpha, first_frame + first, nb, true, list, n_active);
                              });
+}
+
+}  // extern "C"
+
+// ---- exact replay on a binary code set (ldpc_hip_mt_*_codes): the generator of ldpc_mt_api.hpp draws the [piece][N] LLRs of upstream's
+// own stream ONCE into the set's workspace and every code decodes them -- what a search that calls reset_random() before each
+// candidate computes, in one launch per piece.
+namespace {
+
+int mt_codes_ctx(const ldpc_hip_ctx *c, const char *who) {
+    if (!c || !c->codes) return fail(LDPC_HIP_EINVAL, "%s: not a binary code-set context (ldpc_hip_open_codes and its kin)", who);
+    return 0;
+}
+
+// the next nb frames of the stream -> w_llr (after codeset_reserve) -> set decode -> set count, for the n_active codes of `list` (null: all)
+int mt_codes_piece_launch(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, long long nb, bool want_info,
+                          const int32_t *list, int n_active) {
+    ldpc_codeset_state *s = c->codes;
+    if (int rc = mt_llr_rows(c, snr_db, 0, punctured_blocks, nb, 0, nb, s->w_llr, nullptr)) return rc;
+    if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, list, n_active)) return rc;
+    return codeset_count_launch(c, s->w_hard, s->w_iters, nb, want_info ? s->w_info : nullptr, s->w_cnt, nullptr, list, n_active);
+}
+
+// what mt_frame_proto refuses, before anything is drawn or reserved
+int mt_codes_channel_check(ldpc_hip_ctx *c, double snr_db, int punctured_blocks) {
+    ldpc_mt::PolarArgs a{};
+    return mt_frame_proto(c, snr_db, 0, punctured_blocks, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_hip_mt_set_state_codes(ldpc_hip_ctx *c, const uint32_t state[624], int pos) {
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_set_state_codes")) return rc;
+    if (!state || pos < 0 || pos > 624) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_set_state_codes: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = mt_prepare(c)) return rc;
+    HIP_TRY(hipMemcpy(c->mt.d_state, state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyHostToDevice));
+    c->mt.pos = pos;
+    c->mt.set = true;
+    c->mt.frames_taken = 0;
+    return 0;
+}
+
+int ldpc_hip_mt_get_state_codes(ldpc_hip_ctx *c, uint32_t state[624], int *pos) {
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_get_state_codes")) return rc;
+    if (!state || !pos) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_get_state_codes: bad argument");
+    if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call ldpc_hip_mt_set_state first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(state, c->mt.d_state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToHost));
+    *pos = (int)c->mt.pos;
+    return 0;
+}
+
+int ldpc_hip_mt_advance_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, long long frames) {
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_advance_codes")) return rc;
+    if (frames < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_advance_codes: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    return mt_llr_rows(c, snr_db, 0, punctured_blocks, frames, 0, 0, nullptr, nullptr);
+}
+
+int ldpc_hip_mt_simulate_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, long long B,
+                               unsigned long long *counters, int32_t *frame_info, int32_t *iters) {
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_simulate_codes")) return rc;
+    if (!counters || B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_simulate_codes: bad argument");
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_simulate_codes: maxiter must be >= 1 (got %d)", maxiter);
+    if (int rc = mt_codes_channel_check(c, snr_db, punctured_blocks)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    ldpc_codeset_state *s = c->codes;
+    const long long piece = codeset_piece(c, B);
+    if (int rc = codeset_reserve(c, piece)) return rc;
+    const size_t C = (size_t)s->C;
+    return codeset_simulate_loop(*s, piece, B, counters, frame_info, [&](long long first, long long nb) -> int {
+        if (int rc = mt_codes_piece_launch(c, snr_db, punctured_blocks, maxiter, alpha, nb, frame_info != nullptr, nullptr, 0)) return rc;
+        if (iters)   // [C][nb] on the device -> columns [first, first + nb) of the caller's [C][B]
+            HIP_TRY(hipMemcpy2D(iters + first, sizeof(int32_t) * (size_t)B, s->w_iters, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int ldpc_hip_frames_codes_host(ldpc_hip_ctx *c, const double *llr, long long B, int maxiter, double alpha, unsigned long long *counters,
+                               int32_t *frame_info, int32_t *iters) {
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_frames_codes_host")) return rc;
+    if (!counters || B < 0 || (B > 0 && !llr)) return fail(LDPC_HIP_EINVAL, "ldpc_hip_frames_codes_host: bad argument");
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_frames_codes_host: maxiter must be >= 1 (got %d)", maxiter);
+    HIP_TRY(hipSetDevice(c->device));
+    ldpc_codeset_state *s = c->codes;
+    const long long piece = codeset_piece(c, B);
+    if (int rc = codeset_reserve(c, piece)) return rc;
+    const size_t C = (size_t)s->C;
+    return codeset_simulate_loop(*s, piece, B, counters, frame_info, [&](long long first, long long nb) -> int {
+        HIP_TRY(hipMemcpy(s->w_llr, llr + (size_t)first * (size_t)c->N, sizeof(double) * (size_t)nb * (size_t)c->N, hipMemcpyHostToDevice));
+        if (int rc = codeset_decode_launch(c, s->w_llr, 1, nb, maxiter, alpha, s->w_hard, s->w_iters, nullptr, nullptr, nullptr, 0)) return rc;
+        if (int rc = codeset_count_launch(c, s->w_hard, s->w_iters, nb, frame_info ? s->w_info : nullptr, s->w_cnt, nullptr)) return rc;
+        if (iters)
+            HIP_TRY(hipMemcpy2D(iters + first, sizeof(int32_t) * (size_t)B, s->w_iters, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int ldpc_hip_mt_simulate_codes_stop(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, double alpha, int n_frame_errors,
+                                    long long n_experiments, double reference_frame_error, long long first_batch, long long max_batch,
+                                    unsigned long long *state) {
+    using namespace ldpc_mt;
+    if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_simulate_codes_stop")) return rc;
+    if (int rc = codeset_stop_args("ldpc_hip_mt_simulate_codes_stop", state, 0, first_batch, max_batch, maxiter)) return rc;
+    if (int rc = mt_codes_channel_check(c, snr_db, punctured_blocks)) return rc;
+    std::memset(state, 0, sizeof(unsigned long long) * 6 * (size_t)c->codes->C);
+    if (n_frame_errors <= 0 || n_experiments < 0) return 0;   // :591 fails before the first frame
+    HIP_TRY(hipSetDevice(c->device));
+    const long long piece = codeset_piece(c, max_batch < n_experiments + 1 ? max_batch : n_experiments + 1);
+    if (int rc = codeset_reserve(c, piece)) return rc;
+    // the codes stop at different frames: the generator goes back to where it was, ldpc_hip_mt_advance_codes takes it to one code's end
+    DeviceState &m = c->mt;
+    std::vector<uint32_t> entry(MTN);
+    const long long entry_pos = m.pos, entry_frames = m.frames_taken;
+    HIP_TRY(hipMemcpy(entry.data(), m.d_state, sizeof(uint32_t) * MTN, hipMemcpyDeviceToHost));
+    const int rc = codeset_stop_loop(*c->codes, piece, n_frame_errors, n_experiments, reference_frame_error, first_batch, max_batch, state,
+                                     [&](long long, long long nb, const int32_t *list, int n_active) -> int {   // pieces come in frame order
+                                         return mt_codes_piece_launch(c, snr_db, punctured_blocks, maxiter, alpha, nb, true, list, n_active);
+                                     }, true);
+    if (hipMemcpy(m.d_state, entry.data(), sizeof(uint32_t) * MTN, hipMemcpyHostToDevice) != hipSuccess && rc == 0)
+        return fail(LDPC_HIP_EHIP, "ldpc_hip_mt_simulate_codes_stop: the generator's state could not be put back");
+    m.pos = entry_pos; m.frames_taken = entry_frames;
+    return rc;
 }
 
 }  // extern "C"

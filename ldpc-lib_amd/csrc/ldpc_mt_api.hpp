@@ -228,10 +228,14 @@ int mt_frame_proto(ldpc_hip_ctx *c, double snr_db, int modulation_type, int punc
     if ((unsigned long long)c->N > kRoundItems) return fail(LDPC_HIP_EUNSUPPORTED, "code length %d is beyond one generation round", c->N);
     a = PolarArgs{};
     if (int rc = awgn_sigma(c, snr_db, modulation_type, punctured_blocks, &a.sigma)) return rc;
-    if (int rc = prepare_chain(c, modulation_type)) return rc;
     a.per_frame = c->N;
-    a.tx = c->ncw > 0 ? c->d_tx : nullptr; a.ncw = c->ncw > 0 ? c->ncw : 1; a.ntx = c->chain_ntx;
-    a.scatter = c->d_scatter;
+    if (c->codes) {   // a binary code set (ldpc_hip_mt_*_codes): the all-zero word and the identity interleaver, which the emit pass
+        a.tx = nullptr; a.ncw = 1; a.ntx = c->N; a.scatter = nullptr;   // takes from null tables -- a set keeps no chain
+    } else {
+        if (int rc = prepare_chain(c, modulation_type)) return rc;
+        a.tx = c->ncw > 0 ? c->d_tx : nullptr; a.ncw = c->ncw > 0 ? c->ncw : 1; a.ntx = c->chain_ntx;
+        a.scatter = c->d_scatter;
+    }
     a.punct_start = c->N - c->M * punctured_blocks;
     a.punct_val = punctured_llr(c->decoder_id);
     return 0;

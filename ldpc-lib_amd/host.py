@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from .binding import DEC_IMS, DEC_LMS, DEC_MS, DEC_SP, DEC_TASP, LdpcHip, LdpcHipError
+from .binding import DEC_IMS, DEC_LMS, DEC_MS, DEC_SP, DEC_TASP, LdpcHip, LdpcHipCodes, LdpcHipError
 
 MODULATION_SKIP, MODULATION_QAM4, MODULATION_QAM16 = 0, 1, 2  # modulation.h:4-11
 
@@ -265,3 +265,23 @@ def bp_simulation(H, tailbite_length, max_iterations, n_frame_errors, n_experime
     ber = state["nse"] / state["experiment"] / (n - r)
     fer = state["nde"] / state["experiment"]
     return (ber, fer, state) if return_state else (ber, fer)
+
+
+def bp_simulation_codes(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr, reference_frame_error,
+                        decoder_type=DEC_MS, punctured_blocks=0, device=0, alpha=0.8, first_batch=1024, max_batch=65536, return_state=False,
+                        exact_seed=1):
+    """EXACT REPLAY on a set of candidate codes [C, rh, nh] of one shape: what `for H in codes: reset_random(); bp_simulation(H, ...)`
+    returns with initial_random_seed = exact_seed, from one LdpcHipCodes.mt_simulate_until call -- the noise of std::mt19937(exact_seed)
+    after the (nh - rh) * M codeword draws is drawn once and every code decodes it (BPSK, permutation_type 0).  Returns a list of
+    (BER, FER) per code; with return_state=True also the list of dict(nse, nde, nue, experiment, sum_abs_iters, frames_decoded)."""
+    codes = np.asarray(codes)
+    nh_minus_rh = codes.shape[2] - codes.shape[1]
+    with LdpcHipCodes(decoder_type, codes, tailbite_length, device) as cs:
+        cs.mt_set_state(*mt19937_state(exact_seed, nh_minus_rh * tailbite_length))
+        state = cs.mt_simulate_until(snr, max_iterations, n_frame_errors, n_experiments, reference_frame_error, first_batch=first_batch,
+                                     max_batch=max_batch, punctured_blocks=punctured_blocks, alpha=alpha)
+        info_len = cs.N - cs.R
+    keys = ("experiment", "nse", "nde", "nue", "sum_abs_iters", "frames_decoded")
+    states = [dict(zip(keys, (int(v) for v in row))) for row in state]
+    pairs = [(s["nse"] / s["experiment"] / info_len, s["nde"] / s["experiment"]) for s in states]
+    return (pairs, states) if return_state else pairs
