@@ -464,7 +464,12 @@ ldpc_hip_ctx *open_code_set(std::vector<Mat> const &codes, int M, int decoder_ty
         for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[((size_t)q * b + i) * c + j] = (int16_t)codes[(size_t)q](i, j);
     }
     ldpc_hip_ctx *ctx = nullptr;
-    if ((decoder_type == LDPC_HIP_TASP_DEC   ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
+    // MS_DEC, TASP_DEC and LMS_DEC beyond the 16 block rows (MS_DEC: or 32 block columns) of their register-resident set kernels:
+    // ldpc_hip_open_codes_wide, the records in LDS
+    const bool wide = (decoder_type == LDPC_HIP_MS_DEC || decoder_type == LDPC_HIP_TASP_DEC || decoder_type == LDPC_HIP_LMS_DEC) &&
+                      (b > 16 || (decoder_type == LDPC_HIP_MS_DEC && c > 32));
+    if ((wide                                ? ldpc_hip_open_codes_wide(decoder_type, b, c, M, hd.data(), C, device, &ctx)
+         : decoder_type == LDPC_HIP_TASP_DEC ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
          : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
          : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
          : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
@@ -482,7 +487,8 @@ ldpc_hip_ctx *open_code_set(std::vector<Mat> const &codes, int M, int decoder_ty
 // sequential stopping rule (:591, :805-823) is replayed per code over its ordered records, and a code that has stopped ignores the
 // records of later batches.  With show_process == 0 the whole run is one ldpc_hip_simulate_codes_stop call instead: the same rule on
 // the device, every launch over the codes still running, no records on the host; the results are the same integers.  decoder_type: MS_DEC, LMS_DEC, TASP_DEC (7, ldpc_hip_open_codes_tdmp),
-// IASP_DEC (5, ldpc_hip_open_codes_iasp), LCHE_DEC (9, ldpc_hip_open_codes_lche), IMS_DEC (4, ldpc_hip_open_codes_ims), SP_DEC or ASP_DEC (1, 2, ldpc_hip_open_codes_sp).  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// IASP_DEC (5, ldpc_hip_open_codes_iasp), LCHE_DEC (9, ldpc_hip_open_codes_lche), IMS_DEC (4, ldpc_hip_open_codes_ims), SP_DEC or ASP_DEC (1, 2, ldpc_hip_open_codes_sp); MS_DEC, TASP_DEC and LMS_DEC beyond 16 block rows (MS_DEC: or 32 block columns)
+// through ldpc_hip_open_codes_wide, so no shape is refused for its block rows or columns.  counters_out: nse, nde and experiment per code (the [C][B] records carry
 // no iteration counts, so nue and sum_abs_iters stay 0).
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,

@@ -444,13 +444,15 @@ int ldpc_hip_simulate_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_
  * decoder_id: LDPC_HIP_MS_DEC or LDPC_HIP_LMS_DEC; results are bit-identical to a context opened with ldpc_hip_open on the same matrix.
  * LDPC_HIP_EINVAL: another decoder id, C < 1, M > 512, rh > 16, nh > 32 (MS_DEC), a row weight above 16, an all-empty block row or
  * column, a shift outside [-1, M); LDPC_HIP_EUNSUPPORTED: nh * M * floor(64 / M) float64 values beyond the 160 KiB LDS image.
+ * More block rows or columns: ldpc_hip_open_codes_wide.
  * The context serves the *_codes* entry points only: the single-code, GF(q) and multi-device entry points return LDPC_HIP_EINVAL
  * on it, and the *_codes* entry points return LDPC_HIP_EINVAL on any other context.  Close with ldpc_hip_close. */
 int ldpc_hip_open_codes(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 /* The same for TDMP sum-product (LDPC_HIP_TASP_DEC; tdmp_sum_prod_gf2_decod_qc_lm, decoders.cpp:2584-2744, map_bin :2191-2228): an
  * ordinary code-set context, served by the entry points below (alpha is ignored).  Limits: M <= 512, rh <= 16, row weights 2 .. 16
  * (LDPC_HIP_EINVAL; map_bin reads SB[1]), no empty block column, any nh; LDPC_HIP_EUNSUPPORTED when the LDS image of a workgroup,
- * floor(64 / M) * 8 * (nh * M + ne_max * M) + 16 bytes with ne_max the largest number of circulants of a code, exceeds 160 KiB. */
+ * floor(64 / M) * 8 * (nh * M + ne_max * M) + 16 bytes with ne_max the largest number of circulants of a code, exceeds 160 KiB.
+ * More block rows: ldpc_hip_open_codes_wide (the same kernel). */
 int ldpc_hip_open_codes_tdmp(int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 /* The same for the integer advanced sum-product decoder (LDPC_HIP_IASP_DEC; isum_prod_gf2_decod_qc_lm, decoders.cpp:3822-4121, imap_bin
  * :2235-2271), both of its branches: a code whose block columns all hold two circulants takes upstream's own branch, decided per code.
@@ -522,6 +524,27 @@ int ldpc_hip_open_codes_ims(int rh, int nh, int M, const int16_t *hd, int C, int
  * 1839 ms at 256 (3.12x), 3.1 against 8.1 ms for one code; M = 126: 64.9 against 315.6 ms (4.86x), 1025 against 5048 ms (4.92x), 4.6
  * against 20.9 ms; 30 x 60: 178.4 against 574.4 ms (3.22x), 2920 against 9446 ms (3.24x), 12.8 against 36.4 ms. */
 int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* Min-sum, TDMP and layered min-sum sets at ANY number of block rows and columns: decoder_id LDPC_HIP_MS_DEC (3), LDPC_HIP_TASP_DEC (7)
+ * or LDPC_HIP_LMS_DEC (8); any other id is LDPC_HIP_EINVAL.  An ordinary code-set context, served by the entry points below exactly as
+ * a context of ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp with the same id is (alpha, puncture fill), and bit-identical to it on
+ * every shape both accept: shapes inside the limits of those entry points are accepted here too.  Kernels
+ * (csrc/ldpc_codeset_wide.hpp): ms_flood_wide_codes_kernel and lms_layered_wide_codes_kernel keep the per-check records (min1, min2, the
+ * sign bits and the slot of min1) in LDS instead of registers, and the flooding kernel reads the channel LLRs from memory again in
+ * every iteration; TDMP runs tasp_layered_codes_kernel itself, which keeps nothing per block row.
+ * Limits: M <= 512, row weights 1 .. 16 (TDMP 2 .. 16), no empty block row or column, shifts in [-1, M), C >= 1 (LDPC_HIP_EINVAL);
+ * LDPC_HIP_EUNSUPPORTED when the LDS image of a workgroup (the message carries the byte count) exceeds 160 KiB: for MS and LMS
+ * floor(64 / M) * (8 * nh * M + 24 * rh * M) bytes rounded up to 16, + 16; for TDMP floor(64 / M) * 8 * (nh * M + ne_max * M) + 16 as in
+ * ldpc_hip_open_codes_tdmp.  30 x 60 at M = 67 with 206 circulants (upstream's input12L.jsonx) takes 80 416 bytes for MS and LMS
+ * and 142 592 for TDMP.  ldpc_hip_open_codes and ldpc_hip_open_codes_tdmp keep their limits.
+ * Measured (profiles/r22_codeset_wide_time.txt; 4096 frames per code, wall time, median of 5).  30 x 60, M = 67, against one
+ * ldpc_hip_open context per code on the shape-unlimited tier, JIT off: MS, 50 iterations, 2.5 dB: 212.6 against 275.1 ms at 16 codes
+ * (1.29x), 3413 against 4416 ms at 256 (1.29x), 15.1 against 16.3 ms for one code; LMS, 50 iterations, 2.0 dB: 202.6 against 452.6 ms
+ * (2.23x), 3161 against 7121 ms (2.25x), 13.9 against 24.5 ms; TDMP, 15 iterations, 1.7 dB: 328.9 against 574.9 ms (1.75x), 5272 against
+ * 9243 ms (1.75x), 21.4 against 36.0 ms.  16 x 32, M = 64, against the register-resident set kernel of ldpc_hip_open_codes: the wide
+ * kernels are SLOWER, MS 48.2 against 15.8 ms at 16 codes and 759.8 against 235.9 ms at 256 (0.33x, 0.31x), LMS 54.6 against 17.1 ms
+ * and 825.0 against 240.9 ms (0.31x, 0.29x); TDMP is the same kernel (56.9 against 56.9 ms).  Use this entry point beyond the limits
+ * of the others, as the layers above do.  The channel LLRs in LDS instead of re-read: 1.88x slower at 30 x 60 (667 against 354 ms). */
+int ldpc_hip_open_codes_wide(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
 /* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
  * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
@@ -547,6 +570,11 @@ int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int 
  * shift, columns then rows ascending.  (ldpc_hip_codes_table_host(1 | 2, ...) stays LDPC_HIP_EINVAL.) */
 int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                                  long long capacity, long long *length);
+/* The table ldpc_hip_open_codes_wide uploads, with its checks and return codes (no GPU needed): for all three ids the record of
+ * MS_DEC, per code row_start[rh + 1] followed by its edges (block column << 16) | shift in row-major order.
+ * (ldpc_hip_codes_table_host keeps its limits.) */
+int ldpc_hip_codes_table_wide_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                   long long capacity, long long *length);
 /* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
  * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
  * maxiter >= 1.  Asynchronous on `stream`.  An IMS set (ldpc_hip_open_codes_ims) quantises into the context's workspace first: one

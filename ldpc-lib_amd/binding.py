@@ -186,7 +186,7 @@ def load_library():
     lib.ldpc_hip_gfq_channel_dev.argtypes = [vp, vp, vp, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_count_errors_gfq_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
-    for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, *_CODES_ROUTE.values()):
+    for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, _CODES_WIDE, *_CODES_ROUTE.values()):
         getattr(lib, open_codes).argtypes = [i32] * open_id + [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
         getattr(lib, codes_table_host).argtypes = [i32] * table_id + [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
@@ -670,20 +670,31 @@ _CODES_ROUTE = {
     DEC_TASP: ("ldpc_hip_open_codes_tdmp", False, "ldpc_hip_codes_table_host", True),
     DEC_LCHE: ("ldpc_hip_open_codes_lche", False, "ldpc_hip_codes_table_lche_host", False),
 }
+# DEC_MS, DEC_TASP and DEC_LMS beyond the block rows (and, for DEC_MS, block columns) that their register-resident set kernels hold
+_CODES_WIDE = ("ldpc_hip_open_codes_wide", True, "ldpc_hip_codes_table_wide_host", True)
 
 
-def codes_table(decoder_id, codes, M):
+def _codes_route(decoder_id, rh, nh):
+    """The entry points that serve a set of rh x nh codes: the decoder's own where the shape fits them, the wide ones for DEC_MS,
+    DEC_TASP and DEC_LMS exactly when rh > 16, or nh > 32 for DEC_MS."""
+    if decoder_id in (DEC_MS, DEC_TASP, DEC_LMS) and (rh > 16 or (decoder_id == DEC_MS and nh > 32)):
+        return _CODES_WIDE
+    return _CODES_ROUTE.get(decoder_id, _CODES_GENERIC)
+
+
+def codes_table(decoder_id, codes, M, wide=False):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
     DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order.  DEC_LCHE: the record of
     DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host); DEC_IMS: the same record under integer min-sum's limits
     (ldpc_hip_codes_table_ims_host); DEC_SP, DEC_ASP: the record of DEC_IASP under the limits of the flooding sum-product set kernels
-    (ldpc_hip_codes_table_sp_host)."""
+    (ldpc_hip_codes_table_sp_host).  DEC_MS, DEC_TASP and DEC_LMS beyond 16 block rows (DEC_MS: or 32 block columns): the record of
+    DEC_MS under the limits of ldpc_hip_open_codes_wide (ldpc_hip_codes_table_wide_host); wide=True asks that entry point on any shape."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
     n = C.c_longlong()
-    _, _, who, takes_id = _CODES_ROUTE.get(int(decoder_id), _CODES_GENERIC)
+    _, _, who, takes_id = _CODES_WIDE if wide else _codes_route(int(decoder_id), rh, nh)
     head = (int(decoder_id),) if takes_id else ()
     call = lambda off, tab, cap, length: getattr(lib, who)(*head, rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
     _check(lib, call(None, None, 0, C.byref(n)), who)
@@ -696,15 +707,17 @@ def codes_table(decoder_id, codes, M):
 class LdpcHipCodes:
     """C candidate codes of one shape (codes int16 [C, rh, nh], lifting M) on one GPU, decoded C x B frames per launch (ldpc_hip_open_codes
     or the decoder's own open entry point, _CODES_ROUTE): what a code search scores.
-    decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP, DEC_LCHE, DEC_IMS, DEC_SP or DEC_ASP; bit-identical to LdpcHip on each matrix."""
+    decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP, DEC_LCHE, DEC_IMS, DEC_SP or DEC_ASP; bit-identical to LdpcHip on each matrix.
+    Block rows and columns are not limited: DEC_MS, DEC_TASP and DEC_LMS keep their register-resident kernels up to 16 block rows (DEC_MS:
+    and 32 block columns) and open through ldpc_hip_open_codes_wide beyond (records in LDS); wide=True takes that route on any shape."""
 
-    def __init__(self, decoder_id, codes, M, device=0):
+    def __init__(self, decoder_id, codes, M, device=0, wide=False):
         self.lib = load_library()
         codes = _code_stack(codes)
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        who, takes_id, _, _ = _CODES_ROUTE.get(self.decoder_id, _CODES_GENERIC)
+        who, takes_id, _, _ = _CODES_WIDE if wide else _codes_route(self.decoder_id, self.rh, self.nh)
         head = (self.decoder_id,) if takes_id else ()
         rc = getattr(self.lib, who)(*head, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         _check(self.lib, rc, who)

@@ -71,7 +71,11 @@ bool set_takes(const SetGroup &g, int rows, int columns) {
         for (int i = 0; i < rows * columns; ++i) hd[(size_t)q * rows * columns + i] = (int16_t)g.codes[(size_t)q].v[(size_t)i];
     long long len = 0;
     switch (dec) {
-    case LDPC_HIP_MS_DEC: case LDPC_HIP_LMS_DEC: case LDPC_HIP_TASP_DEC: case LDPC_HIP_IASP_DEC:
+    case LDPC_HIP_MS_DEC: case LDPC_HIP_LMS_DEC: case LDPC_HIP_TASP_DEC:
+        if (rows > 16 || (dec == LDPC_HIP_MS_DEC && columns > 32))   // the route open_code_set takes for these shapes
+            return ldpc_hip_codes_table_wide_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+        return ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+    case LDPC_HIP_IASP_DEC:
         return ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
     case LDPC_HIP_LCHE_DEC: return ldpc_hip_codes_table_lche_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
     case LDPC_HIP_IMS_DEC: return ldpc_hip_codes_table_ims_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;

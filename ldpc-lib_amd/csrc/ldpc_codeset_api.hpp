@@ -31,6 +31,7 @@ struct ldpc_codeset_state : codeset_common {
     double *w_coef = nullptr;          // [w_q_frames]
     int16_t *w_q = nullptr;            // [w_q_frames][N]
     long long w_q_frames = 0;
+    int route = 0;                     // the record of codeset_kinds[] the set was opened with: (decoder_id, route)
 };
 
 void codeset_common_release(codeset_common &s) {
@@ -52,7 +53,8 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
 namespace {
 
 // Dynamic LDS of the code-set kernels for F frames per workgroup: the image that the kernel's header describes (ldpc_codeset.hpp,
-// ldpc_codeset_sp.hpp) + 16 for the vote flags.  MS / LMS: the a-posteriori values alone; TDMP: the per-edge state Z[ne_max][M] next to them.
+// ldpc_codeset_sp.hpp, ldpc_codeset_wide.hpp) + 16 for the vote flags.  MS / LMS: the a-posteriori values alone, on the wide route the
+// per-check records next to them; TDMP: the per-edge state Z[ne_max][M] next to them.
 size_t codeset_lds_apost(int F, int, int nh, int M, int) { return sizeof(double) * ((size_t)nh * M) * (size_t)F + 16; }
 size_t codeset_lds_tdmp(int F, int, int nh, int M, int ne_max) { return sizeof(double) * ((size_t)nh * M + (size_t)ne_max * M) * (size_t)F + 16; }
 size_t codeset_lds_iasp(int F, int, int nh, int M, int ne_max) { return ldpc::iasp_codes_words_bytes(F, M, nh * M, ne_max) + 16; }
@@ -60,8 +62,11 @@ size_t codeset_lds_lche(int F, int, int nh, int M, int ne_max) { return ldpc::lc
 size_t codeset_lds_ims(int F, int rh, int nh, int M, int) { return ldpc::ims_codes_image_bytes(F, nh * M, rh * M) + 16; }
 size_t codeset_lds_sp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(false, F, nh * M, rh * M, M, ne_max) + 16; }
 size_t codeset_lds_asp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(true, F, nh * M, rh * M, M, ne_max) + 16; }
+size_t codeset_lds_wide(int F, int rh, int nh, int M, int) { return ldpc::wide_codes_image_bytes(F, nh * M, rh * M) + 16; }
 
-enum codeset_lds_text { LDS_NONE, LDS_LENGTH, LDS_IMS, LDS_IASP, LDS_TDMP, LDS_LCHE, LDS_FLOOD };   // the refusals of codeset_lds_refusal
+enum codeset_lds_text { LDS_NONE, LDS_LENGTH, LDS_IMS, LDS_IASP, LDS_TDMP, LDS_LCHE, LDS_FLOOD, LDS_WIDE };   // the refusals of codeset_lds_refusal
+
+enum : int { ROUTE_RESIDENT = 0, ROUTE_WIDE = 1 };   // ldpc_hip_open_codes and its kin; ldpc_hip_open_codes_wide
 
 enum : unsigned {
     CS_COLS = 1,     // the record goes on with cw2, col_start and col_edges, and a column entry names its edge in 16 bits
@@ -81,6 +86,7 @@ struct codeset_kind {
     unsigned is;                       // CS_*
     size_t (*lds)(int F, int rh, int nh, int M, int ne_max);
     codeset_lds_text early, late;      // the image is checked before the table is built (with ne_max = 0) and once ne_max is known
+    int route = ROUTE_RESIDENT;        // ROUTE_WIDE: the same decoder with its per-check records in LDS, or launched without a block-row limit
 };
 
 const codeset_kind codeset_kinds[] = {
@@ -100,14 +106,25 @@ const codeset_kind codeset_kinds[] = {
      kRHM, 0, kRWM, nullptr, 0, codeset_lds_apost, LDS_LENGTH, LDS_NONE},
     {LDPC_HIP_LCHE_DEC, "lche_layered_codes_kernel", (const void *)ldpc::lche_layered_codes_kernel<kRWM, false>, (const void *)ldpc::lche_layered_codes_kernel<kRWM, true>,
      0, 0, kRWM, nullptr, 0, codeset_lds_lche, LDS_NONE, LDS_LCHE},
+    // ldpc_hip_open_codes_wide: any number of block rows and columns.  TDMP's kernel walks the block rows in a run-time loop and keeps
+    // nothing of a row: the same instances, without the limit
+    {LDPC_HIP_MS_DEC, "ms_flood_wide_codes_kernel", (const void *)ldpc::ms_flood_wide_codes_kernel<false>, (const void *)ldpc::ms_flood_wide_codes_kernel<true>,
+     0, 0, kRWM, nullptr, 0, codeset_lds_wide, LDS_WIDE, LDS_NONE, ROUTE_WIDE},
+    {LDPC_HIP_TASP_DEC, "tasp_layered_codes_kernel", (const void *)ldpc::tasp_layered_codes_kernel<kRWM, false>, (const void *)ldpc::tasp_layered_codes_kernel<kRWM, true>,
+     0, 0, kRWM, "TDMP sum-product", 0, codeset_lds_tdmp, LDS_NONE, LDS_TDMP, ROUTE_WIDE},
+    {LDPC_HIP_LMS_DEC, "lms_layered_wide_codes_kernel", (const void *)ldpc::lms_layered_wide_codes_kernel<false>, (const void *)ldpc::lms_layered_wide_codes_kernel<true>,
+     0, 0, kRWM, nullptr, 0, codeset_lds_wide, LDS_WIDE, LDS_NONE, ROUTE_WIDE},
 };
 
 // The entry points come here with an id that their route serves
-const codeset_kind *codeset_find(int decoder_id) {
+const codeset_kind *codeset_find(int decoder_id, int route = ROUTE_RESIDENT) {
     for (const codeset_kind &k : codeset_kinds)
-        if (k.id == decoder_id) return &k;
+        if (k.id == decoder_id && k.route == route) return &k;
     return nullptr;
 }
+
+// the record a set context was opened with
+const codeset_kind &codeset_kind_of(const ldpc_hip_ctx *c) { return *codeset_find(c->decoder_id, c->codes->route); }
 
 // An image beyond 160 KiB, in the words of its kernel
 int codeset_lds_refusal(const codeset_kind &k, codeset_lds_text text, const char *who, int F, int rh, int nh, int M, int ne_max) {
@@ -118,6 +135,7 @@ int codeset_lds_refusal(const codeset_kind &k, codeset_lds_text text, const char
     case LDS_IMS: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (4 x %d variables + 8 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, rh * M, bytes);
     case LDS_IASP: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d circulants x %d checks + 2 x %d variables) halfwords need an LDS image of %zu bytes; the limit is 160 KiB", who, F, ne_max, M, N, bytes);
     case LDS_TDMP: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori values + %d circulants x %d checks) need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, ne_max, M, bytes);
+    case LDS_WIDE: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (8 x %d variables + 24 x %d checks) bytes, rounded up to 16, + 16 need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, rh * M, bytes);
     case LDS_LCHE: return fail(LDPC_HIP_EUNSUPPORTED, "%s: %d frame(s) per wave x (%d a-posteriori LLRs + %d circulants x %d checks) and the tables of logexp need an LDS image of %zu bytes; the limit is 160 KiB", who, F, N, ne_max, M, bytes);
     default: return fail(LDPC_HIP_EUNSUPPORTED, "%s: one frame's image, 8 x (%d circulants x %d + %d variables%s) + 4 x %d bytes, rounded up to 16, + 16 is %zu bytes; the limit is 160 KiB", who, ne_max, M, N, k.is & CS_CHECKS ? " + the checks" : "", (N + 31) / 32, bytes);
     }
@@ -239,10 +257,16 @@ int codeset_upload(codeset_common &s, int C, int ne_max, std::vector<int32_t> &o
 }
 
 int codeset_table_host(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
-                       long long capacity, long long *length) {
+                       long long capacity, long long *length, int route = ROUTE_RESIDENT) {
     std::vector<int32_t> off, tab;
-    if (int rc = codeset_build(who, *codeset_find(decoder_id), rh, nh, M, hd, C, off, tab)) return rc;
+    if (int rc = codeset_build(who, *codeset_find(decoder_id, route), rh, nh, M, hd, C, off, tab)) return rc;
     return codeset_table_out(who, off, tab, offsets, table, capacity, length);
+}
+
+// what the two wide entry points say to any other id
+int codeset_wide_id(const char *who, int decoder_id) {
+    if (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_TASP_DEC || decoder_id == LDPC_HIP_LMS_DEC) return 0;
+    return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; MS_DEC (3), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
 }
 
 }  // namespace
@@ -266,6 +290,12 @@ int ldpc_hip_codes_table_ims_host(int rh, int nh, int M, const int16_t *hd, int 
     return codeset_table_host("ldpc_hip_codes_table_ims_host", LDPC_HIP_IMS_DEC, rh, nh, M, hd, C, offsets, table, capacity, length);
 }
 
+int ldpc_hip_codes_table_wide_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                   long long capacity, long long *length) {
+    if (int rc = codeset_wide_id("ldpc_hip_codes_table_wide_host", decoder_id)) return rc;
+    return codeset_table_host("ldpc_hip_codes_table_wide_host", decoder_id, rh, nh, M, hd, C, offsets, table, capacity, length, ROUTE_WIDE);
+}
+
 int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                                  long long capacity, long long *length) {
     if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
@@ -277,18 +307,20 @@ int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const in
 
 namespace {
 
-int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out,
+                 int route = ROUTE_RESIDENT) {
     if (out) *out = nullptr;
     if (!out) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     std::vector<int32_t> off, tab;
     int ne_max = 0;
-    const codeset_kind &kind = *codeset_find(decoder_id);
+    const codeset_kind &kind = *codeset_find(decoder_id, route);
     if (int rc = codeset_build(who, kind, rh, nh, M, hd, C, off, tab, &ne_max)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LDPC_HIP_EINVAL, "%s: device %d of %d", who, device, ndev);
     std::unique_ptr<ldpc_hip_ctx, void (*)(ldpc_hip_ctx *)> c(new ldpc_hip_ctx(), ldpc_hip_close);
     ldpc_codeset_state *s = c->codes = new ldpc_codeset_state();
+    s->route = route;
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
     c->ne = kind.is & CS_COLS ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
@@ -352,7 +384,7 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
     a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
     a.alpha = alpha; a.ne_max = s->ne_max;
-    const codeset_kind &kind = *codeset_find(c->decoder_id);
+    const codeset_kind &kind = codeset_kind_of(c);
     const void *k = c->multiwave ? kind.multiwave : kind.wave;
     if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
     ProfTimer timer;
@@ -380,7 +412,7 @@ long long codeset_piece(size_t bytes_per_frame, const char *cap_env, long long B
 
 long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
     size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
-    if (codeset_find(c->decoder_id)->is & CS_QUANT) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
+    if (codeset_kind_of(c).is & CS_QUANT) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
     return codeset_piece(per_frame, "LDPC_HIP_CODES_PIECE", B);
 }
 
@@ -539,6 +571,12 @@ int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t 
     if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes_sp: decoder id %d; SP_DEC (1) or ASP_DEC (2)", decoder_id);
     return codeset_open("ldpc_hip_open_codes_sp", decoder_id, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_wide(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (int rc = codeset_wide_id("ldpc_hip_open_codes_wide", decoder_id)) return rc;
+    return codeset_open("ldpc_hip_open_codes_wide", decoder_id, rh, nh, M, hd, C, device, out, ROUTE_WIDE);
 }
 
 int ldpc_hip_decode_codes_dev(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,

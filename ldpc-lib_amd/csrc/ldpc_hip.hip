@@ -23,6 +23,7 @@
 #include "ldpc_jit.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_codeset.hpp"
+#include "ldpc_codeset_wide.hpp"
 #include "ldpc_codeset_sp.hpp"
 #include "ldpc_global.hpp"
 #include "ldpc_ms_fast.hpp"
