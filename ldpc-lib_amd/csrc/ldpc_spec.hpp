@@ -491,11 +491,22 @@ constexpr int ms_m64_keep_budget() {
     return regs > cut ? regs - cut : 0;
 }
 
-template <class C>
+// Which carried rows form their magnitudes from prefix and suffix minima (see `keep` in ms_m64_body): rows [0, KP), the rows
+// [KP, KR) select between min1 and min2 by value equality as round 20 did.  Such a row holds its RW v2c values and RW - 1 prefix
+// minima at once, about 2 RW - 2 registers more at its peak than the equality form; STATE3 has no channel value in flight, and the
+// peak of the body stays in STATE2.  KP = KR for every code: checked by cross-compiling the same instances as the budget rule
+// (none spills a VGPR or uses scratch, profiles/r23_flagship_isa_histogram.txt).  KPCAP lowers it for tools/ab_flagship.hip.
+template <int KPCAP>
+constexpr int ms_m64_prefix_rows(int kr) { return KPCAP < kr ? (KPCAP > 0 ? KPCAP : 0) : kr; }
+
+template <class C, int KPCAP = 1 << 30>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
     constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) carry their decoded c2v values, see `keep`
+    // rows [0, KP) of them by prefix / suffix minima.  A type, not a second constant: STATE3's closure would capture the constant, and
+    // with that one pointer more a 30 x 60 protograph that carries no row spilled 240 VGPRs (profiles/r23_flagship_isa_histogram.txt).
+    typedef IC<ms_m64_prefix_rows<KPCAP>(KR)> KP;
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -580,17 +591,25 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         // made of in registers.  Block rows [0, KR) therefore form cv there, once, and CARRY it in keep[j][s] to the next
         // STATE3: STATE1 scatters keep as it is, x = keep * |alpha| is ONE v_mul_f64, and the row has no record.  That takes out
         // both decodes of the row (compare, two selects, bfi, add per edge and state) and the two products m1 * alpha, m2 * alpha.
-        // The row does not even track the slot of its smallest magnitude: after its min loop slot s takes nm2 where
-        // |tt[s]| == nm1 and nm1 elsewhere, one v_cmp_eq_f64 in front of the two selects instead of v_cmp_lt_f64 + a select of
-        // npos per slot inside the loop.  The bits are those of the record's decode:
-        //   - the magnitude.  (nm1, nm2) are the two smallest of the multiset {K, K, v_0 .. v_RW-1}, K = kMaxVal, v_s = |tt[s]|
-        //     (fmin / fmax drop NaNs; fabs leaves no -0.0, so equal values are equal bits).  (v_s == nm1 ? nm2 : nm1) and
-        //     (s == npos ? nm2 : nm1) can differ in two ways only.  v_s == nm1 and s != npos: the multiset holds nm1 twice, so
-        //     nm2 == nm1 bit for bit and the choice does not matter.  s == npos and v_s != nm1: a slot whose c1 = (v < nm1) held
-        //     last would be npos and equal nm1, so no c1 ever held, npos is its start value 0 and v_0 is a NaN or above K:
-        //     nm1 == nm2 == K.  NaN, +-inf, v >= K, ties of any order and denormals all fall under these cases
-        //     (tests/test_ms_m64_eqslot_cpu.py is the argument as executable text);
-        //   - the sign.  W is the word the record would hold in meta's upper bits, shifted by the same twice() per slot;
+        // The row computes neither min1 and min2 nor the slot of the smallest magnitude.  The magnitude on slot s is
+        // min(K, v_s' over the OTHER slots s'), K = kMaxVal, v_s = |tt[s]|, and exclusive prefix and suffix minima give just that:
+        // ascending s leaves pf[s] = min(K, v_0 .. v_s), descending s meets pf[s - 1] with suf = min(K, v_s+1 .. v_RW-1), about
+        // 3 RW - 4 v_min_f64 per row where min / max / min per slot, v_cmp_eq_f64 and two selects per slot stood (rows [KP, KR) keep
+        // that equality form; KP == KR in every shipped instance, ms_m64_prefix_rows).  The bits are those of the record's decode:
+        //   - the magnitude.  (nm1, nm2) of the record are the two smallest of the multiset {K, K, v_0 .. v_RW-1}.  The minimum of
+        //     that multiset with ONE occurrence of v_s taken out is nm2 where s is an argmin (at npos, and at every slot tied
+        //     with it, where nm2 == nm1 bit for bit) and nm1 elsewhere: what (s == npos ? nm2 : nm1) selects.  With one K left in
+        //     the multiset the minimum is min(K, v over the other slots), the exclusive minimum formed here; a second K would
+        //     change nothing.  Ties of any order, v >= K (the clamp wins), +-inf and denormals fall under it; fabs leaves no -0.0,
+        //     so equal values are equal bits and the order in which v_min_f64 meets them does not matter.  A row of width 1 takes K.
+        //     A NaN v2c is dropped by every fmin, which is upstream's rule (both of its `<` are false, nothing moves: :4729-4743).
+        //     The min / max chain of a row with a record turns a NaN into a copy of the running min1 instead and leaves upstream
+        //     from width 2 on; a NaN can only come from a NaN channel LLR, which no caller supplies, so it is outside the contract
+        //     on both tiers (tests/test_ms_m64_prefix_cpu.py is the argument as executable text, NaN rows included;
+        //     tests/test_ms_m64_eqslot_cpu.py that of the equality form);
+        //   - the sign: the v2c's own sign xor the row parity.  A row below KP folds hi32(tt) of its slots into nS with one
+        //     full-rate xor each, which leaves the parity on bit 31, and slot s takes bit 31 of hi32(tt_[s]) ^ nS: the bit the
+        //     record's word holds for the slot (a row past KP builds that word W, slot s on bit 31 - s, shifted by twice());
         //   - x = keep * |alpha|.  The second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's
         //     sign); nm1 and nm2 are finite and in [0, 32767]; IEEE multiplication is sign-symmetric, so (+-m) * |alpha| and
         //     +-(m * |alpha|) are the same bits, zeros and denormals included; -ffp-contract=off keeps this product and the
@@ -729,11 +748,38 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 }
             };
             if constexpr (j < KR) {
-                static_for<0, RW>([&](auto S) {
-                    constexpr int s = decltype(S)::value;
-                    sy ^= hi32(r[s]);
-                    step(S, keep[j][s] * alpha_mag);     // the carried value: no decode, see `keep`
-                });
+                if constexpr (j < KP::value) {
+                    // A carried row below KP: no min1 / min2, no `step`.  Ascending s leaves the prefix minima pf[s] = min(K, v_0 .. v_s)
+                    // (pf[RW - 1] is never needed) and the row parity on bit 31 of nS; descending s then meets them with the suffix
+                    // minima: mag[s] = min(pf[s - 1], suf), the minimum over the other slots and K, see `keep`.
+                    double pf[RW > 1 ? RW - 1 : 1];
+                    static_for<0, RW>([&](auto S) {
+                        constexpr int s = decltype(S)::value;
+                        sy ^= hi32(r[s]);
+                        const double tt = r[s] - keep[j][s] * alpha_mag;   // v2c; the carried value: no decode, see `keep`
+                        nS ^= hi32(tt);
+                        tt_[s] = tt;
+                        if constexpr (s == 0 && RW > 1) pf[0] = fmin(fabs(tt), kMaxVal);
+                        else if constexpr (s > 0 && s < RW - 1) pf[s] = fmin(fabs(tt), pf[s - 1]);
+                    });
+                    double suf = kMaxVal;                // min(K, v_s+1 .. v_RW-1)
+                    static_for<0, RW>([&](auto S) {
+                        constexpr int s = RW - 1 - decltype(S)::value;
+                        double mag;
+                        if constexpr (RW == 1) mag = kMaxVal;
+                        else if constexpr (s == RW - 1) mag = pf[RW - 2];
+                        else if constexpr (s == 0) mag = suf;
+                        else mag = fmin(pf[s - 1], suf);
+                        if constexpr (s > 0) suf = fmin(fabs(tt_[s]), suf);
+                        keep[j][s] = signed_mag(mag, hi32(tt_[s]) ^ nS);   // own v2c sign xor row parity, on bit 31
+                    });
+                } else {
+                    static_for<0, RW>([&](auto S) {
+                        constexpr int s = decltype(S)::value;
+                        sy ^= hi32(r[s]);
+                        step(S, keep[j][s] * alpha_mag);     // the carried value: no decode, see `keep`
+                    });
+                }
             } else {
                 const u32 pos = mt & 0xffu;
                 u32 Wt = mt;   // the record keeps the sign word ready: slot s on bit 31 - s, row parity folded in
@@ -760,12 +806,14 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             failw |= sy;
             asm volatile("" : "+v"(failw));
             if constexpr (j < KR) {
-                u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);   // slot s on bit 31 - s, row parity folded in
-                static_for<0, RW>([&](auto S) {
-                    constexpr int s = decltype(S)::value;
-                    keep[j][s] = signed_mag(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
-                    W = twice(W);
-                });
+                if constexpr (j >= KP::value) {             // a row below KP has formed its new c2v values above
+                    u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);   // slot s on bit 31 - s, row parity folded in
+                    static_for<0, RW>([&](auto S) {
+                        constexpr int s = decltype(S)::value;
+                        keep[j][s] = signed_mag(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
+                        W = twice(W);
+                    });
+                }
             } else {
                 m1[j] = nm1; m2[j] = nm2; meta[j] = ((nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW)) | npos;
             }

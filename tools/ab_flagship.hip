@@ -2,7 +2,10 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r20_flagship_variants.txt (round 19's variants -- local block columns, plain 64-bit image reads -- are in
+// Results: profiles/r23_flagship_variants.txt: the carried rows [0, KP) of ms_m64_body form their magnitudes from prefix and suffix
+// minima, KP = 0 (round 20's body: every carried row selects between min1 and min2 by value equality), 9, 11 and 13 = all carried
+// rows, through the KPCAP parameter of the header's body.  Round 20's variants -- carried rows, the min1 slot by equality -- are in
+// profiles/r20_flagship_variants.txt and still switches of ms_m64_body_y here (round 19's variants -- local block columns, plain 64-bit image reads -- are in
 // profiles/r19_flagship_variants.txt and still switches of ms_m64_body_y here; round 18's variants -- the 32-bit syndrome word, carried c2v values, scalar wrap masks -- are in
 // profiles/r18_flagship_variants.txt and still switches of ms_m64_body_y here; round 13's variants -- where the channel LLRs are loaded, how many edges are kept from
 // STATE1 to STATE3 -- are in profiles/r13_flagship_variants.txt, round 6's in profiles/r06_flagship_variants.txt, round 2's in
@@ -683,6 +686,13 @@ VARIANT(k_le61,  true, true, 61, false, true, false, true)
 VARIANT(k_le68,  true, true, 68, false, true, false, true)
 VARIANT(k_lei61, true, true, 61, false, true, false, true, true)
 VARIANT(k_lei68, true, true, 68, false, true, false, true, true)
+// round 23: ms_m64_body of the header with its prefix / suffix rows capped at KPCAP block rows; 0 is the body round 20 shipped
+#define PREFIX(name, kpcap) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, kpcap>(a); }
+PREFIX(k_p0, 0)
+PREFIX(k_p9, 9)
+PREFIX(k_p11, 11)
+PREFIX(k_p13, 13)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 
 struct Variant { const void *kern; const char *name; size_t lds; };
@@ -702,6 +712,10 @@ int main(int argc, char **argv) {
         {(const void *)k_le68, "carried, equality, rows 0-12 (68 edges)", L},
         {(const void *)k_lei61, "carried, equality, 61 edges, record decode interleaved", L},
         {(const void *)k_lei68, "carried, equality, 68 edges, record decode interleaved", L},
+        {(const void *)k_p0, "round 20's body: 13 carried rows, none by prefix / suffix minima", L},
+        {(const void *)k_p9, "prefix / suffix minima on rows 0-8, equality on rows 9-12", L},
+        {(const void *)k_p11, "prefix / suffix minima on rows 0-10, equality on rows 11-12", L},
+        {(const void *)k_p13, "prefix / suffix minima on rows 0-12 (all carried rows)", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
     };
     constexpr int NV = sizeof var / sizeof var[0];
