@@ -354,9 +354,7 @@ int codeset_ims_quantise(ldpc_hip_ctx *c, const double *d_llr, long long frames,
         s->w_q_frames = frames;
     }
     if ((frames + 63) / 64 > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %lld received words are more than one launch takes", frames);
-    ldpc::ImsCoefArgs ca{d_llr, s->w_coef, frames, c->N};
-    hipLaunchKernelGGL(ldpc::ims_coef_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, stream, ca);
-    HIP_TRY(hipGetLastError());
+    if (int rc = ims_coef_launch(d_llr, s->w_coef, frames, c->N, stream)) return rc;
     ldpc::ImsQuantArgs qa{d_llr, s->w_coef, s->w_q, frames * (long long)c->N, c->N, c->ims_thr, (1 << (c->ims_qbits - 1)) - 1};
     long long blocks = (qa.total + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;

@@ -1,6 +1,9 @@
 // ldpc_hip.hip -- C-ABI (include/ldpc_hip.h) over the gfx950 kernels.  Host side: context, code tables,
 // launch geometry, workspaces, HIP-event timing.  No CPU decode path exists in this library: every entry
 // point either runs the HIP kernels or fails with a message.
+// A binary decoder is, on the host, one record of decoder_kinds[] (its kernels and names on the shape-unlimited and the table-driven
+// tier, what the harness around it needs to know), one case of plan_spec (which code-specialised body takes which shape) and its
+// kAot[] instances.  ldpc_hip_open picks the tier from these, ldpc_hip_decode_dev calls launch_spec, launch_generic or launch_global.
 #include "../../include/ldpc_hip.h"
 #include "../../include/ldpc/interleaver.h"
 #include "../../include/ldpc/encoder.h"
@@ -70,6 +73,7 @@ namespace {
 struct CodeTables {
     int rh = 0, nh = 0, M = 0, ne = 0, max_rw = 0, min_rw = 1 << 30, max_cw = 0;
     bool all_cols_used = true;
+    bool all_cw2 = true;   // every block column holds exactly two circulants: decoders 2 and 5 have their own branch for such codes
     std::vector<int32_t> row_start, col_start;
     std::vector<uint32_t> edges;      // (block column << 16) | shift
     std::vector<uint32_t> col_edges;  // (block row << 16) | shift, column-major
@@ -103,6 +107,7 @@ struct CodeTables {
             const int cw = (int)col_edges.size() - col_start[k];
             max_cw = cw > max_cw ? cw : max_cw;
             all_cols_used = all_cols_used && cw > 0;
+            all_cw2 = all_cw2 && cw == 2;
         }
         col_start[nh] = (int32_t)col_edges.size();
     }
@@ -167,6 +172,52 @@ __global__ void __launch_bounds__(256) iasp_channel_prior_kernel(double *x, long
         x[i] = ldpc_spec::iasp::prior(x[i]);
 }
 
+namespace {
+
+// What a binary decoder is on the host, beside its case in plan_spec and its kAot[] instances: one record per built id
+struct decoder_kind {
+    int id;
+    // shape-unlimited tier (ldpc_global.hpp)
+    void (*global)(ldpc::GlobArgs);
+    const char *global_name;
+    int glob_edge_arrays;     // per-edge arrays of its workspace (glob_ws_bytes).  IASP: u16 state + i16 products in the one array; LCHE: Z
+    bool global_min_rw2;      // it needs every row weight >= 2
+    // table-driven tier: the instance for M <= 64 and the one for M > 64; null where no such kernel exists.  sp_flood_kernel has a geometry
+    // of its own (ldpc_hip_open)
+    const void *wave, *multiwave;
+    const char *generic_name; // "<multiwave>" appended when M > 64
+    bool needs_nh;            // it keeps the channel LLRs of kNHM block columns in VGPRs
+    bool queue;               // the code-specialised body takes frames from the persistent queue (SpecArgs::queue)
+    // the harness around the decoder
+    double punctured_llr;     // what the channel writes at a punctured position (bp_simulation.cpp:700 (sic), out_type :451-466)
+    bool soft_is_input;       // soft[] is the working array upstream: decode_host leaves the soft values in the input array (decoders.cpp:1950,2124)
+    void (*prior)(double *, long long);   // or this kernel's transform of the channel LLRs; null: the input array is left alone
+    bool ignores_decision;    // the result is always hard (decoders.cpp:2737-2738, :3005-3006)
+};
+
+#define LDPC_PAIR(k, ...) (const void *)ldpc::k<__VA_ARGS__, false>, (const void *)ldpc::k<__VA_ARGS__, true>, #k
+const decoder_kind decoder_kinds[] = {
+    {LDPC_HIP_BP_DEC, ldpc::bp_global_kernel, "bp_global_kernel", 1, false, nullptr, nullptr, nullptr, false, false, 0.5, true, nullptr, false},
+    {LDPC_HIP_SP_DEC, ldpc::sp_global_kernel, "sp_global_kernel", 1, false, (const void *)ldpc::sp_flood_kernel, (const void *)ldpc::sp_flood_kernel,
+     "sp_flood_kernel", false, false, 0.0, true, nullptr, false},
+    {LDPC_HIP_ASP_DEC, ldpc::asp_global_kernel, "asp_global_kernel", 3, true, nullptr, nullptr, nullptr, false, false, 0.0, false, channel_prior_kernel, false},
+    {LDPC_HIP_MS_DEC, ldpc::ms_global_kernel, "ms_global_kernel", 0, false, LDPC_PAIR(ms_flood_kernel, kRHM, kNHM), true, true, 0.5, false, nullptr, false},
+    {LDPC_HIP_IMS_DEC, ldpc::ims_global_kernel, "ims_global_kernel", 0, false, LDPC_PAIR(ims_flood_kernel, kRHM, kNHM), true, false, 0.5, false, nullptr, false},
+    {LDPC_HIP_IASP_DEC, ldpc::iasp_global_kernel, "iasp_global_kernel", 1, true, nullptr, nullptr, nullptr, false, false, 0.0, false, iasp_channel_prior_kernel, false},
+    {LDPC_HIP_TASP_DEC, ldpc::tasp_global_kernel, "tasp_global_kernel", 4, true, nullptr, nullptr, nullptr, false, false, 0.0, false, channel_prior_kernel, true},
+    {LDPC_HIP_LMS_DEC, ldpc::lms_global_kernel, "lms_global_kernel", 1, false, LDPC_PAIR(lms_layered_kernel, kRHM, kRWM), false, true, 0.5, false, nullptr, false},
+    {LDPC_HIP_LCHE_DEC, ldpc::lche_global_kernel, "lche_global_kernel", 1, false, nullptr, nullptr, nullptr, false, false, 0.0, false, nullptr, true},
+};
+#undef LDPC_PAIR
+
+const decoder_kind *decoder_find(int id) {
+    for (const decoder_kind &k : decoder_kinds)
+        if (k.id == id) return &k;
+    return nullptr;
+}
+
+}  // namespace
+
 struct ldpc_gfq_state;                       // FHT_DEC (GF(q)) contexts: ldpc_gfq_api.hpp
 void ldpc_gfq_release(ldpc_gfq_state *g);
 struct ldpc_codeset_state;                   // code-set contexts (C codes of one shape): ldpc_codeset_api.hpp
@@ -189,7 +240,7 @@ struct ldpc_hip_ctx {
     double ims_thr = 1.4;  // MS_THR, MS_QBITS, MS_DBITS (decoders.h:46-48), see ldpc_hip_set_ims_params
     int ims_qbits = 6, ims_dbits = 8;
     // shape-unlimited tier (ldpc_global.hpp): message state in a workspace in global memory
-    bool asp_cw2 = false;    // ASP_DEC / IASP_DEC on a code whose block columns all hold two circulants: upstream's own branch, on this tier only
+    bool asp_cw2 = false;    // the block columns all hold two circulants: ASP_DEC / IASP_DEC take upstream's own branch, on this tier only
     bool global_tier = false;
     char *d_glob_ws = nullptr;
     size_t glob_stride = 0;
@@ -355,6 +406,14 @@ struct SpecPlan { const char *body = nullptr; int threads = 0; size_t lds = 0; b
 
 constexpr size_t kLdsBudget = 160 * 1024 - 64;   // the bodies' dynamic LDS image; the rest is the frame queue's ticket word
 
+// tasp_body and lche_body, registers of a lane: its half of every row's Z (2 each), the packed LDS addresses, ~85 temporaries (ldpc_jit.hpp
+// picks one or two waves per SIMD from the same estimate); rounds 1-2 (the whole row in one lane) stopped at 144 circulants
+int tasp_lane_regs(const CodeTables &t) {
+    int regs = 85;
+    for (int j = 0; j < t.rh; ++j) { const int L = (t.row_start[j + 1] - t.row_start[j] + 1) / 2; regs += 2 * L + (L + 1) / 2; }
+    return regs;
+}
+
 SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
     SpecPlan p;
     const int M = t.M, N = t.nh * t.M, W = (M + 63) / 64;
@@ -400,17 +459,13 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
     case LDPC_HIP_ASP_DEC: {
         p.required = true;  // code-specialised instances only; upstream's all-columns-of-weight-2 branch (decoders.cpp:2431-2480) runs on the shape-unlimited tier
         const size_t lds = sizeof(double) * (size_t)t.ne * M + (((size_t)N + 15) & ~(size_t)15) + 16;
-        bool all_cw2 = true;
-        for (int k = 0; k < t.nh; ++k) all_cw2 = all_cw2 && (t.col_start[k + 1] - t.col_start[k] == 2);
-        if (t.min_rw >= 2 && !all_cw2 && lds <= kLdsBudget) { p.body = "asp_body"; p.threads = 512; p.lds = lds; }
+        if (t.min_rw >= 2 && !t.all_cw2 && lds <= kLdsBudget) { p.body = "asp_body"; p.threads = 512; p.lds = lds; }
         break;
     }
     case LDPC_HIP_IASP_DEC: {
         p.required = true;  // code-specialised instances only; the all-columns-of-weight-2 branch (decoders.cpp:3915-3977) runs on the shape-unlimited tier
         const size_t lds = (((size_t)2 * t.ne * M + 15) & ~(size_t)15) + (((size_t)N + 15) & ~(size_t)15) + 16;   // u16 state, hard bits, vote
-        bool all_cw2 = true;
-        for (int k = 0; k < t.nh; ++k) all_cw2 = all_cw2 && (t.col_start[k + 1] - t.col_start[k] == 2);
-        if (t.min_rw >= 2 && !all_cw2 && lds <= kLdsBudget) { p.body = "iasp_body"; p.threads = 512; p.lds = lds; }
+        if (t.min_rw >= 2 && !t.all_cw2 && lds <= kLdsBudget) { p.body = "iasp_body"; p.threads = 512; p.lds = lds; }
         break;
     }
     case LDPC_HIP_TASP_DEC:
@@ -418,11 +473,7 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
         {   // 2 M threads per frame; LDS: a-posteriori probabilities + one spare slot per thread + flag words
             const int th = 64 * ((2 * M + 63) / 64);
             const size_t lds = sizeof(double) * ((size_t)N + (size_t)th) + 16;
-            // registers of a lane: its half of every row's Z (2 each), the packed LDS addresses, ~85 temporaries (ldpc_jit.hpp picks one
-            // or two waves per SIMD from the same estimate); rounds 1-2 (the whole row in one lane) stopped at 144 circulants
-            int regs = 85;
-            for (int j = 0; j < t.rh; ++j) { const int L = (t.row_start[j + 1] - t.row_start[j] + 1) / 2; regs += 2 * L + (L + 1) / 2; }
-            if (M <= 256 && t.min_rw >= 2 && t.rh <= 64 && regs <= 480 && lds <= kLdsBudget) { p.body = "tasp_body"; p.threads = th; p.lds = lds; }
+            if (M <= 256 && t.min_rw >= 2 && t.rh <= 64 && tasp_lane_regs(t) <= 480 && lds <= kLdsBudget) { p.body = "tasp_body"; p.threads = th; p.lds = lds; }
         }
         break;
     case LDPC_HIP_LCHE_DEC:
@@ -430,9 +481,7 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
         {   // LDS: a-posteriori LLRs + one spare slot per thread + flag words + the phi tables and step sums
             const int th = 64 * ((2 * M + 63) / 64);
             const size_t lds = sizeof(double) * ((size_t)N + (size_t)th) + 16 + sizeof(double) * (ldpc_spec::lche::kTabWords + ldpc_spec::lche::kStepWords);
-            int regs = 85;   // the same estimate as TASP's (ldpc_jit.hpp)
-            for (int j = 0; j < t.rh; ++j) { const int L = (t.row_start[j + 1] - t.row_start[j] + 1) / 2; regs += 2 * L + (L + 1) / 2; }
-            if (M <= 256 && t.min_rw >= 1 && t.rh <= 64 && regs <= 480 && lds <= kLdsBudget) { p.body = "lche_body"; p.threads = th; p.lds = lds; }
+            if (M <= 256 && t.min_rw >= 1 && t.rh <= 64 && tasp_lane_regs(t) <= 480 && lds <= kLdsBudget) { p.body = "lche_body"; p.threads = th; p.lds = lds; }
         }
         break;
     default: break;
@@ -491,6 +540,149 @@ int run_bp_chain(ldpc_hip_ctx *c, long long B, int32_t *d_iters, hipStream_t str
     return 0;
 }
 
+// IMS_DEC's per-frame quantiser scale of `frames` received words into coef[frames]
+int ims_coef_launch(const double *d_llr, double *coef, long long frames, int N, hipStream_t stream) {
+    ldpc::ImsCoefArgs ca{d_llr, coef, frames, N};
+    hipLaunchKernelGGL(ldpc::ims_coef_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, stream, ca);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ... into the context's own array, grown on demand
+int ims_scale(ldpc_hip_ctx *c, const double *d_llr, long long B, hipStream_t stream) {
+    if (B > c->ims_coef_frames) {
+        if (c->d_ims_coef) (void)hipFree(c->d_ims_coef);
+        c->d_ims_coef = nullptr; c->ims_coef_frames = 0;
+        HIP_TRY(hipMalloc(&c->d_ims_coef, sizeof(double) * (size_t)B));
+        c->ims_coef_frames = B;
+    }
+    return ims_coef_launch(d_llr, c->d_ims_coef, B, c->N, stream);
+}
+
+int ims_ialpha(double alpha) { return (int)(alpha * (1 << 4)); }   // decoders.cpp:5458, MS_ALPHA_FPP = 4
+
+// One decode call (ldpc_hip_decode_dev, after its argument checks) and the three tiers that serve it
+struct DecodeCall {
+    const double *llr; long long B; int maxiter; double alpha;
+    uint32_t *hard; int32_t *iters; double *soft;
+    hipStream_t stream;
+};
+
+// shape-unlimited tier
+int launch_global(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d) {
+    // one workgroup per frame, capped: the workspace is per workgroup and does not grow with the batch
+    int grid = (int)(d.B < 1024 ? d.B : 1024);
+    while (grid > 16 && (size_t)grid * c->glob_stride > ((size_t)8 << 30)) grid /= 2;
+    if (grid > c->glob_grid) {
+        if (c->d_glob_ws) (void)hipFree(c->d_glob_ws);
+        c->d_glob_ws = nullptr; c->glob_grid = 0;
+        HIP_TRY(hipMalloc(&c->d_glob_ws, (size_t)grid * c->glob_stride));
+        c->glob_grid = grid;
+    }
+    ldpc::GlobArgs ga{};
+    ga.d.llr = d.llr; ga.d.hard = d.hard; ga.d.iters = d.iters; ga.d.soft_out = d.soft;
+    ga.d.row_start = c->d_row_start; ga.d.edges = c->d_edges; ga.d.col_start = c->d_col_start; ga.d.col_edges = c->d_col_edges;
+    ga.d.col_slot = c->d_col_slot; ga.d.edge_row = c->d_edge_row;
+    ga.d.B = d.B; ga.d.rh = c->rh; ga.d.nh = c->nh; ga.d.M = c->M; ga.d.N = c->N; ga.d.F = 1; ga.d.maxiter = d.maxiter;
+    ga.d.hard_words = c->hard_words; ga.d.alpha = d.alpha;
+    ga.ws = c->d_glob_ws; ga.ws_stride = c->glob_stride; ga.ne = c->ne; ga.asp_cw2 = c->asp_cw2 ? 1 : 0;
+    if (c->decoder_id == LDPC_HIP_IMS_DEC) {
+        if (int rc = ims_scale(c, d.llr, d.B, d.stream)) return rc;
+        ga.ims_coef = c->d_ims_coef;
+        ga.d.ims_thr = c->ims_thr; ga.d.ims_qbits = c->ims_qbits; ga.d.ims_dbits = c->ims_dbits;
+    }
+    auto glaunch = [&](long long slots, const ChainIo &io) -> int {
+        ga.slots = slots; ga.stale = io.stale; ga.synd_out = io.synd_out; ga.frame_idx = io.frame_idx;
+        if (io.iters) ga.d.iters = io.iters;
+        hipLaunchKernelGGL(kind.global, dim3((unsigned)(slots < grid ? slots : grid)), dim3((unsigned)ldpc::glob_threads(c->N)), 0, d.stream, ga);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    if (c->decoder_id == LDPC_HIP_BP_DEC && c->bp_chain) return run_bp_chain(c, d.B, d.iters, d.stream, glaunch);
+    ChainIo io;
+    io.iters = d.iters;
+    return glaunch(d.B, io);
+}
+
+// code-specialised kernel: one frame per workgroup
+int launch_spec(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d) {
+    ldpc_spec::SpecArgs sa{};
+    if (c->decoder_id == LDPC_HIP_IMS_DEC) {
+        if (int rc = ims_scale(c, d.llr, d.B, d.stream)) return rc;
+        sa.ims_coef = c->d_ims_coef; sa.ims_thr = c->ims_thr;
+        sa.ims_max_quant = (1 << (c->ims_qbits - 1)) - 1; sa.ims_max_data = (1 << (c->ims_dbits - 1)) - 1; sa.ims_ialpha = ims_ialpha(d.alpha);
+    }
+    sa.llr = d.llr; sa.hard = d.hard; sa.iters = d.iters; sa.soft_out = d.soft; sa.maxiter = d.maxiter; sa.alpha = d.alpha;
+    sa.nframes = d.B;
+    // One frame per workgroup, min-sum and layered min-sum bodies (the frame loop costs the integer, SP and ASP bodies spilled
+    // registers and the TDMP body 7 % of its speed; BP has its frame chain, the small-lifting bodies several frames per
+    // workgroup): PERSISTENT workgroups, one per
+    // resident slot of the chip, that pull frames from a queue (SpecArgs::queue) -- frames converge after different numbers of
+    // iterations, and the next frame should start the moment a slot is free, without a workgroup launch in between
+    static const bool persist_on = !(getenv("LDPC_HIP_PERSISTENT") && atoi(getenv("LDPC_HIP_PERSISTENT")) == 0);
+    const bool persistent = persist_on && c->spec_frames_per_block == 1 && kind.queue;
+    if (persistent) {
+        if (!c->d_queue) HIP_TRY(hipMalloc(&c->d_queue, 64));
+        if (c->persist_grid == 0 || c->persist_jit != (c->spec_aot == nullptr)) {   // resident workgroups: occupancy x CUs (8 x 256 for the flagship)
+            int per_cu = 0, cus = 0;
+            if (c->spec_aot) { if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc; }
+            hipError_t e = c->spec_aot ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_aot, c->spec_threads, c->spec_lds)
+                                       : hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_jit->fn, c->spec_threads, c->spec_lds);
+            if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+            c->persist_grid = per_cu * (cus > 0 ? cus : 256);
+            c->persist_jit = c->spec_aot == nullptr;
+        }
+    }
+    auto launch = [&](long long frames) -> int {
+        long long blocks = (frames + c->spec_frames_per_block - 1) / c->spec_frames_per_block;
+        if (persistent && blocks > c->persist_grid) {
+            HIP_TRY(hipMemsetAsync(c->d_queue, 0, sizeof(unsigned), d.stream));
+            sa.queue = c->d_queue;
+            blocks = c->persist_grid;
+        }
+        void *kargs[] = {&sa};
+        if (c->spec_aot) {
+            if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc;
+            HIP_TRY(hipLaunchKernel(c->spec_aot, dim3((unsigned)blocks), dim3((unsigned)c->spec_threads), kargs, c->spec_lds, d.stream));
+        } else {
+            HIP_TRY(hipModuleLaunchKernel(c->spec_jit->fn, (unsigned)blocks, 1, 1, (unsigned)c->spec_threads, 1, 1, (unsigned)c->spec_lds,
+                                          d.stream, kargs, nullptr));
+        }
+        return 0;
+    };
+    if (c->decoder_id == LDPC_HIP_BP_DEC && c->bp_chain)
+        return run_bp_chain(c, d.B, d.iters, d.stream, [&](long long frames, const ChainIo &io) -> int {
+            sa.stale = io.stale; sa.synd_out = io.synd_out; sa.frame_idx = io.frame_idx; sa.iters = io.iters;
+            return launch(frames);
+        });
+    return launch(d.B);
+}
+
+// table-driven kernel: c->F frames per workgroup
+int launch_generic(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d) {
+    ldpc::DecArgs a{};
+    a.llr = d.llr; a.hard = d.hard; a.iters = d.iters; a.soft_out = d.soft;
+    a.row_start = c->d_row_start; a.edges = c->d_edges;
+    a.col_start = c->d_col_start; a.col_edges = c->d_col_edges; a.col_slot = c->d_col_slot; a.edge_row = c->d_edge_row;
+    a.B = d.B; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F;
+    a.maxiter = d.maxiter; a.hard_words = c->hard_words; a.alpha = d.alpha;
+    a.ims_thr = c->ims_thr; a.ims_qbits = c->ims_qbits; a.ims_dbits = c->ims_dbits;
+    const dim3 grid((unsigned)((d.B + c->F - 1) / c->F)), block((unsigned)c->threads);
+    if (c->fast_m64) {   // MS_DEC on a shape the packed descriptors hold
+        void *fargs[] = {&a, &c->fast_tab};
+        const void *k = c->variant == 1 ? (const void *)ldpc::ms_flood_m64_kernel<false> : (const void *)ldpc::ms_flood_m64_kernel<true>;
+        HIP_TRY(hipLaunchKernel(k, grid, block, fargs, c->lds_bytes, d.stream));
+        return 0;
+    }
+    const void *k = c->multiwave ? kind.multiwave : kind.wave;
+    if (!k) return fail(LDPC_HIP_EUNSUPPORTED, "decoder %d has no generic kernel", c->decoder_id);
+    void *kargs[] = {&a};
+    if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
+    HIP_TRY(hipLaunchKernel(k, grid, block, kargs, c->lds_bytes, d.stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -508,9 +700,8 @@ int ldpc_hip_device_count(void) {
 int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int device, ldpc_hip_ctx **out) {
     if (out) *out = nullptr;
     if (!out || !hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_open: bad argument");
-    if (decoder_id != LDPC_HIP_MS_DEC && decoder_id != LDPC_HIP_LMS_DEC && decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_IMS_DEC &&
-        decoder_id != LDPC_HIP_TASP_DEC && decoder_id != LDPC_HIP_ASP_DEC && decoder_id != LDPC_HIP_BP_DEC && decoder_id != LDPC_HIP_IASP_DEC &&
-        decoder_id != LDPC_HIP_LCHE_DEC)
+    const decoder_kind *kind = decoder_find(decoder_id);
+    if (!kind)
         return fail(LDPC_HIP_EUNSUPPORTED, "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, IASP=5, TASP=7, LMS=8, LCHE=9)", decoder_id);
     if (M >= 65536 || nh >= 65536 || rh >= 65536) return fail(LDPC_HIP_EUNSUPPORTED, "M, rh and nh must be < 65536");
     if ((long long)nh * M >= (1LL << 28)) return fail(LDPC_HIP_EUNSUPPORTED, "code length nh * M = %lld: at most 2^28 - 1 is supported (32-bit indices)", (long long)nh * M);
@@ -532,15 +723,18 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
 
     // ---- generic (table-driven) kernel for this decoder, where one exists
     bool have_generic = false;
-    if (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_LMS_DEC || decoder_id == LDPC_HIP_IMS_DEC) {
-        const bool needs_nh = decoder_id != LDPC_HIP_LMS_DEC;  // the flooding kernels keep the channel LLRs of kNHM block columns in VGPRs
+    if (decoder_id == LDPC_HIP_SP_DEC) {   // sp_flood_kernel's own geometry
+        c->multiwave = true; c->F = 1; c->threads = ldpc::kSpThreads;
+        c->lds_bytes = ldpc::sp_lds_bytes(t.ne, M, c->R, c->N);
+        c->kernel_name = kind->generic_name;
+        have_generic = c->N <= ldpc::kSpNVM * c->threads && c->lds_bytes <= 160 * 1024;
+    } else if (kind->wave) {
         c->multiwave = M > 64;
         c->F = c->multiwave ? 1 : 64 / M;
         c->threads = c->multiwave ? ((M + 63) / 64) * 64 : 64;
         c->lds_bytes = sizeof(double) * (size_t)c->N * c->F + 16;
-        have_generic = rh <= kRHM && t.max_rw <= kRWM && (!needs_nh || nh <= kNHM) && M <= 512 && c->lds_bytes <= 160 * 1024;
-        const char *base = decoder_id == LDPC_HIP_MS_DEC ? "ms_flood_kernel" : decoder_id == LDPC_HIP_IMS_DEC ? "ims_flood_kernel" : "lms_layered_kernel";
-        c->kernel_name = std::string(base) + (c->multiwave ? "<multiwave>" : "");
+        have_generic = rh <= kRHM && t.max_rw <= kRWM && (!kind->needs_nh || nh <= kNHM) && M <= 512 && c->lds_bytes <= 160 * 1024;
+        c->kernel_name = std::string(kind->generic_name) + (c->multiwave ? "<multiwave>" : "");
         if (have_generic && decoder_id == LDPC_HIP_MS_DEC && M == 64 && rh <= ldpc::kFastRows && nh <= ldpc::kFastCols && t.all_cols_used &&
             t.max_rw <= ldpc::kFastSlots && c->variant >= 0) {
             // table-driven M = 64 kernel: 64 dwords of packed descriptors that stay in SGPRs
@@ -557,24 +751,18 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
             }
             c->lds_bytes = sizeof(double) * 2048;
         }
-    } else if (decoder_id == LDPC_HIP_SP_DEC) {
-        c->multiwave = true; c->F = 1; c->threads = ldpc::kSpThreads;
-        c->lds_bytes = ldpc::sp_lds_bytes(t.ne, M, c->R, c->N);
-        c->kernel_name = "sp_flood_kernel";
-        have_generic = c->N <= ldpc::kSpNVM * c->threads && c->lds_bytes <= 160 * 1024;
     }
 
     c->have_generic = have_generic;
     if (have_generic) c->generic_name = c->kernel_name;
 
-    bool all_cw2 = true;   // decoders 2 and 5 have their own branch for codes whose block columns all hold two circulants (decoders.cpp:1027-1044,
-                           // :2431-2480; :1062-1095, :3915-3977): the shape-unlimited tier runs it (asp_global_kernel, iasp_global_kernel),
-                           // the resident asp_body / iasp_body are the general branch
-    for (int k = 0; k < nh; ++k) all_cw2 = all_cw2 && (t.col_start[k + 1] - t.col_start[k] == 2);
-    c->asp_cw2 = (decoder_id == LDPC_HIP_ASP_DEC || decoder_id == LDPC_HIP_IASP_DEC) && all_cw2;
-    const bool can_global = decoder_id == LDPC_HIP_BP_DEC || decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_LMS_DEC || decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_IMS_DEC ||
-                            (decoder_id == LDPC_HIP_TASP_DEC && t.min_rw >= 2) || (decoder_id == LDPC_HIP_ASP_DEC && t.min_rw >= 2) ||
-                            (decoder_id == LDPC_HIP_IASP_DEC && t.min_rw >= 2) || decoder_id == LDPC_HIP_LCHE_DEC;
+    // decoders 2 and 5 have their own branch for codes whose block columns all hold two circulants (decoders.cpp:1027-1044, :2431-2480;
+    // :1062-1095, :3915-3977): the shape-unlimited tier runs it (asp_global_kernel, iasp_global_kernel, the only readers of
+    // GlobArgs::asp_cw2), the resident asp_body / iasp_body are the general branch
+    c->asp_cw2 = t.all_cw2;
+    const bool can_global = !kind->global_min_rw2 || t.min_rw >= 2;
+    const char *genv = getenv("LDPC_HIP_FORCE_GLOBAL");   // tests: run the shape-unlimited tier on shapes the resident kernels take
+    const bool forced_global = genv && atoi(genv) != 0;
 
     // ---- code-specialised instance: ahead of time for the shipped example code, hiprtc for anything else
     const SpecPlan plan = plan_spec(decoder_id, t);
@@ -588,8 +776,6 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
                 break;
             }
         const int jit_mode = jit_mode_effective();
-        const char *fg = getenv("LDPC_HIP_FORCE_GLOBAL");
-        const bool forced_global = fg && atoi(fg) != 0;
         if (!c->spec_aot && jit_mode != 0 && !forced_global) {
             // background compile only where another HIP tier can serve the first launches
             const bool has_fallback = have_generic || can_global;
@@ -611,18 +797,14 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
             why_not = forced_global ? "LDPC_HIP_FORCE_GLOBAL" : "LDPC_HIP_JIT=0";
         }
     }
-    const char *genv = getenv("LDPC_HIP_FORCE_GLOBAL");   // tests: run the shape-unlimited tier on shapes the resident kernels take
-    if (can_global && ((genv && atoi(genv) != 0) || (!c->spec_aot && !c->spec_jit && !have_generic))) {
+    if (can_global && (forced_global || (!c->spec_aot && !c->spec_jit && !have_generic))) {
         c->global_tier = true;
         c->global_is_fallback = c->jit_job != nullptr;   // until the background instance arrives
         c->spec_aot = nullptr; c->spec_jit = nullptr;
-        c->kernel_name = decoder_id == LDPC_HIP_MS_DEC ? "ms_global_kernel" : decoder_id == LDPC_HIP_LMS_DEC ? "lms_global_kernel" : decoder_id == LDPC_HIP_IMS_DEC ? "ims_global_kernel" : decoder_id == LDPC_HIP_ASP_DEC ? "asp_global_kernel" : decoder_id == LDPC_HIP_IASP_DEC ? "iasp_global_kernel" : decoder_id == LDPC_HIP_BP_DEC ? "bp_global_kernel" :
-                         decoder_id == LDPC_HIP_LCHE_DEC ? "lche_global_kernel" :
-                         decoder_id == LDPC_HIP_SP_DEC ? "sp_global_kernel" : "tasp_global_kernel";
-        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, (decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) ? 0 : decoder_id == LDPC_HIP_TASP_DEC ? 4 : decoder_id == LDPC_HIP_ASP_DEC ? 3 : 1);   // IASP: u16 state + i16 products in the one edge array; LCHE: Z
+        c->kernel_name = kind->global_name;
     }
-    if (decoder_id == LDPC_HIP_IMS_DEC && !c->global_tier)   // parameters beyond int8 may send a launch to the global tier later
-        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, 0);
+    if (c->global_tier || decoder_id == LDPC_HIP_IMS_DEC)   // IMS: parameters beyond int8 may send a launch to the global tier later
+        c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, kind->glob_edge_arrays);
     if (!c->spec_aot && !c->spec_jit && !c->global_tier) {
         if (!have_generic)
             return fail(LDPC_HIP_EUNSUPPORTED, "decoder %d, code %dx%d lifting %d: not supported by the generic kernel (limits: %d block rows, "
@@ -719,173 +901,17 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
 
     ProfTimer timer;
     if (int rc = timer.begin(c, stream)) return rc;
+    const decoder_kind &kind = *decoder_find(c->decoder_id);   // set_device: a context of ldpc_hip_open
+    const DecodeCall d{d_llr, B, maxiter, alpha, d_hard, d_iters, d_soft, stream};
     bool use_spec = c->spec_aot || c->spec_jit;
     bool use_global = c->global_tier;
-    const int ims_ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5458, MS_ALPHA_FPP = 4
-    if (use_spec && c->decoder_id == LDPC_HIP_IMS_DEC && (c->ims_dbits > 8 || c->ims_qbits > 8 || ims_ialpha < 0 || ims_ialpha > 16)) {
+    const int ialpha = ims_ialpha(alpha);
+    if (use_spec && c->decoder_id == LDPC_HIP_IMS_DEC && (c->ims_dbits > 8 || c->ims_qbits > 8 || ialpha < 0 || ialpha > 16)) {
         use_spec = false;   // values beyond int8 (messages, or quantised inputs): table-driven int32 kernel, or the global tier's
         if (!c->have_generic) use_global = true;
     }
-    c->last_launch = use_global ? (c->global_tier ? c->kernel_name.c_str() : "ims_global_kernel") : use_spec ? c->kernel_name.c_str() : c->generic_name.c_str();
-    if (use_global) {
-        // one workgroup per frame, capped: the workspace is per workgroup and does not grow with the batch
-        int grid = (int)(B < 1024 ? B : 1024);
-        while (grid > 16 && (size_t)grid * c->glob_stride > ((size_t)8 << 30)) grid /= 2;
-        if (grid > c->glob_grid) {
-            if (c->d_glob_ws) (void)hipFree(c->d_glob_ws);
-            c->d_glob_ws = nullptr; c->glob_grid = 0;
-            HIP_TRY(hipMalloc(&c->d_glob_ws, (size_t)grid * c->glob_stride));
-            c->glob_grid = grid;
-        }
-        ldpc::GlobArgs ga{};
-        ga.d.llr = d_llr; ga.d.hard = d_hard; ga.d.iters = d_iters; ga.d.soft_out = d_soft;
-        ga.d.row_start = c->d_row_start; ga.d.edges = c->d_edges; ga.d.col_start = c->d_col_start; ga.d.col_edges = c->d_col_edges;
-        ga.d.col_slot = c->d_col_slot; ga.d.edge_row = c->d_edge_row;
-        ga.d.B = B; ga.d.rh = c->rh; ga.d.nh = c->nh; ga.d.M = c->M; ga.d.N = c->N; ga.d.F = 1; ga.d.maxiter = maxiter;
-        ga.d.hard_words = c->hard_words; ga.d.alpha = alpha;
-        ga.ws = c->d_glob_ws; ga.ws_stride = c->glob_stride; ga.ne = c->ne; ga.asp_cw2 = c->asp_cw2 ? 1 : 0;
-        if (c->decoder_id == LDPC_HIP_IMS_DEC) {
-            if (B > c->ims_coef_frames) {
-                if (c->d_ims_coef) (void)hipFree(c->d_ims_coef);
-                c->d_ims_coef = nullptr; c->ims_coef_frames = 0;
-                HIP_TRY(hipMalloc(&c->d_ims_coef, sizeof(double) * (size_t)B));
-                c->ims_coef_frames = B;
-            }
-            ldpc::ImsCoefArgs ca{d_llr, c->d_ims_coef, B, c->N};
-            hipLaunchKernelGGL(ldpc::ims_coef_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, ca);
-            HIP_TRY(hipGetLastError());
-            ga.ims_coef = c->d_ims_coef;
-            ga.d.ims_thr = c->ims_thr; ga.d.ims_qbits = c->ims_qbits; ga.d.ims_dbits = c->ims_dbits;
-        }
-        auto glaunch = [&](long long slots, const ChainIo &io) -> int {
-            ga.slots = slots; ga.stale = io.stale; ga.synd_out = io.synd_out; ga.frame_idx = io.frame_idx;
-            if (io.iters) ga.d.iters = io.iters;
-            const dim3 gg((unsigned)(slots < grid ? slots : grid)), bb((unsigned)ldpc::glob_threads(c->N));
-            switch (c->decoder_id) {
-            case LDPC_HIP_MS_DEC: hipLaunchKernelGGL(ldpc::ms_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_LMS_DEC: hipLaunchKernelGGL(ldpc::lms_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_IMS_DEC: hipLaunchKernelGGL(ldpc::ims_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_ASP_DEC: hipLaunchKernelGGL(ldpc::asp_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_IASP_DEC: hipLaunchKernelGGL(ldpc::iasp_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_LCHE_DEC: hipLaunchKernelGGL(ldpc::lche_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_SP_DEC: hipLaunchKernelGGL(ldpc::sp_global_kernel, gg, bb, 0, stream, ga); break;
-            case LDPC_HIP_BP_DEC: hipLaunchKernelGGL(ldpc::bp_global_kernel, gg, bb, 0, stream, ga); break;
-            default: hipLaunchKernelGGL(ldpc::tasp_global_kernel, gg, bb, 0, stream, ga); break;
-            }
-            HIP_TRY(hipGetLastError());
-            return 0;
-        };
-        if (c->decoder_id == LDPC_HIP_BP_DEC && c->bp_chain) {
-            if (int rc = run_bp_chain(c, B, d_iters, stream, glaunch)) return rc;
-        } else {
-            ChainIo io;
-            io.iters = d_iters;
-            if (int rc = glaunch(B, io)) return rc;
-        }
-    } else if (use_spec) {
-        // code-specialised kernel: one frame per workgroup
-        ldpc_spec::SpecArgs sa{};
-        if (c->decoder_id == LDPC_HIP_IMS_DEC) {
-            if (B > c->ims_coef_frames) {
-                if (c->d_ims_coef) (void)hipFree(c->d_ims_coef);
-                c->d_ims_coef = nullptr; c->ims_coef_frames = 0;
-                HIP_TRY(hipMalloc(&c->d_ims_coef, sizeof(double) * (size_t)B));
-                c->ims_coef_frames = B;
-            }
-            ldpc::ImsCoefArgs ca{d_llr, c->d_ims_coef, B, c->N};
-            hipLaunchKernelGGL(ldpc::ims_coef_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, ca);
-            HIP_TRY(hipGetLastError());
-            sa.ims_coef = c->d_ims_coef; sa.ims_thr = c->ims_thr;
-            sa.ims_max_quant = (1 << (c->ims_qbits - 1)) - 1; sa.ims_max_data = (1 << (c->ims_dbits - 1)) - 1; sa.ims_ialpha = ims_ialpha;
-        }
-        sa.llr = d_llr; sa.hard = d_hard; sa.iters = d_iters; sa.soft_out = d_soft; sa.maxiter = maxiter; sa.alpha = alpha;
-        sa.nframes = B;
-        // One frame per workgroup, min-sum and layered min-sum bodies (the frame loop costs the integer, SP and ASP bodies spilled
-        // registers and the TDMP body 7 % of its speed; BP has its frame chain, the small-lifting bodies several frames per
-        // workgroup): PERSISTENT workgroups, one per
-        // resident slot of the chip, that pull frames from a queue (SpecArgs::queue) -- frames converge after different numbers of
-        // iterations, and the next frame should start the moment a slot is free, without a workgroup launch in between
-        static const bool persist_on = !(getenv("LDPC_HIP_PERSISTENT") && atoi(getenv("LDPC_HIP_PERSISTENT")) == 0);
-        const bool persistent = persist_on && c->spec_frames_per_block == 1 &&
-                                (c->decoder_id == LDPC_HIP_MS_DEC || c->decoder_id == LDPC_HIP_LMS_DEC);
-        if (persistent) {
-            if (!c->d_queue) HIP_TRY(hipMalloc(&c->d_queue, 64));
-            if (c->persist_grid == 0 || c->persist_jit != (c->spec_aot == nullptr)) {   // resident workgroups: occupancy x CUs (8 x 256 for the flagship)
-                int per_cu = 0, cus = 0;
-                if (c->spec_aot) { if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc; }
-                hipError_t e = c->spec_aot ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_aot, c->spec_threads, c->spec_lds)
-                                           : hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_jit->fn, c->spec_threads, c->spec_lds);
-                if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-                HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-                c->persist_grid = per_cu * (cus > 0 ? cus : 256);
-                c->persist_jit = c->spec_aot == nullptr;
-            }
-        }
-        auto launch = [&](long long frames) -> int {
-            long long blocks = (frames + c->spec_frames_per_block - 1) / c->spec_frames_per_block;
-            if (persistent && blocks > c->persist_grid) {
-                HIP_TRY(hipMemsetAsync(c->d_queue, 0, sizeof(unsigned), stream));
-                sa.queue = c->d_queue;
-                blocks = c->persist_grid;
-            }
-            void *kargs[] = {&sa};
-            if (c->spec_aot) {
-                if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc;
-                HIP_TRY(hipLaunchKernel(c->spec_aot, dim3((unsigned)blocks), dim3((unsigned)c->spec_threads), kargs, c->spec_lds, stream));
-            } else {
-                HIP_TRY(hipModuleLaunchKernel(c->spec_jit->fn, (unsigned)blocks, 1, 1, (unsigned)c->spec_threads, 1, 1, (unsigned)c->spec_lds,
-                                              stream, kargs, nullptr));
-            }
-            return 0;
-        };
-        if (c->decoder_id == LDPC_HIP_BP_DEC && c->bp_chain) {
-            if (int rc = run_bp_chain(c, B, d_iters, stream, [&](long long frames, const ChainIo &io) -> int {
-                    sa.stale = io.stale; sa.synd_out = io.synd_out; sa.frame_idx = io.frame_idx; sa.iters = io.iters;
-                    return launch(frames);
-                }))
-                return rc;
-        } else {
-            if (int rc = launch(B)) return rc;
-        }
-    } else {
-        ldpc::DecArgs a{};
-        a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.soft_out = d_soft;
-        a.row_start = c->d_row_start; a.edges = c->d_edges;
-        a.col_start = c->d_col_start; a.col_edges = c->d_col_edges; a.col_slot = c->d_col_slot; a.edge_row = c->d_edge_row;
-        a.B = B; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F;
-        a.maxiter = maxiter; a.hard_words = c->hard_words; a.alpha = alpha;
-        a.ims_thr = c->ims_thr; a.ims_qbits = c->ims_qbits; a.ims_dbits = c->ims_dbits;
-        const dim3 grid((unsigned)((B + c->F - 1) / c->F)), block((unsigned)c->threads);
-        void *kargs[] = {&a};
-        const void *k = nullptr;
-        switch (c->decoder_id) {
-        case LDPC_HIP_MS_DEC:
-            if (c->fast_m64) {
-                void *fargs[] = {&a, &c->fast_tab};
-                k = c->variant == 1 ? (const void *)ldpc::ms_flood_m64_kernel<false> : (const void *)ldpc::ms_flood_m64_kernel<true>;
-                HIP_TRY(hipLaunchKernel(k, grid, block, fargs, c->lds_bytes, stream));
-                k = nullptr;
-            } else {
-                k = c->multiwave ? (const void *)ldpc::ms_flood_kernel<kRHM, kNHM, true> : (const void *)ldpc::ms_flood_kernel<kRHM, kNHM, false>;
-            }
-            break;
-        case LDPC_HIP_LMS_DEC:
-            k = c->multiwave ? (const void *)ldpc::lms_layered_kernel<kRHM, kRWM, true> : (const void *)ldpc::lms_layered_kernel<kRHM, kRWM, false>;
-            break;
-        case LDPC_HIP_IMS_DEC:
-            k = c->multiwave ? (const void *)ldpc::ims_flood_kernel<kRHM, kNHM, true> : (const void *)ldpc::ims_flood_kernel<kRHM, kNHM, false>;
-            break;
-        case LDPC_HIP_SP_DEC:
-            k = (const void *)ldpc::sp_flood_kernel;
-            break;
-        default:
-            return fail(LDPC_HIP_EUNSUPPORTED, "decoder %d has no generic kernel", c->decoder_id);
-        }
-        if (k) {
-            if (int rc = set_lds_limit(k, c->lds_bytes)) return rc;
-            HIP_TRY(hipLaunchKernel(k, grid, block, kargs, c->lds_bytes, stream));
-        }
-    }
+    c->last_launch = use_global ? kind.global_name : use_spec ? c->kernel_name.c_str() : c->generic_name.c_str();
+    if (int rc = use_global ? launch_global(c, kind, d) : use_spec ? launch_spec(c, kind, d) : launch_generic(c, kind, d)) return rc;
     HIP_TRY(hipGetLastError());
     return timer.end();
 }
@@ -895,11 +921,9 @@ int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter,
     if (!c || !llr || B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_host: bad argument");
     if (B == 0) return 0;
     if (int rc = set_device(c)) return rc;
-    const bool sp = c->decoder_id == LDPC_HIP_SP_DEC || c->decoder_id == LDPC_HIP_BP_DEC;  // soft[] is the working array upstream
-    const bool tasp = c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_ASP_DEC;  // probability-domain decoders
-    const bool iasp = c->decoder_id == LDPC_HIP_IASP_DEC;   // the same, its input transform without the * 0.5
-    if (c->decoder_id == LDPC_HIP_TASP_DEC || c->decoder_id == LDPC_HIP_LCHE_DEC) decision = 0;  // upstream ignores `decision` for these decoders: the
-                                                                                                 // result is always hard (decoders.cpp:2737-2738, :3005-3006)
+    const decoder_kind &kind = *decoder_find(c->decoder_id);
+    const bool sp = kind.soft_is_input;
+    if (kind.ignores_decision) decision = 0;
     const bool need_soft = decision != 0 || (sp && clobber_sp_input);
     if (int rc = ensure_workspace(c, B, need_soft)) return rc;
     const size_t nllr = (size_t)B * c->N;
@@ -926,11 +950,10 @@ int ldpc_hip_decode_host(ldpc_hip_ctx *c, double *llr, long long B, int maxiter,
         }
     }
     if (sp && clobber_sp_input) std::memcpy(llr, soft.data(), sizeof(double) * nllr);  // decoders.cpp:1950,2124
-    if ((tasp || iasp) && clobber_sp_input) {  // decoders.cpp:2611-2618 / :3858-3863: soft[] is left holding P(bit = 1) of the channel -- same exp() as the decoder's
+    if (kind.prior && clobber_sp_input) {  // decoders.cpp:2611-2618 / :3858-3863: soft[] is left holding P(bit = 1) of the channel -- same exp() as the decoder's
         long long blocks = ((long long)nllr + 255) / 256;
         if (blocks > 256 * 16) blocks = 256 * 16;
-        if (iasp) hipLaunchKernelGGL(iasp_channel_prior_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
-        else hipLaunchKernelGGL(channel_prior_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
+        hipLaunchKernelGGL(kind.prior, dim3((unsigned)blocks), dim3(256), 0, nullptr, c->w_llr, (long long)nllr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(llr, c->w_llr, sizeof(double) * nllr, hipMemcpyDeviceToHost));
     }
@@ -944,11 +967,8 @@ int ldpc_hip_set_bp_chain(ldpc_hip_ctx *c, int on, int reset_carry) {
     return 0;
 }
 
-// What the channel writes at a punctured position for this decoder (bp_simulation.cpp:700 (sic), out_type :451-466)
-static double punctured_llr(int decoder_id) {
-    return (decoder_id == LDPC_HIP_SP_DEC || decoder_id == LDPC_HIP_TASP_DEC || decoder_id == LDPC_HIP_ASP_DEC ||
-            decoder_id == LDPC_HIP_IASP_DEC || decoder_id == LDPC_HIP_LCHE_DEC) ? 0.0 : 0.5;
-}
+// What the channel writes at a punctured position for this decoder; single codes and code sets open with a built id only
+static double punctured_llr(int decoder_id) { return decoder_find(decoder_id)->punctured_llr; }
 
 static int awgn_sigma(const ldpc_hip_ctx *c, double snr_db, int modulation_type, int punctured_blocks, double *sigma) {
     const int b = c->rh, cc = c->nh;

@@ -48,6 +48,31 @@ def test_jit_mode_switch():
     assert lib.ldpc_hip_set_jit_mode(1) == 0
 
 
+_NOT_BUILT = "ldpc_hip_open: decoder id %d is not built (built: BP=0, SP=1, ASP=2, MS=3, IMS=4, IASP=5, TASP=7, LMS=8, LCHE=9)"
+
+
+@pytest.mark.parametrize("dec,rh,nh,M,hd,out,code,text", [
+    (3, 2, 3, 4, False, True, -1, "ldpc_hip_open: bad argument"),                  # a null hd
+    (3, 0, 3, 4, True, True, -1, "ldpc_hip_open: bad argument"),                   # rh = 0
+    (6, 2, 3, 4, True, True, -2, _NOT_BUILT % 6),                                  # FHT_DEC opens with ldpc_hip_open_gfq
+    (10, 2, 3, 4, True, True, -2, _NOT_BUILT % 10),
+    (-1, 2, 3, 4, True, True, -2, _NOT_BUILT % -1),
+    (3, 2, 3, 65536, True, True, -2, "M, rh and nh must be < 65536"),
+    (3, 1, 32768, 8192, True, True, -2, "code length nh * M = 268435456: at most 2^28 - 1 is supported (32-bit indices)"),
+    (3, 2, 3, 4, True, False, -1, "ldpc_hip_open: bad argument"),                  # a null out
+])
+def test_open_refusals_that_need_no_device(dec, rh, nh, M, hd, out, code, text):
+    """ldpc_hip_open returns before it asks for a device in these cases: the return code (LDPC_HIP_EINVAL -1, LDPC_HIP_EUNSUPPORTED -2)
+    and the whole message, as the library gave them before the decoders were described by decoder_kinds[]."""
+    import ldpc_lib_amd
+    lib = ldpc_lib_amd.load_library()
+    H = np.zeros((max(rh, 1), nh), dtype=np.int16)
+    h = C.c_void_p()
+    rc = lib.ldpc_hip_open(dec, rh, nh, M, H.ctypes.data_as(C.c_void_p) if hd else None, 0, C.byref(h) if out else None)
+    assert (rc, lib.ldpc_hip_last_error().decode()) == (code, text)
+    assert not h.value
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     import torch
     if torch.cuda.is_available():
