@@ -80,8 +80,73 @@ __device__ inline GlobView glob_view(char *p, int N, int R, int ne, int M, int e
     return v;
 }
 
-template <int KIND = 0>   // hard decision: 0 soft < 0 (LLR decoders), 1 soft > 0.5 (probability domain, :2734), 2 soft < 1.0 (likelihood ratios, :2172)
-__device__ inline void glob_outputs(const DecArgs &a, const GlobView &w, long long fr, int res) {
+// What every kernel of this tier does the same way stands once, here: the frame-invariant values of a workgroup (GlobFrame,
+// glob_frame), the two directions of edge addressing (var_pos / var_idx, chk_pos), check_syndrome (glob_syndrome), the reset of the
+// min-sum records (glob_reset_records), upstream's clamps (mind, maxd) and the outputs of a frame (glob_outputs).  What differs
+// between decoders -- the test that decides a bit, the conversion of the a-posteriori word -- arrives as a functor.  The functors
+// capture the pointers they read by value ([=]), as in ldpc_kernels.hpp (profiles/kernel_refactor_resources.txt).
+// lche_global_kernel calls only glob_outputs: with the rest it measured slower (profiles/global_tier_refactor_time.txt).
+
+// what a workgroup keeps over all its frames: its workspace slice and the sizes (lifting, variables, checks, circulants)
+struct GlobFrame : GlobView {
+    int M, N, R, ne;
+};
+__device__ __forceinline__ GlobFrame glob_frame(const GlobArgs &g, int edge_arrays) {
+    const int M = g.d.M, N = g.d.N, R = g.d.rh * M, ne = g.ne;
+    return GlobFrame{glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, edge_arrays), M, N, R, ne};
+}
+
+// Check n of a block row reaches over edge word d = (block column k << 16) | shift c the variable (k, (n + c) mod M): its position
+// inside the block column, and its index among the N variables.
+__device__ __forceinline__ int var_pos(uint32_t d, int n, int M) {
+    int i = n + (int)(d & 0xffffu);
+    if (i >= M) i -= M;
+    return i;
+}
+__device__ __forceinline__ int var_idx(uint32_t d, int n, int M) { return (int)(d >> 16) * M + var_pos(d, n, M); }
+// The mirror: position i of a block column is seen over column edge word d = (block row j << 16) | shift c by check (i - c) mod M of row j.
+__device__ __forceinline__ int chk_pos(uint32_t d, int i, int M) {
+    int n = i - (int)(d & 0xffffu);
+    if (n < 0) n += M;
+    return n;
+}
+
+__device__ __forceinline__ double mind(double x, double y) { return x < y ? x : y; }   // decoders.cpp:104-105
+__device__ __forceinline__ double maxd(double x, double y) { return x < y ? y : x; }
+
+// check_syndrome (decoders.cpp:793-814; check_syndrome_thr :2274-2306, icheck_syndrome :3772-3803) for the whole workgroup: the OR over
+// all checks of the XOR over a check's variables of bit(variable index).  sink(chk, synd) receives a check's result and start(j, n) is
+// the value its XOR begins with (bp_global_kernel: left[] and the stale bit).  Ends in a barrier; every thread returns the OR.
+template <class Bit, class Sink, class Start>
+__device__ __forceinline__ int glob_syndrome(const DecArgs &a, const GlobFrame &w, Bit bit, Sink sink, Start start) {
+    const int M = w.M;
+    int fail = 0;
+    for (int chk = threadIdx.x; chk < w.R; chk += (int)blockDim.x) {
+        const int j = chk / M, n = chk - j * M;
+        int synd = start(j, n);
+        for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) synd ^= (int)bit(var_idx(a.edges[e], n, M));
+        sink(chk, synd);
+        fail |= synd;
+    }
+    return __syncthreads_or(fail);
+}
+template <class Bit>
+__device__ __forceinline__ int glob_syndrome(const DecArgs &a, const GlobFrame &w, Bit bit) {
+    return glob_syndrome(a, w, bit, [](int, int) {}, [](int, int) { return 0; });
+}
+
+// The min-sum records at the start of a frame: min1 = min2 = 0, position 0, parity and edge signs 0 (:4579-4596, :5462-5470).  m1 / m2
+// are the kernel's own view of w.m1 / w.m2, doubles or -- ims_global_kernel -- ints.  The caller's barrier follows.
+template <class T>
+__device__ __forceinline__ void glob_reset_records(const GlobFrame &w, T *m1, T *m2) {
+    for (int c = threadIdx.x; c < w.R; c += (int)blockDim.x) { m1[c] = 0; m2[c] = 0; w.pos[c] = 0; w.par[c] = 0; }
+    for (size_t i = threadIdx.x; i < (size_t)w.ne * w.M; i += (int)blockDim.x) w.sgn[i] = 0;
+}
+
+// The outputs of a frame, called by the whole workgroup: the iteration result, the hard decisions bit(variable) packed 32 to a word
+// and the soft values soft(variable).
+template <class Bit, class Soft>
+__device__ __forceinline__ void glob_outputs(const DecArgs &a, long long fr, int res, Bit bit, Soft soft) {
     const int N = a.N;
     if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
     if (a.hard) {
@@ -89,24 +154,23 @@ __device__ inline void glob_outputs(const DecArgs &a, const GlobView &w, long lo
             uint32_t bits = 0;
             for (int b = 0; b < 32; ++b) {
                 const int v = 32 * wd + b;
-                if (v < N) bits |= (uint32_t)(KIND == 1 ? w.soft[v] > 0.5 : KIND == 2 ? w.soft[v] < 1.0 : w.soft[v] < 0) << b;      // decword[k] = soft[k] < 0  (:4683, :5418)
+                if (v < N) bits |= (uint32_t)bit(v) << b;
             }
             a.hard[fr * a.hard_words + wd] = bits;
         }
     }
     if (a.soft_out)
-        for (int v = threadIdx.x; v < N; v += (int)blockDim.x) a.soft_out[fr * N + v] = w.soft[v];
+        for (int v = threadIdx.x; v < N; v += (int)blockDim.x) a.soft_out[fr * N + v] = soft(v);
 }
 
 __global__ void __launch_bounds__(kGlobThreads) ms_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
+    const GlobFrame w = glob_frame(g, 0);
+    const int M = w.M, N = w.N, R = w.R;
     const double alpha = a.alpha;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 0);
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         const double *y = a.llr + fr * N;
-        for (int c = threadIdx.x; c < R; c += (int)blockDim.x) { w.m1[c] = 0.0; w.m2[c] = 0.0; w.pos[c] = 0; w.par[c] = 0; }   // :4579-4596
-        for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) w.sgn[i] = 0;
+        glob_reset_records(w, w.m1, w.m2);                                        // :4579-4596
         __syncthreads();
         int res = -a.maxiter;
         for (int iter = 0; iter < a.maxiter; ++iter) {
@@ -116,9 +180,7 @@ __global__ void __launch_bounds__(kGlobThreads) ms_global_kernel(const GlobArgs 
                 double acc = 0.0;                                                 // memset(soft, 0) :4630
                 for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {       // block rows ascending
                     const uint32_t d = a.col_edges[q];
-                    const int j = (int)(d >> 16), c = (int)(d & 0xffffu), e = (int)a.col_slot[q];
-                    int n = i - c;                                                // check n of row j sees variable (k, (n + c) mod M)
-                    if (n < 0) n += M;
+                    const int j = (int)(d >> 16), e = (int)a.col_slot[q], n = chk_pos(d, i, M);
                     const int chk = j * M + n;
                     const double tmp = w.pos[chk] == e - a.row_start[j] ? w.m2[chk] : w.m1[chk];
                     const double cv = (w.sgn[(size_t)e * M + n] ^ w.par[chk]) ? -tmp : tmp;
@@ -139,11 +201,7 @@ __global__ void __launch_bounds__(kGlobThreads) ms_global_kernel(const GlobArgs 
                 int np = 0, synd = 0;
                 uint8_t npar = 0;
                 for (int e = e0; e < e1; ++e) {
-                    const uint32_t d = a.edges[e];
-                    const int k = (int)(d >> 16), c = (int)(d & 0xffffu);
-                    int i = n + c;
-                    if (i >= M) i -= M;
-                    const double r = w.soft[k * M + i];
+                    const double r = w.soft[var_idx(a.edges[e], n, M)];
                     synd ^= (int)(r < 0);                                         // :4712
                     double val = (po == e - e0 ? o2 : o1) * alpha;               // :4720
                     double t = (w.sgn[(size_t)e * M + n] ^ pa) ? -val : val;
@@ -161,37 +219,22 @@ __global__ void __launch_bounds__(kGlobThreads) ms_global_kernel(const GlobArgs 
             }
             if (!__syncthreads_or(fail)) { res = iter + 1; break; }               // :4757-4766 (the barrier also fences the next STATE1)
         }
-        glob_outputs(a, w, fr, res);
+        glob_outputs(a, fr, res, [=](int v) { return w.soft[v] < 0; }, [=](int v) { return w.soft[v]; });   // decword[k] = soft[k] < 0 (:4683)
         __syncthreads();                                                          // the slice is reused by this workgroup's next frame
     }
 }
 
 __global__ void __launch_bounds__(kGlobThreads) lms_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
-    auto syndrome = [&]() -> int {                                                // check_syndrome, decoders.cpp:793-814
-        int fail = 0;
-        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-            const int j = chk / M, n = chk - j * M;
-            int synd = 0;
-            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                const uint32_t d = a.edges[e];
-                int i = n + (int)(d & 0xffffu);
-                if (i >= M) i -= M;
-                synd ^= (int)(w.soft[(int)(d >> 16) * M + i] < 0);
-            }
-            fail |= synd;
-        }
-        return __syncthreads_or(fail);
-    };
+    const GlobFrame w = glob_frame(g, 1);
+    const int M = w.M, N = w.N;
+    const auto bit = [=](int v) { return w.soft[v] < 0; };                         // check_syndrome, decoders.cpp:793-814; decword[] :5418
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         const double *y = a.llr + fr * N;
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) w.soft[v] = y[v];    // :5088
-        for (int c = threadIdx.x; c < R; c += (int)blockDim.x) { w.m1[c] = 0.0; w.m2[c] = 0.0; w.pos[c] = 0; w.par[c] = 0; }
-        for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) w.sgn[i] = 0;
+        glob_reset_records(w, w.m1, w.m2);
         __syncthreads();
-        int parity = syndrome();                                                   // :5111-5115
+        int parity = glob_syndrome(a, w, bit);                                     // :5111-5115
         int iter = 0;
         for (; iter < a.maxiter; ++iter) {
             if (parity == 0) break;                                                // :5119
@@ -206,12 +249,9 @@ __global__ void __launch_bounds__(kGlobThreads) lms_global_kernel(const GlobArgs
                     int np = 0;
                     uint8_t npar = 0;
                     for (int e = e0; e < e1; ++e) {                                // :5141-5177
-                        const uint32_t d = a.edges[e];
-                        int i = n + (int)(d & 0xffffu);
-                        if (i >= M) i -= M;
                         const double prev_abs = po == e - e0 ? o2 : o1;
                         const double prev_val = (w.sgn[(size_t)e * M + n] ^ pa) ? -prev_abs : prev_abs;
-                        const double t = w.soft[(int)(d >> 16) * M + i] - prev_val;
+                        const double t = w.soft[var_idx(a.edges[e], n, M)] - prev_val;
                         const uint8_t sign = t < 0;
                         double mag = t < 0.0 ? -t : t;
                         mag -= 0.4;                                                 // beta :5163
@@ -224,46 +264,29 @@ __global__ void __launch_bounds__(kGlobThreads) lms_global_kernel(const GlobArgs
                     }
                     w.m1[chk] = nm1; w.m2[chk] = nm2; w.pos[chk] = np; w.par[chk] = npar;
                     for (int e = e0; e < e1; ++e) {                                // :5182-5206
-                        const uint32_t d = a.edges[e];
-                        int i = n + (int)(d & 0xffffu);
-                        if (i >= M) i -= M;
                         const double c_abs = np == e - e0 ? nm2 : nm1;
                         const double c_val = (w.sgn[(size_t)e * M + n] ^ npar) ? -c_abs : c_abs;
-                        w.soft[(int)(d >> 16) * M + i] = w.tmp[(size_t)e * M + n] + c_val;
+                        w.soft[var_idx(a.edges[e], n, M)] = w.tmp[(size_t)e * M + n] + c_val;
                     }
                 }
                 __syncthreads();
             }
-            parity = syndrome();                                                   // :5281-5288
+            parity = glob_syndrome(a, w, bit);                                     // :5281-5288
             if (parity == 0) break;
         }
-        glob_outputs(a, w, fr, parity ? -iter : iter + 1);                         // :5424
+        glob_outputs(a, fr, parity ? -iter : iter + 1, bit, [=](int v) { return w.soft[v]; });   // :5424
         __syncthreads();
     }
 }
 
 __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
+    const GlobFrame w = glob_frame(g, 4);
+    const int M = w.M, N = w.N, ne = w.ne;
     const double T = 0.0001, TT = 0;                                                // :2597-2598
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 4);
     const size_t EM = glob_align(sizeof(double) * (size_t)ne * M) / sizeof(double);
     double *const Z = w.tmp, *const Y = w.tmp + EM, *const SF = w.tmp + 2 * EM, *const SB = w.tmp + 3 * EM;   // [e * M + k]
-    auto syndrome = [&]() -> int {                                                  // check_syndrome_thr :2274-2306, thr 0.5
-        int fail = 0;
-        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-            const int j = chk / M, n = chk - j * M;
-            int synd = 0;
-            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                const uint32_t d = a.edges[e];
-                int i = n + (int)(d & 0xffffu);
-                if (i >= M) i -= M;
-                synd ^= (int)(w.soft[(int)(d >> 16) * M + i] > 0.5);
-            }
-            fail |= synd;
-        }
-        return __syncthreads_or(fail);
-    };
+    const auto bit = [=](int v) { return w.soft[v] > 0.5; };                        // check_syndrome_thr :2274-2306, thr 0.5; decword[] :2734
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                       // :2611-2618
             const double x = a.llr[fr * N + v] * 0.5;
@@ -273,7 +296,7 @@ __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArg
         }
         for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) Z[i] = 0.5;   // :2637
         __syncthreads();
-        int synd = syndrome();                                                      // :2653-2660
+        int synd = glob_syndrome(a, w, bit);                                        // :2653-2660
         int steps = 0;
         if (synd != 0) {
             while (steps < a.maxiter) {
@@ -281,10 +304,7 @@ __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArg
                     const int e0 = a.row_start[j], e1 = a.row_start[j + 1], rw = e1 - e0;
                     for (int k = threadIdx.x; k < M; k += (int)blockDim.x) {
                         for (int e = e0; e < e1; ++e) {                             // :2676-2697
-                            const uint32_t d = a.edges[e];
-                            int i = k + (int)(d & 0xffffu);
-                            if (i >= M) i -= M;
-                            const double x = w.soft[(int)(d >> 16) * M + i];
+                            const double x = w.soft[var_idx(a.edges[e], k, M)];
                             const double aa = Z[(size_t)e * M + k];
                             double v = x * (1.0 - aa) / (aa + x - 2.0 * aa * x);    // rho = gamma - lambda
                             if (v < TT) v = TT;
@@ -309,21 +329,18 @@ __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArg
                             Z[(size_t)(e0 + i) * M + k] = q;
                         }
                         for (int e = e0; e < e1; ++e) {                             // :2707-2720
-                            const uint32_t d = a.edges[e];
-                            int i = k + (int)(d & 0xffffu);
-                            if (i >= M) i -= M;
                             const double y = Y[(size_t)e * M + k], q = Z[(size_t)e * M + k];
-                            w.soft[(int)(d >> 16) * M + i] = y * q / (1.0 - y - q + 2 * y * q);   // gamma = rho + lambda
+                            w.soft[var_idx(a.edges[e], k, M)] = y * q / (1.0 - y - q + 2 * y * q);   // gamma = rho + lambda
                         }
                     }
                     __syncthreads();
                 }
-                synd = syndrome();                                                  // :2723 (the value after the last layer)
+                synd = glob_syndrome(a, w, bit);                                    // :2723 (the value after the last layer)
                 steps = steps + 1;
                 if (synd == 0) break;
             }
         }
-        glob_outputs<1>(a, w, fr, synd ? -steps : steps);                        // :2734-2743 (0 when the input was a codeword)
+        glob_outputs(a, fr, synd ? -steps : steps, bit, [=](int v) { return w.soft[v]; });   // :2734-2743 (0 when the input was a codeword)
         __syncthreads();
     }
 }
@@ -336,6 +353,8 @@ __global__ void __launch_bounds__(kGlobThreads) tasp_global_kernel(const GlobArg
 __global__ void __launch_bounds__(kGlobThreads) lche_global_kernel(const GlobArgs g) {
     namespace E = ldpc_spec::lche;
     const DecArgs &a = g.d;
+    // This kernel keeps its own prologue, syndrome and edge decode: with glob_frame, glob_syndrome and var_idx it was 1 % slower
+    // (profiles/global_tier_refactor_time.txt); as written here its instructions are the ones it had before the helpers existed.
     const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
     const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
     double *const Z = w.tmp;
@@ -396,7 +415,7 @@ __global__ void __launch_bounds__(kGlobThreads) lche_global_kernel(const GlobArg
                 if (synd == 0) break;
             }
         }
-        glob_outputs(a, w, fr, synd ? -steps : steps);                              // :3005-3011 (0 when the input was a codeword)
+        glob_outputs(a, fr, synd ? -steps : steps, [=](int v) { return w.soft[v] < 0; }, [=](int v) { return w.soft[v]; });   // :3005-3011 (0 when the input was a codeword)
         __syncthreads();
     }
 }
@@ -405,26 +424,10 @@ __global__ void __launch_bounds__(kGlobThreads) lche_global_kernel(const GlobArg
 // the workspace: ZZ[e][t] per edge and variable position, yd / soft per variable, the check products in m1[].
 __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
+    const GlobFrame w = glob_frame(g, 1);
+    const int M = w.M, N = w.N, R = w.R, ne = w.ne;
     double *const ZZ = w.tmp, *const yd = w.aux, *const S = w.m1;
-    auto mind = [](double x, double y) { return x < y ? x : y; };   // decoders.cpp:104-105
-    auto maxd = [](double x, double y) { return x < y ? y : x; };
-    auto syndrome = [&]() -> int {                                                  // :1964-2002 / :2129-2149
-        int fail = 0;
-        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-            const int j = chk / M, n = chk - j * M;
-            int synd = 0;
-            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                const uint32_t d = a.edges[e];
-                int i = n + (int)(d & 0xffffu);
-                if (i >= M) i -= M;
-                synd ^= (int)(w.soft[(int)(d >> 16) * M + i] < 1.0);
-            }
-            fail |= synd;
-        }
-        return __syncthreads_or(fail);
-    };
+    const auto bit = [=](int v) { return w.soft[v] < 1.0; };                        // the syndromes :1964-2002 / :2129-2149; decword[] :2172
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                       // :1947-1951
             const double yl = maxd(mind(a.llr[fr * N + v], 20.0), -20.0);
@@ -433,7 +436,7 @@ __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs 
         for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) ZZ[i] = 1.0;   // :1957-1959
         __syncthreads();
         int res = -a.maxiter;
-        bool conv = syndrome() == 0;
+        bool conv = glob_syndrome(a, w, bit) == 0;
         if (conv) res = 0;
         for (int iter = 0; !conv && iter < a.maxiter; ++iter) {
             for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                   // phase A :2017-2060
@@ -453,11 +456,7 @@ __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs 
             for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {             // phase B :2047-2050
                 const int j = chk / M, n = chk - j * M;
                 double s = 1.0;
-                for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                    int i = n + (int)(a.edges[e] & 0xffffu);
-                    if (i >= M) i -= M;
-                    s *= ZZ[(size_t)e * M + i];
-                }
+                for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) s *= ZZ[(size_t)e * M + var_pos(a.edges[e], n, M)];
                 S[chk] = s;
             }
             __syncthreads();
@@ -466,9 +465,7 @@ __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs 
                 double soft = yd[v];
                 for (int u = a.col_start[k]; u < a.col_start[k + 1]; ++u) {
                     const uint32_t d = a.col_edges[u];
-                    const int j = (int)(d >> 16), c = (int)(d & 0xffffu);
-                    int nn = t - c;
-                    if (nn < 0) nn += M;
+                    const int j = (int)(d >> 16), nn = chk_pos(d, t, M);
                     const size_t zi = (size_t)a.col_slot[u] * M + t;
                     double A = S[j * M + nn] / ZZ[zi];
                     A = (1 + A) / (1 - A);
@@ -479,9 +476,9 @@ __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs 
                 w.soft[v] = soft;
             }
             __syncthreads();
-            if (syndrome() == 0) { conv = true; res = iter + 1; }                   // :2151-2166
+            if (glob_syndrome(a, w, bit) == 0) { conv = true; res = iter + 1; }     // :2151-2166
         }
-        glob_outputs<2>(a, w, fr, res);
+        glob_outputs(a, fr, res, bit, [=](int v) { return w.soft[v]; });
         __syncthreads();
     }
 }
@@ -491,8 +488,8 @@ __global__ void __launch_bounds__(kGlobThreads) sp_global_kernel(const GlobArgs 
 // Workspace: soft / iy as ints in the soft / aux arrays, min1 / min2 as ints in m1 / m2.
 __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 0);
+    const GlobFrame w = glob_frame(g, 0);
+    const int M = w.M, N = w.N, R = w.R;
     int *const soft = reinterpret_cast<int *>(w.soft), *const iy = reinterpret_cast<int *>(w.aux);
     int *const m1 = reinterpret_cast<int *>(w.m1), *const m2 = reinterpret_cast<int *>(w.m2);
     const int max_data = (1 << (a.ims_dbits - 1)) - 1;   // :5445
@@ -510,8 +507,7 @@ __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs
             const int ival = (int)(short)floor(val * max_quant / a.ims_thr + 0.5);
             iy[v] = sign ? -ival : ival;
         }
-        for (int c = threadIdx.x; c < R; c += (int)blockDim.x) { m1[c] = 0; m2[c] = 0; w.pos[c] = 0; w.par[c] = 0; }   // :5462-5470
-        for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) w.sgn[i] = 0;
+        glob_reset_records(w, m1, m2);                                              // :5462-5470
         __syncthreads();
         int res = -a.maxiter;
         for (int iter = 0; iter < a.maxiter; ++iter) {
@@ -520,9 +516,7 @@ __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs
                 int acc = 0;
                 for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {         // block rows ascending: saturation after EVERY add (:5568)
                     const uint32_t d = a.col_edges[q];
-                    const int j = (int)(d >> 16), c = (int)(d & 0xffffu), e = (int)a.col_slot[q];
-                    int n = i - c;
-                    if (n < 0) n += M;
+                    const int j = (int)(d >> 16), e = (int)a.col_slot[q], n = chk_pos(d, i, M);
                     const int chk = j * M + n;
                     int tmp = w.pos[chk] == e - a.row_start[j] ? m2[chk] : m1[chk];
                     tmp = (tmp * ialpha) >> 4;                                       // :5554
@@ -541,10 +535,7 @@ __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs
                 int nm1 = max_data, nm2 = max_data, np = 0, synd = 0;
                 uint8_t npar = 0;
                 for (int e = e0; e < e1; ++e) {
-                    const uint32_t d = a.edges[e];
-                    int i = n + (int)(d & 0xffffu);
-                    if (i >= M) i -= M;
-                    const int r = soft[(int)(d >> 16) * M + i];
+                    const int r = soft[var_idx(a.edges[e], n, M)];
                     synd ^= (int)(r < 0);
                     const int val = ((po == e - e0 ? o2 : o1) * ialpha) >> 4;       // :5640
                     const int t = (w.sgn[(size_t)e * M + n] ^ pa) ? -val : val;
@@ -562,16 +553,7 @@ __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs
             }
             if (!__syncthreads_or(fail)) { res = iter + 1; break; }                 // :5684-5689
         }
-        if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
-        if (a.hard) {
-            for (int wd = threadIdx.x; wd < a.hard_words; wd += (int)blockDim.x) {
-                uint32_t bits = 0;
-                for (int b = 0; b < 32; ++b) if (32 * wd + b < N) bits |= (uint32_t)(soft[32 * wd + b] < 0) << b;
-                a.hard[fr * a.hard_words + wd] = bits;
-            }
-        }
-        if (a.soft_out)
-            for (int v = threadIdx.x; v < N; v += (int)blockDim.x) a.soft_out[fr * N + v] = (double)soft[v];
+        glob_outputs(a, fr, res, [=](int v) { return soft[v] < 0; }, [=](int v) { return (double)soft[v]; });
         __syncthreads();
     }
 }
@@ -582,27 +564,11 @@ __global__ void __launch_bounds__(kGlobThreads) ims_global_kernel(const GlobArgs
 // backward products; channel P(bit = 1) in aux, a-posteriori values in soft.
 __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 3);
+    const GlobFrame w = glob_frame(g, 3);
+    const int M = w.M, N = w.N, R = w.R, ne = w.ne;
     const size_t EM = glob_align(sizeof(double) * (size_t)ne * M) / sizeof(double);
     double *const ST = w.tmp, *const SF = w.tmp + EM, *const SB = w.tmp + 2 * EM, *const p1ch = w.aux;
-    auto mind = [](double x, double y) { return x < y ? x : y; };
-    auto maxd = [](double x, double y) { return x < y ? y : x; };
-    auto syndrome = [&]() -> int {                                                  // check_syndrome_thr :2274-2306, thr 0.5
-        int fail = 0;
-        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-            const int j = chk / M, n = chk - j * M;
-            int synd = 0;
-            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                const uint32_t d = a.edges[e];
-                int i = n + (int)(d & 0xffffu);
-                if (i >= M) i -= M;
-                synd ^= (int)(w.soft[(int)(d >> 16) * M + i] > 0.5);
-            }
-            fail |= synd;
-        }
-        return __syncthreads_or(fail);
-    };
+    const auto bit = [=](int v) { return w.soft[v] > 0.5; };                        // check_syndrome_thr :2274-2306, thr 0.5; the decision too
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                    // :2351-2379
             const int k = v / M, t = v - k * M;
@@ -611,14 +577,11 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
             const double e0 = ldpc_spec::exp_glibc(y), e1 = ldpc_spec::exp_glibc(-y);
             const double p = e1 / (e0 + e1);
             p1ch[v] = w.soft[v] = p;
-            for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {             // state <- rotated channel probability
-                int nn = t - (int)(a.col_edges[q] & 0xffffu);
-                if (nn < 0) nn += M;
-                ST[(size_t)a.col_slot[q] * M + nn] = p;
-            }
+            for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q)               // state <- rotated channel probability
+                ST[(size_t)a.col_slot[q] * M + chk_pos(a.col_edges[q], t, M)] = p;
         }
         __syncthreads();
-        int synd = syndrome();                                                      // :2393-2399
+        int synd = glob_syndrome(a, w, bit);                                        // :2393-2399
         int steps = 0;
         while (synd != 0 && steps < a.maxiter) {
             for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {          // check nodes: map_bin(&state[0][i*m+k], rw, r) :2191-2228
@@ -643,9 +606,7 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
                 for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {
                     const int k = v / M, t = v - k * M;
                     const int q0 = a.col_start[k], q1 = q0 + 1;                     // hci[i][0] < hci[i][1]: rows ascending
-                    int n0 = t - (int)(a.col_edges[q0] & 0xffffu), n1 = t - (int)(a.col_edges[q1] & 0xffffu);
-                    if (n0 < 0) n0 += M;
-                    if (n1 < 0) n1 += M;
+                    const int n0 = chk_pos(a.col_edges[q0], t, M), n1 = chk_pos(a.col_edges[q1], t, M);
                     const size_t z0 = (size_t)a.col_slot[q0] * M + n0, z1 = (size_t)a.col_slot[q1] * M + n1;
                     const double d0 = ST[z0], d1 = ST[z1];                          // data0[k], data1[k] :2449-2450
                     double p1 = p1ch[v];
@@ -665,18 +626,14 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
                 const int k = v / M, t = v - k * M;
                 double P1 = p1ch[v], P0 = 1 - p1ch[v];
                 for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {         // rows ascending
-                    int nn = t - (int)(a.col_edges[q] & 0xffffu);
-                    if (nn < 0) nn += M;
-                    const double d = ST[(size_t)a.col_slot[q] * M + nn];
+                    const double d = ST[(size_t)a.col_slot[q] * M + chk_pos(a.col_edges[q], t, M)];
                     P1 *= d;
                     P0 *= 1 - d;
                 }
                 const double so = P1 / (P0 + P1);
                 w.soft[v] = so;
                 for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {
-                    int nn = t - (int)(a.col_edges[q] & 0xffffu);
-                    if (nn < 0) nn += M;
-                    const size_t zi = (size_t)a.col_slot[q] * M + nn;
+                    const size_t zi = (size_t)a.col_slot[q] * M + chk_pos(a.col_edges[q], t, M);
                     const double sos = ST[zi];
                     const double p1 = so / sos;
                     const double p0 = (1 - so) / (1 - sos);
@@ -685,10 +642,10 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
                 }
             }
             __syncthreads();
-            synd = syndrome();                                                      // :2566
+            synd = glob_syndrome(a, w, bit);                                        // :2566
             steps = steps + 1;
         }
-        glob_outputs<1>(a, w, fr, synd ? -steps : steps);                           // 0: codeword at the input; converged after `steps`; else -steps
+        glob_outputs(a, fr, synd ? -steps : steps, bit, [=](int v) { return w.soft[v]; });   // 0: codeword at the input; converged after `steps`; else -steps
         __syncthreads();
     }
 }
@@ -700,39 +657,22 @@ __global__ void __launch_bounds__(kGlobThreads) asp_global_kernel(const GlobArgs
 __global__ void __launch_bounds__(kGlobThreads) iasp_global_kernel(const GlobArgs g) {
     namespace I = ldpc_spec::iasp;
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
+    const GlobFrame w = glob_frame(g, 1);
+    const int M = w.M, N = w.N, R = w.R, ne = w.ne;
     uint16_t *const ST = reinterpret_cast<uint16_t *>(w.tmp);
     int16_t *const SF = reinterpret_cast<int16_t *>(ST + (size_t)ne * M);          // 4 B per slot of the 8 B edge array
     uint16_t *const so = reinterpret_cast<uint16_t *>(w.soft), *const ych = reinterpret_cast<uint16_t *>(w.aux);
-    auto syndrome = [&]() -> int {                                                  // icheck_syndrome :3772-3803
-        int fail = 0;
-        for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-            const int j = chk / M, n = chk - j * M;
-            int synd = 0;
-            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                const uint32_t d = a.edges[e];
-                int i = n + (int)(d & 0xffffu);
-                if (i >= M) i -= M;
-                synd ^= so[(int)(d >> 16) * M + i] >> 15;
-            }
-            fail |= synd;
-        }
-        return __syncthreads_or(fail);
-    };
+    const auto bit = [=](int v) { return so[v] >> 15; };                            // icheck_syndrome :3772-3803; decision 1 of imake_output
     for (long long fr = blockIdx.x; fr < a.B; fr += gridDim.x) {
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                    // :3858-3897
             const int k = v / M, t = v - k * M;
             const uint32_t q = I::q12(I::prior(a.llr[fr * N + v]));
-            for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {             // state <- rotated Q12 value
-                int nn = t - (int)(a.col_edges[c] & 0xffffu);
-                if (nn < 0) nn += M;
-                ST[(size_t)a.col_slot[c] * M + nn] = (uint16_t)q;
-            }
+            for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c)               // state <- rotated Q12 value
+                ST[(size_t)a.col_slot[c] * M + chk_pos(a.col_edges[c], t, M)] = (uint16_t)q;
             so[v] = ych[v] = (uint16_t)(q << 4);                                    // then the words, Q16
         }
         __syncthreads();
-        int synd = syndrome();                                                      // :3899-3906
+        int synd = glob_syndrome(a, w, bit);                                        // :3899-3906
         int steps = 0;
         while (synd != 0 && steps < a.maxiter) {
             for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {          // imap_bin :2235-2271, any row weight >= 2
@@ -758,9 +698,7 @@ __global__ void __launch_bounds__(kGlobThreads) iasp_global_kernel(const GlobArg
                 for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {            // :3915-3977
                     const int k = v / M, t = v - k * M;
                     const int c0 = a.col_start[k], c1 = c0 + 1;                     // hci[i][0] < hci[i][1]: rows ascending
-                    int n0 = t - (int)(a.col_edges[c0] & 0xffffu), n1 = t - (int)(a.col_edges[c1] & 0xffffu);
-                    if (n0 < 0) n0 += M;
-                    if (n1 < 0) n1 += M;
+                    const int n0 = chk_pos(a.col_edges[c0], t, M), n1 = chk_pos(a.col_edges[c1], t, M);
                     const size_t z0 = (size_t)a.col_slot[c0] * M + n0, z1 = (size_t)a.col_slot[c1] * M + n1;
                     uint32_t s, d0, d1;
                     I::cw2(ych[v], ST[z0], ST[z1], s, d0, d1);
@@ -772,35 +710,20 @@ __global__ void __launch_bounds__(kGlobThreads) iasp_global_kernel(const GlobArg
             for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {                // :3978-4100
                 const int k = v / M, t = v - k * M;
                 uint32_t P1 = (uint32_t)ych[v] << 16, P0 = (65536u - ych[v]) << 16;
-                for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {         // rows ascending
-                    int nn = t - (int)(a.col_edges[c] & 0xffffu);
-                    if (nn < 0) nn += M;
-                    I::col_mul(P1, P0, ST[(size_t)a.col_slot[c] * M + nn]);
-                }
+                for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c)           // rows ascending
+                    I::col_mul(P1, P0, ST[(size_t)a.col_slot[c] * M + chk_pos(a.col_edges[c], t, M)]);
                 const uint32_t s = I::col_soft(P1, P0);
                 so[v] = (uint16_t)s;
                 for (int c = a.col_start[k]; c < a.col_start[k + 1]; ++c) {
-                    int nn = t - (int)(a.col_edges[c] & 0xffffu);
-                    if (nn < 0) nn += M;
-                    const size_t zi = (size_t)a.col_slot[c] * M + nn;
+                    const size_t zi = (size_t)a.col_slot[c] * M + chk_pos(a.col_edges[c], t, M);
                     ST[zi] = (uint16_t)I::local_update(s, ST[zi]);
                 }
             }
             __syncthreads();
-            synd = syndrome();                                                      // :4104-4113
+            synd = glob_syndrome(a, w, bit);                                        // :4104-4113
             steps = steps + 1;
         }
-        const int res = synd ? -steps : steps;
-        if (threadIdx.x == 0 && a.iters) a.iters[fr] = res;
-        if (a.hard) {
-            for (int wd = threadIdx.x; wd < a.hard_words; wd += (int)blockDim.x) {
-                uint32_t bits = 0;
-                for (int b = 0; b < 32; ++b) if (32 * wd + b < N) bits |= (uint32_t)(so[32 * wd + b] >> 15) << b;
-                a.hard[fr * a.hard_words + wd] = bits;
-            }
-        }
-        if (a.soft_out)                                                             // imake_output :3805-3820, decision 1
-            for (int v = threadIdx.x; v < N; v += (int)blockDim.x) a.soft_out[fr * N + v] = (double)so[v] / 65536.0;
+        glob_outputs(a, fr, synd ? -steps : steps, bit, [=](int v) { return (double)so[v] / 65536.0; });   // imake_output :3805-3820, decision 1
         __syncthreads();
     }
 }
@@ -811,39 +734,24 @@ __global__ void __launch_bounds__(kGlobThreads) iasp_global_kernel(const GlobArg
 // (stale syndrome in, syndrome left behind out, re-decode passes) works exactly as in the resident kernel.
 __global__ void __launch_bounds__(kGlobThreads) bp_global_kernel(const GlobArgs g) {
     const DecArgs &a = g.d;
-    const int M = a.M, N = a.N, R = a.rh * M, ne = g.ne, CH = (M + 63) / 64;
-    const GlobView w = glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, N, R, ne, M, 1);
+    const GlobFrame w = glob_frame(g, 1);
+    const int M = w.M, N = w.N, R = w.R, ne = w.ne, CH = (M + 63) / 64, SW = a.rh * CH;
     double *const ZZ = w.tmp, *const yd = w.aux, *const S = w.m1;
     uint8_t *const BB = w.sgn, *const bs = w.par;
     uint8_t *const left = reinterpret_cast<uint8_t *>(w.pos);                       // [R] syndrome bits as last computed (upstream's st->syndr)
-    auto mind = [](double x, double y) { return x < y ? x : y; };
-    auto maxd = [](double x, double y) { return x < y ? y : x; };
+    const unsigned long long *const stale = reinterpret_cast<const unsigned long long *>(g.stale);
+    const auto bit = [=](int v) { return w.soft[v] < 0; };                          // the syndromes :1742-1766 / :1869-1893 and the decision
+    const auto keep = [=](int chk, int sy) { left[chk] = (uint8_t)sy; };
     for (long long slot = blockIdx.x; slot < g.slots; slot += gridDim.x) {
         const long long fr = g.frame_idx ? g.frame_idx[slot] : slot;
-        auto syndrome = [&](bool with_stale) -> int {                               // :1742-1766 / :1869-1893
-            int fail = 0;
-            for (int chk = threadIdx.x; chk < R; chk += (int)blockDim.x) {
-                const int j = chk / M, n = chk - j * M;
-                int sy = 0;
-                if (with_stale && g.stale) sy = (int)((reinterpret_cast<const unsigned long long *>(g.stale)[fr * (a.rh * CH) + j * CH + (n >> 6)] >> (n & 63)) & 1ull);
-                for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                    const uint32_t d = a.edges[e];
-                    int i = n + (int)(d & 0xffffu);
-                    if (i >= M) i -= M;
-                    sy ^= (int)(w.soft[(int)(d >> 16) * M + i] < 0);
-                }
-                left[chk] = (uint8_t)sy;
-                fail |= sy;
-            }
-            return __syncthreads_or(fail);
-        };
         for (int v = threadIdx.x; v < N; v += (int)blockDim.x) {
             const double y = maxd(mind(a.llr[fr * N + v], 20.0), -20.0);            // :1738 INPUT_LIMIT
             yd[v] = w.soft[v] = y;
         }
         for (size_t i = threadIdx.x; i < (size_t)ne * M; i += (int)blockDim.x) ZZ[i] = 0.0;   // :1731-1733
         __syncthreads();
-        int fail = syndrome(true);
+        int fail = glob_syndrome(a, w, bit, keep,                                   // :1742-1766, on top of what the previous frame left behind
+                                 [=](int j, int n) { return stale ? (int)((stale[fr * SW + j * CH + (n >> 6)] >> (n & 63)) & 1ull) : 0; });
         // re-decode pass: nothing can change unless the frame was a codeword at its input (see bp_body)
         if (g.frame_idx && fail && a.iters && a.iters[fr] != 0) { __syncthreads(); continue; }
         int iter = 0;
@@ -864,8 +772,7 @@ __global__ void __launch_bounds__(kGlobThreads) bp_global_kernel(const GlobArgs 
                 double s = 0.0;
                 unsigned b = 0;
                 for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                    int i = n + (int)(a.edges[e] & 0xffffu);
-                    if (i >= M) i -= M;
+                    const int i = var_pos(a.edges[e], n, M);
                     s += ZZ[(size_t)e * M + i];
                     b ^= BB[(size_t)e * M + i];
                 }
@@ -878,9 +785,7 @@ __global__ void __launch_bounds__(kGlobThreads) bp_global_kernel(const GlobArgs 
                 double soft = yd[v];
                 for (int q = a.col_start[k]; q < a.col_start[k + 1]; ++q) {         // rows ascending
                     const uint32_t d = a.col_edges[q];
-                    const int j = (int)(d >> 16);
-                    int nn = t - (int)(d & 0xffffu);
-                    if (nn < 0) nn += M;
+                    const int j = (int)(d >> 16), nn = chk_pos(d, t, M);
                     const size_t zi = (size_t)a.col_slot[q] * M + t;
                     double A = ldpc_spec::exp_glibc_wide(S[j * M + nn] - ZZ[zi], ldpc_spec::kExpTab);
                     const int b = bs[j * M + nn] ^ BB[zi];
@@ -892,18 +797,18 @@ __global__ void __launch_bounds__(kGlobThreads) bp_global_kernel(const GlobArgs 
                 w.soft[v] = soft;
             }
             __syncthreads();
-            fail = syndrome(false);
+            fail = glob_syndrome(a, w, bit, keep, [](int, int) { return 0; });      // :1869-1893
             iter = iter + 1;
         }
         if (g.synd_out) {
-            for (int u = threadIdx.x; u < a.rh * CH; u += (int)blockDim.x) {        // one u64 per block row and 64-lane chunk
+            for (int u = threadIdx.x; u < SW; u += (int)blockDim.x) {               // one u64 per block row and 64-lane chunk
                 const int j = u / CH, ch = u - j * CH;
                 unsigned long long bits = 0;
                 for (int l = 0; l < 64 && ch * 64 + l < M; ++l) bits |= (unsigned long long)left[j * M + ch * 64 + l] << l;
-                reinterpret_cast<unsigned long long *>(g.synd_out)[fr * (a.rh * CH) + u] = bits;
+                reinterpret_cast<unsigned long long *>(g.synd_out)[fr * SW + u] = bits;
             }
         }
-        glob_outputs<0>(a, w, fr, fail ? -iter : iter);
+        glob_outputs(a, fr, fail ? -iter : iter, bit, [=](int v) { return w.soft[v]; });
         __syncthreads();
     }
 }
