@@ -476,7 +476,8 @@ constexpr int ms_m64_keep_rows(int budget) {
 // kind: profiles/r19_flagship_isa_histogram.txt, profiles/r13_flagship_variants.txt.)
 constexpr int kMsM64KeepEdges = 68, kMsM64KeepRowsOfExample = 13;
 // What the carried rows share the 256 registers with grows with the code: 5 per block row with a record, 2 per block column in
-// flight in STATE2 (at most 24 columns of channel values) and 2 per slot of the widest row (STATE3 reads a whole row before it
+// flight in STATE2 (taken as min(NH, 24) columns of channel values, the window of the schedule of that round; what really was in
+// flight is ms_m64_y_in_flight_r23 below, 17 for the example code, and since round 25 it is kMsM64YDepth) and 2 per slot of the widest row (STATE3 reads a whole row before it
 // uses it).  The example code (16 rows, 24 columns, width 8) leaves 2 * 68 - 5 * 13 = 71 registers to the carried rows on top of
 // that; a code that needs more for the rest gives the difference back, register for register.  A code of 30 block rows is left
 // with nothing and carries no row: such codes run as they did before any value was kept.  Checked by cross-compiling: the shipped
@@ -494,16 +495,77 @@ constexpr int ms_m64_keep_budget() {
 // Which carried rows form their magnitudes from prefix and suffix minima (see `keep` in ms_m64_body): rows [0, KP), the rows
 // [KP, KR) select between min1 and min2 by value equality as round 20 did.  Such a row holds its RW v2c values and RW - 1 prefix
 // minima at once, about 2 RW - 2 registers more at its peak than the equality form; STATE3 has no channel value in flight, and the
-// peak of the body stays in STATE2.  KP = KR for every code: checked by cross-compiling the same instances as the budget rule
+// peak of the body stayed in STATE2 (until round 25: ms_m64_carry_rows below).  KP = KR for every code: checked by cross-compiling the same instances as the budget rule
 // (none spills a VGPR or uses scratch, profiles/r23_flagship_isa_histogram.txt).  KPCAP lowers it for tools/ab_flagship.hip.
 template <int KPCAP>
 constexpr int ms_m64_prefix_rows(int kr) { return KPCAP < kr ? (KPCAP > 0 ? KPCAP : 0) : kr; }
 
-template <class C, int KPCAP = 1 << 30>
+// STATE2 of ms_m64_body loads the channel LLRs of the block columns that are NOT local, in ascending order (a local column takes
+// its channel value in STATE3): how many there are, and the n-th of them (or -1).  A block column without an edge counts: STATE2
+// still forms its soft value.
+template <class C>
+constexpr int ms_m64_nonlocal_cols() {
+    int n = 0;
+    for (int k = 0; k < C::NH; ++k) n += ms_m64_local_col<C>(k) ? 0 : 1;
+    return n;
+}
+template <class C>
+constexpr int ms_m64_nonlocal_col(int n) {
+    for (int k = 0; k < C::NH; ++k)
+        if (!ms_m64_local_col<C>(k) && n-- == 0) return k;
+    return -1;
+}
+// The loads are a stream over those columns, kMsM64YDepth of them ahead: the first min(depth, count) are issued together, two
+// more at every second column that is processed, so at most depth + 1 channel values (2 VGPRs each) are in flight.  Until
+// round 25 the schedule ran over ALL block columns -- 16 at once, then 8 more at each group of 8, 16 ahead -- and bounded nothing
+// once the first columns of a code were local: what was in flight at its peak is ms_m64_y_in_flight_r23.
+constexpr int kMsM64YDepth = 8;
+template <class C>
+constexpr int ms_m64_y_in_flight_r23() {
+    int peak = 0;
+    for (int k0 = 0; k0 < C::NH; k0 += 8) {   // at group k0 the columns below k0 + 24 are loaded, those below k0 are used up
+        int n = 0;
+        for (int k = k0; k < C::NH && k < k0 + 24; ++k) n += ms_m64_local_col<C>(k) ? 0 : 1;
+        peak = n > peak ? n : peak;
+    }
+    return peak;
+}
+// The block rows ms_m64_body carries: round 20's rule (ms_m64_keep_rows of ms_m64_keep_budget, which stay as they were: the term
+// of round 20) with what the stream gives back added to its budget -- two registers per channel value that is no longer in flight
+// at STATE2's peak, ms_m64_y_in_flight_r23 less min(depth, count), derived from the code and the depth, not a constant of the
+// example code.  With those registers STATE2 is no longer the peak of the body; STATE3 of the widest row is.  There a carried
+// row holds 2 VGPRs for EVERY edge, those of local columns included (the value formed in STATE3 of row j waits for the column's
+// first block row of the next iteration), a row with a record 5, and the row at work its v2c values and prefix minima (4 WMAX - 2).
+// Rows beyond round 20's count are carried while that sum stays within kMsM64State3Regs: 243 for 15 block rows of the example code
+// (255 VGPRs, no spill), 254 for all 16 (6 spilled, 20 B of scratch: profiles/r25_flagship_isa_histogram.txt).  A code that
+// carries no row under round 20's rule -- its records alone use up the registers -- still carries none: the two 30 x 60 codes of
+// that table spill with rows carried (the one of the tests 5 VGPRs at 12 rows, the synthetic one 38 at fewer) and do not without.
+constexpr int kMsM64State3Regs = 244;
+template <class C>
+constexpr int ms_m64_state3_regs(int rows) {
+    int e = 0;
+    for (int j = 0; j < rows; ++j) e += C::RW[j];
+    return 2 * e + 5 * (C::RH - rows) + 4 * C::WMAX - 2;
+}
+template <class C, int YD>
+constexpr int ms_m64_carry_rows() {
+    constexpr int nl = ms_m64_nonlocal_cols<C>(), depth = YD < nl ? YD : nl, was = ms_m64_y_in_flight_r23<C>();
+    constexpr int base = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());
+    constexpr int more = base > 0 ? ms_m64_keep_rows<C>(ms_m64_keep_budget<C>() + 2 * (was > depth ? was - depth : 0)) : 0;
+    int rows = base;
+    while (rows < more && ms_m64_state3_regs<C>(rows + 1) <= kMsM64State3Regs) ++rows;
+    return rows;
+}
+
+// KPCAP, YD, YROW and KRSET are switches for tools/ab_flagship.hip, defaulted to what ships: the cap of ms_m64_prefix_rows; the
+// depth of STATE2's stream of channel loads; where its first group is issued (-1: at the start of STATE2, j >= 0: after block row
+// j of STATE1); the number of carried rows (-1: ms_m64_carry_rows).
+template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
+    static_assert(YD >= 1 && YROW >= -1 && YROW < C::RH && KRSET <= C::RH, "ms_m64_body: switch out of range");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
-    constexpr int KR = ms_m64_keep_rows<C>(ms_m64_keep_budget<C>());   // block rows [0, KR) carry their decoded c2v values, see `keep`
+    constexpr int KR = KRSET >= 0 ? KRSET : ms_m64_carry_rows<C, YD>();   // block rows [0, KR) carry their decoded c2v values, see `keep`
     // rows [0, KP) of them by prefix / suffix minima.  A type, not a second constant: STATE3's closure would capture the constant, and
     // with that one pointer more a 30 x 60 protograph that carries no row spilled 240 VGPRs (profiles/r23_flagship_isa_histogram.txt).
     typedef IC<ms_m64_prefix_rows<KPCAP>(KR)> KP;
@@ -532,9 +594,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // it, STATE3 forms its soft value in a register at the column's first block row, see there.
 
   while (fr < a.nframes) {   // one pass without a queue
-    const double *const yrow = a.llr + fr * N + lane;  // this frame's channel LLRs, variable (k, lane) at yrow[64 k]
-    // The same values as a buffer, for the local columns: resource and column offset are scalars, the lane's offset is lane8, so
-    // a load costs no address arithmetic on the vector unit (a 64-bit address per block row did: 3 instructions per column).
+    // This frame's channel LLRs as a buffer, variable (k, lane) at byte 512 k + lane8: resource and column offset are scalars, the
+    // lane's offset is lane8, so a load costs no address arithmetic on the vector unit and no 64-bit address is held in VGPRs
+    // across the iterations (STATE2 read through such a pointer until round 25: 2 VGPRs, 18 address instructions per iteration).
     const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
 
     // What a block row hands from STATE3 of one iteration to the next iteration, in one of two forms:
@@ -556,18 +618,24 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     for (int iter = 0; iter < a.maxiter; ++iter) {
         // The channel LLRs are needed only in STATE2.  Instead of pinning 64 VGPRs for the whole kernel they are
         // re-read every iteration (16 KiB per frame: L2 / Infinity-Cache hits after the first pass), and not before
-        // STATE2 itself: 16 block columns between STATE1 and STATE2, then 8 more at each group of 8 columns, 16 columns
-        // ahead.  At most 24 columns (48 VGPRs) are in flight, and none during STATE1 and STATE3 -- the registers go to
-        // `keep`.  (Until round 13 all 32 columns were loaded here, "under STATE1's ALU work"; the other wave of the SIMD
-        // covers the latency just as well: profiles/r13_flagship_variants.txt, placements (a), (b), (c).)
+        // STATE2 itself (or the last rows of STATE1, YROW): a stream over the columns that are not local, YD of them ahead
+        // (ms_m64_nonlocal_col, kMsM64YDepth).  At most YD channel values (2 YD VGPRs) are in flight, and none during
+        // STATE3 -- the registers go to `keep`.  (Until round 13 all 32 columns were loaded here, "under STATE1's ALU work";
+        // the other wave of the SIMD covers the latency just as well: profiles/r13_flagship_variants.txt, placements (a),
+        // (b), (c).  Until round 25 the schedule counted local columns too: ms_m64_y_in_flight_r23.)
+        constexpr int NL = ms_m64_nonlocal_cols<C>(), YAHEAD = YD < NL ? YD : NL;
         double y[NH];
-        auto load_y = [&](auto K0, auto K1) {   // columns [K0, min(K1, NH))
-            int yo = 0;
-            asm volatile("" : "+v"(yo));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
-            static_for<decltype(K0)::value, (decltype(K1)::value < NH ? decltype(K1)::value : NH)>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                if constexpr (!ms_m64_local_col<C>(k)) y[k] = yrow[yo + k * 64];
-            });
+        auto load_y = [&](auto N0, auto N1) {   // non-local columns number [N0, min(N1, NL))
+            if constexpr (decltype(N0)::value < NL && decltype(N0)::value < decltype(N1)::value) {
+u32 so = 0;
+                asm volatile("" : "+s"(so));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
+                static_for<decltype(N0)::value, (decltype(N1)::value < NL ? decltype(N1)::value : NL)>([&](auto I) {
+                    constexpr int k = ms_m64_nonlocal_col<C>(decltype(I)::value);
+                    typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
+                    y[k] = mk(v.y, v.x);
+                });
+            }
         };
         // The channel values of the local columns whose first block row is JN: STATE3 loads them one block row ahead.
         double yl[NH], soft_l[NH];
@@ -659,18 +727,22 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 });
             }
             __builtin_amdgcn_sched_barrier(0);  // one block row at a time: keeps the live set (and the spills) small
+            if constexpr (j == YROW) {           // the stream's first group under the last rows of STATE1
+                load_y(IC<0>{}, IC<YAHEAD>{});
+                __builtin_amdgcn_sched_barrier(0);
+            }
         });
         // ---------------- STATE2 (:4670-4685): soft = y + acc*alpha (two roundings)
-        load_y(IC<0>{}, IC<16>{});
-        static_for<0, NH>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            if constexpr (k % 8 == 0 && k + 16 < NH) load_y(IC<k + 16>{}, IC<k + 24>{});
-            if constexpr (!ms_m64_local_col<C>(k)) {
-                double *p = own(K);
-                const double pr = *p * alpha;
-                *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
-            }
-            if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // 8 columns in flight, not 32 (VGPR budget)
+        // A code whose columns are all local has nothing here.  The stream goes on in pairs of columns: one opaque offset and one
+        // scheduling region per pair, so at most YAHEAD + 1 values are in flight.
+        if constexpr (YROW < 0) load_y(IC<0>{}, IC<YAHEAD>{});
+        static_for<0, NL>([&](auto I) {
+            constexpr int i = decltype(I)::value, k = ms_m64_nonlocal_col<C>(i);
+            if constexpr (i % 2 == 0) load_y(IC<i + YAHEAD>{}, IC<i + YAHEAD + 2>{});
+            double *p = own(IC<k>{});
+            const double pr = *p * alpha;
+            *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            if constexpr (i % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // YAHEAD columns in flight, not all of them (VGPR budget)
         });
         load_yl(IC<0>{});
         // ---------------- STATE3 (:4690-4755)
@@ -823,21 +895,27 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     }
 
     // ---------------- outputs
+    // The lane as the outputs use it is opaque: the NH masks `lane == k` and the lane's output addresses are formed here, after the
+    // iterations, not hoisted in front of the frame loop and held (or spilled) across it -- 2 VGPRs and 64 SGPRs that the 15th
+    // carried row of the example code needs.  Only where rows are carried: a body that carries none has the registers, and the
+    // synthetic 30 x 60 protograph, sensitive as ever (see KP above), spilled 245 VGPRs with the asm in place.
+    int ol = lane;
+    if constexpr (KR > 0) asm volatile("" : "+v"(ol));
     if (lane == 0 && a.iters) a.iters[fr] = res;
     if (a.hard) {
         u64 mine = 0ull;
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
             const u64 b = __ballot((hi32(*own(K)) >> 31) != 0);
-            if (lane == k) mine = b;
+            if (ol == k) mine = b;
         });
         // block column k = variables 64k..64k+63 = packed words 2k, 2k+1
-        if (lane < NH) reinterpret_cast<u64 *>(a.hard + fr * (N / 32))[lane] = mine;
+        if (ol < NH) reinterpret_cast<u64 *>(a.hard + fr * (N / 32))[ol] = mine;
     }
     if (a.soft_out) {
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            a.soft_out[fr * N + k * 64 + lane] = *own(K);
+            a.soft_out[fr * N + k * 64 + ol] = *own(K);
         });
     }
     if (!a.queue) break;

@@ -2,7 +2,10 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r23_flagship_variants.txt: the carried rows [0, KP) of ms_m64_body form their magnitudes from prefix and suffix
+// Results: profiles/r25_flagship_variants.txt: STATE2 of ms_m64_body streams its channel loads over the non-local block columns, YD
+// of them ahead, first group at the start of STATE2 or after a block row of STATE1 (YROW), and the body carries KR block rows -- the
+// YD, YROW and KRSET parameters of the header's body; depth 32 issues every load at once, which is what the schedule before round 25
+// amounted to on this code (the variants of round 23 below are held at that and at 13 rows).  profiles/r23_flagship_variants.txt: the carried rows [0, KP) of ms_m64_body form their magnitudes from prefix and suffix
 // minima, KP = 0 (round 20's body: every carried row selects between min1 and min2 by value equality), 9, 11 and 13 = all carried
 // rows, through the KPCAP parameter of the header's body.  Round 20's variants -- carried rows, the min1 slot by equality -- are in
 // profiles/r20_flagship_variants.txt and still switches of ms_m64_body_y here (round 19's variants -- local block columns, plain 64-bit image reads -- are in
@@ -686,13 +689,26 @@ VARIANT(k_le61,  true, true, 61, false, true, false, true)
 VARIANT(k_le68,  true, true, 68, false, true, false, true)
 VARIANT(k_lei61, true, true, 61, false, true, false, true, true)
 VARIANT(k_lei68, true, true, 68, false, true, false, true, true)
-// round 23: ms_m64_body of the header with its prefix / suffix rows capped at KPCAP block rows; 0 is the body round 20 shipped
+// round 23: ms_m64_body of the header with its prefix / suffix rows capped at KPCAP block rows; 0 is the body round 20 shipped.  Held
+// at what round 23 had otherwise: 13 carried rows, every channel load of STATE2 issued at once (depth 32)
 #define PREFIX(name, kpcap) \
-    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, kpcap>(a); }
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, kpcap, 32, -1, 13>(a); }
 PREFIX(k_p0, 0)
 PREFIX(k_p9, 9)
 PREFIX(k_p11, 11)
 PREFIX(k_p13, 13)
+// round 25: the depth of STATE2's stream of channel loads, the place of its first group and the number of carried rows
+#define STREAM(name, yd, yrow, kr) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, yd, yrow, kr>(a); }
+STREAM(k_y8_13, 8, -1, 13)
+STREAM(k_y4_13, 4, -1, 13)
+STREAM(k_y8_14, 8, -1, 14)
+STREAM(k_y4_15, 4, -1, 15)
+STREAM(k_y6_15, 6, -1, 15)
+STREAM(k_y8_15, 8, -1, 15)
+STREAM(k_y8r12_15, 8, 12, 15)
+STREAM(k_y8r15_15, 8, 15, 15)
+STREAM(k_y4r15_15, 4, 15, 15)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 
 struct Variant { const void *kern; const char *name; size_t lds; };
@@ -715,7 +731,16 @@ int main(int argc, char **argv) {
         {(const void *)k_p0, "round 20's body: 13 carried rows, none by prefix / suffix minima", L},
         {(const void *)k_p9, "prefix / suffix minima on rows 0-8, equality on rows 9-12", L},
         {(const void *)k_p11, "prefix / suffix minima on rows 0-10, equality on rows 11-12", L},
-        {(const void *)k_p13, "prefix / suffix minima on rows 0-12 (all carried rows)", L},
+        {(const void *)k_p13, "round 23's body: 13 carried rows, every channel load at once", L},
+        {(const void *)k_y8_13, "stream depth 8, 13 carried rows", L},
+        {(const void *)k_y4_13, "stream depth 4, 13 carried rows", L},
+        {(const void *)k_y8_14, "stream depth 8, 14 carried rows", L},
+        {(const void *)k_y4_15, "stream depth 4, 15 carried rows", L},
+        {(const void *)k_y6_15, "stream depth 6, 15 carried rows", L},
+        {(const void *)k_y8_15, "stream depth 8, 15 carried rows", L},
+        {(const void *)k_y8r12_15, "stream depth 8, first group after STATE1 row 12, 15 carried rows", L},
+        {(const void *)k_y8r15_15, "stream depth 8, first group after STATE1 row 15, 15 carried rows", L},
+        {(const void *)k_y4r15_15, "stream depth 4, first group after STATE1 row 15, 15 carried rows", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
     };
     constexpr int NV = sizeof var / sizeof var[0];
