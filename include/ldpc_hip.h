@@ -84,6 +84,9 @@ int ldpc_hip_set_jit_mode_thread(int mode);
 /* Name of the kernel the last ldpc_hip_decode_dev call on this context launched.  It differs from ldpc_hip_kernel_name only
  * for IMS_DEC with parameters beyond int8 (MS_DBITS > 8, MS_QBITS > 8 or alpha > 1), which run on the table-driven int32 kernel. */
 const char *ldpc_hip_last_launch(const ldpc_hip_ctx *ctx);
+/* 1 when that launch ran the instance of its kernel that holds no soft values: the M = 64 min-sum body has one (same name, same
+ * bits) and takes it when the call passes no soft_out; 0 for every other launch. */
+int ldpc_hip_last_launch_without_soft(const ldpc_hip_ctx *ctx);
 
 /* Batched replacement of the decoder entry points (decoders.h:297,299,304; dispatch bp_simulation.cpp:716-729):
  *   MS_DEC : min_sum_decod_qc_lm(st, y, decword, maxiter, decision, alpha)

@@ -18,6 +18,7 @@
     }
 
 LDPC_AOT_DECLARE(ms_spec_appendix_c_m64_kernel, 64, 2)
+LDPC_AOT_DECLARE(ms_spec_appendix_c_m64_hard_kernel, 64, 2)   // the same body without soft values: launches without soft_out
 LDPC_AOT_DECLARE(ms_spec_appendix_c_m126_kernel, 128, 2)
 LDPC_AOT_DECLARE(ms_chunk_appendix_c_m126_kernel, 64, 1)
 LDPC_AOT_DECLARE(ms_spec_appendix_c_m512_kernel, 512, 2)

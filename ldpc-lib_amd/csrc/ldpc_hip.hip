@@ -134,9 +134,11 @@ struct AotInstance {
     int threads;
     const char *name;
     bool (CodeTables::*matches)() const;
+    const void *fn_hard = nullptr;   // ms_m64_body: the instance without soft values (ms_m64_hard_body), for launches without soft_out
 };
 const AotInstance kAot[] = {
-    {LDPC_HIP_MS_DEC, (const void *)ms_spec_appendix_c_m64_kernel, 64, "ms_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>},
+    {LDPC_HIP_MS_DEC, (const void *)ms_spec_appendix_c_m64_kernel, 64, "ms_spec_appendix_c_m64_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM64>,
+     (const void *)ms_spec_appendix_c_m64_hard_kernel},
     {LDPC_HIP_MS_DEC, (const void *)ms_spec_appendix_c_m126_kernel, 128, "ms_spec_appendix_c_m126_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM126>},
     {LDPC_HIP_MS_DEC, (const void *)ms_chunk_appendix_c_m126_kernel, 64, "ms_chunk_appendix_c_m126_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM126>},
     {LDPC_HIP_MS_DEC, (const void *)ms_spec_appendix_c_m512_kernel, 512, "ms_spec_appendix_c_m512_kernel", &CodeTables::is<ldpc_spec::CodeAppendixCM512>},
@@ -253,6 +255,13 @@ struct ldpc_hip_ctx {
     // code-specialised kernel (ldpc_spec.hpp): one frame per workgroup of spec_threads threads
     const void *spec_aot = nullptr;
     const ldpc_jit::Kernel *spec_jit = nullptr;
+    // ms_m64_body has a second instance, without soft values (ms_m64_hard_body): launch_spec takes it when the caller passes no
+    // soft_out.  Ahead of time it comes with spec_aot; a hiprtc instance is compiled when a launch first needs it, not at open
+    bool spec_has_hard = false;
+    const void *spec_aot_hard = nullptr;
+    const ldpc_jit::Kernel *spec_jit_hard = nullptr;
+    std::shared_ptr<ldpc_jit::Job> jit_job_hard;   // LDPC_HIP_JIT=async: until it is ready the instance with soft values runs (identical bits)
+    std::vector<std::vector<std::pair<int, int>>> spec_rows;   // the opened code, as ldpc_jit::get takes it
     int spec_threads = 64;
     int spec_frames_per_block = 1;
     size_t spec_lds = 0;
@@ -261,11 +270,12 @@ struct ldpc_hip_ctx {
     bool global_is_fallback = false;
     // persistent launch of the one-wave-per-frame min-sum body (SpecArgs::queue)
     unsigned *d_queue = nullptr;
-    int persist_grid = 0;     // resident waves of that kernel on this device (0: not determined yet)
-    bool persist_jit = false; // ... determined for the hiprtc instance (a context may move from one to the other)
+    const void *persist_for[2] = {nullptr, nullptr};   // per instance ([1]: without soft values): the kernel or function that ...
+    int persist_grid[2] = {0, 0};                      // ... this many resident waves on this device were determined for
     std::string kernel_name;  // what this context launches (ldpc_hip_kernel_name)
     std::string generic_name; // the table-driven kernel of this decoder, if one serves this code shape
     const char *last_launch = "";  // ldpc_hip_last_launch
+    bool last_without_soft = false;  // ldpc_hip_last_launch_without_soft
     // BP_DEC: upstream's input check sees the syndrome the previous frame left in DEC_STATE::syndr (decoders.cpp:1742-1762)
     bool bp_chain = true;                 // ldpc_hip_set_bp_chain
     std::vector<uint32_t> bp_carry;       // [R/32] syndrome left behind by the last frame decoded on this context
@@ -404,7 +414,7 @@ struct ProfTimer {
 // Which code-specialised body serves this decoder / code shape, if any.  `required`: no generic kernel exists.
 struct SpecPlan { const char *body = nullptr; int threads = 0; size_t lds = 0; bool required = false; int frames_per_block = 1; };
 
-constexpr size_t kLdsBudget = 160 * 1024 - 64;   // the bodies' dynamic LDS image; the rest is the frame queue's ticket word
+constexpr size_t kLdsBudget = ldpc_spec::kMsM64LdsBudget;   // the bodies' dynamic LDS image; the rest is the frame queue's ticket word
 
 // tasp_body and lche_body, registers of a lane: its half of every row's Z (2 each), the packed LDS addresses, ~85 temporaries (ldpc_jit.hpp
 // picks one or two waves per SIMD from the same estimate); rounds 1-2 (the whole row in one lane) stopped at 144 circulants
@@ -421,7 +431,7 @@ SpecPlan plan_spec(int decoder_id, const CodeTables &t) {
     if (!t.all_cols_used || t.max_rw > 16 || t.rh > 64 || t.nh > 64) return p;
     switch (decoder_id) {
     case LDPC_HIP_MS_DEC:
-        if (M == 64) { p.body = "ms_m64_body"; p.threads = 64; p.lds = ldpc_spec::kMsM64LdsBytes((size_t)N); }
+        if (M == 64) { p.body = "ms_m64_body"; p.threads = 64; p.lds = ldpc_spec::kMsM64FrameLdsBytes((size_t)N); }   // the frame's share of the CU: the body's own rule lays it out
         else if (M <= 32) {   // several frames per wavefront
             p.body = "ms_small_body"; p.threads = 64; p.frames_per_block = 64 / M; p.lds = sizeof(double) * (size_t)N * (size_t)(64 / M);
         }
@@ -604,6 +614,32 @@ int launch_global(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d
     return glaunch(d.B, io);
 }
 
+// The hiprtc instance of ms_m64_hard_body, at the first launch that needs it: from the process cache, else compiled here
+// -- or, where the context asked for background compiles, by the worker, and until that delivers spec_jit_hard stays null and the
+// caller runs the instance with soft values.
+int jit_hard_instance(ldpc_hip_ctx *c) {
+    if (c->spec_jit_hard) return 0;
+    std::string err;
+    if (c->jit_job_hard) {
+        const int st = c->jit_job_hard->state.load(std::memory_order_acquire);
+        if (st == 0) return 0;
+        const ldpc_jit::Kernel *k = c->jit_job_hard->kernel;
+        err = c->jit_job_hard->err;
+        c->jit_job_hard.reset();
+        if (st == 1) { c->spec_jit_hard = k; return 0; }
+        return fail(LDPC_HIP_EUNSUPPORTED, "ms_m64_hard_body: no hiprtc instance (%s)", err.c_str());
+    }
+    const bool background = jit_mode_effective() == 2;
+    c->spec_jit_hard = ldpc_jit::get(c->device, "ms_m64_hard_body", c->spec_rows, c->nh, c->M, err, /*compile=*/!background, /*disk=*/false);
+    if (c->spec_jit_hard) return 0;
+    if (!background) return fail(LDPC_HIP_EUNSUPPORTED, "ms_m64_hard_body: no hiprtc instance (%s)", err.c_str());
+    auto job = std::make_shared<ldpc_jit::Job>();
+    job->device = c->device; job->nh = c->nh; job->M = c->M; job->body = "ms_m64_hard_body"; job->disk = false; job->rows = c->spec_rows;
+    ldpc_jit::Worker::instance().submit(job);
+    c->jit_job_hard = job;
+    return 0;
+}
+
 // code-specialised kernel: one frame per workgroup
 int launch_spec(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d) {
     ldpc_spec::SpecArgs sa{};
@@ -621,32 +657,44 @@ int launch_spec(ldpc_hip_ctx *c, const decoder_kind &kind, const DecodeCall &d) 
     // iterations, and the next frame should start the moment a slot is free, without a workgroup launch in between
     static const bool persist_on = !(getenv("LDPC_HIP_PERSISTENT") && atoi(getenv("LDPC_HIP_PERSISTENT")) == 0);
     const bool persistent = persist_on && c->spec_frames_per_block == 1 && kind.queue;
+    // the instance of this launch: without soft_out the one that holds no soft values, where the body has one
+    const void *aot = c->spec_aot;
+    const ldpc_jit::Kernel *jit = c->spec_jit;
+    int which = 0;
+    if (c->spec_has_hard && !d.soft) {
+        if (c->spec_aot) aot = c->spec_aot_hard;
+        else if (int rc = jit_hard_instance(c)) return rc;
+        else if (c->spec_jit_hard) jit = c->spec_jit_hard;
+        which = (aot != c->spec_aot || jit != c->spec_jit) ? 1 : 0;
+    }
+    c->last_without_soft = which == 1;
     if (persistent) {
         if (!c->d_queue) HIP_TRY(hipMalloc(&c->d_queue, 64));
-        if (c->persist_grid == 0 || c->persist_jit != (c->spec_aot == nullptr)) {   // resident workgroups: occupancy x CUs (8 x 256 for the flagship)
+        const void *key = aot ? aot : (const void *)jit->fn;
+        if (c->persist_for[which] != key) {   // resident workgroups: occupancy x CUs (8 x 256 for the flagship)
             int per_cu = 0, cus = 0;
-            if (c->spec_aot) { if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc; }
-            hipError_t e = c->spec_aot ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_aot, c->spec_threads, c->spec_lds)
-                                       : hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->spec_jit->fn, c->spec_threads, c->spec_lds);
+            if (aot) { if (int rc = set_lds_limit(aot, c->spec_lds)) return rc; }
+            hipError_t e = aot ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, aot, c->spec_threads, c->spec_lds)
+                               : hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, jit->fn, c->spec_threads, c->spec_lds);
             if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            c->persist_grid = per_cu * (cus > 0 ? cus : 256);
-            c->persist_jit = c->spec_aot == nullptr;
+            c->persist_grid[which] = per_cu * (cus > 0 ? cus : 256);
+            c->persist_for[which] = key;
         }
     }
     auto launch = [&](long long frames) -> int {
         long long blocks = (frames + c->spec_frames_per_block - 1) / c->spec_frames_per_block;
-        if (persistent && blocks > c->persist_grid) {
+        if (persistent && blocks > c->persist_grid[which]) {
             HIP_TRY(hipMemsetAsync(c->d_queue, 0, sizeof(unsigned), d.stream));
             sa.queue = c->d_queue;
-            blocks = c->persist_grid;
+            blocks = c->persist_grid[which];
         }
         void *kargs[] = {&sa};
-        if (c->spec_aot) {
-            if (int rc = set_lds_limit(c->spec_aot, c->spec_lds)) return rc;
-            HIP_TRY(hipLaunchKernel(c->spec_aot, dim3((unsigned)blocks), dim3((unsigned)c->spec_threads), kargs, c->spec_lds, d.stream));
+        if (aot) {
+            if (int rc = set_lds_limit(aot, c->spec_lds)) return rc;
+            HIP_TRY(hipLaunchKernel(aot, dim3((unsigned)blocks), dim3((unsigned)c->spec_threads), kargs, c->spec_lds, d.stream));
         } else {
-            HIP_TRY(hipModuleLaunchKernel(c->spec_jit->fn, (unsigned)blocks, 1, 1, (unsigned)c->spec_threads, 1, 1, (unsigned)c->spec_lds,
+            HIP_TRY(hipModuleLaunchKernel(jit->fn, (unsigned)blocks, 1, 1, (unsigned)c->spec_threads, 1, 1, (unsigned)c->spec_lds,
                                           d.stream, kargs, nullptr));
         }
         return 0;
@@ -771,7 +819,7 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         c->spec_threads = plan.threads; c->spec_lds = plan.lds; c->spec_frames_per_block = plan.frames_per_block;
         for (const AotInstance &inst : kAot)
             if (inst.decoder == decoder_id && inst.threads == plan.threads && (t.*inst.matches)()) {
-                c->spec_aot = inst.fn;
+                c->spec_aot = inst.fn; c->spec_aot_hard = inst.fn_hard;
                 c->kernel_name = std::string(inst.name) + " (ahead of time)";
                 break;
             }
@@ -796,6 +844,10 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         } else if (!c->spec_aot) {
             why_not = forced_global ? "LDPC_HIP_FORCE_GLOBAL" : "LDPC_HIP_JIT=0";
         }
+    }
+    if (plan.body && std::string(plan.body) == "ms_m64_body") {   // (a context that starts on another tier may still move over: adopt_jit)
+        c->spec_has_hard = c->spec_aot ? c->spec_aot_hard != nullptr : true;
+        if (!c->spec_aot) c->spec_rows = t.rows();
     }
     if (can_global && (forced_global || (!c->spec_aot && !c->spec_jit && !have_generic))) {
         c->global_tier = true;
@@ -836,6 +888,7 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
 void ldpc_hip_close(ldpc_hip_ctx *c) {
     if (!c) return;
     if (c->jit_job) c->jit_job->cancelled.store(true);   // not compiled yet: drop it
+    if (c->jit_job_hard) c->jit_job_hard->cancelled.store(true);
     (void)hipSetDevice(c->device);
     free_workspace(c);
     if (c->d_row_start) (void)hipFree(c->d_row_start);
@@ -885,6 +938,7 @@ int ldpc_hip_set_jit_mode_thread(int mode) {
     return before;
 }
 const char *ldpc_hip_last_launch(const ldpc_hip_ctx *c) { return c ? c->last_launch : ""; }
+int ldpc_hip_last_launch_without_soft(const ldpc_hip_ctx *c) { return c && c->last_without_soft ? 1 : 0; }
 
 int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int maxiter, double alpha,
                         uint32_t *d_hard, int32_t *d_iters, double *d_soft, void *stream_) {
@@ -911,6 +965,7 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
         if (!c->have_generic) use_global = true;
     }
     c->last_launch = use_global ? kind.global_name : use_spec ? c->kernel_name.c_str() : c->generic_name.c_str();
+    c->last_without_soft = false;   // launch_spec says otherwise
     if (int rc = use_global ? launch_global(c, kind, d) : use_spec ? launch_spec(c, kind, d) : launch_generic(c, kind, d)) return rc;
     HIP_TRY(hipGetLastError());
     return timer.end();

@@ -114,8 +114,10 @@ inline std::string this_library_dir() {
 // Returns the cached or freshly compiled kernel for (device, decoder body, rows, M); nullptr + err on failure.
 // body: "ms_m64_body" (needs M == 64, 64 threads per frame) or "lms_body" (ceil(M/64)*64 threads per frame).
 // compile == false: answer from the process cache or the on-disk cache only (nullptr, err empty when neither has it).
+// disk == false: the process cache alone.  The on-disk cache holds one code object per (decoder, code); the instance of the min-sum
+// body without soft values (ms_m64_hard_body), which a context compiles at its first launch without soft_out, is not kept there.
 inline const Kernel *get(int device, const char *body, const std::vector<std::vector<std::pair<int, int>>> &rows, int nh,
-                         int M, std::string &err, bool compile = true) {
+                         int M, std::string &err, bool compile = true, bool disk = true) {
     static std::mutex mu;
     static std::map<std::string, Kernel> &cache = *new std::map<std::string, Kernel>();   // never destroyed: a background compile may outlive main()
     const std::string code = code_struct(rows, nh, M);
@@ -164,7 +166,7 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
     if (const char *dir = getenv("LDPC_HIP_CACHE_DIR")) cache_dir = dir;
     else if (const char *x = getenv("XDG_CACHE_HOME")) cache_dir = std::string(x) + "/ldpc_hip";
     else if (const char *h = getenv("HOME")) cache_dir = std::string(h) + "/.cache/ldpc_hip";
-    if (cache_dir == "off" || cache_dir == "0") cache_dir.clear();
+    if (cache_dir == "off" || cache_dir == "0" || !disk) cache_dir.clear();
     if (!cache_dir.empty()) {
         for (size_t i = 1; i <= cache_dir.size(); ++i)     // mkdir -p, best effort
             if (i == cache_dir.size() || cache_dir[i] == '/') (void)mkdir(cache_dir.substr(0, i).c_str(), 0755);
@@ -241,6 +243,7 @@ inline const Kernel *get(int device, const char *body, const std::vector<std::ve
 struct Job {
     int device = 0, nh = 0, M = 0;
     std::string body;
+    bool disk = true;                   // see get()
     std::vector<std::vector<std::pair<int, int>>> rows;
     std::atomic<int> state{0};          // 0 queued / compiling, 1 ready, 2 failed or dropped
     std::atomic<bool> cancelled{false};
@@ -299,7 +302,7 @@ private:
                 q_.pop_back();
             }
             if (j->cancelled.load()) { j->state.store(2); continue; }
-            j->kernel = get(j->device, j->body.c_str(), j->rows, j->nh, j->M, j->err, true);
+            j->kernel = get(j->device, j->body.c_str(), j->rows, j->nh, j->M, j->err, true, j->disk);
             j->state.store(j->kernel ? 1 : 2, std::memory_order_release);
         }
     }

@@ -515,6 +515,61 @@ constexpr int ms_m64_nonlocal_col(int n) {
         if (!ms_m64_local_col<C>(k) && n-- == 0) return k;
     return -1;
 }
+// RESIDENT channel values.  The first R non-local columns keep their canonical channel value y + 0.0 in LDS for the life of the
+// frame: the frame prologue loads them once, STATE2 reads the slot instead of global memory and forms y_c + pr, the same bits
+// (y + 0.0 only turns -0.0 into +0.0).  The slots come from two reserves, neither of which lowers the frames a CU holds:
+//   - the SPARE of the frame's LDS budget, kMsM64FrameLdsBytes: whole 512 B columns behind the image, slots NH, NH + 1, ...;
+//   - with SOFT == false (no soft_out: the hard bit of a local column is folded into a bit word, see `hb` in the body) the image
+//     slots of the LOCAL columns, in ascending column order: nothing in the iteration reads or writes them.
+// Resident column number i takes the spare slots first.  The NL - R columns that are left keep STATE2's stream as it is.
+// The example code (NH = 32: spare 6, 17 non-local and 15 local columns) has R = 17 without soft values and R = 6 with them.
+constexpr unsigned long kMsM64LdsBudget = 160 * 1024 - 64;   // a CU's LDS less the frame queue's ticket word (the host's kLdsBudget)
+constexpr int kMsM64FramesPerCu = 8;                         // two waves per SIMD
+constexpr unsigned long kMsM64FrameLdsBytes(unsigned long n) {   // what the host passes as dynamic LDS: the budget of one frame
+    const unsigned long fit = kMsM64LdsBudget / kMsM64LdsBytes(n), frames = fit < kMsM64FramesPerCu ? fit : kMsM64FramesPerCu;
+    const unsigned long share = frames ? kMsM64LdsBudget / frames / 512 * 512 : 0;
+    return share > kMsM64LdsBytes(n) ? share : kMsM64LdsBytes(n);   // (an image beyond the budget: the launch is refused as before)
+}
+template <class C>
+constexpr int ms_m64_spare_cols() { return (int)((kMsM64FrameLdsBytes(C::NH * 64) - kMsM64LdsBytes(C::NH * 64)) / 512); }
+template <class C>
+constexpr int ms_m64_local_cols() { return C::NH - ms_m64_nonlocal_cols<C>(); }
+template <class C, bool SOFT>
+constexpr int ms_m64_resident_cols() {
+    const int room = ms_m64_spare_cols<C>() + (SOFT ? 0 : ms_m64_local_cols<C>()), nl = ms_m64_nonlocal_cols<C>();
+    return room < nl ? room : nl;
+}
+template <class C>
+constexpr int ms_m64_resident_slot(int i) {   // image slot (512 B units from `hi`) of resident column number i
+    const int spare = ms_m64_spare_cols<C>();
+    if (i < spare) return C::NH + i;
+    int n = i - spare;
+    for (int k = 0; k < C::NH; ++k)
+        if (ms_m64_local_col<C>(k) && n-- == 0) return k;
+    return -1;
+}
+// The hard bits of the local columns without LDS: STATE3 forms the soft value of a local column at the column's first block row,
+// in ascending (block row, slot) order, and shifts its sign into word p / 32 of `hb`, p = the column's place in that order.
+// Which place, and which bit of its word the column has once the word's last column is in (the first one in sits highest).
+template <class C>
+constexpr int ms_m64_local_place(int k) {
+    int p = 0;
+    for (int j = 0; j < C::RH; ++j)
+        for (int s = 0; s < C::RW[j]; ++s) {
+            const int kk = C::COL[j][s];
+            if (ms_m64_local_col<C>(kk) && ms_m64_first_row<C>(kk) == j) {
+                if (kk == k) return p;
+                ++p;
+            }
+        }
+    return -1;
+}
+template <class C>
+constexpr int ms_m64_local_bit(int k) {
+    const int p = ms_m64_local_place<C>(k), w = p / 32, left = ms_m64_local_cols<C>() - 32 * w;
+    return (left < 32 ? left : 32) - 1 - (p - 32 * w);
+}
+
 // The loads are a stream over those columns, kMsM64YDepth of them ahead: the first min(depth, count) are issued together, two
 // more at every second column that is processed, so at most depth + 1 channel values (2 VGPRs each) are in flight.  Until
 // round 25 the schedule ran over ALL block columns -- 16 at once, then 8 more at each group of 8, 16 ahead -- and bounded nothing
@@ -560,16 +615,25 @@ constexpr int ms_m64_carry_rows() {
 // KPCAP, YD, YROW and KRSET are switches for tools/ab_flagship.hip, defaulted to what ships: the cap of ms_m64_prefix_rows; the
 // depth of STATE2's stream of channel loads; where its first group is issued (-1: at the start of STATE2, j >= 0: after block row
 // j of STATE1); the number of carried rows (-1: ms_m64_carry_rows).
-template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1>
+// SOFT is not a tool's switch: the host launches the SOFT == false instance (ms_m64_hard_body) when the caller passes no soft_out.
+// That instance never writes the soft value of a local column to the image; it folds the value's sign into the bit word `hb`, the
+// outputs ballot that bit, and the image slots of the local columns hold resident channel values (ms_m64_resident_cols).  RSET and
+// BITW are switches for the tool again: the number of resident columns (-1: the rule; at most the rule's), and whether the hard
+// bits of the local columns come from the bit word (-1: exactly when SOFT is false, which cannot do without).
+template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1, bool SOFT = true, int RSET = -1, int BITW = -1>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     static_assert(YD >= 1 && YROW >= -1 && YROW < C::RH && KRSET <= C::RH, "ms_m64_body: switch out of range");
+    static_assert(RSET <= ms_m64_resident_cols<C, SOFT>() && (SOFT || BITW != 0), "ms_m64_body: switch out of range");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
+    constexpr int RES = RSET >= 0 ? RSET : ms_m64_resident_cols<C, SOFT>();   // non-local columns number [0, RES) are resident
+    constexpr bool BITS = BITW < 0 ? !SOFT : BITW != 0;
+    constexpr int NLOC = ms_m64_local_cols<C>(), HBW = BITS ? (NLOC + 31) / 32 : 0;
     constexpr int KR = KRSET >= 0 ? KRSET : ms_m64_carry_rows<C, YD>();   // block rows [0, KR) carry their decoded c2v values, see `keep`
     // rows [0, KP) of them by prefix / suffix minima.  A type, not a second constant: STATE3's closure would capture the constant, and
     // with that one pointer more a 30 x 60 protograph that carries no row spilled 240 VGPRs (profiles/r23_flagship_isa_histogram.txt).
     typedef IC<ms_m64_prefix_rows<KPCAP>(KR)> KP;
-    extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N)
+    extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N); then the spare slots, up to kMsM64FrameLdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
     long long fr = blockIdx.x;  // one wave per frame; with a.queue the wave goes on to further frames (uniform: an SGPR pair)
@@ -598,6 +662,14 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // lane's offset is lane8, so a load costs no address arithmetic on the vector unit and no 64-bit address is held in VGPRs
     // across the iterations (STATE2 read through such a pointer until round 25: 2 VGPRs, 18 address instructions per iteration).
     const __amdgpu_buffer_rsrc_t ybuf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.llr + fr * N), 0, N * 8, 0x00020000);
+    // The resident channel values (ms_m64_resident_cols), once per frame: canonical (+ 0.0, see STATE2), each into its slot.  A wave
+    // of a persistent launch refills them here for its next frame; the outputs of the frame before read none of these slots.
+    static_for<0, RES>([&](auto I) {
+        constexpr int i = decltype(I)::value, k = ms_m64_nonlocal_col<C>(i);
+        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, k * 512, 0);
+        *own(IC<ms_m64_resident_slot<C>(i)>{}) = mk(v.y, v.x) + 0.0;
+    });
 
     // What a block row hands from STATE3 of one iteration to the next iteration, in one of two forms:
     //   rows [KR, RH)  a RECORD: m1, m2 and a word with the signs and the slot of the smallest magnitude, decoded edge by edge in
@@ -614,6 +686,8 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         if constexpr (j < KR) static_for<0, C::RW[j]>([&](auto S) { keep[j][decltype(S)::value] = 0.0; });
     });
 
+    u32 hb[HBW > 0 ? HBW : 1];   // BITS: the signs of the local columns' soft values, see ms_m64_local_place
+    static_for<0, HBW>([&](auto W) { hb[decltype(W)::value] = 0u; });
     int res = -a.maxiter;
     for (int iter = 0; iter < a.maxiter; ++iter) {
         // The channel LLRs are needed only in STATE2.  Instead of pinning 64 VGPRs for the whole kernel they are
@@ -623,14 +697,16 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         // STATE3 -- the registers go to `keep`.  (Until round 13 all 32 columns were loaded here, "under STATE1's ALU work";
         // the other wave of the SIMD covers the latency just as well: profiles/r13_flagship_variants.txt, placements (a),
         // (b), (c).  Until round 25 the schedule counted local columns too: ms_m64_y_in_flight_r23.)
-        constexpr int NL = ms_m64_nonlocal_cols<C>(), YAHEAD = YD < NL ? YD : NL;
+        // The stream runs over the NS non-local columns that are not resident, numbers [RES, NL); a resident one is read from its
+        // slot in STATE2, and with every non-local column resident there is no stream at all.
+        constexpr int NL = ms_m64_nonlocal_cols<C>(), NS = NL - RES, YAHEAD = YD < NS ? YD : NS;
         double y[NH];
-        auto load_y = [&](auto N0, auto N1) {   // non-local columns number [N0, min(N1, NL))
-            if constexpr (decltype(N0)::value < NL && decltype(N0)::value < decltype(N1)::value) {
-u32 so = 0;
+        auto load_y = [&](auto N0, auto N1) {   // streamed columns number [N0, min(N1, NS))
+            if constexpr (decltype(N0)::value < NS && decltype(N0)::value < decltype(N1)::value) {
+                u32 so = 0;
                 asm volatile("" : "+s"(so));  // opaque where it stands: the loads are neither hoisted out of the loop nor moved up
-                static_for<decltype(N0)::value, (decltype(N1)::value < NL ? decltype(N1)::value : NL)>([&](auto I) {
-                    constexpr int k = ms_m64_nonlocal_col<C>(decltype(I)::value);
+                static_for<decltype(N0)::value, (decltype(N1)::value < NS ? decltype(N1)::value : NS)>([&](auto I) {
+                    constexpr int k = ms_m64_nonlocal_col<C>(RES + decltype(I)::value);
                     typedef u32 u32x2 __attribute__((ext_vector_type(2)));
                     const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
                     y[k] = mk(v.y, v.x);
@@ -738,11 +814,20 @@ u32 so = 0;
         if constexpr (YROW < 0) load_y(IC<0>{}, IC<YAHEAD>{});
         static_for<0, NL>([&](auto I) {
             constexpr int i = decltype(I)::value, k = ms_m64_nonlocal_col<C>(i);
-            if constexpr (i % 2 == 0) load_y(IC<i + YAHEAD>{}, IC<i + YAHEAD + 2>{});
             double *p = own(IC<k>{});
-            const double pr = *p * alpha;
-            *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
-            if constexpr (i % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // YAHEAD columns in flight, not all of them (VGPR budget)
+            if constexpr (i < RES) {
+                // resident: the slot holds y + 0.0 (frame prologue).  Slot and sum sit at the same lane offset, whole block columns
+                // apart: one ds_read2st64_b64 fetches both
+                const double yc = *own(IC<ms_m64_resident_slot<C>(i)>{});
+                const double pr = *p * alpha;
+                *p = yc + pr;
+            } else {
+                if constexpr ((i - RES) % 2 == 0) load_y(IC<i - RES + YAHEAD>{}, IC<i - RES + YAHEAD + 2>{});
+                const double pr = *p * alpha;
+                *p = (y[k] + 0.0) + pr;   // + 0.0 canonicalises a -0.0 input (see ldpc_kernels.hpp); exact otherwise
+            }
+            // YAHEAD columns in flight, not all of them (VGPR budget)
+            if constexpr (i < RES ? i % 2 == 1 : (i - RES) % 2 == 1) __builtin_amdgcn_sched_barrier(0);
         });
         load_yl(IC<0>{});
         // ---------------- STATE3 (:4690-4755)
@@ -774,7 +859,8 @@ u32 so = 0;
                     // one taken as it is (what the FIRST store and the ds_add_f64 did); then the same product and sum as STATE2,
                     // three roundings in all.  A decoded value goes into keep[][] of its own row, where x = keep * |alpha| takes
                     // it out again (the bits of the second decode, see `keep`); the soft value stays in soft_l until the column's
-                    // last row.  It is also written to the image once, for the outputs: the loop can end after any iteration.
+                    // last row.  The outputs get it too, the loop can end after any iteration: written to the image once (SOFT), or
+                    // its sign alone shifted into its bit word (BITS).
                     if constexpr (ms_m64_first_row<C>(k) == j) {
                         double acc = 0.0;
                         static_for<j, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
@@ -793,7 +879,13 @@ u32 so = 0;
                         });
                         const double pr = acc * alpha;
                         soft_l[k] = (yl[k] + 0.0) + pr;
-                        *own(IC<k>{}) = soft_l[k];
+                        // for the outputs.  The hard decision needs the sign alone: one v_alignbit_b32 as nS has it, (word << 1) | sign,
+                        // and without soft values no store -- the slot then belongs to a resident channel value
+                        if constexpr (BITS) {
+                            constexpr int w = ms_m64_local_place<C>(k) / 32;
+                            hb[w] = __builtin_amdgcn_alignbit(hb[w], hi32(soft_l[k]), 31);
+                        }
+                        if constexpr (SOFT) *own(IC<k>{}) = soft_l[k];
                     }
                     r[s] = soft_l[k];
                 }
@@ -903,20 +995,39 @@ u32 so = 0;
     if constexpr (KR > 0) asm volatile("" : "+v"(ol));
     if (lane == 0 && a.iters) a.iters[fr] = res;
     if (a.hard) {
+        // bit 31: the sign of the lane's variable of block column k.  Two closures, chosen outside them: where the bit words are not
+        // used, nothing names them (a name in a discarded branch of a generic closure is still a capture, and see KP on those).
+        // The bit words as the outputs use them are an opaque copy, as the lane is: their bit tests stay here, behind the iterations.
+        // Without that the shipped instance spilled 360 VGPRs and a 30 x 60 protograph 350.
+        auto sign_of = [&] {
+            if constexpr (BITS) {
+                u32 ho[HBW > 0 ? HBW : 1];
+                static_for<0, HBW>([&](auto W) { ho[decltype(W)::value] = hb[decltype(W)::value]; asm volatile("" : "+v"(ho[decltype(W)::value])); });
+                return [&, ho](auto K) -> u32 {
+                    constexpr int k = decltype(K)::value;
+                    if constexpr (ms_m64_local_col<C>(k)) {
+                        constexpr int w = ms_m64_local_place<C>(k) / 32, up = 31 - ms_m64_local_bit<C>(k);   // constants, not code
+                        return ho[w] << up >> 31;
+                    } else return hi32(*own(K)) >> 31;
+                };
+            } else return [&](auto K) -> u32 { return hi32(*own(K)) >> 31; };
+        }();
         u64 mine = 0ull;
         static_for<0, NH>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            const u64 b = __ballot((hi32(*own(K)) >> 31) != 0);
+            const u64 b = __ballot(sign_of(K) != 0);
             if (ol == k) mine = b;
         });
         // block column k = variables 64k..64k+63 = packed words 2k, 2k+1
         if (ol < NH) reinterpret_cast<u64 *>(a.hard + fr * (N / 32))[ol] = mine;
     }
-    if (a.soft_out) {
-        static_for<0, NH>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            a.soft_out[fr * N + k * 64 + ol] = *own(K);
-        });
+    if constexpr (SOFT) {   // the instance without soft values holds none for the local columns: the host passes it no soft_out
+        if (a.soft_out) {
+            static_for<0, NH>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                a.soft_out[fr * N + k * 64 + ol] = *own(K);
+            });
+        }
     }
     if (!a.queue) break;
     u32 ticket = 0;
@@ -924,6 +1035,9 @@ u32 so = 0;
     fr = (long long)gridDim.x + (long long)(u32)__builtin_amdgcn_readfirstlane((int)ticket);   // every wave ends here: fr >= nframes
   }
 }
+// ms_m64_body for a launch without soft_out (SOFT == false there), as a body of its own name: an ahead-of-time instance, a hiprtc key.
+template <class C>
+__device__ __forceinline__ void ms_m64_hard_body(const SpecArgs &a) { ms_m64_body<C, 1 << 30, kMsM64YDepth, -1, -1, false>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Flooding min-sum for ANY lifting M <= 512 (one frame per workgroup of W = ceil(M/64) wavefronts): the algorithm of

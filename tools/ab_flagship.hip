@@ -1,8 +1,9 @@
 // ab_flagship.hip -- A/B harness for variants of the flagship min-sum body (ldpc_spec::ms_m64_body) on the shipped example code:
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
-// -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds]
-// Results: profiles/r25_flagship_variants.txt: STATE2 of ms_m64_body streams its channel loads over the non-local block columns, YD
+// -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds] [persistent 0|1] [first variant timed in every round]
+// Results: profiles/r26_flagship_variants.txt: resident channel values, soft values kept or not, the bit word -- the SOFT, RSET and
+// BITW parameters of the header's body -- in both launch forms (argument 4).  profiles/r25_flagship_variants.txt: STATE2 of ms_m64_body streams its channel loads over the non-local block columns, YD
 // of them ahead, first group at the start of STATE2 or after a block row of STATE1 (YROW), and the body carries KR block rows -- the
 // YD, YROW and KRSET parameters of the header's body; depth 32 issues every load at once, which is what the schedule before round 25
 // amounted to on this code (the variants of round 23 below are held at that and at 13 rows).  profiles/r23_flagship_variants.txt: the carried rows [0, KP) of ms_m64_body form their magnitudes from prefix and suffix
@@ -710,15 +711,29 @@ STREAM(k_y8r12_15, 8, 12, 15)
 STREAM(k_y8r15_15, 8, 15, 15)
 STREAM(k_y4r15_15, 4, 15, 15)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
+// round 26: how many non-local columns keep their channel value in LDS (RSET), whether the local columns' soft values are stored
+// (SOFT), whether their hard bits come from the bit word (BITW).  15 carried rows, stream depth 8 for what is not resident.
+#define RESIDENT(name, soft, rset, bitw) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, 8, -1, 15, soft, rset, bitw>(a); }
+RESIDENT(k_s_r0, true, 0, 0)
+RESIDENT(k_s_r0_b, true, 0, 1)
+RESIDENT(k_s_r6, true, 6, 0)
+RESIDENT(k_h_r0, false, 0, 1)
+RESIDENT(k_h_r6, false, 6, 1)
+RESIDENT(k_h_r12, false, 12, 1)
+RESIDENT(k_h_r17, false, 17, 1)
+extern "C" __global__ void __launch_bounds__(64, 2) k_shipped_hard(const SpecArgs a) { ldpc_spec::ms_m64_hard_body<Code>(a); }
 
-struct Variant { const void *kern; const char *name; size_t lds; };
+struct Variant { const void *kern; const char *name; size_t lds; bool soft = true; };   // soft: the kernel writes soft_out
 
 int main(int argc, char **argv) {
     const long long B = argc > 1 ? atoll(argv[1]) : 65536;
     const double snr = argc > 2 ? atof(argv[2]) : 0.0;
     const int rounds = argc > 3 ? atoi(argv[3]) : 8;
+    const bool persistent = argc > 4 && atoi(argv[4]) != 0;   // the library's launch form: resident waves that pull frames from a queue
+    const int first = argc > 5 ? atoi(argv[5]) : 1;           // time the baseline and the variants from this one on
     const int N = 2048;
-    const size_t L = ldpc_spec::kMsM64LdsBytes(N);
+    const size_t L = ldpc_spec::kMsM64FrameLdsBytes(N);   // what the library passes: the frame's share of the CU (the older bodies use less of it)
     const Variant var[] = {
         {(const void *)k_parent, "baseline: the body round 19 shipped (rows 0-10 kept, 57 edges)", L},
         {(const void *)k_l57, "round 20's switches off, 57 edges (must equal the baseline)", L},
@@ -742,6 +757,14 @@ int main(int argc, char **argv) {
         {(const void *)k_y8r15_15, "stream depth 8, first group after STATE1 row 15, 15 carried rows", L},
         {(const void *)k_y4r15_15, "stream depth 4, first group after STATE1 row 15, 15 carried rows", L},
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
+        {(const void *)k_s_r0, "soft values, no resident column, no bit word (round 25's body)", L},
+        {(const void *)k_s_r0_b, "soft values, no resident column, hard bits from the bit word", L},
+        {(const void *)k_s_r6, "soft values, 6 resident columns", L},
+        {(const void *)k_h_r0, "no soft values (no store per local column), no resident column", L, false},
+        {(const void *)k_h_r6, "no soft values, 6 resident columns", L, false},
+        {(const void *)k_h_r12, "no soft values, 12 resident columns", L, false},
+        {(const void *)k_h_r17, "no soft values, 17 resident columns (all)", L, false},
+        {(const void *)k_shipped_hard, "ms_m64_hard_body as shipped (ldpc_spec.hpp)", L, false},
     };
     constexpr int NV = sizeof var / sizeof var[0];
     const long long distinct = std::min<long long>(B, 4096);
@@ -761,21 +784,35 @@ int main(int argc, char **argv) {
         CK(hipMalloc(&d_hard[v], 4 * (size_t)B * (N / 32)));
         CK(hipMalloc(&d_it[v], 4 * (size_t)B));
     }
+    unsigned *d_queue;
+    CK(hipMalloc(&d_queue, 64));
+    int cus = 0;
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+    const long long resident = (long long)ldpc_spec::kMsM64FramesPerCu * cus;
     std::vector<float> best(NV, 1e9f), worst(NV, 0.f), sum(NV, 0.f);
+    std::vector<int> timed(NV, 0);
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int r = 0; r <= rounds; ++r)   // round 0 warms up
         for (int v = 0; v < NV; ++v) {
+            if (v && v < first && r > 1) continue;   // (one timed round all the same: the comparison below needs every variant's outputs)
             SpecArgs a{};
             a.llr = d_llr; a.hard = d_hard[v]; a.iters = d_it[v]; a.soft_out = nullptr; a.maxiter = 50; a.alpha = 0.8; a.nframes = B;
             void *args[] = {&a};
+            long long grid = B;
+            if (persistent && B > resident) {
+                CK(hipMemsetAsync(d_queue, 0, sizeof(unsigned), 0));
+                a.queue = d_queue;
+                grid = resident;
+            }
+            CK(hipFuncSetAttribute(var[v].kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var[v].lds));
             CK(hipEventRecord(e0, 0));
-            CK(hipLaunchKernel(var[v].kern, dim3((unsigned)B), dim3(64), args, var[v].lds, 0));
+            CK(hipLaunchKernel(var[v].kern, dim3((unsigned)grid), dim3(64), args, var[v].lds, 0));
             CK(hipEventRecord(e1, 0));
             CK(hipEventSynchronize(e1));
             float ms;
             CK(hipEventElapsedTime(&ms, e0, e1));
-            if (r) { best[v] = std::min(best[v], ms); worst[v] = std::max(worst[v], ms); sum[v] += ms; }
+            if (r) { best[v] = std::min(best[v], ms); worst[v] = std::max(worst[v], ms); sum[v] += ms; ++timed[v]; }
         }
     // soft values on the first 4096 frames + bitwise comparison with the baseline
     std::vector<unsigned> hh[NV];
@@ -786,7 +823,7 @@ int main(int argc, char **argv) {
         SpecArgs a{};
         a.llr = d_llr; a.hard = nullptr; a.iters = nullptr; a.soft_out = d_soft[v]; a.maxiter = 50; a.alpha = 0.8; a.nframes = BS;
         void *args[] = {&a};
-        CK(hipLaunchKernel(var[v].kern, dim3((unsigned)BS), dim3(64), args, var[v].lds, 0));
+        if (var[v].soft) CK(hipLaunchKernel(var[v].kern, dim3((unsigned)BS), dim3(64), args, var[v].lds, 0));
         CK(hipDeviceSynchronize());
         hh[v].resize((size_t)B * (N / 32)); hi[v].resize((size_t)B); hs[v].resize((size_t)BS * N);
         CK(hipMemcpy(hh[v].data(), d_hard[v], 4 * hh[v].size(), hipMemcpyDeviceToHost));
@@ -796,13 +833,16 @@ int main(int argc, char **argv) {
     double mean_it = 0;
     for (int x : hi[0]) mean_it += std::abs(x);
     mean_it /= (double)B;
-    printf("# %lld frames, Eb/N0 %.1f dB, mean |iters| %.2f, %d interleaved rounds; spread = max - min over the rounds\n", B, snr, mean_it, rounds);
+    printf("# %lld frames, Eb/N0 %.1f dB, mean |iters| %.2f, %d interleaved rounds, %s; spread = max - min over the rounds\n", B, snr, mean_it, rounds,
+           persistent ? "resident waves with a frame queue" : "one workgroup per frame");
     bool all_same = true;
     for (int v = 0; v < NV; ++v) {
-        const bool same = hh[v] == hh[0] && hi[v] == hi[0] && !memcmp(hs[v].data(), hs[0].data(), 8 * hs[0].size());
+        const bool same = hh[v] == hh[0] && hi[v] == hi[0] && (!var[v].soft || !memcmp(hs[v].data(), hs[0].data(), 8 * hs[0].size()));
         all_same = all_same && same;
-        printf("%-68s min %8.3f ms  mean %8.3f ms  max %8.3f ms  spread %5.2f %%  %6.3f Mframes/s  outputs %s\n", var[v].name, best[v],
-               sum[v] / rounds, worst[v], 100.0 * (worst[v] - best[v]) / best[v], B / best[v] / 1e3,
+        int per_cu = 0;   // what the runtime says a CU holds of this kernel with this much dynamic LDS
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, var[v].kern, 64, var[v].lds));
+        printf("%-68s %d per CU  min %8.3f ms  mean %8.3f ms  max %8.3f ms  spread %5.2f %%  %6.3f Mframes/s  outputs %s\n", var[v].name,
+               per_cu, best[v], sum[v] / std::max(timed[v], 1), worst[v], 100.0 * (worst[v] - best[v]) / best[v], B / best[v] / 1e3,
                same ? "bit-identical to the baseline" : "DIFFER");
     }
     return all_same ? 0 : 2;

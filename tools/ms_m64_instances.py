@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers of every instance of ms_m64_body that the GPU tests compile with hiprtc, and of five synthetic protographs: each one
-cross-compiled as a one-kernel translation unit (__launch_bounds__(64, 2), the Code struct as ldpc_jit.hpp writes it).
-usage: ms_m64_instances.py [--csrc DIR] [--args "<template arguments after the code>"] [name ...]
+cross-compiled as a one-kernel translation unit (__launch_bounds__(64, 2), the Code struct as ldpc_jit.hpp writes it), in both
+variants: ms_m64_body (with soft values) and ms_m64_hard_body (without: what a launch without soft_out runs).
+usage: ms_m64_instances.py [--csrc DIR] [--args "<template arguments after the code>"] [--body NAME] [name ...]
 --csrc: a directory with another ldpc_spec.hpp (a parent commit's, say), for a before / after table.  Needs hipcc, no GPU."""
 import argparse
 import os
@@ -51,33 +52,48 @@ def instances():
     return out
 
 
-def build(csrc, H, targs):
+BODIES = ("ms_m64_body", "ms_m64_hard_body")
+
+
+def build_asm(csrc, H, targs="", body="ms_m64_body"):
+    """the instance's assembly text"""
     with tempfile.TemporaryDirectory() as td:
         src, out = os.path.join(td, "k.hip"), os.path.join(td, "k.s")
         open(src, "w").write(f'#include "{csrc}/ldpc_spec.hpp"\n{_code_struct(H)}'
                              'extern "C" __global__ void __launch_bounds__(64, 2) k(const ldpc_spec::SpecArgs a) '
-                             f'{{ ldpc_spec::ms_m64_body<Code{targs}>(a); }}\n')
+                             f'{{ ldpc_spec::{body}<Code{targs}>(a); }}\n')
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
                                "-S", src, "-o", out], stderr=subprocess.DEVNULL)
-        asm = open(out).read()
+        return open(out).read()
+
+
+def figures(asm):
     meta = {k: int(re.search(r"^\s*" + re.escape(k) + r":\s*(\d+)", asm, re.M).group(1))
             for k in (".vgpr_count", ".vgpr_spill_count", ".private_segment_fixed_size")}
     return meta, len(re.findall(r"^\s+ds_add_f64\s", asm, re.M))
+
+
+def build(csrc, H, targs, body="ms_m64_body"):
+    return figures(build_asm(csrc, H, targs, body))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--csrc", default=os.path.join(ROOT, "ldpc-lib_amd", "csrc"))
     ap.add_argument("--args", default="")
+    ap.add_argument("--body", default=None, choices=BODIES, help="one variant only (--args applies to ms_m64_body)")
     ap.add_argument("names", nargs="*")
     a = ap.parse_args()
     todo = {n: H for n, H in instances().items() if not a.names or n in a.names}
     targs = ", " + a.args if a.args else ""
+    bodies = (a.body,) if a.body else BODIES[:1] if a.args else BODIES
+    jobs = [(n, b) for n in todo for b in bodies]
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
-        res = dict(zip(todo, ex.map(lambda H: build(a.csrc, H, targs), todo.values())))
-    for n, H in todo.items():
-        meta, adds = res[n]
-        print(f"  {n:38s}{H.shape[0]:3d} x {H.shape[1]:<3d}{int((H >= 0).sum()):4d} edges   VGPRs {meta['.vgpr_count']:3d}   spilled {meta['.vgpr_spill_count']:3d}   "
+        res = dict(zip(jobs, ex.map(lambda nb: build(a.csrc, todo[nb[0]], targs if nb[1] == BODIES[0] else "", nb[1]), jobs)))
+    for n, b in jobs:
+        H = todo[n]
+        meta, adds = res[n, b]
+        print(f"  {n:38s}{'hard' if b == BODIES[1] else 'soft'}{H.shape[0]:3d} x {H.shape[1]:<3d}{int((H >= 0).sum()):4d} edges   VGPRs {meta['.vgpr_count']:3d}   spilled {meta['.vgpr_spill_count']:3d}   "
               f"scratch {meta['.private_segment_fixed_size']:4d} B   ds_add_f64 {adds:3d} (expected {_atomics_expected(H):3d})   "
               f"carried rows {eqslot.carried_rows(H):2d} -> {allrows.carry_rows(H):2d} of {H.shape[0]:2d}")
 
