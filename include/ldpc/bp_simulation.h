@@ -9,7 +9,9 @@
  * generator is rolled back and re-advanced so that it is left exactly where upstream's frame-by-frame loop leaves it (later
  * callers draw from it: main_good_code_search.cpp:316).
  * Result, counters and generator state are identical to upstream's for q_mod == 2, modulation SKIP/QAM4,
- * permutation_type 0 (the only mode the shipped configurations use, files/default_constants.jsonx:6).
+ * permutation_type 0 (the only mode the shipped configurations use, files/default_constants.jsonx:6), and for q_mod > 2
+ * (FHT_DEC, MODULATION_SKIP, permutation_type 0: bp_simulation_gfq_t below) up to the one spot upstream leaves undefined, the
+ * message beyond its first eight symbols, which include/ldpc_hip.h defines.
  *
  *   ldpc::bp_simulation_throughput_t() the same harness in THROUGHPUT mode: channel noise drawn on the GPUs (counter-based Philox
  *                                      keyed by the global frame index), frames sharded over `devices` behind the C-ABI
@@ -18,9 +20,11 @@
  *   LDPC_HIP_DEVICES="0,1,2,3" | "all" selects the GPUs for every entry point below that takes no explicit list.
  *   ldpc::bp_simulation_t<Mat, Env>()  generic over the matrix type (needs n_rows(), n_cols(), operator()(i,j))
  *                                      and over the environment that owns the generator (see RngEnv below);
- *   ldpc::bp_simulation()              standalone: ldpc::Matrix + the library's own generator (ldpc::reset_random).
+ *   ldpc::bp_simulation()              standalone: ldpc::Matrix + the library's own generator (ldpc::reset_random); q_mod > 2 goes
+ *                                      to ldpc::bp_simulation_gfq_t<Mat, Env>(), upstream's q-ary harness on the GF(q) decoder.
  *   ldpc::bp_simulation_codes_exact()  a set of candidate codes of one shape in exact-replay mode: the stream of the reset generator
  *                                      drawn once and decoded by every candidate in one launch per batch (_t: generic as above).
+ *   ldpc::bp_simulation_codes_gfq_exact()  the same for candidates over GF(q): upstream's q-ary set-up and an own word per candidate.
  * The drop-in definition of upstream's exact `bp_simulation(int, matrix<int> const&, matrix<int>&, ...)` symbol is
  * csrc/compat/bp_simulation_dropin.cpp (compiled inside the upstream tree).
  */
@@ -196,7 +200,7 @@ std::pair<double, double> bp_simulation_t(int q_mod, Mat const &H, int tailbite_
                                           int permutation_type, int punctured_blocks, int show_process,
                                           SimCounters *counters_out, const std::vector<int> &devices, long long max_batch = 4096,
                                           int permutation_block = 128, int permutation_inter = 1) {
-    if (q_mod != 2) Env::fail("bp_simulation: only binary codes (q_mod == 2) are built in ldpc-lib_amd");
+    if (q_mod != 2) Env::fail("bp_simulation_t: binary codes (q_mod == 2) only; q_mod > 2 runs through bp_simulation() / bp_simulation_gfq_t");
     if (modulation_type != MODULATION_SKIP_ && modulation_type != MODULATION_QAM4_)
         Env::fail("bp_simulation: exact-replay mode supports MODULATION_SKIP and MODULATION_QAM4 (upstream's QAM16+ wiring "
                   "is broken, SURVEY Appendix B Q5/Q6; use the device-side chain ldpc_hip_awgn_qam16_llr_dev)");
@@ -669,7 +673,8 @@ inline std::vector<std::pair<double, double>> bp_simulation_codes_exact(std::vec
 // One pair <SER, FER> per code: symbol errors at the information positions per frame and information symbol, and frame errors per
 // frame, each equal to what a frame-by-frame run of ldpc_hip_simulate_gfq (random_messages = 0) gives for that code alone under the
 // same rule.  show_process == 0 is one ldpc_hip_simulate_codes_gfq_stop call; otherwise ldpc_hip_simulate_codes_gfq per batch with the
-// rule replayed on the host.  bp_simulation() itself keeps failing for q_mod > 2: a single GF(q) code is not built in this layer.
+// rule replayed on the host.  This form runs over Philox noise and the all-zero word; upstream's own stream and message for ONE code:
+// bp_simulation(q_mod > 2, ...) / bp_simulation_gfq_t below.
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_gfq_t(int q_mod, std::vector<Mat> const &codes, std::vector<Mat> const &coefs,
                                                                  int tailbite_length, int max_iterations, int n_frame_errors,
@@ -734,8 +739,305 @@ inline std::vector<std::pair<double, double>> bp_simulation_codes(std::vector<Ma
                                                     show_process, seed, device, counters_out, first_batch, max_batch);
 }
 
-// Standalone entry point with upstream's argument list (bp_simulation.h:9-27); coef_matrix / ncols2convert only
-// matter for q_mod > 2 (not built) and are accepted and ignored.
+// ---- what the two q-ary harnesses below share ------------------------------------------------------------------------------------
+// q_bits of q_mod, after the checks of what upstream's q-ary path has at all
+template <class Env>
+int gfq_harness_check(int q_mod, int decoder_type, int modulation_type, int permutation_type) {
+    int q_bits = 0;
+    while ((1 << q_bits) < q_mod) ++q_bits;
+    if (q_mod < 4 || q_mod > 1024 || (1 << q_bits) != q_mod) Env::fail("bp_simulation: q_mod > 2 must be a power of two in 4 .. 1024");
+    if (decoder_type != LDPC_HIP_FHT_DEC) Env::fail("bp_simulation: q_mod > 2 decodes with FHT_DEC (decoder_type 6) only");
+    if (modulation_type != MODULATION_SKIP_)
+        Env::fail("bp_simulation: q_mod > 2 takes MODULATION_SKIP only (upstream's switch at bp_simulation.cpp:635-678 has no other case)");
+    if (permutation_type != 0) Env::fail("bp_simulation: q_mod > 2 takes permutation_type 0 only (upstream never inverts the permutation, :683-686)");
+    return q_bits;
+}
+
+// Upstream's set-up of one code (:348-399) and its word (:537-557): hb, hc [b][c] as the frame loop uses them (after ncols2convert and
+// left2right), the rewritten coefficients written back into coef_matrix (:384-389), word [n] = the encoded message.  Returns whether
+// the encoder produced a codeword (false: flag == 0 or a code the encoder refuses -- the all-zero word is sent, word is zero).
+// keep != null: the context opened on (hb, hc) is handed out instead of closed.
+template <class Mat, class Env>
+bool gfq_harness_setup(int q_bits, Mat const &H, Mat &coef_matrix, int ncols2convert, int M, int device, std::vector<int16_t> &hb,
+                       std::vector<int16_t> &hc, std::vector<int16_t> &word, ldpc_hip_ctx **keep) {
+    const int b = H.n_rows(), c = H.n_cols();
+    if (coef_matrix.n_rows() != b || coef_matrix.n_cols() != c) Env::fail("bp_simulation: coef_matrix must have the shape of the code matrix");
+    hb.assign((size_t)b * c, 0); hc.assign((size_t)b * c, 0);
+    for (int i = 0; i < b; ++i)
+        for (int j = 0; j < c; ++j) { hb[(size_t)i * c + j] = (int16_t)H(i, j); hc[(size_t)i * c + j] = (int16_t)coef_matrix(i, j); }   // :359-366
+    ldpc_hip_ctx *ctx = nullptr;
+    if (ldpc_hip_open_gfq(q_bits, b, c, M, hb.data(), hc.data(), ncols2convert, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());     // :368-382
+    if (ldpc_hip_gfq_coefficients(ctx, hc.data()) != 0) Env::fail(ldpc_hip_last_error());
+    ldpc_hip_close(ctx);
+    ctx = nullptr;
+    for (int i = 0; i < b; ++i)
+        for (int j = 0; j < c; ++j) coef_matrix(i, j) = hc[(size_t)i * c + j];                                                           // :384-389
+    if (ldpc_hip_gfq_left2right(hb.data(), b, c) != 0 || ldpc_hip_gfq_left2right(hc.data(), b, c) != 0) Env::fail(ldpc_hip_last_error());   // :391-394
+    if (ldpc_hip_open_gfq(q_bits, b, c, M, hb.data(), hc.data(), 0, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());                 // :396-399
+    const int K = ldpc_hip_gfq_k(ctx);                                                                                                   // :537-557
+    std::vector<int16_t> msg((size_t)(K > 0 ? K : 1));
+    word.assign((size_t)c * M, 0);
+    int32_t ok = 0;
+    if (ldpc_hip_gfq_upstream_message(q_bits, K, msg.data()) != 0) Env::fail(ldpc_hip_last_error());
+    const int rc = ldpc_hip_encode_gfq_host(ctx, msg.data(), 1, word.data(), &ok);
+    if (rc != 0 && rc != LDPC_HIP_EUNSUPPORTED) Env::fail(ldpc_hip_last_error());
+    const bool encoded = rc == 0 && ok != 0;
+    if (!encoded) word.assign((size_t)c * M, 0);
+    if (keep) *keep = ctx; else ldpc_hip_close(ctx);
+    return encoded;
+}
+
+// Once per process, on a binary context of the same shape (the probe draws plain samples, which a GF(q) context does not serve): does
+// the device reproduce this host's std::normal_distribution?  A shape the binary opener refuses leaves the verdict open, and the
+// draws then stay on the host.
+inline void gfq_harness_probe(const std::vector<int16_t> &hb, int b, int c, int M, int device) {
+    if (device_stream_verdict().load() >= 0) return;
+    std::vector<int16_t> hd(hb.size());
+    for (size_t i = 0; i < hd.size(); ++i) hd[i] = (int16_t)(hb[i] < 0 ? -1 : hb[i] % M);
+    ldpc_hip_ctx *probe = nullptr;
+    const int jit_before = ldpc_hip_set_jit_mode_thread(0);   // the probe decodes nothing
+    const int open_rc = ldpc_hip_open(LDPC_HIP_MS_DEC, b, c, M, hd.data(), device, &probe);
+    (void)ldpc_hip_set_jit_mode_thread(jit_before);
+    if (open_rc == 0) {
+        (void)device_stream_matches_host(probe);
+        ldpc_hip_close(probe);
+    }
+}
+
+// frames of a batch whose Gaussians are drawn on the host: at most 256 MiB of doubles at a time, whatever the batch schedule says
+inline long long gfq_host_noise_frames(long long per_frame) {
+    const long long cap = ((long long)256 << 20) / ((long long)sizeof(double) * (per_frame > 0 ? per_frame : 1));
+    return cap < 1 ? 1 : cap;
+}
+
+// bp_simulation() for q_mod > 2: upstream's q-ary harness (bp_simulation.cpp with q_mod > 2) in exact-replay mode on FHT_DEC.
+//   set-up (:348-399)   decod_init with ncols2convert on the matrices as given; the rewritten coefficients go back into coef_matrix
+//                       (:384-389); left2right on both; decod_init again with 0 -- ldpc_hip_open_gfq(ncols2convert),
+//                       ldpc_hip_gfq_coefficients, ldpc_hip_gfq_left2right, ldpc_hip_open_gfq(0);
+//   message (:537-557)  the message include/ldpc_hip.h defines (ldpc_hip_gfq_upstream_message: upstream's eight symbols reduced
+//                       with & (q - 1), then zeros) through the encoder; ok = 0 or a code the encoder refuses sends the all-zero word;
+//   frames              no draw before the loop, n * q_bits Gaussians per frame (:638-642), p_thr = 0, the binary accounting and
+//                       stopping rule; batches x 4, the snapshot and roll-forward after a stop inside a batch, the show_process line.
+// The noise is the generator's own stream continued on the device (ldpc_hip_mt_frames_gfq) when the device reproduces this host's
+// std::normal_distribution; otherwise, or with LDPC_HIP_EXACT_NOISE=host, Env::gaussian() through ldpc_hip_frames_gfq_noise_host.
+// Only decoder_type 6, MODULATION_SKIP and permutation_type 0 mean anything upstream for q_mod > 2 (the switch at :635-678 has no other
+// case, the permutation is never inverted, :683-686); anything else fails with the reason.  punctured_blocks enters sigma only.
+template <class Mat, class Env>
+std::pair<double, double> bp_simulation_gfq_t(int q_mod, Mat const &H, Mat &coef_matrix, int ncols2convert, int tailbite_length, int max_iterations,
+                                              int n_frame_errors, int n_experiments, double snr, double reference_frame_error, int decoder_type,
+                                              int modulation_type, int permutation_type, int punctured_blocks, int show_process,
+                                              SimCounters *counters_out = nullptr, int device = 0, long long max_batch = 65536) {
+    const int q_bits = gfq_harness_check<Env>(q_mod, decoder_type, modulation_type, permutation_type);
+    const int b = H.n_rows(), c = H.n_cols(), M = tailbite_length;
+    const long long r = (long long)b * M, n = (long long)c * M;
+    const std::vector<int> devs = devices_from_env(device);   // the first device of the list is used
+    device = devs[0];
+    std::vector<int16_t> hb, hc, word;
+    ldpc_hip_ctx *ctx = nullptr;
+    const bool encoded = gfq_harness_setup<Mat, Env>(q_bits, H, coef_matrix, ncols2convert, M, device, hb, hc, word, &ctx);
+    if (ldpc_hip_gfq_set_codeword(ctx, encoded ? word.data() : nullptr) != 0) Env::fail(ldpc_hip_last_error());   // flag == 0: the all-zero word
+
+    SimCounters k;
+    std::vector<int32_t> info, iters;
+    bool stop = n_frame_errors <= 0 || n_experiments < 0;                                        // :591 fails before the first frame
+    const auto show = [&] {
+        if (show_process)
+            printf("SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", snr, (int)k.experiment, (int)k.nse, (int)k.nde,
+                   (int)k.nue, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
+    };
+    const auto record = [&](long long f) { return std::make_pair(info[(size_t)f], (int)iters[(size_t)f]); };
+
+    uint32_t mt_words[624];
+    int mt_pos = 0;
+    const char *noise_env = getenv("LDPC_HIP_EXACT_NOISE");
+    bool device_noise = !(noise_env && std::string(noise_env) == "host") && mt_export(Env::generator(), mt_words, mt_pos);
+    if (device_noise) gfq_harness_probe(hb, b, c, M, device);
+    device_noise = device_noise && device_stream_verdict().load() == 1;
+
+    long long batch = max_batch < 256 ? max_batch : 256;
+    if (device_noise) {
+        if (ldpc_hip_mt_set_state_gfq(ctx, mt_words, mt_pos) != 0) Env::fail(ldpc_hip_last_error());
+        while (!stop) {
+            const long long room = (long long)n_experiments + 1 - k.experiment;
+            const long long B = batch < room ? batch : room;
+            info.resize((size_t)B); iters.resize((size_t)B);
+            if (ldpc_hip_mt_get_state_gfq(ctx, mt_words, &mt_pos) != 0) Env::fail(ldpc_hip_last_error());   // snapshot
+            if (ldpc_hip_mt_frames_gfq(ctx, snr, punctured_blocks, max_iterations, B, info.data(), iters.data()) != 0) Env::fail(ldpc_hip_last_error());
+            const StopReplay rp = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B, record, show);
+            stop = rp.stop;
+            if (rp.used < B) {  // stopped inside the batch: put the generator where the frame-by-frame loop leaves it
+                if (ldpc_hip_mt_set_state_gfq(ctx, mt_words, mt_pos) != 0) Env::fail(ldpc_hip_last_error());
+                if (ldpc_hip_mt_advance_gfq(ctx, rp.used) != 0) Env::fail(ldpc_hip_last_error());
+            }
+            if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+        }
+        if (ldpc_hip_mt_get_state_gfq(ctx, mt_words, &mt_pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!mt_import(Env::generator(), mt_words, mt_pos)) Env::fail("bp_simulation: could not hand the generator state back to std::mt19937");
+    } else {
+        const long long per_frame = n * q_bits, host_cap = gfq_host_noise_frames(per_frame);
+        std::vector<double> noise;
+        while (!stop) {
+            const long long room = (long long)n_experiments + 1 - k.experiment;
+            long long B = batch < room ? batch : room;
+            if (B > host_cap) B = host_cap;   // the batch carries B * n * q_bits doubles through host memory
+            info.resize((size_t)B); iters.resize((size_t)B); noise.resize((size_t)(B * per_frame));
+            const std::mt19937 snapshot = Env::generator();
+            for (double &g : noise) g = Env::gaussian();                                         // :638-642, index order
+            if (ldpc_hip_frames_gfq_noise_host(ctx, noise.data(), snr, punctured_blocks, max_iterations, B, info.data(), iters.data()) != 0)
+                Env::fail(ldpc_hip_last_error());
+            const StopReplay rp = replay_stop_rule(k, n_frame_errors, n_experiments, reference_frame_error, B, record, show);
+            stop = rp.stop;
+            if (rp.used < B) {  // stopped inside the batch: leave the generator where the frame-by-frame loop would
+                Env::generator() = snapshot;
+                for (long long i = 0, cnt = rp.used * per_frame; i < cnt; ++i) (void)Env::gaussian();
+            }
+            if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+        }
+    }
+    ldpc_hip_close(ctx);                                                                         // :831
+    if (counters_out) *counters_out = k;
+    return std::make_pair((double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);   // :840
+}
+
+// The same for a set of candidate codes over GF(q) of one shape: what `for (candidate) { reset_random(); bp_simulation(q_mod, HM, HC,
+// ...); }` computes (search_ggp/scenario_based_code_generation.cpp:754, :852, :883), with the shape and contract of
+// bp_simulation_codes_exact_t.  Call it where the loop would call reset_random() for its first candidate.  Every candidate gets
+// upstream's set-up (its coefficients are rewritten in coefs[q], as bp_simulation does) and its own word; the noise of the generator's
+// stream is drawn once per batch and all candidates are decoded in one launch (ldpc_hip_mt_simulate_codes_gfq*).  show_process == 0
+// runs the rule on the device; otherwise the records come back per batch, the rule is replayed per code on the host and a line is
+// printed per error frame.  LDPC_HIP_EXACT_NOISE=host, or a host whose stream the device does not reproduce, draws the Gaussians on the
+// host (ldpc_hip_frames_codes_gfq_noise_host).  Afterwards Env::generator() holds the state after the last frame code `leave_at`
+// consumed (-1: the last code).  One pair and one SimCounters per code, each equal to bp_simulation_gfq_t on that candidate.
+template <class Mat, class Env>
+std::vector<std::pair<double, double>> bp_simulation_codes_gfq_exact_t(int q_mod, std::vector<Mat> const &codes, std::vector<Mat> &coefs, int ncols2convert,
+                                                                       int tailbite_length, int max_iterations, int n_frame_errors,
+                                                                       long long n_experiments, double snr, double reference_frame_error,
+                                                                       int decoder_type, int modulation_type, int permutation_type,
+                                                                       int punctured_blocks, int show_process, int device = 0,
+                                                                       std::vector<SimCounters> *counters_out = nullptr, long long first_batch = 1024,
+                                                                       long long max_batch = 65536, int leave_at = -1) {
+    if (codes.empty() || codes.size() != coefs.size()) Env::fail("bp_simulation_codes_gfq_exact: empty code set, or not one coefficient matrix per code");
+    if (first_batch < 1 || max_batch < first_batch) Env::fail("bp_simulation_codes_gfq_exact: bad batch sizes");
+    const int q_bits = gfq_harness_check<Env>(q_mod, decoder_type, modulation_type, permutation_type);
+    const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols(), M = tailbite_length;
+    const long long r = (long long)b * M, n = (long long)c * M;
+    if (leave_at < -1 || leave_at >= C) Env::fail("bp_simulation_codes_gfq_exact: leave_at names no code of the set");
+    const int leave = leave_at < 0 ? C - 1 : leave_at;
+    device = devices_from_env(device)[0];
+
+    std::vector<int16_t> hb((size_t)C * b * c), hc((size_t)C * b * c), words((size_t)C * (size_t)n), hb1, hc1, word1;
+    bool any_word = false;
+    for (int q = 0; q < C; ++q) {
+        if (codes[(size_t)q].n_rows() != b || codes[(size_t)q].n_cols() != c) Env::fail("bp_simulation_codes_gfq_exact: the codes of a set share one shape");
+        any_word = gfq_harness_setup<Mat, Env>(q_bits, codes[(size_t)q], coefs[(size_t)q], ncols2convert, M, device, hb1, hc1, word1, nullptr) || any_word;
+        std::copy(hb1.begin(), hb1.end(), hb.begin() + (size_t)q * b * c);
+        std::copy(hc1.begin(), hc1.end(), hc.begin() + (size_t)q * b * c);
+        std::copy(word1.begin(), word1.end(), words.begin() + (size_t)q * (size_t)n);
+    }
+    ldpc_hip_ctx *ctx = nullptr;
+    if (ldpc_hip_open_codes_gfq(q_bits, b, c, M, hb.data(), hc.data(), C, device, &ctx) != 0) Env::fail(ldpc_hip_last_error());
+    if (ldpc_hip_codes_gfq_set_codewords(ctx, any_word ? words.data() : nullptr) != 0) Env::fail(ldpc_hip_last_error());   // no word: shared soft values
+
+    uint32_t mt_words[624];
+    int mt_pos = 0;
+    const char *noise_env = getenv("LDPC_HIP_EXACT_NOISE");
+    bool device_noise = !(noise_env && std::string(noise_env) == "host") && mt_export(Env::generator(), mt_words, mt_pos);
+    if (device_noise) gfq_harness_probe(hb, b, c, M, device);   // the first code's shifts stand at the front
+    device_noise = device_noise && device_stream_verdict().load() == 1;
+
+    std::vector<SimCounters> cnt((size_t)C);
+    const bool nothing = n_frame_errors <= 0 || n_experiments < 0;   // :591 fails before the first frame
+    const auto line = [&](int q) {
+        const SimCounters &k = cnt[(size_t)q];
+        printf("code=%d,SNR=%5.3lf,step=%4d,s_ers=%d,f_ers=%d,u_ers=%d,BER=%5.3le,FER=%5.3le\n", q, snr, (int)k.experiment, (int)k.nse, (int)k.nde,
+               (int)k.nue, (double)k.nse / k.experiment / (double)(n - r), (double)k.nde / k.experiment);
+    };
+    // The per-batch run of both noise sources: frames(B, totals, info, iters) gives the records of the next B frames for all codes
+    const auto batches = [&](long long frame_cap, auto frames) {
+        std::vector<char> running((size_t)C, 1);
+        std::vector<unsigned long long> totals((size_t)C * 5);
+        std::vector<int32_t> info, iters;
+        int n_running = nothing ? 0 : C;
+        long long first = 0, batch = first_batch;
+        while (n_running > 0) {   // every running code has replayed the same number of frames so far: `first`
+            const long long room = n_experiments + 1 - first;
+            long long B = batch < room ? batch : room;
+            if (B > frame_cap) B = frame_cap;
+            if (B <= 0) break;
+            info.resize((size_t)C * (size_t)B); iters.resize((size_t)C * (size_t)B);
+            frames(B, totals.data(), info.data(), iters.data());
+            for (int q = 0; q < C; ++q) {
+                if (!running[(size_t)q]) continue;
+                const int32_t *rec = info.data() + (size_t)q * (size_t)B, *it = iters.data() + (size_t)q * (size_t)B;
+                if (replay_stop_rule(cnt[(size_t)q], n_frame_errors, n_experiments, reference_frame_error, B,
+                                     [&](long long f) { return std::make_pair(rec[f], (int)it[f]); }, [&] { if (show_process) line(q); }).stop) {
+                    running[(size_t)q] = 0; --n_running;
+                }
+            }
+            first += B;
+            if (batch < max_batch) batch = batch * 4 < max_batch ? batch * 4 : max_batch;
+        }
+    };
+
+    if (device_noise) {
+        if (ldpc_hip_mt_set_state_codes_gfq(ctx, mt_words, mt_pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!show_process) {   // nothing to print per error frame: the rule runs on the device
+            std::vector<unsigned long long> state((size_t)C * 6);
+            if (ldpc_hip_mt_simulate_codes_gfq_stop(ctx, snr, punctured_blocks, max_iterations, n_frame_errors, n_experiments, reference_frame_error,
+                                                    first_batch, max_batch, state.data()) != 0)
+                Env::fail(ldpc_hip_last_error());
+            for (int q = 0; q < C; ++q) {
+                const unsigned long long *st = state.data() + (size_t)q * 6;
+                SimCounters &k = cnt[(size_t)q];
+                k.experiment = (long long)st[0]; k.nse = (long long)st[1]; k.nde = (long long)st[2]; k.nue = (long long)st[3];
+                k.sum_abs_iters = (long long)st[4];
+            }
+        } else {
+            batches(max_batch, [&](long long B, unsigned long long *totals, int32_t *info, int32_t *iters) {
+                if (ldpc_hip_mt_simulate_codes_gfq(ctx, snr, punctured_blocks, max_iterations, B, totals, info, iters) != 0) Env::fail(ldpc_hip_last_error());
+            });
+            if (ldpc_hip_mt_set_state_codes_gfq(ctx, mt_words, mt_pos) != 0) Env::fail(ldpc_hip_last_error());   // back to the state at entry
+        }
+        // the generator where upstream's loop leaves it for code `leave`
+        if (ldpc_hip_mt_advance_codes_gfq(ctx, cnt[(size_t)leave].experiment) != 0) Env::fail(ldpc_hip_last_error());
+        if (ldpc_hip_mt_get_state_codes_gfq(ctx, mt_words, &mt_pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!mt_import(Env::generator(), mt_words, mt_pos)) Env::fail("bp_simulation_codes_gfq_exact: could not hand the generator state back to std::mt19937");
+    } else {
+        const std::mt19937 entry = Env::generator();
+        const long long per_frame = n * q_bits;
+        std::vector<double> noise;
+        batches(gfq_host_noise_frames(per_frame), [&](long long B, unsigned long long *totals, int32_t *info, int32_t *iters) {
+            noise.resize((size_t)(B * per_frame));
+            for (double &g : noise) g = Env::gaussian();                                         // :638-642, index order
+            if (ldpc_hip_frames_codes_gfq_noise_host(ctx, noise.data(), snr, punctured_blocks, max_iterations, B, totals, info, iters) != 0)
+                Env::fail(ldpc_hip_last_error());
+        });
+        Env::generator() = entry;
+        for (long long i = 0, draws = cnt[(size_t)leave].experiment * per_frame; i < draws; ++i) (void)Env::gaussian();
+    }
+    ldpc_hip_close(ctx);
+    std::vector<std::pair<double, double>> out((size_t)C);
+    for (int q = 0; q < C; ++q)
+        out[(size_t)q] = std::make_pair((double)cnt[(size_t)q].nse / cnt[(size_t)q].experiment / (double)(n - r),   // :840
+                                        (double)cnt[(size_t)q].nde / cnt[(size_t)q].experiment);
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+// the standalone form: ldpc::Matrix and the library's own generator
+inline std::vector<std::pair<double, double>> bp_simulation_codes_gfq_exact(int q_mod, std::vector<Matrix> const &codes, std::vector<Matrix> &coefs,
+                                                                            int ncols2convert, int tailbite_length, int max_iterations,
+                                                                            int n_frame_errors, int n_experiments, double snr,
+                                                                            double reference_frame_error, int punctured_blocks, int show_process,
+                                                                            int device = 0, std::vector<SimCounters> *counters_out = nullptr,
+                                                                            long long first_batch = 1024, long long max_batch = 65536, int leave_at = -1) {
+    return bp_simulation_codes_gfq_exact_t<Matrix, OwnRngEnv>(q_mod, codes, coefs, ncols2convert, tailbite_length, max_iterations, n_frame_errors,
+                                                              n_experiments, snr, reference_frame_error, LDPC_HIP_FHT_DEC, MODULATION_SKIP_, 0,
+                                                              punctured_blocks, show_process, device, counters_out, first_batch, max_batch, leave_at);
+}
+
+// Standalone entry point with upstream's argument list (bp_simulation.h:9-27); q_mod > 2 goes to bp_simulation_gfq_t, which reads
+// and rewrites coef_matrix and takes ncols2convert; a binary run ignores both.
 std::pair<double, double> bp_simulation(int q_mod, Matrix const &code_generating_matrix, Matrix &coef_matrix,
                                         int ncols2convert, int tailbite_length, int max_iterations, int n_frame_errors,
                                         int n_experiments, double snr, double reference_frame_error, int decoder_type,

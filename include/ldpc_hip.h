@@ -441,6 +441,42 @@ int ldpc_hip_count_errors_gfq_dev(ldpc_hip_ctx *ctx, const int16_t *d_qhard, con
 int ldpc_hip_simulate_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame, long long B,
                           int random_messages, unsigned long long counters[5]);
 
+/* ---- Exact replay of upstream's q-ary frame loop on a GF(q) context (csrc/ldpc_gfq_exact_api.hpp) ---------------------------------
+ * bp_simulation(q_mod > 2, ...) draws no sample before its frame loop and then, per frame, N * q_bits values of
+ * next_random_gaussian() in index order (bp_simulation.cpp:638-642): B frames are the next B * N * q_bits samples of the generator of
+ * ldpc_hip_mt_normal_dev.  Every frame carries the same word (:537-557, :581-582), the decoder runs with p_thr = 0, and the records
+ * are those of ldpc_hip_count_errors_gfq_dev against that word.  Only MODULATION_SKIP and permutation_type 0 exist upstream for
+ * q_mod > 2 (the switch at :635-678 has no other case, the permutation is never inverted, :683-686), so neither is an argument.
+ * The binary ldpc_hip_mt_* entry points keep refusing a GF(q) context; these names serve a GF(q) context only and return
+ * LDPC_HIP_EINVAL on any other kind, on bad arguments and (where they draw) without a generator state.  A refused call launches nothing
+ * and leaves the word and the generator alone.  One device; multi-device and rank-sharded q-ary replay are not built.
+ *
+ * The message upstream encodes: bp_simulation.cpp:539-546 writes the eight symbols {6, 11, 0, 4, 2, 1, 2, 5} into a malloc()ed array of
+ * n ints and encode_NBQCLDPC reads K = (nh - rh) * M of them -- the rest is uninitialised memory, and symbol 11 does not exist for
+ * q < 16.  DEFINED HERE: the message is those eight symbols (the first K of them when K < 8), each reduced with & (q - 1), followed by
+ * zeros.  HOST only, no GPU: msg [K] out.  LDPC_HIP_EINVAL for q_bits outside 2 .. 10, K < 0 or a null msg with K > 0. */
+int ldpc_hip_gfq_upstream_message(int q_bits, int K, int16_t *msg);
+/* The word every frame of the two entry points below carries: codeword HOST [N], symbols 0 .. q-1 (LDPC_HIP_EINVAL otherwise), or NULL =
+ * the all-zero word (the default; what upstream sends when encode_NBQCLDPC returns 0, :552-556). */
+int ldpc_hip_gfq_set_codeword(ldpc_hip_ctx *ctx, const int16_t *codeword);
+/* As ldpc_hip_mt_set_state / ldpc_hip_mt_get_state, for a GF(q) context. */
+int ldpc_hip_mt_set_state_gfq(ldpc_hip_ctx *ctx, const uint32_t state[624], int pos);
+int ldpc_hip_mt_get_state_gfq(ldpc_hip_ctx *ctx, uint32_t state[624], int *pos);
+/* Draws and drops the frames * N * q_bits samples of `frames` frames. */
+int ldpc_hip_mt_advance_gfq(ldpc_hip_ctx *ctx, long long frames);
+/* noise -> channel -> ldpc_hip_decode_gfq_dev -> count for the next B frames of the stream; synchronous.  frame_info [B], iters [B]:
+ * HOST arrays, as ldpc_hip_mt_frames fills them.  sigma = sqrt(pow(10, -snr_db / 10) / 2 / ((nh - rh) / (double)(nh - punctured_blocks)))
+ * (:444-445): punctured_blocks (0 .. nh-1) enters sigma only, no position is punctured (:711-714).  The work is done in pieces of at
+ * most 1 GiB of soft values (LDPC_HIP_GFQ_PIECE=n caps the frames per piece further); the records do not depend on the pieces, on
+ * LDPC_HIP_GFQ_SLOTS or on how B is split over calls.  LDPC_HIP_EUNSUPPORTED: a frame whose N * q_bits samples exceed one generation
+ * round (2^27). */
+int ldpc_hip_mt_frames_gfq(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, long long B, int32_t *frame_info,
+                           int32_t *iters);
+/* The same records from Gaussians the caller drew: noise HOST [B][N * q_bits], the values of next_random_gaussian() in upstream's
+ * order.  The route of a host whose std::normal_distribution the device generator does not reproduce; needs no generator state. */
+int ldpc_hip_frames_gfq_noise_host(ldpc_hip_ctx *ctx, const double *noise, double snr_db, int punctured_blocks, int maxiter, long long B,
+                                   int32_t *frame_info, int32_t *iters);
+
 /* ---- Code sets: C candidate codes of one shape x B frames in one launch (csrc/ldpc_codeset.hpp) -----------------------------------
  * What a code search does (upstream's `search` / `ggp` drivers): many base matrices with the same rh, nh and M, each scored by a short
  * Monte-Carlo run over the SAME noise.  hd [C][rh][nh]: the C base matrices one after the other, shifts in [0, M), -1 = empty block.
@@ -699,6 +735,38 @@ int ldpc_hip_simulate_codes_gfq(ldpc_hip_ctx *ctx, double snr_db, int maxiter, u
 int ldpc_hip_simulate_codes_gfq_stop(ldpc_hip_ctx *ctx, double snr_db, int maxiter, uint64_t seed, long long first_frame,
                                      int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
                                      long long max_batch, unsigned long long *state);
+
+/* ---- Exact replay on a GF(q) code set: what a search computes that calls reset_random() and bp_simulation(q_mod, HM, HC, ...) for
+ * every candidate (search_ggp/scenario_based_code_generation.cpp:754, :852, :883), one launch per piece.  The stream, sigma and the
+ * records are those of ldpc_hip_mt_frames_gfq above; results per code are identical to ldpc_hip_mt_frames_gfq on a context opened
+ * with that code's matrices and carrying that code's word, from the same generator state.  These serve GF(q) code-set contexts only
+ * (LDPC_HIP_EINVAL on any other kind, on bad arguments and -- where they draw -- without ldpc_hip_mt_set_state_codes_gfq before);
+ * the five binary ldpc_hip_mt_*_codes keep refusing a GF(q) set.  A refused call launches nothing and leaves words and generator alone.
+ * Synchronous, one call at a time per context, null stream.  Pieces: LDPC_HIP_GFQ_PIECE.
+ * ldpc_hip_codes_gfq_set_codewords: words HOST [C][N], the word code c sends (upstream encodes a message per candidate), symbols
+ *   0 .. q-1; NULL = every code sends the all-zero word (the default).  Without words the soft values of a piece are formed once and
+ *   shared by the codes; with words they are formed per code (gfq_channel_codes_kernel) and a piece holds C * q * N * 8 bytes of them per
+ *   frame.  The words are read by the entry points of this section only: ldpc_hip_simulate_codes_gfq(_stop) send the all-zero word.
+ * ldpc_hip_mt_set_state_codes_gfq / _get_state_codes_gfq: as ldpc_hip_mt_set_state / _get_state.
+ * ldpc_hip_mt_advance_codes_gfq: draws and drops the frames * N * q_bits samples of `frames` frames.
+ * ldpc_hip_mt_simulate_codes_gfq: the next B frames for all C codes; counters [C][5] (HOST, overwritten), frame_info [C][B] and
+ *   iters [C][B] (HOST, each may be NULL).  The generator is B frames further on afterwards.
+ * ldpc_hip_mt_simulate_codes_gfq_stop: the contract of ldpc_hip_mt_simulate_codes_stop -- the rule of an exact replay per code on the
+ *   device, state [C][6] = experiment, nse (wrong information SYMBOLS), nde, nue, sum |iters|, frames_decoded; the generator and its frame index are put BACK to the
+ *   state at entry, and ldpc_hip_mt_advance_codes_gfq(ctx, state[c][0]) then leaves it where upstream's loop leaves it for code c.
+ * ldpc_hip_frames_codes_gfq_noise_host: the twin of ldpc_hip_frames_codes_host -- the records of ldpc_hip_mt_simulate_codes_gfq from
+ *   Gaussians the caller drew, noise HOST [B][N * q_bits]; needs no generator state. */
+int ldpc_hip_codes_gfq_set_codewords(ldpc_hip_ctx *ctx, const int16_t *words);
+int ldpc_hip_mt_set_state_codes_gfq(ldpc_hip_ctx *ctx, const uint32_t state[624], int pos);
+int ldpc_hip_mt_get_state_codes_gfq(ldpc_hip_ctx *ctx, uint32_t state[624], int *pos);
+int ldpc_hip_mt_advance_codes_gfq(ldpc_hip_ctx *ctx, long long frames);
+int ldpc_hip_mt_simulate_codes_gfq(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, long long B,
+                                   unsigned long long *counters, int32_t *frame_info, int32_t *iters);
+int ldpc_hip_mt_simulate_codes_gfq_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, int n_frame_errors,
+                                        long long n_experiments, double reference_frame_error, long long first_batch, long long max_batch,
+                                        unsigned long long *state);
+int ldpc_hip_frames_codes_gfq_noise_host(ldpc_hip_ctx *ctx, const double *noise, double snr_db, int punctured_blocks, int maxiter,
+                                         long long B, unsigned long long *counters, int32_t *frame_info, int32_t *iters);
 
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */

@@ -186,6 +186,13 @@ def load_library():
     lib.ldpc_hip_gfq_channel_dev.argtypes = [vp, vp, vp, f64, u64, i64, i64, vp, vp]
     lib.ldpc_hip_count_errors_gfq_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_gfq.argtypes = [vp, f64, i32, u64, i64, i64, i32, C.POINTER(C.c_ulonglong)]
+    lib.ldpc_hip_gfq_upstream_message.argtypes = [i32, i32, vp]
+    lib.ldpc_hip_gfq_set_codeword.argtypes = [vp, vp]
+    lib.ldpc_hip_mt_set_state_gfq.argtypes = [vp, vp, i32]
+    lib.ldpc_hip_mt_get_state_gfq.argtypes = [vp, vp, C.POINTER(i32)]
+    lib.ldpc_hip_mt_advance_gfq.argtypes = [vp, i64]
+    lib.ldpc_hip_mt_frames_gfq.argtypes = [vp, f64, i32, i32, i64, vp, vp]
+    lib.ldpc_hip_frames_gfq_noise_host.argtypes = [vp, vp, f64, i32, i32, i64, vp, vp]
     for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, _CODES_WIDE, *_CODES_ROUTE.values()):
         getattr(lib, open_codes).argtypes = [i32] * open_id + [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
         getattr(lib, codes_table_host).argtypes = [i32] * table_id + [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
@@ -206,6 +213,13 @@ def load_library():
     lib.ldpc_hip_count_errors_codes_gfq_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.ldpc_hip_simulate_codes_gfq.argtypes = [vp, f64, i32, u64, i64, i64, vp, vp]
     lib.ldpc_hip_simulate_codes_gfq_stop.argtypes = [vp, f64, i32, u64, i64, i32, i64, f64, i64, i64, vp]
+    lib.ldpc_hip_codes_gfq_set_codewords.argtypes = [vp, vp]
+    lib.ldpc_hip_mt_set_state_codes_gfq.argtypes = [vp, vp, i32]
+    lib.ldpc_hip_mt_get_state_codes_gfq.argtypes = [vp, vp, C.POINTER(i32)]
+    lib.ldpc_hip_mt_advance_codes_gfq.argtypes = [vp, i64]
+    lib.ldpc_hip_mt_simulate_codes_gfq.argtypes = [vp, f64, i32, i32, i64, vp, vp, vp]
+    lib.ldpc_hip_mt_simulate_codes_gfq_stop.argtypes = [vp, f64, i32, i32, i32, i64, f64, i64, i64, vp]
+    lib.ldpc_hip_frames_codes_gfq_noise_host.argtypes = [vp, vp, f64, i32, i32, i64, vp, vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -477,6 +491,15 @@ def gfq_left2right(matr):
     return m
 
 
+def gfq_upstream_message(q_bits, K):
+    """The message bp_simulation(q_mod > 2, ...) encodes, as include/ldpc_hip.h defines it: upstream's eight symbols {6, 11, 0, 4, 2, 1,
+    2, 5} (the first K of them when K < 8), each reduced with & (q - 1), followed by zeros.  int16 [K]; no GPU needed."""
+    msg = np.zeros(max(int(K), 0), dtype=np.int16)
+    lib = load_library()
+    _check(lib, lib.ldpc_hip_gfq_upstream_message(int(q_bits), int(K), msg.ctypes.data), "ldpc_hip_gfq_upstream_message")
+    return msg
+
+
 class LdpcHipGfq:
     """One opened QC-LDPC code over GF(q), q = 2^q_bits, on one GPU == upstream's DEC_STATE of decod_open(FHT_DEC, q_bits, ...) with hb,
     hc and fht_ncols2convert filled in and decod_init done.  hb: shifts (-1 empty), hc: coefficients 1 .. q-1 in natural representation."""
@@ -640,6 +663,51 @@ class LdpcHipGfq:
         rc = self.lib.ldpc_hip_simulate_gfq(self.h, float(snr_db), int(maxiter), int(seed), int(first_frame), int(B), 1 if random_messages else 0, cnt)
         _check(self.lib, rc, "ldpc_hip_simulate_gfq")
         return [int(v) for v in cnt]
+
+    # ---- exact replay of upstream's q-ary frame loop: its own mt19937 / normal_distribution stream, one word for all frames ----------
+    def set_codeword(self, codeword=None):
+        """The word every frame of mt_frames / frames_from_noise carries: [N] symbols 0 .. q-1, or None = the all-zero word."""
+        cw = None
+        if codeword is not None:
+            cw = np.ascontiguousarray(codeword, dtype=np.int16)
+            assert cw.shape == (self.N,)
+        _check(self.lib, self.lib.ldpc_hip_gfq_set_codeword(self.h, cw.ctypes.data if cw is not None else None), "ldpc_hip_gfq_set_codeword")
+
+    def mt_set_state(self, state, pos):
+        """state: 624 uint32 words + index of the next word, as libstdc++ streams a std::mt19937."""
+        st = np.ascontiguousarray(state, dtype=np.uint32)
+        assert st.shape == (624,)
+        _check(self.lib, self.lib.ldpc_hip_mt_set_state_gfq(self.h, st.ctypes.data, int(pos)), "ldpc_hip_mt_set_state_gfq")
+
+    def mt_get_state(self):
+        st = np.empty(624, dtype=np.uint32)
+        pos = C.c_int()
+        _check(self.lib, self.lib.ldpc_hip_mt_get_state_gfq(self.h, st.ctypes.data, C.byref(pos)), "ldpc_hip_mt_get_state_gfq")
+        return st, pos.value
+
+    def mt_advance(self, frames):
+        """Draws and drops the frames * N * q_bits samples of `frames` frames."""
+        _check(self.lib, self.lib.ldpc_hip_mt_advance_gfq(self.h, int(frames)), "ldpc_hip_mt_advance_gfq")
+
+    def mt_frames(self, snr_db, maxiter, B, punctured_blocks=0):
+        """noise -> channel -> decode -> count for the next B frames of upstream's stream: (frame_info, iters) int32 numpy arrays."""
+        info = np.empty(max(int(B), 0), dtype=np.int32)
+        its = np.empty(max(int(B), 0), dtype=np.int32)
+        rc = self.lib.ldpc_hip_mt_frames_gfq(self.h, float(snr_db), int(punctured_blocks), int(maxiter), int(B), info.ctypes.data, its.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_mt_frames_gfq")
+        return info, its
+
+    def frames_from_noise(self, noise, snr_db, maxiter, punctured_blocks=0):
+        """The same records from Gaussians the caller drew: noise float64 numpy [B, N * q_bits] in upstream's order."""
+        nz = np.ascontiguousarray(noise, dtype=np.float64)
+        assert nz.ndim == 2 and nz.shape[1] == self.N * self.q_bits
+        B = nz.shape[0]
+        info = np.empty(B, dtype=np.int32)
+        its = np.empty(B, dtype=np.int32)
+        rc = self.lib.ldpc_hip_frames_gfq_noise_host(self.h, nz.ctypes.data, float(snr_db), int(punctured_blocks), int(maxiter), B,
+                                                     info.ctypes.data, its.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_frames_gfq_noise_host")
+        return info, its
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")
@@ -971,6 +1039,67 @@ class LdpcHipCodesGfq:
                                                        int(n_experiments), float(reference_frame_error), int(first_batch), int(max_batch), state.ctypes.data)
         _check(self.lib, rc, "ldpc_hip_simulate_codes_gfq_stop")
         return state
+
+    # ---- exact replay of upstream's q-ary frame loop for every code of the set: one noise stream, a word per code -----------------------
+    def set_codewords(self, words=None):
+        """The word each code sends in mt_simulate / mt_simulate_until / frames_from_noise: [C, N] symbols 0 .. q-1, or None = every code
+        sends the all-zero word and the soft values are shared."""
+        w = None
+        if words is not None:
+            w = np.ascontiguousarray(words, dtype=np.int16)
+            assert w.shape == (self.C, self.N)
+        _check(self.lib, self.lib.ldpc_hip_codes_gfq_set_codewords(self.h, w.ctypes.data if w is not None else None), "ldpc_hip_codes_gfq_set_codewords")
+
+    def mt_set_state(self, state, pos):
+        st = np.ascontiguousarray(state, dtype=np.uint32)
+        assert st.shape == (624,)
+        _check(self.lib, self.lib.ldpc_hip_mt_set_state_codes_gfq(self.h, st.ctypes.data, int(pos)), "ldpc_hip_mt_set_state_codes_gfq")
+
+    def mt_get_state(self):
+        st = np.empty(624, dtype=np.uint32)
+        pos = C.c_int()
+        _check(self.lib, self.lib.ldpc_hip_mt_get_state_codes_gfq(self.h, st.ctypes.data, C.byref(pos)), "ldpc_hip_mt_get_state_codes_gfq")
+        return st, pos.value
+
+    def mt_advance(self, frames):
+        """Draws and drops the frames * N * q_bits samples of `frames` frames."""
+        _check(self.lib, self.lib.ldpc_hip_mt_advance_codes_gfq(self.h, int(frames)), "ldpc_hip_mt_advance_codes_gfq")
+
+    def mt_simulate(self, snr_db, maxiter, frames, punctured_blocks=0, records=False):
+        """The next `frames` frames of upstream's stream for every code.  Returns counters uint64 [C, 5], and with records=True also
+        frame_info and iters int32 [C, frames]: per code what LdpcHipGfq.mt_frames gives for that code and word from the same state."""
+        cnt = np.zeros((self.C, 5), dtype=np.uint64)
+        info = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        its = np.empty((self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_mt_simulate_codes_gfq(self.h, float(snr_db), int(punctured_blocks), int(maxiter), int(frames), cnt.ctypes.data,
+                                                     info.ctypes.data if records else None, its.ctypes.data if records else None)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_gfq")
+        return (cnt, info, its) if records else cnt
+
+    def mt_simulate_until(self, snr_db, maxiter, n_frame_errors, n_experiments, reference_frame_error, first_batch=1024, max_batch=65536,
+                          punctured_blocks=0):
+        """Upstream's stopping rule per code over the exact-replay stream.  Returns uint64 [C, 6] = experiment, nse, nde, nue,
+        sum |iters|, frames_decoded.  The generator is back at its state at entry afterwards; mt_advance(state[c, 0]) takes it to the
+        end of code c's run."""
+        state = np.zeros((self.C, 6), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_mt_simulate_codes_gfq_stop(self.h, float(snr_db), int(punctured_blocks), int(maxiter), int(n_frame_errors),
+                                                          int(n_experiments), float(reference_frame_error), int(first_batch), int(max_batch),
+                                                          state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_gfq_stop")
+        return state
+
+    def frames_from_noise(self, noise, snr_db, maxiter, punctured_blocks=0):
+        """mt_simulate(records=True) from Gaussians the caller drew: noise float64 numpy [B, N * q_bits]."""
+        nz = np.ascontiguousarray(noise, dtype=np.float64)
+        assert nz.ndim == 2 and nz.shape[1] == self.N * self.q_bits
+        B = nz.shape[0]
+        cnt = np.zeros((self.C, 5), dtype=np.uint64)
+        info = np.empty((self.C, B), dtype=np.int32)
+        its = np.empty((self.C, B), dtype=np.int32)
+        rc = self.lib.ldpc_hip_frames_codes_gfq_noise_host(self.h, nz.ctypes.data, float(snr_db), int(punctured_blocks), int(maxiter), B,
+                                                           cnt.ctypes.data, info.ctypes.data, its.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_frames_codes_gfq_noise_host")
+        return cnt, info, its
 
     def profile(self, enable=True):
         _check(self.lib, self.lib.ldpc_hip_profile_enable(self.h, int(enable)), "ldpc_hip_profile_enable")

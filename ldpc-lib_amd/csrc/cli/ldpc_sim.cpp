@@ -1,17 +1,20 @@
-// ldpc_sim.cpp -- `ldpc_sim simulation <scenario.jsonx> <result.jsonx>`: the binary-code path of upstream's `simulation`
-// driver (main_simulation.cpp:222-679) on top of this repository's bp_simulation (GPU decoders, upstream's noise order).
+// ldpc_sim.cpp -- `ldpc_sim simulation <scenario.jsonx> <result.jsonx>`: upstream's `simulation` driver
+// (main_simulation.cpp:222-679) on top of this repository's bp_simulation (GPU decoders, upstream's noise order), for binary codes
+// and for codes over GF(q) (`_q_mod` > 2: decoder 6 whatever `_decoder_type` says, :348-349; `coef` read, :359-360, and reduced,
+// :416-434; ncols2convert = 0; `_q_mod` and `coef` in the result record, :608-614).
 //
 // What it keeps from upstream: the scenario fields (:260-283), the per-code fields (:343-364), the reduction of the shifts
 // modulo the lifting with the special last parity column (:400-414), one generator reset per (code, SNR) so that all codes
 // see the same noise (:483), the call into bp_simulation with reference_frame_error = error_minimization/threshold (:492-510),
 // the result record written per code (:574-606).  What it does not do: girth / ACE tracing (trace_matrix, out of scope:
-// `girth` is copied through), marking files (`_marking` must be "skip"), GF(q) codes (`_q_mod` > 2 are reported and skipped).
+// `girth` is copied through), marking files (`_marking` must be "skip"), GF(q) codes with --throughput (reported and skipped).
 //
 //   --throughput   device-side noise (counter-based Philox, not upstream's mt19937 stream): 10^6-10^7 frames/s per GPU; every
 //                  modulation_type 0..4 and permutation_type 0..4; upstream's stopping rule frame by frame over the ordered records
 //   --code-sets    exact mode only: codes that agree in shape, _decoder_type, _lifting, _punctured_blocks, _iterations and _SNRs are
 //                  scored as ONE set per SNR (ldpc::bp_simulation_codes_exact: the noise of the reset generator drawn once, all codes
-//                  of the group in one launch); the result file is the one without the flag except for `time`
+//                  of the group in one launch); the result file is the one without the flag except for `time`.  Codes over GF(q) of
+//                  one q are grouped the same way into ldpc::bp_simulation_codes_gfq_exact
 //   --device N     GPU ordinal;  --devices 0,1,2,3 | all   shard the frames over several GPUs (RCCL all-reduce of the counters)
 #include <chrono>
 #include <cmath>
@@ -45,21 +48,43 @@ void reduce_shifts(ldpc::Matrix &H, int M) {
             }
 }
 
+// main_simulation.cpp:416-434: where the code has a circulant, a coefficient > -1 is reduced modulo q, and 0 becomes q - 1
+void reduce_coefs(ldpc::Matrix &HC, const ldpc::Matrix &H, int q_mod) {
+    for (int i = 0; i < H.n_rows(); ++i)
+        for (int j = 0; j < H.n_cols(); ++j)
+            if (H(i, j) > -1 && HC(i, j) > -1) {
+                HC(i, j) = HC(i, j) % q_mod;
+                if (HC(i, j) == 0) HC(i, j) = q_mod - 1;
+            }
+}
+
+// the `coef` matrix of a q-ary code record, in the shape of its `code`
+ldpc::Matrix read_coefs(const jsonx::Value &code, size_t code_idx, int rows, int columns) {
+    int r = 0, c = 0;
+    const std::vector<int> cells = code.select("coef").as_int_matrix(r, c);
+    if (r != rows || c != columns) die("code #" + std::to_string(code_idx) + ": 'coef' must have the shape of 'code'");
+    ldpc::Matrix HC(r, c);
+    HC.v = cells;
+    return HC;
+}
+
 struct Pair { double ber, fer; };
 
 // --code-sets: what decides whether two codes of the scenario can share a set
 struct SetKey {
     int decoder_type, lifting, punctured_blocks, iterations;
     std::vector<double> snrs;
+    int q_mod = 2;
     bool operator==(const SetKey &o) const {
         return decoder_type == o.decoder_type && lifting == o.lifting && punctured_blocks == o.punctured_blocks && iterations == o.iterations &&
-               snrs == o.snrs;
+               snrs == o.snrs && q_mod == o.q_mod;
     }
 };
 struct SetGroup {
     SetKey key;
     std::vector<size_t> members;        // indices into the scenario's `results`
     std::vector<ldpc::Matrix> codes;    // shifts already reduced
+    std::vector<ldpc::Matrix> coefs;    // q_mod > 2: coefficients already reduced
 };
 struct SetResult { std::vector<Pair> per_snr; double secs = 0; };
 
@@ -70,6 +95,15 @@ bool set_takes(const SetGroup &g, int rows, int columns) {
     for (int q = 0; q < C; ++q)
         for (int i = 0; i < rows * columns; ++i) hd[(size_t)q * rows * columns + i] = (int16_t)g.codes[(size_t)q].v[(size_t)i];
     long long len = 0;
+    if (g.key.q_mod > 2) {   // the per-code rules of a GF(q) set do not depend on the column order left2right changes
+        int q_bits = 0;
+        while ((1 << q_bits) < g.key.q_mod) ++q_bits;
+        if ((1 << q_bits) != g.key.q_mod) return false;
+        std::vector<int16_t> hc(hd.size());
+        for (int q = 0; q < C; ++q)
+            for (int i = 0; i < rows * columns; ++i) hc[(size_t)q * rows * columns + i] = (int16_t)g.coefs[(size_t)q].v[(size_t)i];
+        return ldpc_hip_codes_gfq_table_host(q_bits, rows, columns, M, hd.data(), hc.data(), C, nullptr, nullptr, 0, &len) == 0;
+    }
     switch (dec) {
     case LDPC_HIP_MS_DEC: case LDPC_HIP_LMS_DEC: case LDPC_HIP_TASP_DEC:
         if (rows > 16 || (dec == LDPC_HIP_MS_DEC && columns > 32))   // the route open_code_set takes for these shapes
@@ -159,22 +193,26 @@ int main(int argc, char **argv) {
             int rows0 = -1, columns0 = -1;
             for (size_t code_idx = 0; code_idx < codes.items.size(); ++code_idx) {
                 const jsonx::Value &code = codes.items[code_idx];
-                if ((code.has("_q_mod") ? (int)code.select("_q_mod").as_int() : 2) > 2) continue;
+                const int q_mod = code.has("_q_mod") ? (int)code.select("_q_mod").as_int() : 2;
                 if (code.select("_marking").as_string() != "skip") break;   // the loop below dies there: nothing behind it is simulated
                 int r = 0, c = 0;
                 const std::vector<int> cells = code.select("code").as_int_matrix(r, c);
                 if (rows0 == -1) { rows0 = r; columns0 = c; }
                 else if (rows0 != r || columns0 != c) continue;
-                SetKey key{(int)code.select("_decoder_type").as_int(), (int)code.select("_lifting").as_int(),
-                           (int)code.select("_punctured_blocks").as_int(), (int)code.select("_iterations").as_int(), code.select("_SNRs").as_doubles()};
+                SetKey key{q_mod > 2 ? LDPC_HIP_FHT_DEC : (int)code.select("_decoder_type").as_int(), (int)code.select("_lifting").as_int(),
+                           (int)code.select("_punctured_blocks").as_int(), (int)code.select("_iterations").as_int(), code.select("_SNRs").as_doubles(),
+                           q_mod};
                 ldpc::Matrix H(r, c);
                 H.v = cells;
                 reduce_shifts(H, key.lifting);
+                ldpc::Matrix HC;
+                if (q_mod > 2) { HC = read_coefs(code, code_idx, r, c); reduce_coefs(HC, H, q_mod); }
                 size_t g = 0;
                 while (g < groups.size() && !(groups[g].key == key)) ++g;
                 if (g == groups.size()) { groups.emplace_back(); groups[g].key = key; }
                 groups[g].members.push_back(code_idx);
                 groups[g].codes.push_back(H);
+                if (q_mod > 2) groups[g].coefs.push_back(HC);
             }
             for (const SetGroup &g : groups) {
                 if (g.members.size() < 2 || g.key.punctured_blocks < 0 || g.key.punctured_blocks >= columns0 || !set_takes(g, rows0, columns0)) continue;
@@ -184,7 +222,12 @@ int main(int argc, char **argv) {
                     printf("set of %zu codes from code #%zu on, SNR = %6.3f\n", g.members.size(), g.members[0], g.key.snrs[s]);
                     ldpc::initial_random_seed = seed;
                     ldpc::reset_random();                                                                                     // :483 all codes are tested with same noise
-                    const std::vector<std::pair<double, double>> p = ldpc::bp_simulation_codes_exact(
+                    std::vector<ldpc::Matrix> coefs = g.coefs;   // the call rewrites them (ncols2convert = 0: with the same values)
+                    const std::vector<std::pair<double, double>> p =
+                        g.key.q_mod > 2 ? ldpc::bp_simulation_codes_gfq_exact(g.key.q_mod, g.codes, coefs, 0, g.key.lifting, g.key.iterations, num_frame_errors,
+                                                                              (int)num_experiments, g.key.snrs[s], error_rate_threshold,
+                                                                              g.key.punctured_blocks, 0, devices[0])
+                                        : ldpc::bp_simulation_codes_exact(
                         g.codes, g.key.lifting, g.key.iterations, num_frame_errors, (int)num_experiments, g.key.snrs[s], error_rate_threshold,
                         g.key.decoder_type, modulation_type, permutation_type, permutation_block, permutation_inter, g.key.punctured_blocks, 0, devices[0]);
                     for (size_t q = 0; q < g.members.size(); ++q) from_set[g.members[q]].per_snr[s] = {p[q].first, p[q].second};
@@ -199,12 +242,12 @@ int main(int argc, char **argv) {
             const jsonx::Value &code = codes.items[code_idx];
             const std::vector<double> snrs = code.select("_SNRs").as_doubles();
             const int q_mod = code.has("_q_mod") ? (int)code.select("_q_mod").as_int() : 2;
-            const int decoder_type = (int)code.select("_decoder_type").as_int();
+            const int decoder_type = q_mod > 2 ? LDPC_HIP_FHT_DEC : (int)code.select("_decoder_type").as_int();   // :348-349
             const int lifting = (int)code.select("_lifting").as_int();
             const int punctured_blocks = (int)code.select("_punctured_blocks").as_int();
             const int iterations = (int)code.select("_iterations").as_int();
             const std::string marking = code.select("_marking").as_string();
-            if (q_mod > 2) { printf("code #%zu: GF(%d) codes (FHT decoder) are not built in ldpc-lib_amd, skipped\n", code_idx, q_mod); continue; }
+            if (q_mod > 2 && throughput) { printf("code #%zu: GF(%d) codes (FHT decoder) are not built in ldpc-lib_amd, skipped\n", code_idx, q_mod); continue; }
             if (marking != "skip") die("code #" + std::to_string(code_idx) + ": marking files are not built (\"_marking\" must be \"skip\")");
             int r = 0, c = 0;
             const std::vector<int> cells = code.select("code").as_int_matrix(r, c);
@@ -213,6 +256,8 @@ int main(int argc, char **argv) {
             ldpc::Matrix H(r, c);
             H.v = cells;
             reduce_shifts(H, lifting);
+            ldpc::Matrix HC;
+            if (q_mod > 2) { HC = read_coefs(code, code_idx, r, c); reduce_coefs(HC, H, q_mod); }                                // :359-360, :416-434
             const double bitrate = (double)(columns - rows) / (columns - punctured_blocks);                                  // :372
 
             std::vector<double> ber(snrs.size()), fer(snrs.size()), esn0(snrs.size());
@@ -229,6 +274,13 @@ int main(int argc, char **argv) {
                         2, H, lifting, iterations, num_frame_errors, num_experiments, snrs[s], error_rate_threshold, decoder_type, modulation_type,
                         permutation_type, permutation_block, permutation_inter, punctured_blocks, 0, (unsigned long long)seed, devices, nullptr, 65536, nullptr,
                         random_codewords);
+                    res = {p.first, p.second};
+                } else if (q_mod > 2) {
+                    ldpc::initial_random_seed = seed;
+                    ldpc::reset_random();                                                                                     // :483
+                    const std::pair<double, double> p = ldpc::bp_simulation_gfq_t<ldpc::Matrix, ldpc::OwnRngEnv>(
+                        q_mod, H, HC, 0, lifting, iterations, num_frame_errors, (int)num_experiments, snrs[s], error_rate_threshold, decoder_type,
+                        modulation_type, permutation_type, punctured_blocks, 0, nullptr, devices[0]);
                     res = {p.first, p.second};
                 } else {
                     ldpc::initial_random_seed = seed;
@@ -269,6 +321,10 @@ int main(int argc, char **argv) {
             for (const char *key : {"column_weights", "row_weights", "girth", "config_index", "matrix_index", "code_index"})
                 if (const jsonx::Value *v = code.find(key)) d.set(key, *v);
             d.set("simulation_logs", jsonx::Value::array({log}));
+            if (q_mod > 2) {                                                                                                 // :608-614
+                d.set("_q_mod", jsonx::Value::number((long long)q_mod));
+                d.set("coef", jsonx::Value::matrix(r, c, HC.v));
+            }
             d.set("time", jsonx::Value::number(std::round(secs * 1000.0) / 1000.0));
             results.items.push_back(std::move(d));
         }

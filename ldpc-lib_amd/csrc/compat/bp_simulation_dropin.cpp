@@ -37,7 +37,11 @@ std::pair<double, double> bp_simulation(int q_mod, matrix<int> const &code_gener
                                         int n_experiments, double snr, double reference_frame_error, int decoder_type,
                                         int modulation_type, int permutation_type, int permutation_block,
                                         int permutation_inter, int punctured_blocks, int show_process) {
-    (void)coef_matrix; (void)ncols2convert;  // q_mod > 2 only
+    if (q_mod > 2)   // upstream's q-ary harness on FHT_DEC: reads and rewrites coef_matrix (bp_simulation.cpp:384-389)
+        return ldpc::bp_simulation_gfq_t<matrix<int>, UpstreamRngEnv>(q_mod, code_generating_matrix, coef_matrix, ncols2convert, tailbite_length,
+                                                                      max_iterations, n_frame_errors, n_experiments, snr, reference_frame_error,
+                                                                      decoder_type, modulation_type, permutation_type, punctured_blocks,
+                                                                      show_process);
     return ldpc::bp_simulation_t<matrix<int>, UpstreamRngEnv>(q_mod, code_generating_matrix, tailbite_length, max_iterations,
                                                               n_frame_errors, n_experiments, snr, reference_frame_error,
                                                               decoder_type, modulation_type, permutation_type,

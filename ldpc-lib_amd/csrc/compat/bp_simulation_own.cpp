@@ -35,10 +35,14 @@ double next_random_gaussian() {  // :174-178: a fresh distribution per call (the
     return dist(random_generator());
 }
 
-std::pair<double, double> bp_simulation(int q_mod, Matrix const &H, Matrix &, int, int tailbite_length, int max_iterations,
+std::pair<double, double> bp_simulation(int q_mod, Matrix const &H, Matrix &coef_matrix, int ncols2convert, int tailbite_length, int max_iterations,
                                         int n_frame_errors, int n_experiments, double snr, double reference_frame_error,
                                         int decoder_type, int modulation_type, int permutation_type, int permutation_block,
                                         int permutation_inter, int punctured_blocks, int show_process) {
+    if (q_mod > 2)
+        return bp_simulation_gfq_t<Matrix, OwnRngEnv>(q_mod, H, coef_matrix, ncols2convert, tailbite_length, max_iterations, n_frame_errors, n_experiments,
+                                                      snr, reference_frame_error, decoder_type, modulation_type, permutation_type, punctured_blocks,
+                                                      show_process);
     return bp_simulation_t<Matrix, OwnRngEnv>(q_mod, H, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr,
                                               reference_frame_error, decoder_type, modulation_type, permutation_type,
                                               punctured_blocks, show_process, nullptr, 0, 4096, permutation_block, permutation_inter);

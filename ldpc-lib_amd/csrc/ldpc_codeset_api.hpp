@@ -661,23 +661,13 @@ extern "C" {
 int ldpc_hip_mt_set_state_codes(ldpc_hip_ctx *c, const uint32_t state[624], int pos) {
     if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_set_state_codes")) return rc;
     if (!state || pos < 0 || pos > 624) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_set_state_codes: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = mt_prepare(c)) return rc;
-    HIP_TRY(hipMemcpy(c->mt.d_state, state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyHostToDevice));
-    c->mt.pos = pos;
-    c->mt.set = true;
-    c->mt.frames_taken = 0;
-    return 0;
+    return mt_state_store(c, state, pos);
 }
 
 int ldpc_hip_mt_get_state_codes(ldpc_hip_ctx *c, uint32_t state[624], int *pos) {
     if (int rc = mt_codes_ctx(c, "ldpc_hip_mt_get_state_codes")) return rc;
     if (!state || !pos) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_get_state_codes: bad argument");
-    if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call ldpc_hip_mt_set_state first");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy(state, c->mt.d_state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToHost));
-    *pos = (int)c->mt.pos;
-    return 0;
+    return mt_state_load(c, "ldpc_hip_mt_set_state", state, pos);
 }
 
 int ldpc_hip_mt_advance_codes(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, long long frames) {

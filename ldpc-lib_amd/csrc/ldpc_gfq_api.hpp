@@ -31,6 +31,11 @@ struct ldpc_gfq_state {
     int32_t *w_ok = nullptr, *w_it = nullptr;
     unsigned long long *w_cnt = nullptr;
     long long w_frames = 0;
+    // exact replay (ldpc_gfq_exact_api.hpp)
+    int16_t *d_word = nullptr;    // [N] the word every frame carries (ldpc_hip_gfq_set_codeword); null = the all-zero word
+    double *x_noise = nullptr;    // [x_frames][N * q_bits] Gaussians of a piece
+    int32_t *x_info = nullptr;    // [x_frames] frame records of a piece
+    long long x_frames = 0;
 };
 
 void ldpc_gfq_release(ldpc_gfq_state *g) {
@@ -38,7 +43,7 @@ void ldpc_gfq_release(ldpc_gfq_state *g) {
     if (g->d_i32) (void)hipFree(g->d_i32);
     if (g->d_i16) (void)hipFree(g->d_i16);
     if (g->d_ws) (void)hipFree(g->d_ws);
-    void *chain[] = {g->d_enc, g->w_soft, g->w_msg, g->w_cw, g->w_qh, g->w_ok, g->w_it, g->w_cnt};
+    void *chain[] = {g->d_enc, g->w_soft, g->w_msg, g->w_cw, g->w_qh, g->w_ok, g->w_it, g->w_cnt, g->d_word, g->x_noise, g->x_info};
     for (void *p : chain)
         if (p) (void)hipFree(p);
     delete g;

@@ -19,6 +19,8 @@
 // Channel.  Lane = position i of a frame, so that for a fixed symbol s a wave stores 64 consecutive doubles of d_soft[b][s][:].
 // q <= 16 keeps the q likelihoods in VGPRs; beyond that the lane re-reads its own stores for the normalisation.  The values are
 // upstream's: lh accumulates from 0 in the order k = 0 .. q_bits - 1, no contraction, correctly rounded division, glibc's exp.
+// The transmitted word is per frame ([B][N]) or one [N] word for all frames (exact replay of upstream's harness, which encodes one
+// message before its frame loop); the count kernel takes it the same way.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,7 +197,8 @@ __global__ __launch_bounds__(256) void gfq_message_kernel(const MsgArgs a) {
 }
 
 struct QChanArgs {
-    const int16_t *codeword;   // [B][N] or null = the all-zero word
+    const int16_t *codeword;   // [B][N], or one [N] word for all frames (cw_stride = 0), or null = the all-zero word
+    long long cw_stride;       // symbols from one frame's word to the next: N or 0
     const int32_t *ok;         // [B] or null; a frame with ok = 0 goes out as the all-zero word (bp_simulation.cpp:552-556)
     const double *noise;       // [B][N * q_bits] or null = Philox
     double *soft;              // [B][q][N]
@@ -205,10 +208,42 @@ struct QChanArgs {
     uint64_t seed;
 };
 
+// The symbol probabilities of one position (bp_simulation.cpp:641, :644-676) from the q_bits Gaussians g[] of the position and the
+// symbol sym that was sent there: out[s * N], s = 0 .. q-1.  The one statement of this arithmetic: the single-code channel and the
+// channel of a code set with per-code words (ldpc_gfq_codeset.hpp) both call it.  q <= 16 keeps the q likelihoods in VGPRs; beyond that
+// the lane re-reads its own stores for the normalisation.
+template <int QB>
+__device__ __forceinline__ void gfq_symbol_probabilities(int sym, const double (&g)[QB], double sigma, double s2, double *out, int N) {
+    constexpr int qb = QB, q = 1 << QB, QREG = QB <= 4 ? q : 0;
+    double x[QB];
+#pragma unroll
+    for (int k = 0; k < qb; ++k) {
+        const double c = (double)((sym >> (qb - 1 - k)) & 1);   // word2bin: most significant bit first
+        x[k] = sigma * g[k] + 2.0 * c - 1.0;                   // :641
+    }
+    auto likelihood = [&](int s) -> double {
+        double lh = 0;
+#pragma unroll
+        for (int k = 0; k < qb; ++k) lh += ((s >> (qb - 1 - k)) & 1) ? x[k] : -x[k];   // V[k] * x[k], V = +-1 (:656-662)
+        return ldpc_spec::exp_glibc_wide(lh / s2, ldpc_spec::kExpTab);                // :664, :670
+    };
+    if constexpr (QREG != 0) {
+        double e[QREG ? QREG : 1], sum = 0.0;
+#pragma unroll
+        for (int s = 0; s < QREG; ++s) { e[s] = likelihood(s); sum += e[s]; }
+#pragma unroll
+        for (int s = 0; s < QREG; ++s) out[(size_t)s * N] = e[s] / sum;
+    } else {
+        double sum = 0.0;
+        for (int s = 0; s < q; ++s) { const double e = likelihood(s); out[(size_t)s * N] = e; sum += e; }
+        for (int s = 0; s < q; ++s) out[(size_t)s * N] /= sum;   // the lane's own stores
+    }
+}
+
 // One instance per q_bits, so that the bits of a symbol and (q <= 16) its likelihoods sit in VGPRs under static indices.
 template <int QB>
 __global__ __launch_bounds__(256) void gfq_channel_kernel(const QChanArgs a) {
-    constexpr int qb = QB, q = 1 << QB, QREG = QB <= 4 ? q : 0;
+    constexpr int qb = QB, q = 1 << QB;
     const int N = a.N;
     const long long total = a.B * (long long)N;
     const double s2 = a.sigma * a.sigma;
@@ -216,48 +251,29 @@ __global__ __launch_bounds__(256) void gfq_channel_kernel(const QChanArgs a) {
         const long long b = t / N;
         const int i = (int)(t - b * N);
         int sym = 0;
-        if (a.codeword && (!a.ok || a.ok[b])) sym = a.codeword[t];
-        double x[QB];
+        if (a.codeword && (!a.ok || a.ok[b])) sym = a.codeword[b * a.cw_stride + i];
+        double g[QB];
         uint32_t have = 0xffffffffu;
         double g0 = 0, g1 = 0;
 #pragma unroll
         for (int k = 0; k < qb; ++k) {
             const long long bit = (long long)i * qb + k;   // index of the bit within the frame
-            double g;
             if (a.noise) {
-                g = a.noise[b * ((long long)N * qb) + bit];
+                g[k] = a.noise[b * ((long long)N * qb) + bit];
             } else {
                 const uint32_t pair = (uint32_t)(bit >> 1);
                 if (pair != have) { ldpc::gauss_pair(a.seed, (uint64_t)(a.first_frame + b), pair, kTagNoise, g0, g1); have = pair; }
-                g = (bit & 1) ? g1 : g0;
+                g[k] = (bit & 1) ? g1 : g0;
             }
-            const double c = (double)((sym >> (qb - 1 - k)) & 1);   // word2bin: most significant bit first
-            x[k] = a.sigma * g + 2.0 * c - 1.0;                    // :641
         }
-        double *out = a.soft + (size_t)b * q * N + i;
-        auto likelihood = [&](int s) -> double {
-            double lh = 0;
-#pragma unroll
-            for (int k = 0; k < qb; ++k) lh += ((s >> (qb - 1 - k)) & 1) ? x[k] : -x[k];   // V[k] * x[k], V = +-1 (:656-662)
-            return ldpc_spec::exp_glibc_wide(lh / s2, ldpc_spec::kExpTab);                // :664, :670
-        };
-        if constexpr (QREG != 0) {
-            double e[QREG ? QREG : 1], sum = 0.0;
-#pragma unroll
-            for (int s = 0; s < QREG; ++s) { e[s] = likelihood(s); sum += e[s]; }
-#pragma unroll
-            for (int s = 0; s < QREG; ++s) out[(size_t)s * N] = e[s] / sum;
-        } else {
-            double sum = 0.0;
-            for (int s = 0; s < q; ++s) { const double e = likelihood(s); out[(size_t)s * N] = e; sum += e; }
-            for (int s = 0; s < q; ++s) out[(size_t)s * N] /= sum;   // the lane's own stores
-        }
+        gfq_symbol_probabilities<QB>(sym, g, a.sigma, s2, a.soft + (size_t)b * q * N + i, N);
     }
 }
 
 struct QCountArgs {
     const int16_t *qhard;      // [B][N]
-    const int16_t *codeword;   // [B][N] or null = zero
+    const int16_t *codeword;   // [B][N], or one [N] word for all frames (cw_stride = 0), or null = zero
+    long long cw_stride;       // symbols from one frame's word to the next: N or 0
     const int32_t *ok;         // [B] or null; ok = 0: the frame carried the all-zero word
     const int32_t *iters;      // [B]
     int32_t *frame_info;       // [B] or null
@@ -275,7 +291,7 @@ __global__ __launch_bounds__(256) void gfq_count_kernel(const QCountArgs a) {
         const bool sent = a.codeword && (!a.ok || a.ok[fr]);
         uint32_t all = 0, info = 0;
         for (int i = lane; i < a.N; i += 64) {
-            const int16_t want = sent ? a.codeword[fr * a.N + i] : (int16_t)0;
+            const int16_t want = sent ? a.codeword[fr * a.cw_stride + i] : (int16_t)0;
             if (a.qhard[fr * a.N + i] != want) {   // :748
                 all += 1;
                 if (i >= a.R) info += 1;           // :751

@@ -101,11 +101,12 @@ int gfq_grid(int num_cu, long long items, int per_block) {
 }
 int gfq_grid(const ldpc_gfq_state *g, long long items, int per_block) { return gfq_grid(g->num_cu, items, per_block); }
 
-// the channel of a code of length N over GF(2^q_bits); a code-set context (ldpc_gfq_codeset_api.hpp) launches it too
+// the channel of a code of length N over GF(2^q_bits); a code-set context (ldpc_gfq_codeset_api.hpp) launches it too.  one_word: d_codeword
+// is a single [N] word that every frame carries (the exact-replay entry points), not [B][N]
 int gfq_channel_launch(int num_cu, int N, int q_bits, const int16_t *d_codeword, const int32_t *d_ok, const double *d_noise, double sigma, uint64_t seed,
-                       long long first_frame, long long B, double *d_soft, hipStream_t stream) {
+                       long long first_frame, long long B, double *d_soft, hipStream_t stream, bool one_word = false) {
     ldpc_gfq::QChanArgs a{};
-    a.codeword = d_codeword; a.ok = d_ok; a.noise = d_noise; a.soft = d_soft;
+    a.codeword = d_codeword; a.cw_stride = one_word ? 0 : N; a.ok = d_ok; a.noise = d_noise; a.soft = d_soft;
     a.B = B; a.first_frame = first_frame; a.N = N; a.q_bits = q_bits; a.sigma = sigma; a.seed = seed;
     const dim3 grid((unsigned)gfq_grid(num_cu, B * (long long)N, 256)), block(256);
     switch (q_bits) {
@@ -123,14 +124,14 @@ int gfq_channel_launch(int num_cu, int N, int q_bits, const int16_t *d_codeword,
     return 0;
 }
 int gfq_channel_launch(ldpc_hip_ctx *c, const int16_t *d_codeword, const int32_t *d_ok, const double *d_noise, double sigma, uint64_t seed,
-                       long long first_frame, long long B, double *d_soft, hipStream_t stream) {
-    return gfq_channel_launch(c->gfq->num_cu, c->N, c->gfq->q_bits, d_codeword, d_ok, d_noise, sigma, seed, first_frame, B, d_soft, stream);
+                       long long first_frame, long long B, double *d_soft, hipStream_t stream, bool one_word = false) {
+    return gfq_channel_launch(c->gfq->num_cu, c->N, c->gfq->q_bits, d_codeword, d_ok, d_noise, sigma, seed, first_frame, B, d_soft, stream, one_word);
 }
 
 int gfq_count_launch(ldpc_hip_ctx *c, const int16_t *d_qhard, const int16_t *d_codeword, const int32_t *d_ok, const int32_t *d_iters, long long B,
-                     unsigned long long *d_counters, int32_t *d_frame_info, hipStream_t stream) {
+                     unsigned long long *d_counters, int32_t *d_frame_info, hipStream_t stream, bool one_word = false) {
     ldpc_gfq::QCountArgs a{};
-    a.qhard = d_qhard; a.codeword = d_codeword; a.ok = d_ok; a.iters = d_iters; a.frame_info = d_frame_info; a.counters = d_counters;
+    a.qhard = d_qhard; a.codeword = d_codeword; a.cw_stride = one_word ? 0 : c->N; a.ok = d_ok; a.iters = d_iters; a.frame_info = d_frame_info; a.counters = d_counters;
     a.B = B; a.N = c->N; a.R = c->R;
     hipLaunchKernelGGL(ldpc_gfq::gfq_count_kernel, dim3((unsigned)gfq_grid(c->gfq, B, 4)), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());

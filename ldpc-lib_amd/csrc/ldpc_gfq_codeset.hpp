@@ -22,6 +22,7 @@
 
 #include "ldpc_codeset.hpp"   // TabPtr
 #include "ldpc_gfq.hpp"
+#include "ldpc_gfq_chain.hpp" // gfq_symbol_probabilities
 
 namespace ldpc_gfq {
 
@@ -134,9 +135,46 @@ __global__ __launch_bounds__(256) void gfq_codes_kernel(const CodesArgs s) {
     }
 }
 
-// Symbol errors against the all-zero word per code: gfq_count_kernel's semantics with codeword = null (ldpc_gfq_chain.hpp;
-// bp_simulation.cpp:746-755, :805-810).  One wavefront per (slot, frame); a workgroup works on one slot only, so its totals go to
-// the row of the slot's code as one atomic per counter.
+// The channel of a set whose codes each carry a word of their own (exact replay of upstream's harness, which encodes a message per
+// candidate): the noise is the same for every code, the transmitted symbol is not, so the soft values are per code.  Work item
+// (frame, position) with lane = position as in gfq_channel_kernel, so that for a fixed symbol s a wave stores 64 consecutive doubles;
+// the q_bits Gaussians of the position are read once into registers, and for every slot of the launch the symbol of the slot's code goes
+// through gfq_symbol_probabilities, the arithmetic of the single-code channel.  The soft values of code c are written at
+// soft[c][f][q][N] -- by code, not by slot: that is where gfq_codes_kernel reads the per-code input of a launch over B frames.
+// A launch over the slots of a stop loop writes the regions of the codes still running and leaves the others as an earlier launch left
+// them (with another B: at other offsets, so they hold no frame's values); nothing reads them, the decode launch covers the same slots.
+struct CodesChanArgs {
+    const int16_t *words;          // [C][N]
+    const double *noise;           // [B][N * q_bits]
+    double *soft;                  // [C][B][q][N]
+    const int32_t *code_list;      // [n_slots] or null (slot s holds code s)
+    long long B;
+    int n_slots, N;
+    double sigma;
+};
+
+template <int QB>
+__global__ __launch_bounds__(256) void gfq_channel_codes_kernel(const CodesChanArgs a) {
+    constexpr int q = 1 << QB;
+    const int N = a.N;
+    const long long total = a.B * (long long)N;
+    const double s2 = a.sigma * a.sigma;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const long long b = t / N;
+        const int i = (int)(t - b * N);
+        double g[QB];
+#pragma unroll
+        for (int k = 0; k < QB; ++k) g[k] = a.noise[t * QB + k];   // bit i * q_bits + k of frame b
+        for (int sl = 0; sl < a.n_slots; ++sl) {
+            const int c = a.code_list ? ldpc::tab_ptr(a.code_list)[sl] : sl;
+            gfq_symbol_probabilities<QB>(a.words[(size_t)c * N + i], g, a.sigma, s2, a.soft + ((size_t)c * a.B + b) * q * N + i, N);
+        }
+    }
+}
+
+// Symbol errors per code against the code's word (words [C][N]) or, words = null, against the all-zero word: gfq_count_kernel's
+// semantics (ldpc_gfq_chain.hpp; bp_simulation.cpp:746-755, :805-810).  One wavefront per (slot, frame); a workgroup works on one slot
+// only, so its totals go to the row of the slot's code as one atomic per counter.
 struct CodesCountArgs {
     const int16_t *qhard;          // [n_active][B][N]
     const int32_t *iters;          // [n_active][B]
@@ -146,6 +184,7 @@ struct CodesCountArgs {
     long long B;
     int blocks_per_code;
     int N, R;
+    const int16_t *words;          // [C][N] the word code c sent, or null = the all-zero word
 };
 
 __global__ __launch_bounds__(256) void gfq_count_codes_kernel(const CodesCountArgs a) {
@@ -158,7 +197,8 @@ __global__ __launch_bounds__(256) void gfq_count_codes_kernel(const CodesCountAr
         const long long g = (long long)cs * a.B + fr;
         uint32_t all = 0, info = 0;
         for (int i = lane; i < a.N; i += 64) {
-            if (a.qhard[g * a.N + i] != 0) {   // :748
+            const int16_t want = a.words ? a.words[(size_t)c * a.N + i] : (int16_t)0;
+            if (a.qhard[g * a.N + i] != want) {   // :748
                 all += 1;
                 if (i >= a.R) info += 1;       // :751
             }

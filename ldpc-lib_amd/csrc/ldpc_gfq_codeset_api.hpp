@@ -11,13 +11,17 @@ struct ldpc_codeset_gfq_state : codeset_common {
     int16_t *d_i16 = nullptr;          // mul | div, q - 1 rows each
     char *d_ws = nullptr;              // message state, one slot per workgroup
     int ws_slots = 0;
-    double *w_soft = nullptr;          // [w_frames][q][N], shared by the codes
+    double *w_soft = nullptr;          // [w_frames][q][N], shared by the codes; [C][w_frames][q][N] while the codes carry words
     int16_t *w_qh = nullptr;           // [C][w_frames][N]
+    // exact replay (ldpc_hip_*_codes_gfq with mt_ / noise_host in the name)
+    int16_t *d_words = nullptr;        // [C][N] the word each code sends (ldpc_hip_codes_gfq_set_codewords); null = all-zero, shared soft values
+    double *x_noise = nullptr;         // [x_frames][N * q_bits] Gaussians of a piece
+    long long x_frames = 0;
 };
 
 void ldpc_codeset_gfq_release(ldpc_codeset_gfq_state *s) {
     if (!s) return;
-    void *dev[] = {s->d_i16, s->d_ws, s->w_soft, s->w_qh};
+    void *dev[] = {s->d_i16, s->d_ws, s->w_soft, s->w_qh, s->d_words, s->x_noise};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     codeset_common_release(*s);
@@ -101,26 +105,32 @@ int codeset_gfq_decode_launch(ldpc_hip_ctx *c, const double *d_soft, int shared_
 }
 
 int codeset_gfq_count_launch(const ldpc_hip_ctx *c, const int16_t *d_qhard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
-                             unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0) {
+                             unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0,
+                             const int16_t *d_words = nullptr) {
     const int C = code_list ? n_slots : c->codes_gfq->C;
     const int bpc = codeset_count_blocks(B, C);
-    ldpc_gfq::CodesCountArgs a{d_qhard, d_iters, d_frame_info, d_counters, code_list, B, bpc, c->N, c->R};
+    ldpc_gfq::CodesCountArgs a{d_qhard, d_iters, d_frame_info, d_counters, code_list, B, bpc, c->N, c->R, d_words};
     hipLaunchKernelGGL(ldpc_gfq::gfq_count_codes_kernel, dim3((unsigned)((long long)bpc * C)), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Frames per piece of the simulate entry points: the shared [piece][q][N] input and the [C][piece] outputs within 1 GiB together, at
-// most 65536, LDPC_HIP_GFQ_PIECE=n caps it (as in ldpc_hip_simulate_gfq).
+// Frames per piece of the simulate entry points: the [piece][q][N] input -- one copy shared by the codes, or C copies while the codes
+// carry words of their own (C * q * N * 8 bytes per frame) -- and the [C][piece] outputs within 1 GiB together, at most 65536,
+// LDPC_HIP_GFQ_PIECE=n caps it (as in ldpc_hip_simulate_gfq).
 long long codeset_gfq_piece(const ldpc_hip_ctx *c, long long B) {
     const ldpc_codeset_gfq_state *g = c->codes_gfq;
-    const size_t per_frame = sizeof(double) * (size_t)g->q * c->N + (size_t)g->C * (sizeof(int16_t) * (size_t)c->N + 2 * sizeof(int32_t));
+    const size_t copies = g->d_words ? (size_t)g->C : 1;
+    const size_t per_frame = copies * sizeof(double) * (size_t)g->q * c->N + (size_t)g->C * (sizeof(int16_t) * (size_t)c->N + 2 * sizeof(int32_t));
     return codeset_piece(per_frame, "LDPC_HIP_GFQ_PIECE", B);
 }
 
+// ldpc_hip_codes_gfq_set_codewords drops the workspace when the set changes between shared and per-code soft values, so w_frames
+// always speaks of buffers of the current kind
 int codeset_gfq_reserve(ldpc_hip_ctx *c, long long piece) {
     ldpc_codeset_gfq_state *g = c->codes_gfq;
-    return codeset_reserve(*g, piece, (void **)&g->w_soft, sizeof(double) * (size_t)g->q * c->N, (void **)&g->w_qh, sizeof(int16_t) * (size_t)c->N);
+    const size_t copies = g->d_words ? (size_t)g->C : 1;
+    return codeset_reserve(*g, piece, (void **)&g->w_soft, copies * sizeof(double) * (size_t)g->q * c->N, (void **)&g->w_qh, sizeof(int16_t) * (size_t)c->N);
 }
 
 // channel (the all-zero word, Philox stream tag 3) -> set decode on the shared soft values -> set count, for frames
@@ -227,6 +237,189 @@ int ldpc_hip_simulate_codes_gfq_stop(ldpc_hip_ctx *c, double snr_db, int maxiter
                              [&](long long first, long long nb, const int32_t *list, int n_active) -> int {
                                  return codeset_gfq_piece_launch(c, sigma, maxiter, seed, first_frame + first, nb, true, list, n_active);
                              });
+}
+
+}  // extern "C"
+
+// ---- exact replay on a GF(q) code set: what a search that calls reset_random() and bp_simulation(q_mod, HM, HC, ...) per candidate
+// computes (search_ggp/scenario_based_code_generation.cpp:754, :852, :883).  The generator of ldpc_mt_api.hpp in sample mode draws the
+// [piece][N * q_bits] Gaussians of upstream's stream once; without words the all-zero word's soft values are shared by the codes, with
+// words (upstream encodes a message per candidate) gfq_channel_codes_kernel forms them per code.
+namespace {
+
+int gfq_exact_codes_workspace(ldpc_hip_ctx *c, long long piece) {
+    ldpc_codeset_gfq_state *g = c->codes_gfq;
+    if (int rc = codeset_gfq_reserve(c, piece)) return rc;
+    if (piece <= g->x_frames) return 0;
+    if (g->x_noise) (void)hipFree(g->x_noise);
+    g->x_noise = nullptr; g->x_frames = 0;
+    HIP_TRY(hipMalloc(&g->x_noise, sizeof(double) * (size_t)c->N * g->q_bits * (size_t)piece));
+    g->x_frames = piece;
+    return 0;
+}
+
+// x_noise [nb][N * q_bits] -> channel -> set decode -> set count, for the n_active codes of `list` (null: all)
+int gfq_exact_codes_piece_launch(ldpc_hip_ctx *c, double sigma, int maxiter, long long nb, bool want_info, const int32_t *list, int n_active) {
+    ldpc_codeset_gfq_state *g = c->codes_gfq;
+    if (!g->d_words) {
+        if (int rc = gfq_channel_launch(g->num_cu, c->N, g->q_bits, nullptr, nullptr, g->x_noise, sigma, 0, 0, nb, g->w_soft, nullptr)) return rc;
+    } else {
+        ldpc_gfq::CodesChanArgs a{g->d_words, g->x_noise, g->w_soft, list, nb, list ? n_active : g->C, c->N, sigma};
+        const dim3 grid((unsigned)gfq_grid(g->num_cu, nb * (long long)c->N, 256)), block(256);
+        switch (g->q_bits) {
+        case 2: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<2>, grid, block, 0, nullptr, a); break;
+        case 3: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<3>, grid, block, 0, nullptr, a); break;
+        case 4: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<4>, grid, block, 0, nullptr, a); break;
+        case 5: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<5>, grid, block, 0, nullptr, a); break;
+        case 6: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<6>, grid, block, 0, nullptr, a); break;
+        case 7: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<7>, grid, block, 0, nullptr, a); break;
+        case 8: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<8>, grid, block, 0, nullptr, a); break;
+        case 9: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<9>, grid, block, 0, nullptr, a); break;
+        default: hipLaunchKernelGGL(ldpc_gfq::gfq_channel_codes_kernel<10>, grid, block, 0, nullptr, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = codeset_gfq_decode_launch(c, g->w_soft, g->d_words ? 0 : 1, nb, maxiter, g->w_qh, g->w_iters, nullptr, nullptr, list, n_active)) return rc;
+    return codeset_gfq_count_launch(c, g->w_qh, g->w_iters, nb, want_info ? g->w_info : nullptr, g->w_cnt, nullptr, list, n_active, g->d_words);
+}
+
+int gfq_exact_codes_draw(ldpc_hip_ctx *c, long long nb) {
+    if (int rc = mt_samples(c, nb * (long long)c->N * c->codes_gfq->q_bits, c->codes_gfq->x_noise, nullptr)) return rc;
+    c->mt.frames_taken += nb;
+    return 0;
+}
+
+// what the entry points that draw refuse before anything is drawn or reserved
+int gfq_exact_codes_check(ldpc_hip_ctx *c, const char *who, double snr_db, int punctured_blocks, int maxiter, double *sigma) {
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "%s: maxiter must be >= 1 (got %d)", who, maxiter);
+    if (int rc = gfq_exact_sigma(c, who, snr_db, punctured_blocks, sigma)) return rc;
+    if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call ldpc_hip_mt_set_state_codes_gfq first");
+    const long long per_frame = (long long)c->N * c->codes_gfq->q_bits;
+    if ((unsigned long long)per_frame > ldpc_mt::kRoundItems)
+        return fail(LDPC_HIP_EUNSUPPORTED, "%s: a frame of %lld samples is beyond one generation round", who, per_frame);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_hip_codes_gfq_set_codewords(ldpc_hip_ctx *c, const int16_t *words) {
+    if (int rc = codeset_gfq_ctx(c, "ldpc_hip_codes_gfq_set_codewords")) return rc;
+    ldpc_codeset_gfq_state *g = c->codes_gfq;
+    const size_t n = (size_t)g->C * c->N;
+    if (words)
+        for (size_t i = 0; i < n; ++i)
+            if (words[i] < 0 || words[i] >= g->q)
+                return fail(LDPC_HIP_EINVAL, "ldpc_hip_codes_gfq_set_codewords: symbol %d at position %zu of code %zu is not an element of GF(%d)", words[i],
+                            i % (size_t)c->N, i / (size_t)c->N, g->q);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((words != nullptr) != (g->d_words != nullptr)) {   // shared <-> per-code soft values: the workspace is sized for one kind
+        void *old[] = {g->w_soft, g->w_qh, g->w_iters, g->w_info};
+        for (void *p : old)
+            if (p) (void)hipFree(p);
+        g->w_soft = nullptr; g->w_qh = nullptr; g->w_iters = nullptr; g->w_info = nullptr; g->w_frames = 0;
+    }
+    if (!words) {
+        if (g->d_words) (void)hipFree(g->d_words);
+        g->d_words = nullptr;
+        return 0;
+    }
+    if (!g->d_words) HIP_TRY(hipMalloc(&g->d_words, sizeof(int16_t) * n));
+    HIP_TRY(hipMemcpy(g->d_words, words, sizeof(int16_t) * n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int ldpc_hip_mt_set_state_codes_gfq(ldpc_hip_ctx *c, const uint32_t state[624], int pos) {
+    if (int rc = codeset_gfq_ctx(c, "ldpc_hip_mt_set_state_codes_gfq")) return rc;
+    if (!state || pos < 0 || pos > 624) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_set_state_codes_gfq: bad argument");
+    return mt_state_store(c, state, pos);
+}
+
+int ldpc_hip_mt_get_state_codes_gfq(ldpc_hip_ctx *c, uint32_t state[624], int *pos) {
+    if (int rc = codeset_gfq_ctx(c, "ldpc_hip_mt_get_state_codes_gfq")) return rc;
+    if (!state || !pos) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_get_state_codes_gfq: bad argument");
+    return mt_state_load(c, "ldpc_hip_mt_set_state_codes_gfq", state, pos);
+}
+
+int ldpc_hip_mt_advance_codes_gfq(ldpc_hip_ctx *c, long long frames) {
+    if (int rc = codeset_gfq_ctx(c, "ldpc_hip_mt_advance_codes_gfq")) return rc;
+    if (frames < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_advance_codes_gfq: bad argument");
+    return mt_drop_frames(c, "ldpc_hip_mt_set_state_codes_gfq", frames, (long long)c->N * c->codes_gfq->q_bits);
+}
+
+int ldpc_hip_mt_simulate_codes_gfq(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, long long B, unsigned long long *counters,
+                                   int32_t *frame_info, int32_t *iters) {
+    const char *who = "ldpc_hip_mt_simulate_codes_gfq";
+    if (int rc = codeset_gfq_ctx(c, who)) return rc;
+    if (!counters || B < 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
+    double sigma = 0;
+    if (int rc = gfq_exact_codes_check(c, who, snr_db, punctured_blocks, maxiter, &sigma)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    ldpc_codeset_gfq_state *g = c->codes_gfq;
+    const long long piece = codeset_gfq_piece(c, B);
+    if (int rc = gfq_exact_codes_workspace(c, piece)) return rc;
+    const size_t C = (size_t)g->C;
+    return codeset_simulate_loop(*g, piece, B, counters, frame_info, [&](long long first, long long nb) -> int {
+        if (int rc = gfq_exact_codes_draw(c, nb)) return rc;
+        if (int rc = gfq_exact_codes_piece_launch(c, sigma, maxiter, nb, frame_info != nullptr, nullptr, 0)) return rc;
+        if (iters)   // [C][nb] on the device -> columns [first, first + nb) of the caller's [C][B]
+            HIP_TRY(hipMemcpy2D(iters + first, sizeof(int32_t) * (size_t)B, g->w_iters, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int ldpc_hip_frames_codes_gfq_noise_host(ldpc_hip_ctx *c, const double *noise, double snr_db, int punctured_blocks, int maxiter, long long B,
+                                         unsigned long long *counters, int32_t *frame_info, int32_t *iters) {
+    const char *who = "ldpc_hip_frames_codes_gfq_noise_host";
+    if (int rc = codeset_gfq_ctx(c, who)) return rc;
+    if (!counters || B < 0 || (B > 0 && !noise)) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
+    if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "%s: maxiter must be >= 1 (got %d)", who, maxiter);
+    double sigma = 0;
+    if (int rc = gfq_exact_sigma(c, who, snr_db, punctured_blocks, &sigma)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    ldpc_codeset_gfq_state *g = c->codes_gfq;
+    const long long piece = codeset_gfq_piece(c, B);
+    if (int rc = gfq_exact_codes_workspace(c, piece)) return rc;
+    const size_t C = (size_t)g->C, per_frame = (size_t)c->N * g->q_bits;
+    return codeset_simulate_loop(*g, piece, B, counters, frame_info, [&](long long first, long long nb) -> int {
+        HIP_TRY(hipMemcpy(g->x_noise, noise + per_frame * (size_t)first, sizeof(double) * per_frame * (size_t)nb, hipMemcpyHostToDevice));
+        if (int rc = gfq_exact_codes_piece_launch(c, sigma, maxiter, nb, frame_info != nullptr, nullptr, 0)) return rc;
+        if (iters)
+            HIP_TRY(hipMemcpy2D(iters + first, sizeof(int32_t) * (size_t)B, g->w_iters, sizeof(int32_t) * (size_t)nb, sizeof(int32_t) * (size_t)nb, C,
+                                hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int ldpc_hip_mt_simulate_codes_gfq_stop(ldpc_hip_ctx *c, double snr_db, int punctured_blocks, int maxiter, int n_frame_errors, long long n_experiments,
+                                        double reference_frame_error, long long first_batch, long long max_batch, unsigned long long *state) {
+    using namespace ldpc_mt;
+    const char *who = "ldpc_hip_mt_simulate_codes_gfq_stop";
+    if (int rc = codeset_gfq_ctx(c, who)) return rc;
+    if (int rc = codeset_stop_args(who, state, 0, first_batch, max_batch, maxiter)) return rc;
+    double sigma = 0;
+    if (int rc = gfq_exact_codes_check(c, who, snr_db, punctured_blocks, maxiter, &sigma)) return rc;
+    std::memset(state, 0, sizeof(unsigned long long) * 6 * (size_t)c->codes_gfq->C);
+    if (n_frame_errors <= 0 || n_experiments < 0) return 0;   // :591 fails before the first frame
+    HIP_TRY(hipSetDevice(c->device));
+    const long long piece = codeset_gfq_piece(c, max_batch < n_experiments + 1 ? max_batch : n_experiments + 1);
+    if (int rc = gfq_exact_codes_workspace(c, piece)) return rc;
+    // the codes stop at different frames: the generator goes back to where it was, ldpc_hip_mt_advance_codes_gfq takes it to one code's end
+    DeviceState &m = c->mt;
+    std::vector<uint32_t> entry(MTN);
+    const long long entry_pos = m.pos, entry_frames = m.frames_taken;
+    HIP_TRY(hipMemcpy(entry.data(), m.d_state, sizeof(uint32_t) * MTN, hipMemcpyDeviceToHost));
+    const int rc = codeset_stop_loop(*c->codes_gfq, piece, n_frame_errors, n_experiments, reference_frame_error, first_batch, max_batch, state,
+                                     [&](long long, long long nb, const int32_t *list, int n_active) -> int {   // pieces come in frame order
+                                         if (int r = gfq_exact_codes_draw(c, nb)) return r;
+                                         return gfq_exact_codes_piece_launch(c, sigma, maxiter, nb, true, list, n_active);
+                                     }, true);
+    if (hipMemcpy(m.d_state, entry.data(), sizeof(uint32_t) * MTN, hipMemcpyHostToDevice) != hipSuccess && rc == 0)
+        return fail(LDPC_HIP_EHIP, "%s: the generator's state could not be put back", who);
+    m.pos = entry_pos; m.frames_taken = entry_frames;
+    return rc;
 }
 
 }  // extern "C"

@@ -219,6 +219,50 @@ int mt_round(ldpc_hip_ctx *c, unsigned long long need, ldpc_mt::PolarArgs proto,
     return 0;
 }
 
+// the next `count` samples of the context's generator -> d_out (null: drawn and dropped); the device is set and the generator has a state
+int mt_samples(ldpc_hip_ctx *c, long long count, double *d_out, hipStream_t st) {
+    long long done = 0;
+    int stalled = 0;
+    while (done < count) {
+        const unsigned long long want = (unsigned long long)(count - done) < ldpc_mt::kRoundItems ? (unsigned long long)(count - done) : ldpc_mt::kRoundItems;
+        ldpc_mt::PolarArgs a{};
+        a.out = d_out ? d_out + done : nullptr;
+        unsigned long long emitted = 0;
+        if (int rc = mt_round(c, want, a, &emitted, st)) return rc;
+        done += (long long)emitted;
+        stalled = emitted == 0 ? stalled + 1 : 0;
+        if (stalled >= 2) return fail(LDPC_HIP_EHIP, "the exact-replay generator made no progress");
+    }
+    return 0;
+}
+
+// What the set_state / get_state / advance entry points of every kind of context do once the caller has checked the kind of context
+// and the arguments: the generator's 624 words and position in and out, and `frames` frames of per_frame samples drawn and dropped.
+// setter: the entry point a caller without a state is sent to.
+int mt_state_store(ldpc_hip_ctx *c, const uint32_t *state, int pos) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = mt_prepare(c)) return rc;
+    HIP_TRY(hipMemcpy(c->mt.d_state, state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyHostToDevice));
+    c->mt.pos = pos;
+    c->mt.set = true;
+    c->mt.frames_taken = 0;
+    return 0;
+}
+int mt_state_load(ldpc_hip_ctx *c, const char *setter, uint32_t *state, int *pos) {
+    if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call %s first", setter);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(state, c->mt.d_state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToHost));
+    *pos = (int)c->mt.pos;
+    return 0;
+}
+int mt_drop_frames(ldpc_hip_ctx *c, const char *setter, long long frames, long long per_frame) {
+    if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call %s first", setter);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = mt_samples(c, frames * per_frame, nullptr, nullptr)) return rc;
+    c->mt.frames_taken += frames;
+    return 0;
+}
+
 // what the emit pass needs to turn samples into decoder inputs of this context's chain (bp_simulation.cpp:603/610, :684, :697-710)
 int mt_frame_proto(ldpc_hip_ctx *c, double snr_db, int modulation_type, int punctured_blocks, ldpc_mt::PolarArgs &a) {
     using namespace ldpc_mt;
@@ -328,21 +372,14 @@ int ldpc_hip_mt_jump_host(const uint32_t state_in[624], int log2_words, uint32_t
 int ldpc_hip_mt_set_state(ldpc_hip_ctx *c, const uint32_t state[624], int pos) {
     if (!c || !state || pos < 0 || pos > 624) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_set_state: bad argument");
     if (int rc = set_device(c)) return rc;
-    if (int rc = mt_prepare(c)) return rc;
-    HIP_TRY(hipMemcpy(c->mt.d_state, state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyHostToDevice));
-    c->mt.pos = pos;
-    c->mt.set = true;
-    c->mt.frames_taken = 0;
-    return 0;
+    return mt_state_store(c, state, pos);
 }
 
 int ldpc_hip_mt_get_state(ldpc_hip_ctx *c, uint32_t state[624], int *pos) {
     if (!c || !state || !pos) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_get_state: bad argument");
     if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call ldpc_hip_mt_set_state first");
     if (int rc = set_device(c)) return rc;
-    HIP_TRY(hipMemcpy(state, c->mt.d_state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToHost));
-    *pos = c->mt.pos;
-    return 0;
+    return mt_state_load(c, "ldpc_hip_mt_set_state", state, pos);
 }
 
 int ldpc_hip_mt_set_frame_index(ldpc_hip_ctx *c, long long frames_taken) {
@@ -357,20 +394,7 @@ int ldpc_hip_mt_normal_dev(ldpc_hip_ctx *c, long long count, double *d_out, void
     if (!c || count < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_mt_normal_dev: bad argument");
     if (!c->mt.set) return fail(LDPC_HIP_EINVAL, "the generator has no state: call ldpc_hip_mt_set_state first");
     if (int rc = set_device(c)) return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    long long done = 0;
-    int stalled = 0;
-    while (done < count) {
-        const unsigned long long want = (unsigned long long)(count - done) < ldpc_mt::kRoundItems ? (unsigned long long)(count - done) : ldpc_mt::kRoundItems;
-        ldpc_mt::PolarArgs a{};
-        a.out = d_out ? d_out + done : nullptr;
-        unsigned long long emitted = 0;
-        if (int rc = mt_round(c, want, a, &emitted, st)) return rc;
-        done += (long long)emitted;
-        stalled = emitted == 0 ? stalled + 1 : 0;
-        if (stalled >= 2) return fail(LDPC_HIP_EHIP, "the exact-replay generator made no progress");
-    }
-    return 0;
+    return mt_samples(c, count, d_out, (hipStream_t)stream_);
 }
 
 int ldpc_hip_mt_normal_host(ldpc_hip_ctx *c, long long count, double *out) {
