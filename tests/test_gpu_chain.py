@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+from frontend_twin import chain_twin_of_mode as _chain_twin
 from ldpc_testlib import (GOLDEN_DIR, LMS_DEC, MS_DEC, SP_DEC, Oracle, _as_double_p, load_base_matrix, oracle_lib, pack_bits,
                           philox_gauss_pairs, relift, unpack_bits)
 
@@ -52,46 +53,6 @@ def test_mapper_equals_the_compiled_reference(L, torch):
         b = np.ascontiguousarray(g[f"q{Q}_bits"])
         oracle_lib().orc_qam_modulate(Q, _as_double_p(b), len(b), _as_double_p(want))
         assert np.array_equal(want, g[f"q{Q}_sym"])
-
-
-def _chain_twin(H, M, cws, first, B, seed, snr, mod, punct, perm, punct_val):
-    """CPU twin of ldpc_hip_channel_llr_dev: bp_simulation.cpp:566-577,596-710 with the device's Philox noise."""
-    from ldpc_lib_amd.binding import build_interleaver
-    rh, nh = H.shape
-    N = nh * M
-    rate = (nh - rh) / (nh - punct)
-    halfmlog = 1 if mod <= 1 else mod
-    m = 2 if mod <= 1 else 2 * mod
-    if perm is not None:
-        direct, inverse = build_interleaver(H, M, perm[0], halfmlog, perm[1], perm[2])
-    else:
-        direct = inverse = np.arange(N)
-    units = (N + m - 1) // m
-    out = np.zeros((B, N))
-    Q = 1 << (2 * mod) if mod >= 1 else 1
-    if mod == 0:
-        sigma = np.sqrt(10.0 ** (-snr / 10.0) / 2 / rate)
-    else:
-        sigma = np.sqrt(10.0 ** (-snr / 10.0) / (2 * rate * halfmlog * 2) * (2.0 * (Q - 1.0) / 3.0))
-    g = philox_gauss_pairs(seed, first + np.arange(B), units, tag=0 if mod <= 1 else 1)
-    for b in range(B):
-        cw = cws[(first + b) % len(cws)] if cws is not None else np.zeros(N, dtype=np.uint8)
-        tx = np.zeros(units * m)
-        tx[:N] = cw[direct]                                            # Permutation(.., 0, ..) :570, zero padding :575
-        if mod <= 1:
-            buf = -2.0 * (sigma * g[b, :N] + 2.0 * tx[:N] - 1.0) / (sigma * sigma)
-        else:
-            x = np.zeros(2 * units)
-            oracle_lib().orc_qam_modulate(Q, _as_double_p(np.ascontiguousarray(tx)), len(tx), _as_double_p(x))
-            x = np.ascontiguousarray(x + sigma * g[b])
-            dem = np.zeros(units * m)
-            oracle_lib().orc_qam_demodulate(Q, 26.0, float(sigma), _as_double_p(x), units, _as_double_p(dem), 0)
-            buf = -dem[:N]
-        y = buf[inverse]                                               # :684
-        if punct:
-            y[N - M * punct:] = punct_val                              # :697-710
-        out[b] = y
-    return out
 
 
 @pytest.mark.parametrize("mod,snr,punct,perm", [
