@@ -768,6 +768,28 @@ int ldpc_hip_mt_simulate_codes_gfq_stop(ldpc_hip_ctx *ctx, double snr_db, int pu
 int ldpc_hip_frames_codes_gfq_noise_host(ldpc_hip_ctx *ctx, const double *noise, double snr_db, int punctured_blocks, int maxiter,
                                          long long B, unsigned long long *counters, int32_t *frame_info, int32_t *iters);
 
+/* ---- Girth spectrum and ACE trace: upstream's trace_bound_pol_mon_pm (trace_pm.cpp:58-299, NATURAL_POLYNOM), the filter of its
+ * searches (search_ggp/scenario_based_code_generation.cpp:527-570) and the source of girth_ / girth_ACE / girth_spectrum in its
+ * result records (main_simulation.cpp:496, :600-603), for a set of candidate codes in one call (csrc/ldpc_girth.hpp).
+ * LDPC_HIP_EINVAL, found before any device call: C < 1, gmax outside 4 .. 20 (GMAX), gtarget < 1, nh > 1000 (upstream's cw[1000]),
+ * a shift outside [-1, M), M, rh or nh < 1, a NULL output.  LDPC_HIP_EUNSUPPORTED: a code whose workspace -- 12 * E^2 * M bytes for
+ * the largest edge count E of the set -- exceeds 4 GiB (the message holds the byte count), rh > 3276.
+ * Arithmetic is 32-bit as upstream's; where upstream's behaviour is undefined (a sum beyond 2^31 - 1) the sums here wrap and bit 1 of
+ * the code's status is set.  Results are upstream's bit for bit on every code without that bit. */
+/* trace_bound_pol_mon_pm for C codes of one shape.  hd HOST [C][rh][nh], shifts in [-1, M); min_ace / max_spec HOST [gmax] or NULL
+ * (upstream's minSA / maxS).  Out, HOST: S [C][gmax], SA [C][gmax], status [C]: bit 0 = upstream's return value, bit 1 = a 32-bit
+ * sum overflowed.  Synchronous.  No context needed.  The codes may differ in their masks.  A set whose workspace exceeds 1 GiB is
+ * worked off in pieces (LDPC_HIP_GIRTH_PIECE=n: n codes per piece, read per call); the result does not depend on the pieces, and the
+ * number of launches and synchronisations per piece does not depend on the number of codes. */
+int ldpc_hip_girth_codes(int rh, int nh, int M, const int16_t *hd, int C, int gmax, int gtarget, const int32_t *min_ace,
+                         const int32_t *max_spec, int device, int32_t *S, int32_t *SA, int32_t *status);
+/* HOST only, no GPU: the sparse graph the kernel walks -- E and, per edge J, its predecessors (j, a, as) in ascending j.  Edges are
+ * the non-empty circulants, column by column with the rows ascending; pred_begin [E + 1] (may be NULL), pred [3 * n] (NULL to size:
+ * then only *E and *n are written). */
+int ldpc_hip_girth_graph_host(int rh, int nh, int M, const int16_t *hd, int *E, int32_t *pred_begin, int32_t *pred, long long *n);
+/* HOST only: main_simulation.cpp:177-201 on one code's S / SA: girth (21 = none found), ACE[4], spectrum[4]. */
+int ldpc_hip_trace_matrix_host(const int32_t *S, const int32_t *SA, int gmax, int *girth, int32_t ACE[4], int32_t spectrum[4]);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

@@ -220,6 +220,9 @@ def load_library():
     lib.ldpc_hip_mt_simulate_codes_gfq.argtypes = [vp, f64, i32, i32, i64, vp, vp, vp]
     lib.ldpc_hip_mt_simulate_codes_gfq_stop.argtypes = [vp, f64, i32, i32, i32, i64, f64, i64, i64, vp]
     lib.ldpc_hip_frames_codes_gfq_noise_host.argtypes = [vp, vp, f64, i32, i32, i64, vp, vp, vp]
+    lib.ldpc_hip_girth_codes.argtypes = [i32, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    lib.ldpc_hip_girth_graph_host.argtypes = [i32, i32, i32, vp, C.POINTER(i32), vp, vp, C.POINTER(i64)]
+    lib.ldpc_hip_trace_matrix_host.argtypes = [vp, vp, i32, C.POINTER(i32), vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
     _lib = lib
@@ -1251,6 +1254,56 @@ def mt_jump_host(state, log2_words):
     out = np.empty(624, dtype=np.uint32)
     _check(lib, lib.ldpc_hip_mt_jump_host(st.ctypes.data, int(log2_words), out.ctypes.data), "ldpc_hip_mt_jump_host")
     return out
+
+
+def girth_codes(hd, M, gmax=20, gtarget=4, min_ace=None, max_spec=None, device=0):
+    """Upstream's trace_bound_pol_mon_pm on a set of codes [C, rh, nh] (or one code [rh, nh]) in one call (ldpc_hip_girth_codes):
+    (S int32 [C, gmax], SA int32 [C, gmax], status int32 [C]; bit 0 = upstream's return value, bit 1 = a 32-bit sum overflowed).
+    min_ace / max_spec: upstream's minSA / maxS, [gmax] each, or None."""
+    lib = load_library()
+    codes = _code_stack(hd)
+    Cn, rh, nh = codes.shape
+    gmax = int(gmax)
+    rows = max(gmax, 0)
+    bounds = [None if b is None else np.ascontiguousarray(b, dtype=np.int32) for b in (min_ace, max_spec)]
+    for b in bounds:
+        assert b is None or b.shape == (gmax,), "min_ace / max_spec: [gmax]"
+    S = np.zeros((Cn, rows), dtype=np.int32)
+    SA = np.zeros((Cn, rows), dtype=np.int32)
+    status = np.zeros(Cn, dtype=np.int32)
+    rc = lib.ldpc_hip_girth_codes(rh, nh, int(M), codes.ctypes.data, Cn, gmax, int(gtarget), *(None if b is None else b.ctypes.data for b in bounds),
+                                  int(device), S.ctypes.data, SA.ctypes.data, status.ctypes.data)
+    _check(lib, rc, "ldpc_hip_girth_codes")
+    return S, SA, status
+
+
+def girth_graph(hd, M):
+    """The graph the girth kernels walk, built on the host (no GPU): (E, pred_begin int32 [E + 1], pred int32 [n, 3]) -- the
+    predecessors (j, a, as) of edge J are pred[pred_begin[J]:pred_begin[J + 1]], j ascending."""
+    lib = load_library()
+    H = np.ascontiguousarray(hd, dtype=np.int16)
+    rh, nh = H.shape
+    E, n = C.c_int(), C.c_longlong()
+    _check(lib, lib.ldpc_hip_girth_graph_host(rh, nh, int(M), H.ctypes.data, C.byref(E), None, None, C.byref(n)), "ldpc_hip_girth_graph_host")
+    begin = np.empty(E.value + 1, dtype=np.int32)
+    pred = np.empty((n.value, 3), dtype=np.int32)
+    _check(lib, lib.ldpc_hip_girth_graph_host(rh, nh, int(M), H.ctypes.data, C.byref(E), begin.ctypes.data, pred.ctypes.data, C.byref(n)),
+           "ldpc_hip_girth_graph_host")
+    return E.value, begin, pred
+
+
+def trace_matrix(S, SA):
+    """main_simulation.cpp:177-201 on one code's S / SA (host, no GPU): (girth -- 21 when no cycle was found --, ACE [4], spectrum [4])."""
+    lib = load_library()
+    S = np.ascontiguousarray(S, dtype=np.int32)
+    SA = np.ascontiguousarray(SA, dtype=np.int32)
+    assert S.ndim == 1 and S.shape == SA.shape, "S, SA: [gmax] of one code"
+    girth = C.c_int()
+    ace = np.zeros(4, dtype=np.int32)
+    spec = np.zeros(4, dtype=np.int32)
+    _check(lib, lib.ldpc_hip_trace_matrix_host(S.ctypes.data, SA.ctypes.data, S.size, C.byref(girth), ace.ctypes.data, spec.ctypes.data),
+           "ldpc_hip_trace_matrix_host")
+    return girth.value, ace.tolist(), spec.tolist()
 
 
 def qam_modulate(bits, Q, device=0, stream=None):

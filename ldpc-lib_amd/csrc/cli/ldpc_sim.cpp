@@ -6,8 +6,8 @@
 // What it keeps from upstream: the scenario fields (:260-283), the per-code fields (:343-364), the reduction of the shifts
 // modulo the lifting with the special last parity column (:400-414), one generator reset per (code, SNR) so that all codes
 // see the same noise (:483), the call into bp_simulation with reference_frame_error = error_minimization/threshold (:492-510),
-// the result record written per code (:574-606).  What it does not do: girth / ACE tracing (trace_matrix, out of scope:
-// `girth` is copied through), marking files (`_marking` must be "skip"), GF(q) codes with --throughput (reported and skipped).
+// the result record written per code (:574-606).  What it does not do: marking files (`_marking` must be "skip"), GF(q) codes with
+// --throughput (reported and skipped).  `girth` is copied through; upstream's own trace is behind --girth.
 //
 //   --throughput   device-side noise (counter-based Philox, not upstream's mt19937 stream): 10^6-10^7 frames/s per GPU; every
 //                  modulation_type 0..4 and permutation_type 0..4; upstream's stopping rule frame by frame over the ordered records
@@ -15,6 +15,11 @@
 //                  scored as ONE set per SNR (ldpc::bp_simulation_codes_exact: the noise of the reset generator drawn once, all codes
 //                  of the group in one launch); the result file is the one without the flag except for `time`.  Codes over GF(q) of
 //                  one q are grouped the same way into ldpc::bp_simulation_codes_gfq_exact
+//   --girth        upstream's trace_matrix per code (:148-205, :496) on the device (ldpc::trace_matrix, include/ldpc/girth.h): every
+//                  record gains girth_, girth_ACE and girth_spectrum behind `girth` (:600-603).  The trace depends on the code alone,
+//                  so it runs once per code and not once per SNR; with --code-sets once per group (ldpc::trace_matrices).  A code
+//                  over GF(q) gets girth_ = 0 and zeros, as upstream traces none (:494-498).  Without the flag the output is
+//                  byte for byte what it always was (and so is the usage text, which does not list the flag)
 //   --device N     GPU ordinal;  --devices 0,1,2,3 | all   shard the frames over several GPUs (RCCL all-reduce of the counters)
 #include <chrono>
 #include <cmath>
@@ -25,6 +30,7 @@
 
 #include "ldpc/bp_simulation.h"
 #include "ldpc/decoders.h"
+#include "ldpc/girth.h"
 #include "ldpc/jsonx.h"
 #include "ldpc_hip.h"
 
@@ -87,6 +93,11 @@ struct SetGroup {
     std::vector<ldpc::Matrix> coefs;    // q_mod > 2: coefficients already reduced
 };
 struct SetResult { std::vector<Pair> per_snr; double secs = 0; };
+struct GirthRecord {   // --girth: what main_simulation.cpp:496 leaves for :601-603
+    bool traced = false;
+    int girth = 0;
+    std::vector<int> ace = std::vector<int>(ldpc::kGirthGTARGET, 0), spectrum = std::vector<int>(ldpc::kGirthGTARGET, 0);
+};
 
 // does a set context take these codes?  The host-side table builders apply the checks of the open entry points without a GPU.
 bool set_takes(const SetGroup &g, int rows, int columns) {
@@ -122,7 +133,7 @@ bool set_takes(const SetGroup &g, int rows, int columns) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool throughput = false, code_sets = false;
+    bool throughput = false, code_sets = false, girth = false;
     int random_codewords = 0;   // --throughput only: transmit this many random codewords encoded on the device instead of the all-zero word
     int device = 0;
     std::string devices_arg;
@@ -130,6 +141,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--throughput")) throughput = true;
         else if (!strcmp(argv[i], "--code-sets")) code_sets = true;
+        else if (!strcmp(argv[i], "--girth")) girth = true;
         else if (!strcmp(argv[i], "--random-codewords") && i + 1 < argc) random_codewords = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices_arg = argv[++i];
@@ -188,6 +200,7 @@ int main(int argc, char **argv) {
         // --code-sets: the groups are scored first, each SNR of a group in one bp_simulation_codes_exact call after reset_random(); the
         // loop below then takes a grouped code's numbers from here and runs every other code as it always did
         std::vector<SetResult> from_set(codes.items.size());
+        std::vector<GirthRecord> traced(codes.items.size());
         if (code_sets && !throughput && modulation_type == 0 && permutation_type == 0) {
             std::vector<SetGroup> groups;
             int rows0 = -1, columns0 = -1;
@@ -234,6 +247,11 @@ int main(int argc, char **argv) {
                 }
                 const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 for (size_t m : g.members) from_set[m].secs = secs / (double)g.members.size();
+                if (girth && g.key.q_mod <= 2) {   // the whole group in one ldpc_hip_girth_codes call
+                    std::vector<std::vector<int>> ace, spectrum;
+                    const std::vector<int> girths = ldpc::trace_matrices(g.codes, g.key.lifting, ldpc::kGirthGTARGET, ace, spectrum, nullptr, nullptr, devices[0]);
+                    for (size_t q = 0; q < g.members.size(); ++q) traced[g.members[q]] = {true, girths[q], ace[q], spectrum[q]};
+                }
             }
         }
 
@@ -259,6 +277,11 @@ int main(int argc, char **argv) {
             ldpc::Matrix HC;
             if (q_mod > 2) { HC = read_coefs(code, code_idx, r, c); reduce_coefs(HC, H, q_mod); }                                // :359-360, :416-434
             const double bitrate = (double)(columns - rows) / (columns - punctured_blocks);                                  // :372
+            GirthRecord &trace = traced[code_idx];
+            if (girth && q_mod <= 2 && !trace.traced) {                                                                      // :494-498
+                trace.girth = ldpc::trace_matrix(H, lifting, ldpc::kGirthGTARGET, trace.ace, trace.spectrum, devices[0]);
+                trace.traced = true;
+            }
 
             std::vector<double> ber(snrs.size()), fer(snrs.size()), esn0(snrs.size());
             const auto t0 = std::chrono::steady_clock::now();
@@ -318,7 +341,14 @@ int main(int argc, char **argv) {
             d.set("_marking", jsonx::Value::string("skip"));
             d.set("code_bitrate", jsonx::Value::number(bitrate));
             d.set("code", jsonx::Value::matrix(r, c, H.v));
-            for (const char *key : {"column_weights", "row_weights", "girth", "config_index", "matrix_index", "code_index"})
+            for (const char *key : {"column_weights", "row_weights", "girth"})
+                if (const jsonx::Value *v = code.find(key)) d.set(key, *v);
+            if (girth) {                                                                                                     // :601-603
+                d.set("girth_", jsonx::Value::number((long long)trace.girth));
+                d.set("girth_ACE", jsonx::Value::numbers(std::vector<long long>(trace.ace.begin(), trace.ace.end())));
+                d.set("girth_spectrum", jsonx::Value::numbers(std::vector<long long>(trace.spectrum.begin(), trace.spectrum.end())));
+            }
+            for (const char *key : {"config_index", "matrix_index", "code_index"})
                 if (const jsonx::Value *v = code.find(key)) d.set(key, *v);
             d.set("simulation_logs", jsonx::Value::array({log}));
             if (q_mod > 2) {                                                                                                 // :608-614
@@ -334,6 +364,8 @@ int main(int argc, char **argv) {
         fwrite(text.data(), 1, text.size(), f);
         fclose(f);
     } catch (const jsonx::Error &e) {
+        die(e.what());
+    } catch (const std::runtime_error &e) {   // ldpc::trace_matrix
         die(e.what());
     }
     return 0;

@@ -37,6 +37,7 @@
 #include "ldpc_gfq.hpp"
 #include "ldpc_gfq_chain.hpp"
 #include "ldpc_gfq_codeset.hpp"
+#include "ldpc_girth.hpp"
 
 namespace {
 
@@ -1437,3 +1438,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_gfq_exact_api.hpp"
 #include "ldpc_codeset_api.hpp"
 #include "ldpc_gfq_codeset_api.hpp"
+#include "ldpc_girth_api.hpp"
