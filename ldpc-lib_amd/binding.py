@@ -17,6 +17,9 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG_DIR)
 _LIB_NAME = "libldpc_hip.so"
 _lib = None
+# hipcc flags of every translation unit of the library (build_library); tests that compile device code of their own against
+# csrc/ import this list, so that they evaluate what the library evaluates.  -ffp-contract=off is part of the numerics contract.
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(_ROOT, "include")]
 
 
 class LdpcHipError(RuntimeError):
@@ -43,7 +46,7 @@ def build_library(force=False, verbose=False, jobs=None):
     obj_dir = os.path.join(_PKG_DIR, "build")
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(_ROOT, "include")]
+    flags = HIPCC_FLAGS
 
     def newer(target, deps):
         return os.path.exists(target) and all(os.path.getmtime(d) <= os.path.getmtime(target) for d in deps)

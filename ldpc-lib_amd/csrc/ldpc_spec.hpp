@@ -141,7 +141,10 @@ struct FrameVote {
 // algorithm (sysdeps/ieee754/dbl-64/e_exp.c of glibc >= 2.28 = ARM optimized-routines exp, N = 128, polynomial order 5) in the
 // evaluation order of the FMA build that x86-64 hosts with FMA select at run time: then the a-posteriori values of SP / ASP /
 // TDMP are IDENTICAL to the CPU reference's, not merely close.  (tools/gen_exp_table.py computes the table;
-// tests/test_host_cpu.py checks a C transcription against libm's exp() bit for bit.)  Valid for |x| < 700; callers clamp to 20.
+// tests/test_host_cpu.py checks a C transcription against libm's exp() bit for bit.)  Equal to glibc's exp for -512 < x < 709.78
+// (tests/test_device_math_cpu.py on the host, tests/test_gpu_device_math.py on the device).  Not beyond: for x <= -512 glibc's
+// special-case path rounds differently (last bit, about 0.07 % of the arguments down to -708), and from glibc's overflow threshold
+// 0x1.62e42fefa39efp+9 on it returns +inf where this returns a finite value.  Callers clamp to +-20 or go through exp_glibc_wide.
 __device__ __attribute__((aligned(16))) const unsigned long long kExpTab[256] = {
     0x0000000000000000ull, 0x3ff0000000000000ull, 0x3c9b3b4f1a88bf6eull, 0x3feff63da9fb3335ull,
     0xbc7160139cd8dc5dull, 0x3fefec9a3e778061ull, 0xbc905e7a108766d1ull, 0x3fefe315e86e7f85ull,
@@ -1771,9 +1774,13 @@ __device__ __forceinline__ void lms_small_body(const SpecArgs &a) {
 // a / b for operands whose range is known: the instruction sequence the compiler emits for an fp64 division is
 //   v_div_scale (x2), v_rcp_f64, two Newton steps, q = a*r, e = fma(-b, q, a), v_div_fmas, v_div_fixup;
 // v_div_scale / v_div_fmas / v_div_fixup only act when the denominator is zero, an operand is infinite / NaN / denormal, the
-// numerator is below 2^-969, or the exponents differ by 768 or more (ISA: V_DIV_SCALE_F64) -- otherwise they pass their input
-// through and the result is fma(e, r, q).  The probability-domain decoders divide quantities that are bounded away from all of
-// that by construction: messages are clamped to [1e-4, 1 - 1e-4] (TDMP) resp. [1e-6, 1 - 1e-6] (ASP), channel priors lie in
+// numerator is below 2^-969, the denominator is 2^1022 or more (its reciprocal is denormal), the numerator's exponent is 768 or
+// more above the denominator's, or the quotient is denormal (ISA: V_DIV_SCALE_F64) -- otherwise they pass their input
+// through and the result is fma(e, r, q).  (A numerator far BELOW the denominator is no such case: TDMP divides 4e-274 by 2.)
+// tests/test_gpu_device_math.py evaluates div_ranged on the device over exactly this domain and over each caller's, against IEEE
+// division, quotients next to a rounding boundary included; it also pins the two deviations the callers know about: a numerator of
+// -0.0 gives +0.0 (ldpc_mt.hpp), and x / 0 for x != 0 gives NaN, not +-inf (sp_body).
+// The probability-domain decoders divide quantities that are bounded away from all of that by construction: messages are clamped to [1e-4, 1 - 1e-4] (TDMP) resp. [1e-6, 1 - 1e-6] (ASP), channel priors lie in
 // [4.2e-18, 1 - 4.2e-18] (LLR / 2 clamped to +-20), so a posterior or extrinsic probability is >= 4.2e-18 * clamp^(column weight):
 // >= 4e-274 for TDMP (column weight <= block rows <= 64) and >= 4e-258 for ASP with column weight <= 40 -- both far above
 // 2^-969 = 2e-292 -- and every denominator is >= the clamp bound (e.g. aa + x - 2 aa x >= min(aa, 1 - aa)) and <= 1e7.  A numerator

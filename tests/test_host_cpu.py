@@ -490,17 +490,8 @@ def test_device_exp_algorithm_equals_libm_exp_bit_for_bit(tmp_path):
     body = hdr[hdr.index("kExpTab[256] = {") + len("kExpTab[256] = {"):]
     body = body[:body.index("};")]
     assert [int(x.strip().rstrip("ull"), 16) for x in body.replace("\n", " ").split(",") if x.strip()] == tab
-    fn = hdr[hdr.index("__device__ __forceinline__ double exp_glibc_t(double x, Tab T) {"):]
-    fn = fn[:fn.index("\n}\n") + 3]
-    c_fn = (fn.replace("__device__ __forceinline__ double exp_glibc_t(double x, Tab T)", "static double exp_glibc(double x)").replace("__fma_rn", "fma")
-              .replace("const ulonglong2 pair = *reinterpret_cast<const ulonglong2 *>(&T[idx]);", "const struct { unsigned long long x, y; } pair = {kExpTab[idx], kExpTab[idx + 1]};")
-              .replace("(unsigned long long)__double_as_longlong(kd)", "asu(kd)")
-              .replace("__longlong_as_double((long long)pair.x)", "asd(pair.x)")
-              .replace("__longlong_as_double((long long)sbits)", "asd(sbits)"))
-    src = ("#include <math.h>\n#include <stdint.h>\n#include <stdio.h>\n#include <string.h>\n"
-           "static unsigned long long asu(double x){unsigned long long u;memcpy(&u,&x,8);return u;}\n"
-           "static double asd(unsigned long long u){double x;memcpy(&x,&u,8);return x;}\n"
-           "static const unsigned long long kExpTab[256] = {" + ",".join("0x%xull" % v for v in tab) + "};\n" + c_fn +
+    from device_math_cases import exp_transcription_c   # shared with tests/test_device_math_cpu.py, which runs it over (-512, 709.78)
+    src = (exp_transcription_c() +
            "int main(){unsigned long long s=88172645463325252ull;long bad=0,n=4000000;\n"
            " for(long i=0;i<n;i++){s^=s<<13;s^=s>>7;s^=s<<17;double x=((double)(s>>11)/9007199254740992.0)*42.0-21.0;\n"
            "  if(i<2000) x=(i-1000)*1e-19; if(asu(exp_glibc(x))!=asu(exp(x))) bad++;}\n"
