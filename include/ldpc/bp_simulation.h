@@ -472,15 +472,21 @@ ldpc_hip_ctx *open_code_set(std::vector<Mat> const &codes, int M, int decoder_ty
     // ldpc_hip_open_codes_wide, the records in LDS
     const bool wide = (decoder_type == LDPC_HIP_MS_DEC || decoder_type == LDPC_HIP_TASP_DEC || decoder_type == LDPC_HIP_LMS_DEC) &&
                       (b > 16 || (decoder_type == LDPC_HIP_MS_DEC && c > 32));
-    if ((wide                                ? ldpc_hip_open_codes_wide(decoder_type, b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_TASP_DEC ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
-         : decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC
-             ? ldpc_hip_open_codes_sp(decoder_type, b, c, M, hd.data(), C, device, &ctx)
-                                             : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx)) != 0)
-        Env::fail(ldpc_hip_last_error());
+    // Any lifting above 512, and any set whose image the entry point below refuses for its size (LDPC_HIP_EUNSUPPORTED): the
+    // global-memory tier of a set, ldpc_hip_open_codes_global.  A structural refusal (LDPC_HIP_EINVAL) stays the first entry point's
+    int rc = LDPC_HIP_EUNSUPPORTED;
+    if (M <= 512) {
+        rc = (wide                                ? ldpc_hip_open_codes_wide(decoder_type, b, c, M, hd.data(), C, device, &ctx)
+             : decoder_type == LDPC_HIP_TASP_DEC ? ldpc_hip_open_codes_tdmp(b, c, M, hd.data(), C, device, &ctx)
+             : decoder_type == LDPC_HIP_IASP_DEC ? ldpc_hip_open_codes_iasp(b, c, M, hd.data(), C, device, &ctx)
+             : decoder_type == LDPC_HIP_LCHE_DEC ? ldpc_hip_open_codes_lche(b, c, M, hd.data(), C, device, &ctx)
+             : decoder_type == LDPC_HIP_IMS_DEC  ? ldpc_hip_open_codes_ims(b, c, M, hd.data(), C, device, &ctx)
+             : decoder_type == LDPC_HIP_SP_DEC || decoder_type == LDPC_HIP_ASP_DEC
+                 ? ldpc_hip_open_codes_sp(decoder_type, b, c, M, hd.data(), C, device, &ctx)
+                                                 : ldpc_hip_open_codes(decoder_type, b, c, M, hd.data(), C, device, &ctx));
+    }
+    if (rc == LDPC_HIP_EUNSUPPORTED) rc = ldpc_hip_open_codes_global(decoder_type, b, c, M, hd.data(), C, device, &ctx);
+    if (rc != 0) Env::fail(ldpc_hip_last_error());
     return ctx;
 }
 
@@ -492,7 +498,7 @@ ldpc_hip_ctx *open_code_set(std::vector<Mat> const &codes, int M, int decoder_ty
 // records of later batches.  With show_process == 0 the whole run is one ldpc_hip_simulate_codes_stop call instead: the same rule on
 // the device, every launch over the codes still running, no records on the host; the results are the same integers.  decoder_type: MS_DEC, LMS_DEC, TASP_DEC (7, ldpc_hip_open_codes_tdmp),
 // IASP_DEC (5, ldpc_hip_open_codes_iasp), LCHE_DEC (9, ldpc_hip_open_codes_lche), IMS_DEC (4, ldpc_hip_open_codes_ims), SP_DEC or ASP_DEC (1, 2, ldpc_hip_open_codes_sp); MS_DEC, TASP_DEC and LMS_DEC beyond 16 block rows (MS_DEC: or 32 block columns)
-// through ldpc_hip_open_codes_wide, so no shape is refused for its block rows or columns.  counters_out: nse, nde and experiment per code (the [C][B] records carry
+// through ldpc_hip_open_codes_wide, and a lifting above 512 or an image beyond the LDS through ldpc_hip_open_codes_global, so no shape is refused.  counters_out: nse, nde and experiment per code (the [C][B] records carry
 // no iteration counts, so nue and sum_abs_iters stay 0).
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,

@@ -584,6 +584,31 @@ int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t 
  * and 825.0 against 240.9 ms (0.31x, 0.29x); TDMP is the same kernel (56.9 against 56.9 ms).  Use this entry point beyond the limits
  * of the others, as the layers above do.  The channel LLRs in LDS instead of re-read: 1.88x slower at 30 x 60 (667 against 354 ms). */
 int ldpc_hip_open_codes_wide(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
+/* A set of ANY shape: the global-memory tier of a code set (csrc/ldpc_codeset_global.hpp), what the shape-unlimited tier of
+ * ldpc_hip_open is to a single code.  decoder_id LDPC_HIP_SP_DEC (1), LDPC_HIP_ASP_DEC (2), LDPC_HIP_MS_DEC (3), LDPC_HIP_IMS_DEC (4),
+ * LDPC_HIP_IASP_DEC (5), LDPC_HIP_TASP_DEC (7), LDPC_HIP_LMS_DEC (8) or LDPC_HIP_LCHE_DEC (9); any other id is LDPC_HIP_EINVAL (Gallager
+ * BP has no set: its frames are not independent).  An ordinary code-set context, served by the entry points below exactly as a
+ * context of the decoder's own open entry point is (alpha, puncture fill, ldpc_hip_set_ims_params), and bit-identical to it on every
+ * shape both accept, and to one ldpc_hip_open context per matrix on every shape.  Kernels: <decoder>_global_codes_kernel, one
+ * workgroup of 256 threads (1024 from N = 16384) per frame, no LDS; a work item is (code, frame), the grid is capped at 1024 workgroups
+ * (halved while their workspace exceeds 8 GiB; LDPC_HIP_CODES_GLOBAL_GRID=n, read per call, caps it lower) and strides over the items.
+ * The message state is in a workspace of one slice per workgroup, sized for the code with the most circulants: it grows with neither
+ * C nor B, is kept by the context (grown, never shrunk) and freed by ldpc_hip_close.  A decode call that needs more slices than the
+ * context holds frees the workspace and allocates a larger one, which waits for the device: that call is not asynchronous.  A code's edge count, row and column weights and
+ * whether all its block columns hold two circulants (decoders 2 and 5 then take upstream's own branch) are read from its own record,
+ * so one set may mix such codes.
+ * Accepted: any M >= 1, rh, nh and row weight that ldpc_hip_open's shape-unlimited tier takes.  LDPC_HIP_EINVAL, naming the code and
+ * the position, before any device call: a null or non-positive argument, C < 1, a shift outside [-1, M), an empty block row or
+ * column, a block row of weight < 2 for ids 2, 5 and 7.  LDPC_HIP_EUNSUPPORTED, naming the limit: an LCHE row of weight > 1024, M, rh
+ * or nh from 65536 (an edge word holds 16 bits of each), nh * M from 2^28, a workspace slice beyond 512 MiB (16 of them within 8 GiB).
+ * Every other entry point keeps its limits and its messages.
+ * Measured (profiles/r29_codeset_global_time.txt; 4096 frames per code, wall time, median of 5, relabelings of the 16 x 32 Appendix C
+ * matrix, against one ldpc_hip_open context per code, JIT off, at 1 / 16 / 256 codes).  TDMP, 15 iterations, 1.7 dB, against
+ * tasp_global_kernel: M = 256 28.7 against 30.4 ms (1.06x), 358.9 against 402.3 ms (1.12x), 5481 against 6478 ms (1.18x); M = 512 1.06x,
+ * 1.11x, 1.13x.  Min-sum, M = 1024, 2.0 dB, against ms_global_kernel: 0.99x for ONE code (SLOWER: 158.4 against 156.5 ms), 1.10x,
+ * 1.15x.  Integer min-sum, 50 iterations, 2.0 dB: these shapes fit the LDS-resident kernels (a single code runs ims_flood_kernel), and
+ * this route is SLOWER than one context per code at every size: M = 256 0.44x, 0.48x (499.4 against 238.5 ms), 0.53x; M = 512 0.57x, 0.64x, 0.67x. */
+int ldpc_hip_open_codes_global(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out);
 int ldpc_hip_codes(const ldpc_hip_ctx *ctx);      /* C; 0 for any other context */
 /* The graph table ldpc_hip_open_codes / ldpc_hip_open_codes_tdmp (decoder_id LDPC_HIP_TASP_DEC) / ldpc_hip_open_codes_iasp (decoder_id
  * LDPC_HIP_IASP_DEC) upload, built on the host (no GPU needed; the same checks and return codes): per code
@@ -614,6 +639,17 @@ int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const in
  * (ldpc_hip_codes_table_host keeps its limits.) */
 int ldpc_hip_codes_table_wide_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
                                    long long capacity, long long *length);
+/* The table ldpc_hip_open_codes_global uploads, with its checks and return codes (no GPU needed), the same record for all eight ids:
+ * per code rh + nh + 3 + 3 ne entries, ne its number of circulants --
+ *   row_start[rh + 1]   relative to the code's own edge list; row_start[rh] = ne
+ *   edges[ne]           (block column << 16) | shift, rows then columns ascending (row-major order)
+ *   cw2                 1: every block column holds exactly two circulants
+ *   col_start[nh + 1]   relative to the code's own column list
+ *   col_edges[ne]       (block ROW << 16) | shift, columns then rows ascending
+ *   col_slot[ne]        for the same entry: the row-major index of that edge in edges[]
+ * -- the five tables of a single-code context.  offsets [C] = index of each code's row_start[0]. */
+int ldpc_hip_codes_table_global_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                     long long capacity, long long *length);
 /* Work item (c, f) decodes frame f of code c.  d_llr: [B][N] when shared_llr != 0 (every code decodes the same B received words) or
  * [C][B][N]; d_hard [C][B][hard_words], d_iters [C][B], d_soft [C][B][N], each optional (NULL) as in ldpc_hip_decode_dev.
  * maxiter >= 1.  Asynchronous on `stream`.  An IMS set (ldpc_hip_open_codes_ims) quantises into the context's workspace first: one

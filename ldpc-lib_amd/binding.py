@@ -196,7 +196,7 @@ def load_library():
     lib.ldpc_hip_mt_advance_gfq.argtypes = [vp, i64]
     lib.ldpc_hip_mt_frames_gfq.argtypes = [vp, f64, i32, i32, i64, vp, vp]
     lib.ldpc_hip_frames_gfq_noise_host.argtypes = [vp, vp, f64, i32, i32, i64, vp, vp]
-    for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, _CODES_WIDE, *_CODES_ROUTE.values()):
+    for open_codes, open_id, codes_table_host, table_id in (_CODES_GENERIC, _CODES_WIDE, _CODES_GLOBAL, *_CODES_ROUTE.values()):
         getattr(lib, open_codes).argtypes = [i32] * open_id + [i32, i32, i32, vp, i32, i32, C.POINTER(vp)]
         getattr(lib, codes_table_host).argtypes = [i32] * table_id + [i32, i32, i32, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_codes.argtypes = [vp]
@@ -746,6 +746,9 @@ _CODES_ROUTE = {
 }
 # DEC_MS, DEC_TASP and DEC_LMS beyond the block rows (and, for DEC_MS, block columns) that their register-resident set kernels hold
 _CODES_WIDE = ("ldpc_hip_open_codes_wide", True, "ldpc_hip_codes_table_wide_host", True)
+# any shape: the global-memory tier of a set (csrc/ldpc_codeset_global.hpp), all eight set decoders
+_CODES_GLOBAL = ("ldpc_hip_open_codes_global", True, "ldpc_hip_codes_table_global_host", True)
+_EUNSUPPORTED = -2
 
 
 def _codes_route(decoder_id, rh, nh):
@@ -756,19 +759,34 @@ def _codes_route(decoder_id, rh, nh):
     return _CODES_ROUTE.get(decoder_id, _CODES_GENERIC)
 
 
-def codes_table(decoder_id, codes, M, wide=False):
+def _codes_entry(decoder_id, rh, nh, M, wide, tier):
+    """The entry points a set opens through.  tier="global": the global-memory tier on any shape; tier="auto": that tier for M > 512
+    (no other set kernel takes such a lifting), else wide=True or _codes_route.  wide=True keeps its entry point at any lifting (it
+    refuses M > 512 as it always did); with tier="global" wide is ignored: the global tier has no wide variant."""
+    if tier not in ("auto", "global"):
+        raise ValueError(f'tier = {tier!r}: "auto" or "global"')
+    if tier == "global" or (M > 512 and not wide):
+        return _CODES_GLOBAL
+    return _CODES_WIDE if wide else _codes_route(decoder_id, rh, nh)
+
+
+def codes_table(decoder_id, codes, M, wide=False, tier="auto"):
     """The graph table of a code set as ldpc_hip_open_codes uploads it, built on the host (needs no GPU): (offsets int32 [C], table
     int32).  Code c owns table[offsets[c]:]: row_start[rh + 1], then its edges (block column << 16) | shift in row-major order; for
     DEC_IASP then cw2, col_start[nh + 1] and col_edges (edge index << 16) | shift in column-major order.  DEC_LCHE: the record of
     DEC_MS under LCHE's limits (ldpc_hip_codes_table_lche_host); DEC_IMS: the same record under integer min-sum's limits
     (ldpc_hip_codes_table_ims_host); DEC_SP, DEC_ASP: the record of DEC_IASP under the limits of the flooding sum-product set kernels
     (ldpc_hip_codes_table_sp_host).  DEC_MS, DEC_TASP and DEC_LMS beyond 16 block rows (DEC_MS: or 32 block columns): the record of
-    DEC_MS under the limits of ldpc_hip_open_codes_wide (ldpc_hip_codes_table_wide_host); wide=True asks that entry point on any shape."""
+    DEC_MS under the limits of ldpc_hip_open_codes_wide (ldpc_hip_codes_table_wide_host); wide=True asks that entry point on any shape.
+    tier="global", and tier="auto" for M > 512: the record of ldpc_hip_open_codes_global (ldpc_hip_codes_table_global_host) for all
+    eight set decoders -- row_start[rh + 1], edges, cw2, col_start[nh + 1], col_edges (block row << 16) | shift and col_slot (the
+    row-major index of the edge).  For M <= 512 tier="auto" answers for the decoder's own entry point, its refusal of an LDS image
+    beyond 160 KiB included: the table of the set LdpcHipCodes then opens is the one of tier="global"."""
     lib = load_library()
     codes = _code_stack(codes)
     Cn, rh, nh = codes.shape
     n = C.c_longlong()
-    _, _, who, takes_id = _CODES_WIDE if wide else _codes_route(int(decoder_id), rh, nh)
+    _, _, who, takes_id = _codes_entry(int(decoder_id), rh, nh, int(M), wide, tier)
     head = (int(decoder_id),) if takes_id else ()
     call = lambda off, tab, cap, length: getattr(lib, who)(*head, rh, nh, int(M), codes.ctypes.data, Cn, off, tab, cap, length)
     _check(lib, call(None, None, 0, C.byref(n)), who)
@@ -783,18 +801,26 @@ class LdpcHipCodes:
     or the decoder's own open entry point, _CODES_ROUTE): what a code search scores.
     decoder_id DEC_MS, DEC_LMS, DEC_TASP, DEC_IASP, DEC_LCHE, DEC_IMS, DEC_SP or DEC_ASP; bit-identical to LdpcHip on each matrix.
     Block rows and columns are not limited: DEC_MS, DEC_TASP and DEC_LMS keep their register-resident kernels up to 16 block rows (DEC_MS:
-    and 32 block columns) and open through ldpc_hip_open_codes_wide beyond (records in LDS); wide=True takes that route on any shape."""
+    and 32 block columns) and open through ldpc_hip_open_codes_wide beyond (records in LDS); wide=True takes that route on any shape.
+    No shape is refused: tier="auto" opens a lifting above 512 through ldpc_hip_open_codes_global (the state in a workspace in global
+    memory), and any other set through the entry point above and, when that one answers LDPC_HIP_EUNSUPPORTED (an LDS image beyond
+    160 KiB), through ldpc_hip_open_codes_global as well; a structural LDPC_HIP_EINVAL is raised under the first entry point's name.
+    tier="global" takes that route on any shape (wide is ignored then).  self.entry names the entry point the set was opened through."""
 
-    def __init__(self, decoder_id, codes, M, device=0, wide=False):
+    def __init__(self, decoder_id, codes, M, device=0, wide=False, tier="auto"):
         self.lib = load_library()
         codes = _code_stack(codes)
         self.C, self.rh, self.nh = codes.shape
         self.M, self.decoder_id, self.device = int(M), int(decoder_id), int(device)
         h = C.c_void_p()
-        who, takes_id, _, _ = _CODES_WIDE if wide else _codes_route(self.decoder_id, self.rh, self.nh)
+        who, takes_id, _, _ = _codes_entry(self.decoder_id, self.rh, self.nh, self.M, wide, tier)
         head = (self.decoder_id,) if takes_id else ()
         rc = getattr(self.lib, who)(*head, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
+        if rc == _EUNSUPPORTED and tier == "auto" and not wide and who != _CODES_GLOBAL[0]:   # the image does not fit the LDS
+            who = _CODES_GLOBAL[0]
+            rc = getattr(self.lib, who)(self.decoder_id, self.rh, self.nh, self.M, codes.ctypes.data, self.C, self.device, C.byref(h))
         _check(self.lib, rc, who)
+        self.entry = who
         self.h = h
         self.N = self.lib.ldpc_hip_n(h)
         self.R = self.lib.ldpc_hip_r(h)

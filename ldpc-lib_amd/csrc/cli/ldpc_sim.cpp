@@ -115,19 +115,25 @@ bool set_takes(const SetGroup &g, int rows, int columns) {
             for (int i = 0; i < rows * columns; ++i) hc[(size_t)q * rows * columns + i] = (int16_t)g.coefs[(size_t)q].v[(size_t)i];
         return ldpc_hip_codes_gfq_table_host(q_bits, rows, columns, M, hd.data(), hc.data(), C, nullptr, nullptr, 0, &len) == 0;
     }
-    switch (dec) {
+    // the rule of open_code_set: a lifting above 512, or a set that the decoder's own entry point refuses for the size of its image
+    // (LDPC_HIP_EUNSUPPORTED), goes to the global-memory tier of a set; a structural refusal stays one
+    int rc = LDPC_HIP_EUNSUPPORTED;
+    if (M <= 512) switch (dec) {
     case LDPC_HIP_MS_DEC: case LDPC_HIP_LMS_DEC: case LDPC_HIP_TASP_DEC:
         if (rows > 16 || (dec == LDPC_HIP_MS_DEC && columns > 32))   // the route open_code_set takes for these shapes
-            return ldpc_hip_codes_table_wide_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
-        return ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
-    case LDPC_HIP_IASP_DEC:
-        return ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
-    case LDPC_HIP_LCHE_DEC: return ldpc_hip_codes_table_lche_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
-    case LDPC_HIP_IMS_DEC: return ldpc_hip_codes_table_ims_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+            rc = ldpc_hip_codes_table_wide_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len);
+        else rc = ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len);
+        break;
+    case LDPC_HIP_IASP_DEC: rc = ldpc_hip_codes_table_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len); break;
+    case LDPC_HIP_LCHE_DEC: rc = ldpc_hip_codes_table_lche_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len); break;
+    case LDPC_HIP_IMS_DEC: rc = ldpc_hip_codes_table_ims_host(rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len); break;
     case LDPC_HIP_SP_DEC: case LDPC_HIP_ASP_DEC:
-        return ldpc_hip_codes_table_sp_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len) == 0;
+        rc = ldpc_hip_codes_table_sp_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len);
+        break;
     default: return false;   // BP_DEC and anything else: one code at a time
     }
+    if (rc == LDPC_HIP_EUNSUPPORTED) rc = ldpc_hip_codes_table_global_host(dec, rows, columns, M, hd.data(), C, nullptr, nullptr, 0, &len);
+    return rc == 0;
 }
 
 }  // namespace

@@ -32,6 +32,10 @@ struct ldpc_codeset_state : codeset_common {
     int16_t *w_q = nullptr;            // [w_q_frames][N]
     long long w_q_frames = 0;
     int route = 0;                     // the record of codeset_kinds[] the set was opened with: (decoder_id, route)
+    // ROUTE_GLOBAL: one slice of glob_stride bytes per workgroup of a decode launch (grown on demand, never shrunk)
+    char *w_glob = nullptr;
+    size_t glob_stride = 0;
+    int glob_grid = 0;
 };
 
 void codeset_common_release(codeset_common &s) {
@@ -46,6 +50,7 @@ void ldpc_codeset_release(ldpc_codeset_state *s) {
     if (s->w_hard) (void)hipFree(s->w_hard);
     if (s->w_coef) (void)hipFree(s->w_coef);
     if (s->w_q) (void)hipFree(s->w_q);
+    if (s->w_glob) (void)hipFree(s->w_glob);
     codeset_common_release(*s);
     delete s;
 }
@@ -63,10 +68,11 @@ size_t codeset_lds_ims(int F, int rh, int nh, int M, int) { return ldpc::ims_cod
 size_t codeset_lds_sp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(false, F, nh * M, rh * M, M, ne_max) + 16; }
 size_t codeset_lds_asp(int F, int rh, int nh, int M, int ne_max) { return ldpc::sp_codes_image_bytes(true, F, nh * M, rh * M, M, ne_max) + 16; }
 size_t codeset_lds_wide(int F, int rh, int nh, int M, int) { return ldpc::wide_codes_image_bytes(F, nh * M, rh * M) + 16; }
+size_t codeset_lds_none(int, int, int, int, int) { return 0; }   // ROUTE_GLOBAL: the state is in the workspace
 
 enum codeset_lds_text { LDS_NONE, LDS_LENGTH, LDS_IMS, LDS_IASP, LDS_TDMP, LDS_LCHE, LDS_FLOOD, LDS_WIDE };   // the refusals of codeset_lds_refusal
 
-enum : int { ROUTE_RESIDENT = 0, ROUTE_WIDE = 1 };   // ldpc_hip_open_codes and its kin; ldpc_hip_open_codes_wide
+enum : int { ROUTE_RESIDENT = 0, ROUTE_WIDE = 1, ROUTE_GLOBAL = 2 };   // ldpc_hip_open_codes and its kin; ldpc_hip_open_codes_wide; ldpc_hip_open_codes_global
 
 enum : unsigned {
     CS_COLS = 1,     // the record goes on with cw2, col_start and col_edges, and a column entry names its edge in 16 bits
@@ -74,6 +80,10 @@ enum : unsigned {
                      // sp_codes_frames and sp_codes_groups x sp_codes_lanes, and a set is refused only when ONE frame's image does not fit
     CS_CHECKS = 4,   // that image holds the R check products
     CS_QUANT = 8,    // the kernel reads the quantiser's int16 words through a second argument (ImsCodesArgs)
+    CS_SLOTS = 16,   // the record goes on with cw2, col_start, col_edges ((block ROW << 16) | shift) and col_slot (the row-major index of the
+                     // edge, a word of its own): the five tables of DecArgs, as the kernels of ldpc_codeset_global.hpp read them
+    CS_GLOBAL = 32,  // the state is in a workspace in global memory (ldpc_codeset_global.hpp): one frame per workgroup of glob_threads(N)
+                     // threads, the grid capped and striding over the n_slots * B items, the argument block a CodesetGlobArgs
 };
 
 // What a set decoder is on the host: the one place where the limits of the set kernels live
@@ -87,6 +97,8 @@ struct codeset_kind {
     size_t (*lds)(int F, int rh, int nh, int M, int ne_max);
     codeset_lds_text early, late;      // the image is checked before the table is built (with ne_max = 0) and once ne_max is known
     int route = ROUTE_RESIDENT;        // ROUTE_WIDE: the same decoder with its per-check records in LDS, or launched without a block-row limit
+    int M_max = 512;                   // the lifting its lanes and LDS image take; 0: any
+    int glob_edge_arrays = 0;          // CS_GLOBAL: the per-edge arrays of a workspace slice (glob_ws_bytes), those of its decoder_kind
 };
 
 const codeset_kind codeset_kinds[] = {
@@ -114,7 +126,26 @@ const codeset_kind codeset_kinds[] = {
      0, 0, kRWM, "TDMP sum-product", 0, codeset_lds_tdmp, LDS_NONE, LDS_TDMP, ROUTE_WIDE},
     {LDPC_HIP_LMS_DEC, "lms_layered_wide_codes_kernel", (const void *)ldpc::lms_layered_wide_codes_kernel<false>, (const void *)ldpc::lms_layered_wide_codes_kernel<true>,
      0, 0, kRWM, nullptr, 0, codeset_lds_wide, LDS_WIDE, LDS_NONE, ROUTE_WIDE},
+    // ldpc_hip_open_codes_global: any shape the single-code shape-unlimited tier takes.  No LDS, no limit on M, rh, nh or the row weight
+    // (LCHE: 1024, upstream's map_bin_llr); one instance per decoder
+#define LDPC_GLOBAL_SET(id, kernel, rw_max, min_rw2, is, edge_arrays)                                                                       \
+    {id, #kernel, (const void *)ldpc::kernel, (const void *)ldpc::kernel, 0, 0, rw_max, min_rw2, CS_SLOTS | CS_GLOBAL | (is), codeset_lds_none, \
+     LDS_NONE, LDS_NONE, ROUTE_GLOBAL, 0, edge_arrays}
+    LDPC_GLOBAL_SET(LDPC_HIP_SP_DEC, sp_global_codes_kernel, 0, nullptr, 0, 1),
+    LDPC_GLOBAL_SET(LDPC_HIP_ASP_DEC, asp_global_codes_kernel, 0, "advanced sum-product", 0, 3),
+    LDPC_GLOBAL_SET(LDPC_HIP_MS_DEC, ms_global_codes_kernel, 0, nullptr, 0, 0),
+    LDPC_GLOBAL_SET(LDPC_HIP_IMS_DEC, ims_global_codes_kernel, 0, nullptr, CS_QUANT, 0),
+    LDPC_GLOBAL_SET(LDPC_HIP_IASP_DEC, iasp_global_codes_kernel, 0, "integer advanced sum-product", 0, 1),
+    LDPC_GLOBAL_SET(LDPC_HIP_TASP_DEC, tasp_global_codes_kernel, 0, "TDMP sum-product", 0, 4),
+    LDPC_GLOBAL_SET(LDPC_HIP_LMS_DEC, lms_global_codes_kernel, 0, nullptr, 0, 1),
+    LDPC_GLOBAL_SET(LDPC_HIP_LCHE_DEC, lche_global_codes_kernel, 1024, nullptr, 0, 1),
+#undef LDPC_GLOBAL_SET
 };
+
+// ROUTE_GLOBAL: a launch takes at most this many workgroups, halved while their slices exceed kGlobSetBytes but not below
+// kGlobSetMinGrid -- the rule of launch_global.  A set whose kGlobSetMinGrid slices exceed kGlobSetBytes is refused when it is opened.
+constexpr int kGlobSetGrid = 1024, kGlobSetMinGrid = 16;
+constexpr size_t kGlobSetBytes = (size_t)8 << 30;
 
 // The entry points come here with an id that their route serves
 const codeset_kind *codeset_find(int decoder_id, int route = ROUTE_RESIDENT) {
@@ -144,12 +175,20 @@ int codeset_lds_refusal(const codeset_kind &k, codeset_lds_text text, const char
 // Checks a code set against the limits of its kernel and builds its table: per code row_start[rh+1] (relative to the code's own edge
 // list) then edges[] ((block column << 16) | shift, rows ascending, columns ascending); off[c] = index of code c's row_start[0].  A
 // CS_COLS record goes on with cw2 (1: every block column holds exactly two circulants, upstream's own branch), col_start[nh+1] and
-// col_edges[] ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).
+// col_edges[] ((row-major index of the edge inside its code << 16) | shift, columns ascending, rows ascending).  A CS_SLOTS record goes
+// on instead with cw2, col_start[nh+1], col_edges[ne] ((block row << 16) | shift, columns ascending, rows ascending) and col_slot[ne]
+// (the row-major index of that edge inside its code): rh + nh + 3 + 3 ne entries per code.
 int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int M, const int16_t *hd, int C, std::vector<int32_t> &off,
                   std::vector<int32_t> &tab, int *ne_max_out = nullptr) {
     if (!hd || rh <= 0 || nh <= 0 || M <= 0) return fail(LDPC_HIP_EINVAL, "%s: bad argument", who);
     if (C < 1) return fail(LDPC_HIP_EINVAL, "%s: C = %d, a code set holds at least one code", who, C);
-    if (M > 512) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= 512", who, M);
+    if (kind.M_max && M > kind.M_max) return fail(LDPC_HIP_EINVAL, "%s: M = %d, the resident table kernels take M <= %d", who, M, kind.M_max);
+    if (kind.is & CS_GLOBAL) {   // what an edge word and the 32-bit indices of the tier hold, as ldpc_hip_open has it
+        if (M >= 65536 || nh >= 65536 || rh >= 65536)
+            return fail(LDPC_HIP_EUNSUPPORTED, "%s: M = %d, rh = %d, nh = %d; an edge word holds a shift and a block row or column in 16 bits each: all below 65536", who, M, rh, nh);
+        if ((long long)nh * M >= (1LL << 28))
+            return fail(LDPC_HIP_EUNSUPPORTED, "%s: code length nh * M = %lld: at most 2^28 - 1 is supported (32-bit indices)", who, (long long)nh * M);
+    }
     if (kind.rh_max && rh > kind.rh_max) return fail(LDPC_HIP_EINVAL, "%s: rh = %d, the resident table kernels take %d block rows", who, rh, kind.rh_max);
     if (kind.nh_max && nh > kind.nh_max)
         return fail(LDPC_HIP_EINVAL, "%s: nh = %d, the flooding table kernel keeps the channel LLRs of %d block columns in registers", who, nh, kind.nh_max);
@@ -160,7 +199,8 @@ int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int
     int ne_max = 0;
     for (int c = 0; c < C; ++c) {
         const int16_t *h = hd + (size_t)c * rh * nh;
-        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (kind.is & CS_COLS ? (size_t)nh + 2 + (size_t)rh * nh : 0) >= ((size_t)1 << 31))
+        if (tab.size() + (size_t)rh + 1 + (size_t)rh * nh + (kind.is & (CS_COLS | CS_SLOTS) ? (size_t)nh + 2 + (size_t)rh * nh : 0) +
+                (kind.is & CS_SLOTS ? (size_t)rh * nh : 0) >= ((size_t)1 << 31))
             return fail(LDPC_HIP_EINVAL, "%s: the table of %d codes exceeds 2^31 entries", who, C);
         off.push_back((int32_t)tab.size());
         const size_t rs = tab.size();
@@ -179,7 +219,8 @@ int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int
                 ++rw; ++ne;
             }
             if (rw == 0) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d is empty", who, c, j);
-            if (kind.rw_max && rw > kind.rw_max) return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kind.rw_max);
+            if (kind.rw_max && rw > kind.rw_max)   // a resident kernel's registers; CS_GLOBAL: upstream's own arrays (map_bin_llr, decoders.cpp:2818-2822)
+                return fail(kind.is & CS_GLOBAL ? LDPC_HIP_EUNSUPPORTED : LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; at most %d", who, c, j, rw, kind.rw_max);
             if (kind.min_rw2 && rw < 2)
                 return fail(LDPC_HIP_EINVAL, "%s: code %d, block row %d has weight %d; %s needs at least 2", who, c, j, rw, kind.min_rw2);
         }
@@ -187,6 +228,24 @@ int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int
         ne_max = ne > ne_max ? ne : ne_max;
         for (int k = 0; k < nh; ++k)
             if (!col_w[(size_t)k]) return fail(LDPC_HIP_EINVAL, "%s: code %d, block column %d is empty", who, c, k);
+        if (kind.is & CS_SLOTS) {
+            bool cw2 = true;   // the rule of ldpc_hip_open, per code
+            for (int k = 0; k < nh; ++k) cw2 = cw2 && col_w[(size_t)k] == 2;
+            tab.push_back(cw2 ? 1 : 0);
+            const size_t cst = tab.size(), ed = rs + (size_t)rh + 1, ce = cst + (size_t)nh + 1, sl = ce + (size_t)ne;
+            tab.resize(sl + (size_t)ne);
+            int q = 0;
+            for (int k = 0; k < nh; ++k) { tab[cst + k] = q; q += col_w[(size_t)k]; }
+            tab[cst + nh] = q;
+            std::vector<int> fill(tab.begin() + (long)cst, tab.begin() + (long)cst + nh);
+            for (int j = 0; j < rh; ++j)   // row-major order: the rows of a column come out ascending
+                for (int e = tab[rs + j]; e < tab[rs + j + 1]; ++e) {
+                    const uint32_t d = (uint32_t)tab[ed + (size_t)e];
+                    const int at = fill[d >> 16]++;
+                    tab[ce + (size_t)at] = (int32_t)(((uint32_t)j << 16) | (d & 0xffffu));
+                    tab[sl + (size_t)at] = e;
+                }
+        }
         if (kind.is & CS_COLS) {
             if (ne > 65535) return fail(LDPC_HIP_EINVAL, "%s: code %d has %d circulants; a column entry names its edge in 16 bits", who, c, ne);
             bool cw2 = true;   // the rule of ldpc_hip_open, per code
@@ -205,6 +264,12 @@ int codeset_build(const char *who, const codeset_kind &kind, int rh, int nh, int
         }
     }
     if (kind.late && kind.lds(F, rh, nh, M, ne_max) > 160 * 1024) return codeset_lds_refusal(kind, kind.late, who, F, rh, nh, M, ne_max);
+    if (kind.is & CS_GLOBAL) {
+        const size_t slice = ldpc::glob_ws_bytes(nh * M, rh * M, ne_max, M, kind.glob_edge_arrays);
+        if (slice > kGlobSetBytes / kGlobSetMinGrid)
+            return fail(LDPC_HIP_EUNSUPPORTED, "%s: a workgroup's workspace slice for %d variables, %d checks and %d circulants x %d is %zu bytes; the limit is %zu (%d slices within 8 GiB)",
+                        who, nh * M, rh * M, ne_max, M, slice, kGlobSetBytes / kGlobSetMinGrid, kGlobSetMinGrid);
+    }
     if (ne_max_out) *ne_max_out = ne_max;
     return 0;
 }
@@ -269,6 +334,12 @@ int codeset_wide_id(const char *who, int decoder_id) {
     return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; MS_DEC (3), TASP_DEC (7) or LMS_DEC (8)", who, decoder_id);
 }
 
+// what the two global entry points say to any other id
+int codeset_global_id(const char *who, int decoder_id) {
+    if (codeset_find(decoder_id, ROUTE_GLOBAL)) return 0;
+    return fail(LDPC_HIP_EINVAL, "%s: decoder id %d; SP_DEC (1), ASP_DEC (2), MS_DEC (3), IMS_DEC (4), IASP_DEC (5), TASP_DEC (7), LMS_DEC (8) or LCHE_DEC (9)", who, decoder_id);
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,6 +365,12 @@ int ldpc_hip_codes_table_wide_host(int decoder_id, int rh, int nh, int M, const 
                                    long long capacity, long long *length) {
     if (int rc = codeset_wide_id("ldpc_hip_codes_table_wide_host", decoder_id)) return rc;
     return codeset_table_host("ldpc_hip_codes_table_wide_host", decoder_id, rh, nh, M, hd, C, offsets, table, capacity, length, ROUTE_WIDE);
+}
+
+int ldpc_hip_codes_table_global_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
+                                     long long capacity, long long *length) {
+    if (int rc = codeset_global_id("ldpc_hip_codes_table_global_host", decoder_id)) return rc;
+    return codeset_table_host("ldpc_hip_codes_table_global_host", decoder_id, rh, nh, M, hd, C, offsets, table, capacity, length, ROUTE_GLOBAL);
 }
 
 int ldpc_hip_codes_table_sp_host(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int32_t *offsets, int32_t *table,
@@ -323,8 +400,9 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     s->route = route;
     c->decoder_id = decoder_id; c->device = device;
     c->rh = rh; c->nh = nh; c->M = M; c->N = nh * M; c->R = rh * M;
-    c->ne = kind.is & CS_COLS ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)   // edges of the whole set
-                              : (int)(tab.size() - (size_t)C * (rh + 1));
+    c->ne = kind.is & CS_SLOTS  ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 3)   // edges of the whole set
+            : kind.is & CS_COLS ? (int)((tab.size() - (size_t)C * (rh + nh + 3)) / 2)
+                                : (int)(tab.size() - (size_t)C * (rh + 1));
     c->hard_words = (c->N + 31) / 32;
     c->multiwave = M > 64;
     c->F = c->multiwave ? 1 : 64 / M;
@@ -332,6 +410,11 @@ int codeset_open(const char *who, int decoder_id, int rh, int nh, int M, const i
     if (kind.is & CS_FLOOD) {   // fewer frames when their images do not fit, several groups of lanes per frame
         c->F = ldpc::sp_codes_frames(!(kind.is & CS_CHECKS), c->N, c->R, M, ne_max);
         c->threads = ldpc::sp_codes_groups(M, nh) * ldpc::sp_codes_lanes(M);
+    }
+    if (kind.is & CS_GLOBAL) {   // one frame per workgroup, whatever the lifting; one instance
+        c->multiwave = false; c->F = 1;
+        c->threads = ldpc::glob_threads(c->N);
+        s->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, ne_max, M, kind.glob_edge_arrays);
     }
     c->lds_bytes = kind.lds(c->F, rh, nh, M, ne_max);
     c->kernel_name = std::string(kind.kernel) + (c->multiwave ? "<multiwave>" : "");
@@ -363,6 +446,27 @@ int codeset_ims_quantise(ldpc_hip_ctx *c, const double *d_llr, long long frames,
     return 0;
 }
 
+// ROUTE_GLOBAL: the workgroups of a launch over `grid` items -- at most kGlobSetGrid, halved while their slices exceed kGlobSetBytes, and
+// at most LDPC_HIP_CODES_GLOBAL_GRID = n (read per call: the tests make a handful of workgroups walk many items) -- and their workspace.
+// A launch that needs more slices than the context holds frees the workspace and allocates a larger one: hipFree waits for the device,
+// so earlier launches that use the old one have finished, and that call is not asynchronous (as launch_global's first calls are not).
+int codeset_glob_reserve(ldpc_codeset_state *s, long long &grid) {
+    long long cap = kGlobSetGrid;
+    while (cap > kGlobSetMinGrid && (size_t)cap * s->glob_stride > kGlobSetBytes) cap /= 2;
+    if (const char *e = getenv("LDPC_HIP_CODES_GLOBAL_GRID")) {
+        const long long n = atoll(e);
+        if (n > 0 && n < cap) cap = n;
+    }
+    if (grid > cap) grid = cap;
+    if (grid > s->glob_grid) {
+        if (s->w_glob) (void)hipFree(s->w_glob);
+        s->w_glob = nullptr; s->glob_grid = 0;
+        HIP_TRY(hipMalloc(&s->w_glob, (size_t)grid * s->glob_stride));
+        s->glob_grid = (int)grid;
+    }
+    return 0;
+}
+
 // The decode launch over n_slots codes: code_list [n_slots] (DEVICE) names them, null = all C codes in order.  Outputs [n_slots][B]...
 int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
                           int32_t *d_iters, double *d_soft, hipStream_t stream, const int32_t *code_list, int n_slots) {
@@ -370,7 +474,7 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
     if (B == 0) return 0;
     if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
-    const ldpc_codeset_state *s = c->codes;
+    ldpc_codeset_state *s = c->codes;
     if (!code_list) n_slots = s->C;
     if (n_slots < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: a launch covers at least one code");   // never a grid of 0 blocks
     const long long bpc = (B + c->F - 1) / c->F;
@@ -392,9 +496,15 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
         if (int rc = codeset_ims_quantise(c, d_llr, shared_llr ? B : B * (long long)s->C, stream)) return rc;
         ia.q = s->w_q; ia.max_data = (1 << (c->ims_dbits - 1)) - 1; ia.ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5445, :5458
     }
-    void *kargs[] = {&a, &ia};
+    long long grid = bpc * n_slots;
+    ldpc::CodesetGlobArgs ga{};   // the first argument of a CS_GLOBAL kernel
+    if (kind.is & CS_GLOBAL) {
+        if (int rc = codeset_glob_reserve(s, grid)) return rc;
+        ga.s = a; ga.ws = s->w_glob; ga.ws_stride = s->glob_stride; ga.items = bpc * n_slots;
+    }
+    void *kargs[] = {kind.is & CS_GLOBAL ? (void *)&ga : (void *)&a, &ia};
     c->last_launch = c->kernel_name.c_str();
-    HIP_TRY(hipLaunchKernel(k, dim3((unsigned)(bpc * n_slots)), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
+    HIP_TRY(hipLaunchKernel(k, dim3((unsigned)grid), dim3((unsigned)c->threads), kargs, c->lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     return timer.end();
 }
@@ -569,6 +679,12 @@ int ldpc_hip_open_codes_sp(int decoder_id, int rh, int nh, int M, const int16_t 
     if (decoder_id != LDPC_HIP_SP_DEC && decoder_id != LDPC_HIP_ASP_DEC)
         return fail(LDPC_HIP_EINVAL, "ldpc_hip_open_codes_sp: decoder id %d; SP_DEC (1) or ASP_DEC (2)", decoder_id);
     return codeset_open("ldpc_hip_open_codes_sp", decoder_id, rh, nh, M, hd, C, device, out);
+}
+
+int ldpc_hip_open_codes_global(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {
+    if (out) *out = nullptr;
+    if (int rc = codeset_global_id("ldpc_hip_open_codes_global", decoder_id)) return rc;
+    return codeset_open("ldpc_hip_open_codes_global", decoder_id, rh, nh, M, hd, C, device, out, ROUTE_GLOBAL);
 }
 
 int ldpc_hip_open_codes_wide(int decoder_id, int rh, int nh, int M, const int16_t *hd, int C, int device, ldpc_hip_ctx **out) {

@@ -29,6 +29,7 @@
 #include "ldpc_codeset_wide.hpp"
 #include "ldpc_codeset_sp.hpp"
 #include "ldpc_global.hpp"
+#include "ldpc_codeset_global.hpp"
 #include "ldpc_ms_fast.hpp"
 #include "ldpc_aot.hpp"   // ldpc_spec.hpp, code_appendix_c_m64.hpp + the declarations of the aot/*.hip kernels
 #include "ldpc_sumprod.hpp"
