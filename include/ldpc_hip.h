@@ -826,6 +826,38 @@ int ldpc_hip_girth_graph_host(int rh, int nh, int M, const int16_t *hd, int *E, 
 /* HOST only: main_simulation.cpp:177-201 on one code's S / SA: girth (21 = none found), ACE[4], spectrum[4]. */
 int ldpc_hip_trace_matrix_host(const int32_t *S, const int32_t *SA, int gmax, int *girth, int32_t ACE[4], int32_t spectrum[4]);
 
+/* ---- Labelling a protograph with circulant shifts under a girth bound: upstream's generate_code (code_generation.cpp:35-115, the
+ * second step of its `search` command) with the equations of equations.cpp / graph_spider.h (csrc/ldpc_label.hpp).
+ * proto HOST [rh][nh]: 0 = empty, 1 = edge with a random shift, any other positive value = edge whose shift is fixed to 0.  Edges are
+ * numbered column by column with the rows ascending; the random edges, in that order, are what an attempt draws.
+ * LDPC_HIP_EINVAL, found before any device call: rh or nh < 1, a NULL proto, a negative entry, no edge, target_girth < 4 and, for
+ * ldpc_hip_label_codes, M outside 2 .. 32767, max_attempts < 1, want < 1, pos_in outside 0 .. 624, a NULL state or output.
+ * LDPC_HIP_EUNSUPPORTED, also found before any device call: more than 2^20 equations or more than 2^22 paths in one layer of the
+ * path tree (the message holds the count reached), target_girth > 64, more than 480 edges with a random shift.  Both are stateless. */
+/* HOST only, no GPU: the equations of the protograph for target_girth.  *tree_girth: the girth the protograph allows (target_girth, or
+ * the length of the shortest closed walk whose edges cancel identically); *n_equations: upstream's `eqs=`; the table holds, per
+ * equation, its terms over the random edges only: eq_begin [n_equations + 1], term_edge [n_terms] (index among the random edges) and
+ * term_mult [n_terms] (signed multiplicity).  A labelling v passes iff no equation's sum of term_mult * v[term_edge] is divisible by M.
+ * *never_accepts = 1 when an equation has no term left.  Table pointers may be NULL: then only the sizes are written. */
+int ldpc_hip_label_equations_host(int rh, int nh, const int16_t *proto, int target_girth, int *tree_girth, int *n_equations, int *n_random,
+                                  long long *n_terms, int *never_accepts, int32_t *eq_begin, int32_t *term_edge, int32_t *term_mult);
+/* generate_code on the device.  Attempt a = 0, 1, ... draws one uniform_int_distribution<int>(0, M - 1) value per random edge from
+ * the std::mt19937 given by (state_in, pos_in) -- as ldpc_hip_mt_set_state takes them -- and is accepted when it passes every
+ * equation and no two columns of the labelled matrix are equal.  The call stops behind the want-th accepted attempt or after
+ * max_attempts.  want = 1 is exactly upstream's call; want = K equals K consecutive calls of upstream's as long as none of them
+ * exhausts its own budget (max_attempts is the total).  Out, HOST: hd_out [want][rh][nh] (the first *found matrices: -1 empty, else
+ * the shift), attempt_index [want] (0-based, counted over the whole call: call k of upstream's tested attempt_index[k] -
+ * attempt_index[k - 1] attempts), *found, *attempts_tested, *tree_girth, and the generator where upstream's loop leaves it: behind the
+ * last draw of the last accepted attempt, or behind all max_attempts attempts; (state_in, pos_in) unchanged, *found = 0 and
+ * *attempts_tested = 0 when *tree_girth < target_girth.  Attempts are tested in rounds that grow eight-fold from 4096
+ * (LDPC_HIP_LABEL_ROUND=n: n attempts per round, read per call); the result does not depend on the rounds.  Synchronous. */
+int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int target_girth, int M, long long max_attempts, int want,
+                         const uint32_t state_in[624], int pos_in, int device, int16_t *hd_out, long long *attempt_index, int *found,
+                         long long *attempts_tested, int *tree_girth, uint32_t state_out[624], int *pos_out);
+/* What this thread's last ldpc_hip_label_codes did: rounds, redraws among the words it consumed, equations evaluated by live lanes,
+ * attempts checked (whole rounds). */
+void ldpc_hip_label_last_stats(long long stats[4]);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

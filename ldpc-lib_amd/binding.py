@@ -225,6 +225,11 @@ def load_library():
     lib.ldpc_hip_frames_codes_gfq_noise_host.argtypes = [vp, vp, f64, i32, i32, i64, vp, vp, vp]
     lib.ldpc_hip_girth_codes.argtypes = [i32, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     lib.ldpc_hip_girth_graph_host.argtypes = [i32, i32, i32, vp, C.POINTER(i32), vp, vp, C.POINTER(i64)]
+    lib.ldpc_hip_label_equations_host.argtypes = [i32, i32, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), vp, vp, vp]
+    lib.ldpc_hip_label_codes.argtypes = [i32, i32, vp, i32, i32, i64, i32, vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), vp,
+                                         C.POINTER(i32)]
+    lib.ldpc_hip_label_last_stats.argtypes = [vp]
+    lib.ldpc_hip_label_last_stats.restype = None
     lib.ldpc_hip_trace_matrix_host.argtypes = [vp, vp, i32, C.POINTER(i32), vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
         raise LdpcHipError("libldpc_hip.so ABI version mismatch")
@@ -1333,6 +1338,53 @@ def trace_matrix(S, SA):
     _check(lib, lib.ldpc_hip_trace_matrix_host(S.ctypes.data, SA.ctypes.data, S.size, C.byref(girth), ace.ctypes.data, spec.ctypes.data),
            "ldpc_hip_trace_matrix_host")
     return girth.value, ace.tolist(), spec.tolist()
+
+
+def label_equations(proto, target_girth):
+    """The equations a labelling of the protograph [rh, nh] (0 empty, 1 random shift, other positive values shift 0) must satisfy to
+    reach target_girth, built on the host (no GPU; ldpc_hip_label_equations_host): a dict with tree_girth, n_equations, n_random,
+    never_accepts and the table eq_begin int32 [n_equations + 1], term_edge, term_mult int32 [n_terms] over the random edges."""
+    lib = load_library()
+    P = np.ascontiguousarray(proto, dtype=np.int16)
+    rh, nh = P.shape
+    tg, ne, nr, never, nt = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+    sizes = (C.byref(tg), C.byref(ne), C.byref(nr), C.byref(nt), C.byref(never))
+    _check(lib, lib.ldpc_hip_label_equations_host(rh, nh, P.ctypes.data, int(target_girth), *sizes, None, None, None), "ldpc_hip_label_equations_host")
+    begin = np.empty(ne.value + 1, dtype=np.int32)
+    edge = np.empty(nt.value, dtype=np.int32)
+    mult = np.empty(nt.value, dtype=np.int32)
+    _check(lib, lib.ldpc_hip_label_equations_host(rh, nh, P.ctypes.data, int(target_girth), *sizes, begin.ctypes.data, edge.ctypes.data, mult.ctypes.data),
+           "ldpc_hip_label_equations_host")
+    return {"tree_girth": tg.value, "n_equations": ne.value, "n_random": nr.value, "never_accepts": bool(never.value), "eq_begin": begin,
+            "term_edge": edge, "term_mult": mult}
+
+
+def label_codes(proto, target_girth, M, max_attempts, state, pos, want=1, device=0):
+    """Upstream's generate_code on the device (ldpc_hip_label_codes): labels the protograph with shifts below M until `want` labellings
+    pass the girth equations and the equal-columns test, or max_attempts are used up, drawing from the std::mt19937 (state uint32
+    [624], pos).  Returns (codes int16 [found, rh, nh], attempt_index int64 [found] -- 0-based over the whole call --, attempts_tested,
+    tree_girth, (state, pos) of the generator afterwards)."""
+    lib = load_library()
+    P = np.ascontiguousarray(proto, dtype=np.int16)
+    rh, nh = P.shape
+    st = np.ascontiguousarray(state, dtype=np.uint32)
+    assert st.shape == (624,), "state: the 624 words of std::mt19937"
+    want = int(want)
+    codes = np.zeros((max(want, 0), rh, nh), dtype=np.int16)
+    index = np.zeros(max(want, 0), dtype=np.int64)
+    out = np.zeros(624, dtype=np.uint32)
+    found, tg, pos_out, tested = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+    rc = lib.ldpc_hip_label_codes(rh, nh, P.ctypes.data, int(target_girth), int(M), int(max_attempts), want, st.ctypes.data, int(pos), int(device),
+                                  codes.ctypes.data, index.ctypes.data, C.byref(found), C.byref(tested), C.byref(tg), out.ctypes.data, C.byref(pos_out))
+    _check(lib, rc, "ldpc_hip_label_codes")
+    return codes[:found.value], index[:found.value], tested.value, tg.value, (out, pos_out.value)
+
+
+def label_last_stats():
+    """(rounds, redraws, equations evaluated by live lanes, attempts checked) of this thread's last label_codes."""
+    s = np.zeros(4, dtype=np.int64)
+    load_library().ldpc_hip_label_last_stats(s.ctypes.data)
+    return tuple(int(v) for v in s)
 
 
 def qam_modulate(bits, Q, device=0, stream=None):

@@ -39,6 +39,7 @@
 #include "ldpc_gfq_chain.hpp"
 #include "ldpc_gfq_codeset.hpp"
 #include "ldpc_girth.hpp"
+#include "ldpc_label.hpp"
 
 namespace {
 
@@ -1440,3 +1441,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_codeset_api.hpp"
 #include "ldpc_gfq_codeset_api.hpp"
 #include "ldpc_girth_api.hpp"
+#include "ldpc_label_api.hpp"
