@@ -26,6 +26,7 @@
 // 1.0 - 1.5 % slower (profiles/kernel_refactor_time.txt).
 #pragma once
 
+#include "ldpc_frontend.hpp"   // packed_word_errors, wave_sum_pair, ErrorTally
 #include "ldpc_kernels.hpp"
 #include "ldpc_spec.hpp"   // exp_glibc, iasp, lche
 
@@ -798,8 +799,8 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Error accounting against the all-zero codeword, count_errors_kernel's semantics (ldpc_frontend.hpp; bp_simulation.cpp:731-759,
-// 805-810) per code: one wavefront per (c, f); a workgroup works on one code only, so its totals go out as one atomic per counter.
+// Error accounting against the all-zero codeword per code, with the shared count of ldpc_frontend.hpp: one wavefront per (slot, frame),
+// blocks_per_code workgroups per slot; a workgroup works on one slot only, so its totals go to the row of the slot's code.
 // ---------------------------------------------------------------------------------------------------------
 struct CodesetCountArgs {
     const uint32_t *hard;          // [n_active][B][hard_words]
@@ -813,46 +814,18 @@ struct CodesetCountArgs {
 };
 
 __global__ void __launch_bounds__(256) count_errors_codes_kernel(const CodesetCountArgs a) {
-    __shared__ unsigned long long part[4][5];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int cs = blockIdx.x / a.blocks_per_code, slot = blockIdx.x - cs * a.blocks_per_code;
     const int c = a.code_list ? tab_ptr(a.code_list)[cs] : cs;
-    unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
+    ErrorTally tally;
     for (long long fr = (long long)slot * 4 + wv; fr < a.B; fr += (long long)a.blocks_per_code * 4) {
         const long long g = (long long)cs * a.B + fr;
         uint32_t all = 0, info = 0;
-        for (int w = lane; w < a.hard_words; w += 64) {
-            const uint32_t x = a.hard[g * a.hard_words + w];
-            all += __popc(x);
-            const int lo = 32 * w;   // information bits are indices >= R (bp_simulation.cpp:738)
-            uint32_t m = 0xffffffffu;
-            if (lo + 32 <= a.R) m = 0u;
-            else if (lo < a.R) m = 0xffffffffu << (a.R - lo);
-            info += __popc(x & m);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            all += __shfl_xor(all, o);
-            info += __shfl_xor(info, o);
-        }
-        if (lane == 0) {
-            const int it = a.iters[g];
-            if (a.frame_info) a.frame_info[g] = (int32_t)info | (all ? (1 << 30) : 0);
-            frames += 1;
-            sit += (unsigned long long)(it < 0 ? -it : it);
-            if (all) {
-                nse += info;
-                nde += 1;
-                if (it >= 0) nue += 1;
-            }
-        }
+        packed_word_errors(a.hard + g * a.hard_words, nullptr, a.hard_words, a.R, lane, all, info);
+        wave_sum_pair(all, info);
+        if (lane == 0) tally.add(all, info, a.iters[g], a.frame_info ? a.frame_info + g : nullptr);
     }
-    if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (t) atomicAdd(&a.counters[(size_t)c * 5 + threadIdx.x], t);
-    }
+    tally.flush(a.counters + (size_t)c * 5);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@
 //                          negated :627-628) -> inverse interleaver (:684) -> puncturing (:697-710)
 //   qam_modulate_kernel    QAM_modulator.cpp:142-194 QAM_modulator(), function level
 //   qam_demod_kernel       QAM_demodulator.cpp:99-566 Demodulate(), Q in {4,16,64,256}
-//   count_errors_kernel    bp_simulation.cpp:731-759,805-810 (against the transmitted codeword)
+//   count_errors_kernel    bp_simulation.cpp:731-759,805-810 (against the transmitted codeword), and the count that the set and
+//                          GF(q) count kernels share with it: packed_word_errors, symbol_errors, wave_sum_pair, ErrorTally
 //
 // These are streaming, HBM-bound byte/word kernels: one element (pair) per lane, coalesced 8/16-byte accesses,
 // grid-stride loops; no LDS.  Noise comes from a counter-based Philox4x32-10 generator keyed by
@@ -265,48 +266,89 @@ struct CountArgs {
     long long first_frame; // global index of frame 0: frame f carried codeword (first_frame + f) % ncw
 };
 
-// One wavefront per frame: lanes read the frame's packed words coalesced, popcount, butterfly-reduce.
-// Block totals go out as one atomic per counter per block (Guideline 12).
-__global__ void __launch_bounds__(256) count_errors_kernel(const CountArgs a) {
-    __shared__ unsigned long long part[4][5];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+// The error count of every count kernel -- this one, count_errors_codes_kernel (ldpc_codeset.hpp), gfq_count_kernel
+// (ldpc_gfq_chain.hpp) and gfq_count_codes_kernel (ldpc_gfq_codeset.hpp) -- is the code below: one wavefront per frame, workgroups
+// of four.  The lanes compare the frame's hard decisions with the word it carried (null = the all-zero word) into `all` (every
+// position) and `info` (positions >= R, the information part: bp_simulation.cpp:738 / :751), a butterfly sums the pair over the
+// wave, and lane 0 keeps the frame in an ErrorTally, which goes out as one atomic per counter per workgroup (Guideline 12).  A
+// kernel keeps only how it deals frames to waves, where a frame's row and word are, and which counter row it adds to.
+
+// binary codes: `row` and `word` are packed 32 bits to a word; decword[i] != codeword[i] (bp_simulation.cpp:735-742)
+__device__ __forceinline__ void packed_word_errors(const uint32_t *row, const uint32_t *word, int hard_words, int R, int lane, uint32_t &all,
+                                                   uint32_t &info) {
+    for (int w = lane; w < hard_words; w += 64) {
+        uint32_t x = row[w];
+        if (word) x ^= word[w];
+        all += __popc(x);
+        const int lo = 32 * w;
+        uint32_t m = 0xffffffffu;
+        if (lo + 32 <= R) m = 0u;
+        else if (lo < R) m = 0xffffffffu << (R - lo);
+        info += __popc(x & m);
+    }
+}
+
+// GF(q) codes: one int16 symbol per position (bp_simulation.cpp:746-755)
+__device__ __forceinline__ void symbol_errors(const int16_t *row, const int16_t *word, int N, int R, int lane, uint32_t &all, uint32_t &info) {
+    for (int i = lane; i < N; i += 64) {
+        const int16_t want = word ? word[i] : (int16_t)0;
+        if (row[i] != want) {   // :748
+            all += 1;
+            if (i >= R) info += 1;   // :751
+        }
+    }
+}
+
+__device__ __forceinline__ void wave_sum_pair(uint32_t &all, uint32_t &info) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        all += __shfl_xor(all, o);
+        info += __shfl_xor(info, o);
+    }
+}
+
+// What lane 0 of a wave has seen: upstream's counters (bp_simulation.cpp:799, :805-810).  iters is in -maxiter .. maxiter, so its
+// 32-bit negation is exact; the 64-bit one is five dependent instructions more per frame (profiles/frame_tally_refactor_time.txt).
+struct ErrorTally {
     unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
+
+    // one frame; frame_info (null or the frame's record) = info symbol errors | bit 30 when the frame is in error
+    __device__ __forceinline__ void add(uint32_t all, uint32_t info, int it, int32_t *frame_info) {
+        if (frame_info) *frame_info = (int32_t)info | (all ? (1 << 30) : 0);
+        frames += 1;
+        sit += (unsigned long long)(it < 0 ? -it : it);
+        if (all) {
+            nse += info;
+            nde += 1;
+            if (it >= 0) nue += 1;
+        }
+    }
+
+    // the workgroup's totals -> counters_row[5] = nse, nde, nue, frames, sum |iters|; called by every thread, once
+    __device__ __forceinline__ void flush(unsigned long long *counters_row) const {
+        __shared__ unsigned long long part[4][5];
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
+        __syncthreads();
+        if (threadIdx.x < 5) {
+            const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+            if (t) atomicAdd(&counters_row[threadIdx.x], t);
+        }
+    }
+};
+
+// frames blockIdx.x * 4 + wave, + 4 * grid, ...; frame f carried codeword (first_frame + f) % ncw
+__global__ void __launch_bounds__(256) count_errors_kernel(const CountArgs a) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    ErrorTally tally;
     for (long long fr = (long long)blockIdx.x * 4 + wv; fr < a.B; fr += (long long)gridDim.x * 4) {
         uint32_t all = 0, info = 0;
-        for (int w = lane; w < a.hard_words; w += 64) {
-            uint32_t x = a.hard[fr * a.hard_words + w];
-            if (a.cw) x ^= a.cw[(size_t)((a.first_frame + fr) % a.ncw) * a.hard_words + w];   // decword[i] != codeword[i] (:735-742)
-            all += __popc(x);
-            // information bits are indices >= R (bp_simulation.cpp:738)
-            const int lo = 32 * w;
-            uint32_t m = 0xffffffffu;
-            if (lo + 32 <= a.R) m = 0u;
-            else if (lo < a.R) m = 0xffffffffu << (a.R - lo);
-            info += __popc(x & m);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            all += __shfl_xor(all, o);
-            info += __shfl_xor(info, o);
-        }
-        if (lane == 0) {
-            const int it = a.iters[fr];
-            if (a.frame_info) a.frame_info[fr] = (int32_t)info | (all ? (1 << 30) : 0);
-            frames += 1;
-            sit += (unsigned long long)(it < 0 ? -it : it);
-            if (all) {                       // :805-810
-                nse += info;
-                nde += 1;
-                if (it >= 0) nue += 1;
-            }
-        }
+        packed_word_errors(a.hard + fr * a.hard_words, a.cw ? a.cw + (size_t)((a.first_frame + fr) % a.ncw) * a.hard_words : nullptr, a.hard_words,
+                           a.R, lane, all, info);
+        wave_sum_pair(all, info);
+        if (lane == 0) tally.add(all, info, a.iters[fr], a.frame_info ? a.frame_info + fr : nullptr);
     }
-    if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (t) atomicAdd(&a.counters[threadIdx.x], t);
-    }
+    tally.flush(a.counters);
 }
 
 // ---- integer min-sum quantiser scale ----------------------------------------------------------------------

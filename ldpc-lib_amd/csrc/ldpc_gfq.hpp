@@ -1,7 +1,9 @@
 // FHT_DEC (decoder id 6): sum-product decoding of QC-LDPC codes over GF(q), q = 2^p, with the check nodes in the Walsh-Hadamard
 // domain -- upstream's sum_prod_gfq_decod_lm (decoders.cpp:7036-7694, the SUM_PROD_GFQ_ORIG build) with map_graph (:6269-6391).
 //
-// One workgroup decodes one frame at a time, all iterations, in one launch; workgroup w takes frames w, w + grid, ...  The message
+// One workgroup decodes one frame at a time, all iterations, in one launch.  The frame is decode_frame<QL, LPC>, written once; two
+// schedulers hand it frames: gfq_kernel here (one code: workgroup w takes frames w, w + grid, ...) and gfq_codes_kernel of
+// ldpc_gfq_codeset.hpp (a set of codes: work items (code, frame), each on the Args view of its code).  The message
 // state of a frame does not fit a CU's LDS in general, so it lives in a per-workgroup slot of a workspace in global memory (L2 /
 // Infinity Cache resident for the codes this decoder is used on), laid out for the machine and not like upstream:
 //   win  [E][M][q]   upstream's fht_soft_in   (symbol -> check), edge e = row_start[j] + slot, check lane k, q values contiguous
@@ -240,69 +242,87 @@ __device__ __forceinline__ void symbol_nodes(const Args &a, const double *soft, 
     }
 }
 
+// The four arrays of a workgroup's slot of the workspace (slot_bytes), for a code with a.E edges.
+struct Slot {
+    double *win, *wout, *post;
+    int16_t *qh;
+};
+__device__ __forceinline__ Slot carve_slot(const Args &a, char *slot) {
+    return {(double *)slot, (double *)(slot + msg_bytes(a.E, a.M, a.q)), (double *)(slot + 2 * msg_bytes(a.E, a.M, a.q)),
+            (int16_t *)(slot + 2 * msg_bytes(a.E, a.M, a.q) + post_bytes(a.N, a.q))};
+}
+
+// One frame, start to end, by the whole workgroup: soft [q][N] is the frame's input, st the workgroup's slot, and the frame's results
+// go to row `item` of the outputs that a has (a.qhard, a.iters, a.post; null = not wanted).  Both schedulers -- gfq_kernel below and
+// gfq_codes_kernel (ldpc_gfq_codeset.hpp, on the view of one code of a set) -- decode through this function, which is why a code
+// gives the same bits in a set as alone.  The output addresses are formed at the end, from a and item, and the slot is carved by
+// the caller (once per launch here, once per item in a set): either one done the other way costs scalar registers through the
+// iteration loop (profiles/frame_tally_refactor_resources.txt).
 template <int QL, int LPC>
-__global__ __launch_bounds__(256) void gfq_kernel(const Args a) {
-    char *slot = a.ws + (size_t)blockIdx.x * a.ws_stride;
-    double *win = (double *)slot;
-    double *wout = (double *)(slot + msg_bytes(a.E, a.M, a.q));
-    double *post = (double *)(slot + 2 * msg_bytes(a.E, a.M, a.q));
-    int16_t *qh = (int16_t *)(slot + 2 * msg_bytes(a.E, a.M, a.q) + post_bytes(a.N, a.q));
+__device__ __forceinline__ void decode_frame(const Args &a, const double *soft, const Slot &st, size_t item) {
+    double *const win = st.win, *const wout = st.wout, *const post = st.post;
+    int16_t *const qh = st.qh;
     const int q = a.q, M = a.M, N = a.N;
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
 
-    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const double *soft = a.soft + (size_t)b * q * N;
-        // symbol -> check messages and a-posteriori vectors start as the input (:7081-7104)
-        for (int t = tid; t < a.E * M; t += nt) {
-            const int e = t / M, k = t - e * M;
-            int n = k + a.e_circ[e];
-            if (n >= M) n -= M;
-            const double *x = soft + a.e_col[e] * M + n;
-            double *v = win + (size_t)t * q;
-            for (int j = 0; j < q; ++j) v[j] = x[(size_t)j * N];
-        }
-        for (int i = tid; i < N; i += nt)
-            for (int j = 0; j < q; ++j) post[(size_t)i * q + j] = soft[(size_t)j * N + i];
-        __syncthreads();
-
-        int result = -a.maxiter;
-        for (int iter = 0; iter < a.maxiter; ++iter) {
-            for (int i = tid; i < N; i += nt) {   // hard decision: first index of the strict maximum (:7124-7143)
-                double mx = 0.0;
-                int pos = 0;
-                const double *p = post + (size_t)i * q;
-                for (int j = 0; j < q; ++j)
-                    if (mx < p[j]) { mx = p[j]; pos = j; }
-                qh[i] = (int16_t)pos;
-            }
-            __syncthreads();
-            int syn = 0;   // syndrome over GF(q) (:5695-5736)
-            for (int c = tid; c < a.R; c += nt) {
-                const int j = c / M, k = c - j * M;
-                int acc = 0;
-                for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                    int n = k + a.e_circ[e];
-                    if (n >= M) n -= M;
-                    acc ^= a.mul[(size_t)a.e_rl[e] * q + qh[a.e_col[e] * M + n]];
-                }
-                syn |= acc;
-            }
-            if (!__syncthreads_or(syn)) { result = iter; break; }
-            check_nodes<QL, LPC>(a, win, wout);
-            __syncthreads();
-            symbol_nodes(a, soft, win, wout, post);
-            __syncthreads();
-        }
-        if (tid == 0 && a.iters) a.iters[b] = result;
-        if (a.qhard)
-            for (int i = tid; i < N; i += nt) a.qhard[(size_t)b * N + i] = qh[i];
-        if (a.post) {
-            double *po = a.post + (size_t)b * q * N;
-            for (int i = tid; i < N; i += nt)
-                for (int j = 0; j < q; ++j) po[(size_t)j * N + i] = post[(size_t)i * q + j];
-        }
-        __syncthreads();   // the slot is reused by this workgroup's next frame
+    // symbol -> check messages and a-posteriori vectors start as the input (:7081-7104)
+    for (int t = tid; t < a.E * M; t += nt) {
+        const int e = t / M, k = t - e * M;
+        int n = k + a.e_circ[e];
+        if (n >= M) n -= M;
+        const double *x = soft + a.e_col[e] * M + n;
+        double *v = win + (size_t)t * q;
+        for (int j = 0; j < q; ++j) v[j] = x[(size_t)j * N];
     }
+    for (int i = tid; i < N; i += nt)
+        for (int j = 0; j < q; ++j) post[(size_t)i * q + j] = soft[(size_t)j * N + i];
+    __syncthreads();
+
+    int result = -a.maxiter;
+    for (int iter = 0; iter < a.maxiter; ++iter) {
+        for (int i = tid; i < N; i += nt) {   // hard decision: first index of the strict maximum (:7124-7143)
+            double mx = 0.0;
+            int pos = 0;
+            const double *p = post + (size_t)i * q;
+            for (int j = 0; j < q; ++j)
+                if (mx < p[j]) { mx = p[j]; pos = j; }
+            qh[i] = (int16_t)pos;
+        }
+        __syncthreads();
+        int syn = 0;   // syndrome over GF(q) (:5695-5736)
+        for (int c = tid; c < a.R; c += nt) {
+            const int j = c / M, k = c - j * M;
+            int acc = 0;
+            for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
+                int n = k + a.e_circ[e];
+                if (n >= M) n -= M;
+                acc ^= a.mul[(size_t)a.e_rl[e] * q + qh[a.e_col[e] * M + n]];
+            }
+            syn |= acc;
+        }
+        if (!__syncthreads_or(syn)) { result = iter; break; }
+        check_nodes<QL, LPC>(a, win, wout);
+        __syncthreads();
+        symbol_nodes(a, soft, win, wout, post);
+        __syncthreads();
+    }
+    if (tid == 0 && a.iters) a.iters[item] = result;
+    if (a.qhard)
+        for (int i = tid; i < N; i += nt) a.qhard[item * N + i] = qh[i];
+    if (a.post) {
+        double *po = a.post + item * q * N;
+        for (int i = tid; i < N; i += nt)
+            for (int j = 0; j < q; ++j) po[(size_t)j * N + i] = post[(size_t)i * q + j];
+    }
+    __syncthreads();   // the slot is free for the workgroup's next frame, which in a set may belong to another code
+}
+
+// The single-code scheduler: workgroup w decodes frames w, w + grid, ... in its slot.
+template <int QL, int LPC>
+__global__ __launch_bounds__(256) void gfq_kernel(const Args a) {
+    const Slot st = carve_slot(a, a.ws + (size_t)blockIdx.x * a.ws_stride);
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x)
+        decode_frame<QL, LPC>(a, a.soft + (size_t)b * a.q * a.N, st, (size_t)b);
 }
 
 #endif  // __HIPCC__

@@ -282,44 +282,19 @@ struct QCountArgs {
     int N, R;
 };
 
-// One wavefront per frame, butterfly reduction, one atomic per counter per block: the q-ary twin of ldpc::count_errors_kernel.
+// The shared count of ldpc_frontend.hpp on symbols: frames blockIdx.x * 4 + wave, + 4 * grid, ...; a frame's word is its row of
+// `codeword` (cw_stride = 0: one word for all), or the all-zero word where ok says that nothing else was sent.
 __global__ __launch_bounds__(256) void gfq_count_kernel(const QCountArgs a) {
-    __shared__ unsigned long long part[4][5];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
+    ldpc::ErrorTally tally;
     for (long long fr = (long long)blockIdx.x * 4 + wv; fr < a.B; fr += (long long)gridDim.x * 4) {
         const bool sent = a.codeword && (!a.ok || a.ok[fr]);
         uint32_t all = 0, info = 0;
-        for (int i = lane; i < a.N; i += 64) {
-            const int16_t want = sent ? a.codeword[fr * a.cw_stride + i] : (int16_t)0;
-            if (a.qhard[fr * a.N + i] != want) {   // :748
-                all += 1;
-                if (i >= a.R) info += 1;           // :751
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            all += __shfl_xor(all, o);
-            info += __shfl_xor(info, o);
-        }
-        if (lane == 0) {
-            const int it = a.iters[fr];
-            if (a.frame_info) a.frame_info[fr] = (int32_t)info | (all ? (1 << 30) : 0);
-            frames += 1;
-            sit += (unsigned long long)(it < 0 ? -(long long)it : it);
-            if (all) {                             // :805-810
-                nse += info;
-                nde += 1;
-                if (it >= 0) nue += 1;
-            }
-        }
+        ldpc::symbol_errors(a.qhard + fr * a.N, sent ? a.codeword + fr * a.cw_stride : nullptr, a.N, a.R, lane, all, info);
+        ldpc::wave_sum_pair(all, info);
+        if (lane == 0) tally.add(all, info, a.iters[fr], a.frame_info ? a.frame_info + fr : nullptr);
     }
-    if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (t) atomicAdd(&a.counters[threadIdx.x], t);
-    }
+    tally.flush(a.counters);
 }
 
 #endif  // __HIPCC__

@@ -14,10 +14,11 @@
 //     read through the constant address space, so they are scalar loads and the view of the code stays in scalar registers;
 //   * the record and a per-code soft slice follow the code; qhard, iters and post follow the slot ([n_active][B]..., which is
 //     index w itself);
-//   * a workgroup that moves on to an item of another code builds that code's view -- record, E, cw2 -- before the item's first
-//     instruction, and the barrier that ends an item stands between the two.
-// The check nodes and symbol nodes are check_nodes<QL, LPC> and symbol_nodes of ldpc_gfq.hpp on that view: the same instances, the
-// same expressions in the same order, hence bit-identical to a single-code context.
+//   * a workgroup that moves on to an item of another code builds that code's view -- record, E, cw2 -- and carves its slot by that
+//     E before the item's first instruction, and the barrier that ends an item stands between the two.
+// gfq_codes_kernel is only this scheduler.  The frame itself -- initial messages, hard decision, syndrome, check nodes, symbol nodes,
+// outputs -- is decode_frame<QL, LPC> of ldpc_gfq.hpp on that view, the function gfq_kernel calls for a single code: one statement
+// of the frame, hence bit-identical to a single-code context.
 #pragma once
 
 #include "ldpc_codeset.hpp"   // TabPtr
@@ -49,11 +50,13 @@ __host__ __device__ inline size_t record_length(int rh, int nh, int E) { return 
 
 #if defined(__HIPCC__)
 
-// The single-code argument block of code c.  Everything is a function of kernel arguments and of c, which is wave-uniform.
+// The single-code argument block of code c.  Everything is a function of kernel arguments and of c, which is wave-uniform.  The
+// outputs are the set's, rows by work item; soft stays null: the caller chooses the item's slice.
 __device__ __forceinline__ Args codes_view(const CodesArgs &s, int c) {
     const int off = ldpc::tab_ptr(s.code_off)[c];
     const ldpc::TabPtr rec = ldpc::tab_ptr(s.tab + off);
     Args a{};
+    a.qhard = s.qhard; a.iters = s.iters; a.post = s.post;
     a.E = rec[0]; a.cw2 = rec[1];
     a.row_start = s.tab + off + kRecHeader;
     a.col_start = a.row_start + s.rh + 1;
@@ -67,71 +70,16 @@ __device__ __forceinline__ Args codes_view(const CodesArgs &s, int c) {
     return a;
 }
 
+// The set scheduler: workgroup g decodes items g, g + grid, ... in its slot, each on the view of the item's code.
 template <int QL, int LPC>
 __global__ __launch_bounds__(256) void gfq_codes_kernel(const CodesArgs s) {
     char *slot = s.ws + (size_t)blockIdx.x * s.ws_stride;
-    const int q = s.q, M = s.M, N = s.N;
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-
     for (unsigned w = blockIdx.x; w < s.items; w += gridDim.x) {
         const unsigned sl = w / s.B, f = w - sl * s.B;
         const int c = s.code_list ? ldpc::tab_ptr(s.code_list)[sl] : (int)sl;
         const Args a = codes_view(s, c);
-        double *win = (double *)slot;
-        double *wout = (double *)(slot + msg_bytes(a.E, M, q));
-        double *post = (double *)(slot + 2 * msg_bytes(a.E, M, q));
-        int16_t *qh = (int16_t *)(slot + 2 * msg_bytes(a.E, M, q) + post_bytes(N, q));
-        const double *soft = s.soft + (long long)c * s.soft_code_stride + (size_t)f * q * N;
-        // from here on gfq_kernel's frame, on the view (ldpc_gfq.hpp; decoders.cpp:7081-7143, :5695-5736)
-        for (int t = tid; t < a.E * M; t += nt) {
-            const int e = t / M, k = t - e * M;
-            int n = k + a.e_circ[e];
-            if (n >= M) n -= M;
-            const double *x = soft + a.e_col[e] * M + n;
-            double *v = win + (size_t)t * q;
-            for (int j = 0; j < q; ++j) v[j] = x[(size_t)j * N];
-        }
-        for (int i = tid; i < N; i += nt)
-            for (int j = 0; j < q; ++j) post[(size_t)i * q + j] = soft[(size_t)j * N + i];
-        __syncthreads();
-
-        int result = -s.maxiter;
-        for (int iter = 0; iter < s.maxiter; ++iter) {
-            for (int i = tid; i < N; i += nt) {
-                double mx = 0.0;
-                int pos = 0;
-                const double *p = post + (size_t)i * q;
-                for (int j = 0; j < q; ++j)
-                    if (mx < p[j]) { mx = p[j]; pos = j; }
-                qh[i] = (int16_t)pos;
-            }
-            __syncthreads();
-            int syn = 0;
-            for (int r = tid; r < a.R; r += nt) {
-                const int j = r / M, k = r - j * M;
-                int acc = 0;
-                for (int e = a.row_start[j]; e < a.row_start[j + 1]; ++e) {
-                    int n = k + a.e_circ[e];
-                    if (n >= M) n -= M;
-                    acc ^= a.mul[(size_t)a.e_rl[e] * q + qh[a.e_col[e] * M + n]];
-                }
-                syn |= acc;
-            }
-            if (!__syncthreads_or(syn)) { result = iter; break; }
-            check_nodes<QL, LPC>(a, win, wout);
-            __syncthreads();
-            symbol_nodes(a, soft, win, wout, post);
-            __syncthreads();
-        }
-        if (tid == 0 && s.iters) s.iters[w] = result;
-        if (s.qhard)
-            for (int i = tid; i < N; i += nt) s.qhard[(size_t)w * N + i] = qh[i];
-        if (s.post) {
-            double *po = s.post + (size_t)w * q * N;
-            for (int i = tid; i < N; i += nt)
-                for (int j = 0; j < q; ++j) po[(size_t)j * N + i] = post[(size_t)i * q + j];
-        }
-        __syncthreads();   // the slot is reused by this workgroup's next item, which may belong to another code
+        const Slot st = carve_slot(a, slot);   // by the E of this code
+        decode_frame<QL, LPC>(a, s.soft + (long long)c * s.soft_code_stride + (size_t)f * s.q * s.N, st, w);
     }
 }
 
@@ -172,9 +120,9 @@ __global__ __launch_bounds__(256) void gfq_channel_codes_kernel(const CodesChanA
     }
 }
 
-// Symbol errors per code against the code's word (words [C][N]) or, words = null, against the all-zero word: gfq_count_kernel's
-// semantics (ldpc_gfq_chain.hpp; bp_simulation.cpp:746-755, :805-810).  One wavefront per (slot, frame); a workgroup works on one slot
-// only, so its totals go to the row of the slot's code as one atomic per counter.
+// Symbol errors per code against the code's word (words [C][N]) or, words = null, against the all-zero word, with the shared count of
+// ldpc_frontend.hpp.  One wavefront per (slot, frame), blocks_per_code workgroups per slot; a workgroup works on one slot only, so its
+// totals go to the row of the slot's code.
 struct CodesCountArgs {
     const int16_t *qhard;          // [n_active][B][N]
     const int32_t *iters;          // [n_active][B]
@@ -188,44 +136,18 @@ struct CodesCountArgs {
 };
 
 __global__ __launch_bounds__(256) void gfq_count_codes_kernel(const CodesCountArgs a) {
-    __shared__ unsigned long long part[4][5];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int cs = blockIdx.x / a.blocks_per_code, blk = blockIdx.x - cs * a.blocks_per_code;
     const int c = a.code_list ? ldpc::tab_ptr(a.code_list)[cs] : cs;
-    unsigned long long nse = 0, nde = 0, nue = 0, frames = 0, sit = 0;
+    ldpc::ErrorTally tally;
     for (long long fr = (long long)blk * 4 + wv; fr < a.B; fr += (long long)a.blocks_per_code * 4) {
         const long long g = (long long)cs * a.B + fr;
         uint32_t all = 0, info = 0;
-        for (int i = lane; i < a.N; i += 64) {
-            const int16_t want = a.words ? a.words[(size_t)c * a.N + i] : (int16_t)0;
-            if (a.qhard[g * a.N + i] != want) {   // :748
-                all += 1;
-                if (i >= a.R) info += 1;       // :751
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            all += __shfl_xor(all, o);
-            info += __shfl_xor(info, o);
-        }
-        if (lane == 0) {
-            const int it = a.iters[g];
-            if (a.frame_info) a.frame_info[g] = (int32_t)info | (all ? (1 << 30) : 0);
-            frames += 1;
-            sit += (unsigned long long)(it < 0 ? -(long long)it : it);
-            if (all) {                         // :805-810
-                nse += info;
-                nde += 1;
-                if (it >= 0) nue += 1;
-            }
-        }
+        ldpc::symbol_errors(a.qhard + g * a.N, a.words ? a.words + (size_t)c * a.N : nullptr, a.N, a.R, lane, all, info);
+        ldpc::wave_sum_pair(all, info);
+        if (lane == 0) tally.add(all, info, a.iters[g], a.frame_info ? a.frame_info + g : nullptr);
     }
-    if (lane == 0) { part[wv][0] = nse; part[wv][1] = nde; part[wv][2] = nue; part[wv][3] = frames; part[wv][4] = sit; }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (t) atomicAdd(&a.counters[(size_t)c * 5 + threadIdx.x], t);
-    }
+    tally.flush(a.counters + (size_t)c * 5);
 }
 
 #endif  // __HIPCC__
