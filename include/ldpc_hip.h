@@ -589,7 +589,8 @@ int ldpc_hip_open_codes_wide(int decoder_id, int rh, int nh, int M, const int16_
  * LDPC_HIP_IASP_DEC (5), LDPC_HIP_TASP_DEC (7), LDPC_HIP_LMS_DEC (8) or LDPC_HIP_LCHE_DEC (9); any other id is LDPC_HIP_EINVAL (Gallager
  * BP has no set: its frames are not independent).  An ordinary code-set context, served by the entry points below exactly as a
  * context of the decoder's own open entry point is (alpha, puncture fill, ldpc_hip_set_ims_params), and bit-identical to it on every
- * shape both accept, and to one ldpc_hip_open context per matrix on every shape.  Kernels: <decoder>_global_codes_kernel, one
+ * shape both accept, and to one ldpc_hip_open context per matrix on every shape.  Kernels: <decoder>_global_codes_kernel (each runs
+ * the frame body of the single code's <decoder>_global_kernel, csrc/ldpc_global.hpp, on the code's own tables), one
  * workgroup of 256 threads (1024 from N = 16384) per frame, no LDS; a work item is (code, frame), the grid is capped at 1024 workgroups
  * (halved while their workspace exceeds 8 GiB; LDPC_HIP_CODES_GLOBAL_GRID=n, read per call, caps it lower) and strides over the items.
  * The message state is in a workspace of one slice per workgroup, sized for the code with the most circulants: it grows with neither

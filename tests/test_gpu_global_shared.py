@@ -30,10 +30,10 @@ SHAPES = {
     # 2 x 5 at lifting 37: N = 185 = 5 * 32 + 25, shifts 0 and 36 = M - 1 in both block rows, block columns of weight 1 and 2
     "2x5-m37": (np.array([[0, 36, 5, _, 17],
                           [36, 0, _, 9, 20]], dtype=np.int16), 37, 4.0),
-    # decoder 5 only: "weight-2 columns, lifting 1" of tests/test_gpu_iasp.py -- upstream's own branch for such codes
+    # decoders 2 and 5 only: "weight-2 columns, lifting 1" of tests/test_gpu_iasp.py -- upstream's own branch for such codes
     "cycle-3x7-m1": (cycle_code(np.random.RandomState(912), 3, 7, 1), 1, 1.0),
 }
-CASES = [(d, s) for s in ("3x7-m1", "2x5-m37") for d in KERNEL] + [(IASP_DEC, "cycle-3x7-m1")]
+CASES = [(d, s) for s in ("3x7-m1", "2x5-m37") for d in KERNEL] + [(IASP_DEC, "cycle-3x7-m1"), (ASP_DEC, "cycle-3x7-m1")]
 REUSE_FRAMES, GRID_CAP = 1032, 1024     # launch_global caps the grid at 1024 workgroups: eight of them take a second frame
 
 

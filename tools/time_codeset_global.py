@@ -6,6 +6,8 @@ Shapes: relabelings of the 16 x 32 Appendix-C matrix (the same pattern, fresh sh
   tdmp256, tdmp512   TDMP sum-product, 15 iterations, M = 256 and M = 512
   ims256, ims512     integer min-sum, 50 iterations, M = 256 and M = 512
   ms1024             min-sum, 50 iterations, M = 1024
+  ms256, lms256, sp256, asp256, iasp256, lche256   the other decoders of the tier at M = 256, on request (--shapes): min-sum and
+                     layered min-sum 50 iterations at 2.0 dB, the sum-product family and LCHE 15 iterations at 1.7 dB
   route A  one LdpcHipCodes(dec, codes, M, tier="global").simulate call: the channel once, the set kernel over all codes, the count;
   route B  what a caller does without a set: C consecutive LdpcHip(dec).simulate calls on pre-opened contexts, JIT mode off.  The
            contexts are opened 32 at a time outside the timed region (each holds a workspace) and the times of the groups are added.
@@ -32,7 +34,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FRAMES, SEED, GROUP = 4096, 1, 32
 # shape -> (decoder id, name, M, iterations, SNR in dB)
 SHAPES = {"tdmp256": (7, "TDMP", 256, 15, 1.7), "tdmp512": (7, "TDMP", 512, 15, 1.7), "ims256": (4, "IMS", 256, 50, 2.0),
-          "ims512": (4, "IMS", 512, 50, 2.0), "ms1024": (3, "MS", 1024, 50, 2.0)}
+          "ims512": (4, "IMS", 512, 50, 2.0), "ms1024": (3, "MS", 1024, 50, 2.0),
+          # the other decoders of the tier at M = 256 (profiles/global_frame_refactor_time.txt); not part of the default run
+          "ms256": (3, "MS", 256, 50, 2.0), "lms256": (8, "LMS", 256, 50, 2.0), "sp256": (1, "SP", 256, 15, 1.7),
+          "asp256": (2, "ASP", 256, 15, 1.7), "iasp256": (5, "IASP", 256, 15, 1.7), "lche256": (9, "LCHE", 256, 15, 1.7)}
+DEFAULT_SHAPES = "tdmp256,tdmp512,ims256,ims512,ms1024"
 
 
 def relabel(base, M, rng):
@@ -55,7 +61,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r29_codeset_global_time.txt"))
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sizes", default="1,16,256")
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--shapes", default=DEFAULT_SHAPES)
     ap.add_argument("--force-global-b", action="store_true", help="route B opens with LDPC_HIP_FORCE_GLOBAL=1: the single-code global tier on every shape")
     ap.add_argument("--append", action="store_true", help="keep what --out already holds")
     a = ap.parse_args()
