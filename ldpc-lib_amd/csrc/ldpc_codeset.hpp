@@ -18,12 +18,13 @@
 // ldpc_spec::lche; IMS: integers behind a quantiser that runs once per received word); only the frame index and the table base differ
 // (and, for TDMP, IASP, LCHE and IMS, where the state lives), so the results are bit-identical to a single-code context.
 // The two flooding sum-product decoders (ids 1 and 2) deal a frame over several waves and live in ldpc_codeset_sp.hpp.
-// Structure: the min-sum, layered min-sum, IASP and integer min-sum set kernels are codeset_view, their own state and arithmetic, and the
-// pieces that ldpc_kernels.hpp holds once for every frame-resident kernel -- frame_lane, edge_idx, row_syndrome, stop_vote / stop_all,
-// frame_outputs.  The flooding min-sum kernel is nothing but the view and ms_flood_body.  Where a shared piece cost registers or time its
-// kernel kept its own: iasp_codes_kernel writes its outputs itself (the reason stands in the kernel), lms_layered_codes_kernel has its own
-// syndrome and edge decode, and tasp_layered_codes_kernel and lche_layered_codes_kernel use none of the pieces: with them they were 0.7 % and
-// 1.0 - 1.5 % slower (profiles/kernel_refactor_time.txt).
+// Structure: the flooding and the layered min-sum set kernels are nothing but codeset_view and the body their single-code kernel runs
+// (ms_flood_body, lms_layered_body).  The IASP and integer min-sum set kernels are codeset_view, their own state, and the pieces that
+// ldpc_kernels.hpp holds once for every frame-resident kernel -- frame_lane, edge_idx, row_syndrome, stop_vote / stop_all, frame_outputs;
+// the integer min-sum kernel calls ims_flood_kernel's row passes (ims_row_add, ims_row_scan) on its halfword image.  Where a shared piece
+// cost registers or time its kernel kept its own: iasp_codes_kernel writes its outputs itself (the reason stands in the kernel),
+// lms_layered_body has its own syndrome, and tasp_layered_codes_kernel and lche_layered_codes_kernel use none of the pieces: with them
+// they were 0.7 % and 1.0 - 1.5 % slower (profiles/kernel_refactor_time.txt).
 #pragma once
 
 #include "ldpc_frontend.hpp"   // packed_word_errors, wave_sum_pair, ErrorTally
@@ -85,104 +86,14 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_codes_kernel(const Cod
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Layered offset min-sum: lms_layered_kernel's arithmetic (ldpc_kernels.hpp; decoders.cpp:5064-5425) on work item (c, w).
-// One difference in form, none in values: lms_layered_kernel keeps the v2c values and LDS addresses of a layer in tv[16] / addr[16]
-// between the layer's two passes, with both passes unrolled 16 times; the block-row loop around them then is too large to unroll,
-// m1 / m2 / meta are indexed at run time and live in scratch memory (272 bytes per lane).  Here the second pass reads the
-// a-posteriori value again and repeats the subtraction, the passes are run-time loops over the row's edges as in the flooding
-// kernel, the block-row loop unrolls, and the per-row records stay in VGPRs: no scratch.
+// Layered offset min-sum: lms_layered_kernel's body (ldpc_kernels.hpp; decoders.cpp:5064-5425) on work item (c, w)
 // ---------------------------------------------------------------------------------------------------------
 template <int RHM, bool MW>
 __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_codes_kernel(const CodesetArgs s) {
     extern __shared__ double lds[];
     int w;
     const DecArgs a = codeset_view(s, w);
-    const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
-    const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
-    int *const sh_flag = (int *)(lds + (size_t)N * F);
-    const double beta = 0.4;
-    const Lane l = frame_lane<MW>(F, M, a.B, w);
-    const int n = l.n, f = l.f;
-    const bool valid = l.valid;
-
-    if (valid) {
-        for (int k = 0; k < nh; ++k)
-            lds[(k * M + n) * F + f] = l.live ? a.llr[l.fr * N + k * M + n] + 0.0 : 0.0;
-    }
-    double m1[RHM], m2[RHM];
-    uint32_t meta[RHM];
-#pragma unroll
-    for (int j = 0; j < RHM; ++j) { m1[j] = 0.0; m2[j] = 0.0; meta[j] = 0u; }
-    if (MW) __syncthreads();
-
-    auto syndrome_fail = [&]() -> bool {
-        uint32_t failw = 0;
-        for (int j = 0; j < rh; ++j) {
-            const int e0 = rs[j], e1 = rs[j + 1];
-            uint32_t sy = 0;
-            for (int e = e0; e < e1; ++e) {
-                const uint32_t d = (uint32_t)ed[e];
-                const int k = d >> 16, c = d & 0xffffu;
-                sy ^= hi32(lds[(k * M + rot_idx(n, c, M)) * F + f]);
-            }
-            failw |= sy;
-        }
-        return valid && (failw >> 31);
-    };
-
-    FrameStop st = stop_init(l, a.maxiter);
-    stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, 1);
-    const bool at_entry = st.done && l.inb;   // no layer ran: upstream's soft[] is y itself, -0.0 included
-    for (int iter = 0; iter < a.maxiter; ++iter) {
-        if (stop_all<MW>(st)) break;
-        const bool wr = !st.done && valid;
-#pragma unroll
-        for (int j = 0; j < RHM; ++j) {
-            if (j < rh) {
-                const int e0 = rs[j], rw = rs[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                double nm1 = kMaxVal, nm2 = kMaxVal;
-                uint32_t npos = 0, nS = 0;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = (uint32_t)ed[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const double r = lds[(k * M + rot_idx(n, c, M)) * F + f];
-                    const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    const double pc = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                    const double t = r - pc;
-                    nS |= (hi32(t) >> 31) << idx;   // sign kept even when the magnitude clips to 0
-                    double mag = fabs(t) - beta;
-                    mag = mag < 0 ? 0 : mag;
-                    const bool c1 = mag < nm1;
-                    nm2 = fmin(fmax(mag, nm1), nm2);
-                    npos = c1 ? (uint32_t)idx : npos;
-                    nm1 = fmin(mag, nm1);
-                }
-                const uint32_t npar = __popc(nS) & 1u;
-                // second pass: v2c = soft - old c2v once more (same operands, same rounding) instead of 16 values and addresses
-                // held per layer -- see the note above the kernel.  No variable of the layer has been written yet: a lane writes
-                // only the variable it has just read, and the block columns of a row are distinct.
-                for (int idx = 0; idx < rw; ++idx) {
-                    const uint32_t d = (uint32_t)ed[e0 + idx];
-                    const int k = d >> 16, c = d & 0xffffu;
-                    const int addr = (k * M + rot_idx(n, c, M)) * F + f;
-                    const double ao = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    const double t = lds[addr] - flip_if(ao, ((mt >> idx) ^ par) & 1u);
-                    const double aa = (npos == (uint32_t)idx) ? nm2 : nm1;
-                    const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
-                    if (wr) lds[addr] = t + cv;
-                }
-                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
-                if (MW) __syncthreads();
-            }
-        }
-        stop_vote<MW>(st, syndrome_fail(), l, F, sh_flag, iter + 1);
-    }
-    write_outputs(a, lds, l, st.res);
-    if (l.live && at_entry && a.soft_out)
-        for (int k = 0; k < a.nh; ++k) a.soft_out[l.fr * N + k * M + n] = a.llr[l.fr * N + k * M + n];
+    lms_layered_body<RHM, MW>(a, lds, w, tab_ptr(a.row_start), tab_ptr(a.edges));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -730,7 +641,6 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
     const Lane l = frame_lane<MW>(F, M, a.B, w);
     const int n = l.n, f = l.f;
     const bool valid = l.valid;
-    auto sat = [&](int x) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); };  // limit_val :4308
 
     if (valid) {
         const int16_t *const qf = q.q + (a.llr - s.llr) + (l.inb ? l.fr : 0) * (long long)N;   // the code's slice, as for the LLRs
@@ -744,53 +654,29 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_codes_kernel(const Co
         if (wr)
             for (int k = 0; k < nh; ++k) soft[(k * M + n) * F + f] = 0;
         if (MW) __syncthreads();
-        for (int j = 0; j < rh; ++j) {   // STATE1 :5540-5576
+        for (int j = 0; j < rh; ++j) {   // STATE1
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             const uint2 rc = rec[(j * M + n) * F + f];
-            const uint32_t mt = rc.y;
-            const uint32_t par = __popc(mt & 0xffffu) & 1u;
-            const uint32_t pos = mt >> kRowBits;
             const int c1 = ((int)(rc.x & 0xffffu) * ialpha) >> 4, c2 = ((int)(rc.x >> 16) * ialpha) >> 4;
-            for (int idx = 0; idx < rw; ++idx) {
-                const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
-                const int tmp = (pos == (uint32_t)idx) ? c2 : c1;
-                const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
-                if (wr) soft[addr] = (int16_t)sat((int)soft[addr] + cv);
-            }
+            ims_row_add(ed, e0, rw, RowRec<int>{c1, c2, rc.y, 0u}, wr, soft, max_data, l, M, F);
             if (MW) __syncthreads();     // the next block row adds into the same variables
         }
         if (wr) {                        // STATE2 :5579-5604
             for (int k = 0; k < nh; ++k) {
                 const int o = (k * M + n) * F + f;
-                soft[o] = (int16_t)sat((int)iy[o] + (int)soft[o]);
+                soft[o] = (int16_t)ims_sat((int)iy[o] + (int)soft[o], max_data);
             }
         }
         if (MW) __syncthreads();
         uint32_t failw = 0;
-        for (int j = 0; j < rh; ++j) {   // STATE3 :5610-5678
+        for (int j = 0; j < rh; ++j) {   // STATE3
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             const int ri = (j * M + n) * F + f;
             const uint2 rc = rec[ri];
-            const uint32_t mt = rc.y;
-            const uint32_t par = __popc(mt & 0xffffu) & 1u;
-            const uint32_t pos = mt >> kRowBits;
             const int c1 = ((int)(rc.x & 0xffffu) * ialpha) >> 4, c2 = ((int)(rc.x >> 16) * ialpha) >> 4;
-            int nm1 = max_data, nm2 = max_data;
-            uint32_t npos = 0, nS = 0, sy = 0;
-            for (int idx = 0; idx < rw; ++idx) {
-                const int r = soft[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
-                sy ^= (uint32_t)r;
-                const int val = (pos == (uint32_t)idx) ? c2 : c1;
-                const int t = (((mt >> idx) ^ par) & 1u) ? -val : val;
-                const int msg = r - t;
-                nS |= ((uint32_t)msg >> 31) << idx;
-                int v = msg < 0 ? -msg : msg;
-                v = v > max_data ? max_data : v;
-                if (v < nm1) { npos = idx; nm2 = nm1; nm1 = v; }
-                else if (v < nm2) nm2 = v;
-            }
-            failw |= sy;
-            if (wr) rec[ri] = make_uint2((uint32_t)nm1 | ((uint32_t)nm2 << 16), nS | (npos << kRowBits));
+            const RowRec<int> nr = ims_row_scan(ed, e0, rw, RowRec<int>{c1, c2, rc.y, 0u}, soft, max_data, l, M, F);
+            failw |= nr.sy;
+            if (wr) rec[ri] = make_uint2((uint32_t)nr.m1 | ((uint32_t)nr.m2 << 16), nr.meta);
         }
         stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :5684-5689
         if (stop_all<MW>(st)) break;

@@ -2,7 +2,8 @@
 //
 // ms_flood_codes_kernel and lms_layered_codes_kernel (ldpc_codeset.hpp) keep the per-check records m1 / m2 / meta of all block rows in
 // VGPRs under an unrolled block-row loop (16 rows), and the flooding kernel the channel LLRs of 32 block columns.  The kernels here
-// compute the same values with the records in LDS, so every loop over block rows or block columns is a run-time loop:
+// call the same row passes (ms_row_add, ms_row_scan, lms_row_layer) with the records in LDS, so every loop over block rows or block
+// columns is a run-time loop:
 //   * soft[N][F] fp64 at the front of the image, as in the register-resident kernels (write_outputs reads it there);
 //   * m1[R][F], m2[R][F] fp64 and meta[R][F], R = rh * M: the record of check n of block row j is entry (j * M + n) * F + f of each
 //     array, so consecutive lanes touch consecutive words.  meta is the u32 of the registers ([15:0] sign bit of the row's idx-th v2c
@@ -46,8 +47,9 @@ __device__ __forceinline__ WideRecords wide_records(double *lds, int F, int N, i
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Flooding normalised min-sum: ms_flood_body's values (ldpc_kernels.hpp; decoders.cpp:4554-4767) on work item (c, w) -- the same
-// expressions in the same operand order, kMaxVal clamp, strict < for the min1 slot, two roundings in STATE2.
+// Flooding normalised min-sum (decoders.cpp:4554-4767) on work item (c, w): ms_flood_body's frame (ldpc_kernels.hpp) around the same
+// two row passes, ms_row_add and ms_row_scan, with the records read from and stored to LDS under wr and the channel value of
+// STATE2 (two roundings) read from memory.
 // ---------------------------------------------------------------------------------------------------------
 template <bool MW>
 __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_wide_codes_kernel(const CodesetArgs s) {
@@ -79,16 +81,7 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_wide_codes_kernel(cons
         for (int j = 0; j < rh; ++j) {
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             const int ri = (j * M + n) * F + f;
-            const double m1 = rec.m1[ri], m2 = rec.m2[ri];
-            const uint32_t mt = rec.meta[ri].x;
-            const uint32_t par = __popc(mt & 0xffffu) & 1u;  // row sign = xor of the row's edge signs
-            const uint32_t pos = mt >> kRowBits;
-            for (int idx = 0; idx < rw; ++idx) {
-                const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
-                const double aa = (pos == (uint32_t)idx) ? m2 : m1;
-                const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                if (wr) lds[addr] = lds[addr] + cv;
-            }
+            ms_row_add(ed, e0, rw, RowRec<double>{rec.m1[ri], rec.m2[ri], rec.meta[ri].x, 0u}, wr, lds, l, M, F);
             if (MW) __syncthreads();  // the next block row adds into the same variables
         }
         // ---- STATE2 (:4670-4685): multiply, then add -- two roundings (no FMA); the channel value from memory, canonicalised
@@ -107,27 +100,9 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_wide_codes_kernel(cons
         for (int j = 0; j < rh; ++j) {
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             const int ri = (j * M + n) * F + f;
-            const uint32_t mt = rec.meta[ri].x;
-            const uint32_t par = __popc(mt & 0xffffu) & 1u;
-            const uint32_t pos = mt >> kRowBits;
-            const double a1 = rec.m1[ri] * alpha, a2 = rec.m2[ri] * alpha;
-            double nm1 = kMaxVal, nm2 = kMaxVal;
-            uint32_t npos = 0, nS = 0, sy = 0;
-            for (int idx = 0; idx < rw; ++idx) {
-                const double r = lds[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
-                sy ^= hi32(r);
-                const double aa = (pos == (uint32_t)idx) ? a2 : a1;
-                const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                const double t = r - x;                       // v2c
-                nS |= (hi32(t) >> 31) << idx;
-                const double v = fmin(fabs(t), kMaxVal);      // :4729-4730
-                const bool c1 = v < nm1;                      // strict: first minimum keeps the position
-                nm2 = fmin(fmax(v, nm1), nm2);                // = c1 ? nm1 : min(v, nm2)
-                npos = c1 ? (uint32_t)idx : npos;
-                nm1 = fmin(v, nm1);
-            }
-            failw |= sy;
-            if (wr) { rec.m1[ri] = nm1; rec.m2[ri] = nm2; rec.meta[ri] = make_uint2(nS | (npos << kRowBits), 0u); }
+            const RowRec<double> nr = ms_row_scan(ed, e0, rw, RowRec<double>{rec.m1[ri] * alpha, rec.m2[ri] * alpha, rec.meta[ri].x, 0u}, lds, l, M, F);
+            failw |= nr.sy;
+            if (wr) { rec.m1[ri] = nr.m1; rec.m2[ri] = nr.m2; rec.meta[ri] = make_uint2(nr.meta, 0u); }
         }
         stop_vote<MW>(st, valid && (failw >> 31), l, F, rec.sh_flag, iter + 1);  // :4761-4766
         if (stop_all<MW>(st)) break;
@@ -136,9 +111,9 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_wide_codes_kernel(cons
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Layered offset min-sum: lms_layered_codes_kernel's values (ldpc_codeset.hpp; decoders.cpp:5064-5425) on work item (c, w): two
-// run-time passes per layer, the second repeating the subtraction; beta = 0.4; result 1 at entry, then iter + 1; the soft output is
-// the LLR itself, -0.0 included, when no layer ran.
+// Layered offset min-sum (decoders.cpp:5064-5425) on work item (c, w): lms_layered_body's frame (ldpc_kernels.hpp) around the same
+// lms_row_layer, one call per layer, with the records read from and stored to LDS under wr; result 1 at entry, then iter + 1; the
+// soft output is the LLR itself, -0.0 included, when no layer ran.
 // ---------------------------------------------------------------------------------------------------------
 template <bool MW>
 __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_wide_codes_kernel(const CodesetArgs s) {
@@ -148,7 +123,6 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_wide_codes_kernel(c
     const TabPtr rs = tab_ptr(a.row_start), ed = tab_ptr(a.edges);
     const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
     const WideRecords rec = wide_records(lds, F, N, rh * M);
-    const double beta = 0.4;
     const Lane l = frame_lane<MW>(F, M, a.B, w);
     const int n = l.n, f = l.f;
     const bool valid = l.valid;
@@ -176,37 +150,8 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_wide_codes_kernel(c
         for (int j = 0; j < rh; ++j) {
             const int e0 = rs[j], rw = rs[j + 1] - e0;
             const int ri = (j * M + n) * F + f;
-            const double m1 = rec.m1[ri], m2 = rec.m2[ri];
-            const uint32_t mt = rec.meta[ri].x;
-            const uint32_t par = __popc(mt & 0xffffu) & 1u;
-            const uint32_t pos = mt >> kRowBits;
-            double nm1 = kMaxVal, nm2 = kMaxVal;
-            uint32_t npos = 0, nS = 0;
-            for (int idx = 0; idx < rw; ++idx) {
-                const double r = lds[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
-                const double aa = (pos == (uint32_t)idx) ? m2 : m1;
-                const double pc = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                const double t = r - pc;
-                nS |= (hi32(t) >> 31) << idx;   // sign kept even when the magnitude clips to 0
-                double mag = fabs(t) - beta;
-                mag = mag < 0 ? 0 : mag;
-                const bool c1 = mag < nm1;
-                nm2 = fmin(fmax(mag, nm1), nm2);
-                npos = c1 ? (uint32_t)idx : npos;
-                nm1 = fmin(mag, nm1);
-            }
-            const uint32_t npar = __popc(nS) & 1u;
-            // second pass: v2c = soft - old c2v once more (same operands, same rounding).  No variable of the layer has been written
-            // yet: a lane writes only the variable it has just read, and the block columns of a row are distinct.
-            for (int idx = 0; idx < rw; ++idx) {
-                const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
-                const double ao = (pos == (uint32_t)idx) ? m2 : m1;
-                const double t = lds[addr] - flip_if(ao, ((mt >> idx) ^ par) & 1u);
-                const double aa = (npos == (uint32_t)idx) ? nm2 : nm1;
-                const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
-                if (wr) lds[addr] = t + cv;
-            }
-            if (wr) { rec.m1[ri] = nm1; rec.m2[ri] = nm2; rec.meta[ri] = make_uint2(nS | (npos << kRowBits), 0u); }
+            const RowRec<double> nr = lms_row_layer(ed, e0, rw, RowRec<double>{rec.m1[ri], rec.m2[ri], rec.meta[ri].x, 0u}, wr, lds, l, M, F);
+            if (wr) { rec.m1[ri] = nr.m1; rec.m2[ri] = nr.m2; rec.meta[ri] = make_uint2(nr.meta, 0u); }
             if (MW) __syncthreads();   // the next layer reads what this one wrote
         }
         stop_vote<MW>(st, syndrome_fail(), l, F, rec.sh_flag, iter + 1);

@@ -210,7 +210,7 @@ const decoder_kind decoder_kinds[] = {
     {LDPC_HIP_IMS_DEC, ldpc::ims_global_kernel, "ims_global_kernel", 0, false, LDPC_PAIR(ims_flood_kernel, kRHM, kNHM), true, false, 0.5, false, nullptr, false},
     {LDPC_HIP_IASP_DEC, ldpc::iasp_global_kernel, "iasp_global_kernel", 1, true, nullptr, nullptr, nullptr, false, false, 0.0, false, iasp_channel_prior_kernel, false},
     {LDPC_HIP_TASP_DEC, ldpc::tasp_global_kernel, "tasp_global_kernel", 4, true, nullptr, nullptr, nullptr, false, false, 0.0, false, channel_prior_kernel, true},
-    {LDPC_HIP_LMS_DEC, ldpc::lms_global_kernel, "lms_global_kernel", 1, false, LDPC_PAIR(lms_layered_kernel, kRHM, kRWM), false, true, 0.5, false, nullptr, false},
+    {LDPC_HIP_LMS_DEC, ldpc::lms_global_kernel, "lms_global_kernel", 1, false, LDPC_PAIR(lms_layered_kernel, kRHM), false, true, 0.5, false, nullptr, false},
     {LDPC_HIP_LCHE_DEC, ldpc::lche_global_kernel, "lche_global_kernel", 1, false, nullptr, nullptr, nullptr, false, false, 0.0, false, nullptr, true},
 };
 #undef LDPC_PAIR

@@ -30,6 +30,14 @@
 // vote stores, the conversion of the soft value -- arrives as a functor or a value.  The functors capture their
 // LDS pointer by value ([=]): captured by reference it sits in a stack slot until the functor is inlined, and the
 // register allocation of the whole kernel moves (profiles/kernel_refactor_resources.txt).
+//
+// The reference-exact arithmetic of the min-sum family is written once per decoder as well, as the work of one lane
+// on one block row: ms_row_add / ms_row_scan (flooding, STATE1 / STATE3), lms_row_layer (both passes of a layer),
+// ims_row_add / ims_row_scan (integer, templated on the LDS word).  Every LDS-tier kernel of the family -- this file,
+// ldpc_codeset.hpp, ldpc_codeset_wide.hpp -- calls them from its own block-row loop (unrolled over VGPR records, or
+// run-time over LDS records) and stores the returned record (RowRec) under its own condition.  Records go in and
+// come out as values; the edge table is a template parameter (plain pointer or TabPtr), handed over with the row's
+// first edge as an index, as the kernels addressed it before (profiles/lds_minsum_rows_resources.txt).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -199,6 +207,17 @@ __device__ __forceinline__ void write_outputs(const DecArgs &a, const double *ld
     frame_outputs(a, a.F, l, res, [=](int i) { return hi32(lds[i]) >> 31; }, [=](int i) { return lds[i]; });
 }
 
+// The min-sum record of one check row, as the row passes below take and return it: the two smallest magnitudes and
+// meta = [15:0] v2c sign bit of the row's idx-th edge, [23:16] idx of the min1 edge.  sy is set by the flooding row
+// scans only: the xor over the row's edges of the a-posteriori word.  Where a kernel keeps its records (VGPRs under an
+// unrolled block-row loop, LDS words under a run-time loop, packed halfwords) is its own business; the passes get and
+// give values, never a reference to a kernel's locals (profiles/lds_minsum_rows_resources.txt).
+template <class T>
+struct RowRec {
+    T m1, m2;
+    uint32_t meta, sy;
+};
+
 // ---------------------------------------------------------------------------------------------------------
 // Flooding normalised min-sum  (min_sum_decod_qc_lm, decoders.cpp:4554-4767; semantics SURVEY Appendix A.1)
 //
@@ -210,7 +229,48 @@ __device__ __forceinline__ void write_outputs(const DecArgs &a, const double *ld
 //
 // The body serves ms_flood_kernel (work item blockIdx.x, the graph through plain global pointers) and
 // ms_flood_codes_kernel (ldpc_codeset.hpp: work item w of a code, the graph through the constant address space).
+// The two row passes below are the arithmetic of one block row for one lane; ms_flood_body calls them with its records in VGPRs,
+// ms_flood_wide_codes_kernel (ldpc_codeset_wide.hpp) with its records in LDS.
 // ---------------------------------------------------------------------------------------------------------
+// STATE1 of a row: add the c2v value of each of the row's rw edges ed[e0 .. e0 + rw) into lds
+template <class Edges>
+__device__ __forceinline__ void ms_row_add(Edges ed, int e0, int rw, RowRec<double> o, bool wr, double *lds, Lane l, int M, int F) {
+    const uint32_t mt = o.meta;
+    const uint32_t par = __popc(mt & 0xffffu) & 1u;  // row sign = xor of the row's edge signs
+    const uint32_t pos = mt >> kRowBits;
+    for (int idx = 0; idx < rw; ++idx) {
+        const int addr = edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f);
+        const double aa = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+        if (wr) lds[addr] = lds[addr] + cv;
+    }
+}
+
+// STATE3 of a row: the new record from v2c = soft - old c2v, o = the old record with m1 and m2 already multiplied by alpha;
+// sy = the xor of the row's a-posteriori words (the sign bit is the syndrome)
+template <class Edges>
+__device__ __forceinline__ RowRec<double> ms_row_scan(Edges ed, int e0, int rw, RowRec<double> o, const double *lds, Lane l, int M, int F) {
+    const uint32_t mt = o.meta;
+    const uint32_t par = __popc(mt & 0xffffu) & 1u;
+    const uint32_t pos = mt >> kRowBits;
+    double nm1 = kMaxVal, nm2 = kMaxVal;
+    uint32_t npos = 0, nS = 0, sy = 0;
+    for (int idx = 0; idx < rw; ++idx) {
+        const double r = lds[edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f)];
+        sy ^= hi32(r);
+        const double aa = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+        const double t = r - x;                       // v2c
+        nS |= (hi32(t) >> 31) << idx;
+        const double v = fmin(fabs(t), kMaxVal);      // :4729-4730
+        const bool c1 = v < nm1;                      // strict: first minimum keeps the position
+        nm2 = fmin(fmax(v, nm1), nm2);                // = c1 ? nm1 : min(v, nm2)
+        npos = c1 ? (uint32_t)idx : npos;
+        nm1 = fmin(v, nm1);
+    }
+    return RowRec<double>{nm1, nm2, nS | (npos << kRowBits), sy};
+}
+
 template <int RHM, int NHM, bool MW, class RowStart, class Edges>
 __device__ __forceinline__ void ms_flood_body(const DecArgs &a, double *lds, int w, RowStart rs, Edges ed) {
     // lds: [N][F] soft / acc, then one flag word (kept behind, so the base stays aligned)
@@ -244,15 +304,7 @@ __device__ __forceinline__ void ms_flood_body(const DecArgs &a, double *lds, int
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
                 const int e0 = rs[j], rw = rs[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;  // row sign = xor of the row's edge signs
-                const uint32_t pos = mt >> kRowBits;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const int addr = edge_idx((uint32_t)ed[e0 + idx], n, M, F, f);
-                    const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    const double cv = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                    if (wr) lds[addr] = lds[addr] + cv;
-                }
+                ms_row_add(ed, e0, rw, RowRec<double>{m1[j], m2[j], meta[j], 0u}, wr, lds, l, M, F);
                 if (MW) __syncthreads();  // the next block row adds into the same variables
             }
         }
@@ -274,27 +326,9 @@ __device__ __forceinline__ void ms_flood_body(const DecArgs &a, double *lds, int
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
                 const int e0 = rs[j], rw = rs[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                const double a1 = m1[j] * alpha, a2 = m2[j] * alpha;
-                double nm1 = kMaxVal, nm2 = kMaxVal;
-                uint32_t npos = 0, nS = 0, sy = 0;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const double r = lds[edge_idx((uint32_t)ed[e0 + idx], n, M, F, f)];
-                    sy ^= hi32(r);
-                    const double aa = (pos == (uint32_t)idx) ? a2 : a1;
-                    const double x = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                    const double t = r - x;                       // v2c
-                    nS |= (hi32(t) >> 31) << idx;
-                    const double v = fmin(fabs(t), kMaxVal);      // :4729-4730
-                    const bool c1 = v < nm1;                      // strict: first minimum keeps the position
-                    nm2 = fmin(fmax(v, nm1), nm2);                // = c1 ? nm1 : min(v, nm2)
-                    npos = c1 ? (uint32_t)idx : npos;
-                    nm1 = fmin(v, nm1);
-                }
-                failw |= sy;
-                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                const RowRec<double> nr = ms_row_scan(ed, e0, rw, RowRec<double>{m1[j] * alpha, m2[j] * alpha, meta[j], 0u}, lds, l, M, F);
+                failw |= nr.sy;
+                if (!st.done) { m1[j] = nr.m1; m2[j] = nr.m2; meta[j] = nr.meta; }
             }
         }
         stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :4761-4766
@@ -313,15 +347,56 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ms_flood_kernel(const DecArgs a
 // Layered offset min-sum  (lmin_sum_decod_qc_lm, decoders.cpp:5064-5425, active branch :5106-5290 with
 // MY_VERSION; semantics SURVEY Appendix A.3).  Block rows (layers) are strictly sequential; inside a layer
 // every variable is touched by exactly one check, so the layer needs no synchronisation of its own.
-// RWM = compile-time bound on the row weight: the v2c values of a layer stay in VGPRs between its two passes.
+//
+// lms_row_layer is one layer for one lane.  Its two passes are run-time loops over the row's edges; nothing but the
+// new record is carried from the first to the second, which reads the a-posteriori value again and repeats the
+// subtraction (same operands, same rounding).  No variable of the layer has been written by then: a lane writes only
+// the variable it has just read, and the block columns of a row are distinct.  The caller stores the record under
+// its own condition.  Callers: lms_layered_body (records in VGPRs) and lms_layered_wide_codes_kernel
+// (ldpc_codeset_wide.hpp, records in LDS).
 // ---------------------------------------------------------------------------------------------------------
-template <int RHM, int RWM, bool MW>
-__global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArgs a) {
-    extern __shared__ double lds[];
+template <class Edges>
+__device__ __forceinline__ RowRec<double> lms_row_layer(Edges ed, int e0, int rw, RowRec<double> o, bool wr, double *lds, Lane l, int M, int F) {
+    const double beta = 0.4;  // :5163 (the alpha/beta arguments are dead upstream)
+    const uint32_t mt = o.meta;
+    const uint32_t par = __popc(mt & 0xffffu) & 1u;
+    const uint32_t pos = mt >> kRowBits;
+    double nm1 = kMaxVal, nm2 = kMaxVal;  // :5133-5134
+    uint32_t npos = 0, nS = 0;
+    for (int idx = 0; idx < rw; ++idx) {  // :5141-5177
+        const double r = lds[edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f)];
+        const double aa = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const double pc = flip_if(aa, ((mt >> idx) ^ par) & 1u);
+        const double t = r - pc;
+        nS |= (hi32(t) >> 31) << idx;   // sign kept even when the magnitude clips to 0 (:5164-5168)
+        double mag = fabs(t) - beta;
+        mag = mag < 0 ? 0 : mag;
+        const bool c1 = mag < nm1;      // process_check_node :5012-5027
+        nm2 = fmin(fmax(mag, nm1), nm2);
+        npos = c1 ? (uint32_t)idx : npos;
+        nm1 = fmin(mag, nm1);
+    }
+    const uint32_t npar = __popc(nS) & 1u;
+    for (int idx = 0; idx < rw; ++idx) {  // :5182-5206
+        const int addr = edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f);
+        const double ao = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const double t = lds[addr] - flip_if(ao, ((mt >> idx) ^ par) & 1u);
+        const double aa = (npos == (uint32_t)idx) ? nm2 : nm1;
+        const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
+        if (wr) lds[addr] = t + cv;
+    }
+    return RowRec<double>{nm1, nm2, nS | (npos << kRowBits), 0u};
+}
+
+// The body serves lms_layered_kernel (work item blockIdx.x, plain global pointers) and lms_layered_codes_kernel
+// (ldpc_codeset.hpp: work item w of a code, the constant address space).  The block-row loop unrolls RHM times and the
+// per-row records stay in VGPRs: no scratch.  The syndrome is written out here; with row_syndrome the set kernel
+// measured slower (profiles/kernel_refactor_time.txt).
+template <int RHM, bool MW, class RowStart, class Edges>
+__device__ __forceinline__ void lms_layered_body(const DecArgs &a, double *lds, int w, RowStart rs, Edges ed) {
     const int M = a.M, F = a.F, N = a.N, rh = a.rh, nh = a.nh;
     int *const sh_flag = (int *)(lds + (size_t)N * F);
-    const double beta = 0.4;  // :5163 (the alpha/beta arguments are dead upstream)
-    const Lane l = frame_lane<MW>(F, M, a.B, blockIdx.x);
+    const Lane l = frame_lane<MW>(F, M, a.B, w);
     const int n = l.n, f = l.f;
     const bool valid = l.valid;
 
@@ -339,10 +414,10 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
     auto syndrome_fail = [&]() -> bool {
         uint32_t failw = 0;
         for (int j = 0; j < rh; ++j) {
-            const int e0 = a.row_start[j], e1 = a.row_start[j + 1];
+            const int e0 = rs[j], e1 = rs[j + 1];
             uint32_t sy = 0;
             for (int e = e0; e < e1; ++e) {
-                const uint32_t d = a.edges[e];
+                const uint32_t d = (uint32_t)ed[e];
                 const int k = d >> 16, c = d & 0xffffu;
                 sy ^= hi32(lds[(k * M + rot_idx(n, c, M)) * F + f]);
             }
@@ -360,44 +435,9 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
 #pragma unroll
         for (int j = 0; j < RHM; ++j) {
             if (j < rh) {
-                const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                double nm1 = kMaxVal, nm2 = kMaxVal;  // :5133-5134
-                uint32_t npos = 0, nS = 0;
-                double tv[RWM];
-                int addr[RWM];
-#pragma unroll
-                for (int idx = 0; idx < RWM; ++idx) {
-                    if (idx < rw) {                     // :5141-5177
-                        const uint32_t d = a.edges[e0 + idx];
-                        const int k = d >> 16, c = d & 0xffffu;
-                        addr[idx] = (k * M + rot_idx(n, c, M)) * F + f;
-                        const double r = lds[addr[idx]];
-                        const double aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                        const double pc = flip_if(aa, ((mt >> idx) ^ par) & 1u);
-                        const double t = r - pc;
-                        tv[idx] = t;
-                        nS |= (hi32(t) >> 31) << idx;   // sign kept even when the magnitude clips to 0 (:5164-5168)
-                        double mag = fabs(t) - beta;
-                        mag = mag < 0 ? 0 : mag;
-                        const bool c1 = mag < nm1;      // process_check_node :5012-5027
-                        nm2 = fmin(fmax(mag, nm1), nm2);
-                        npos = c1 ? (uint32_t)idx : npos;
-                        nm1 = fmin(mag, nm1);
-                    }
-                }
-                const uint32_t npar = __popc(nS) & 1u;
-#pragma unroll
-                for (int idx = 0; idx < RWM; ++idx) {
-                    if (idx < rw) {                     // :5182-5206
-                        const double aa = (npos == (uint32_t)idx) ? nm2 : nm1;
-                        const double cv = flip_if(aa, ((nS >> idx) ^ npar) & 1u);
-                        if (wr) lds[addr[idx]] = tv[idx] + cv;
-                    }
-                }
-                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                const int e0 = rs[j], rw = rs[j + 1] - e0;
+                const RowRec<double> nr = lms_row_layer(ed, e0, rw, RowRec<double>{m1[j], m2[j], meta[j], 0u}, wr, lds, l, M, F);
+                if (!st.done) { m1[j] = nr.m1; m2[j] = nr.m2; meta[j] = nr.meta; }
                 if (MW) __syncthreads();  // the next layer reads what this one wrote
             }
         }
@@ -406,6 +446,12 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
     write_outputs(a, lds, l, st.res);
     if (l.live && at_entry && a.soft_out)
         for (int k = 0; k < a.nh; ++k) a.soft_out[l.fr * N + k * M + n] = a.llr[l.fr * N + k * M + n];
+}
+
+template <int RHM, bool MW>
+__global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArgs a) {
+    extern __shared__ double lds[];
+    lms_layered_body<RHM, MW>(a, lds, blockIdx.x, a.row_start, a.edges);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -418,6 +464,47 @@ __global__ void __launch_bounds__(MW ? 512 : 64) lms_layered_kernel(const DecArg
 // [-2*max_data, 2*max_data], so 32-bit lanes reproduce the reference's int16 arithmetic without wrap-around.
 // LDS: one int32 per variable.
 // ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int ims_sat(int x, int max_data) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); }  // limit_val :4308
+
+// The two row passes of integer min-sum for one lane, W = the LDS word of a variable: int in ims_flood_kernel, int16_t in
+// ims_flood_codes_kernel (ldpc_codeset.hpp).  Both take the old record with m1 and m2 already scaled, (m * ialpha) >> 4.
+// STATE1 of a row (:5540-5576): add the c2v value of each edge into lds, saturating after every add
+template <class W, class Edges>
+__device__ __forceinline__ void ims_row_add(Edges ed, int e0, int rw, RowRec<int> o, bool wr, W *lds, int max_data, Lane l, int M, int F) {
+    const uint32_t mt = o.meta;
+    const uint32_t par = __popc(mt & 0xffffu) & 1u;
+    const uint32_t pos = mt >> kRowBits;
+    for (int idx = 0; idx < rw; ++idx) {
+        const int addr = edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f);
+        const int tmp = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
+        if (wr) lds[addr] = (W)ims_sat((int)lds[addr] + cv, max_data);
+    }
+}
+
+// STATE3 of a row (:5610-5678): the new record (unscaled) and sy = the xor of the row's a-posteriori words
+template <class W, class Edges>
+__device__ __forceinline__ RowRec<int> ims_row_scan(Edges ed, int e0, int rw, RowRec<int> o, const W *lds, int max_data, Lane l, int M, int F) {
+    const uint32_t mt = o.meta;
+    const uint32_t par = __popc(mt & 0xffffu) & 1u;
+    const uint32_t pos = mt >> kRowBits;
+    int nm1 = max_data, nm2 = max_data;
+    uint32_t npos = 0, nS = 0, sy = 0;
+    for (int idx = 0; idx < rw; ++idx) {
+        const int r = lds[edge_idx((uint32_t)ed[e0 + idx], l.n, M, F, l.f)];
+        sy ^= (uint32_t)r;
+        const int val = (pos == (uint32_t)idx) ? o.m2 : o.m1;
+        const int t = (((mt >> idx) ^ par) & 1u) ? -val : val;
+        const int msg = r - t;
+        nS |= ((uint32_t)msg >> 31) << idx;
+        int v = msg < 0 ? -msg : msg;
+        v = v > max_data ? max_data : v;
+        if (v < nm1) { npos = idx; nm2 = nm1; nm1 = v; }
+        else if (v < nm2) nm2 = v;
+    }
+    return RowRec<int>{nm1, nm2, nS | (npos << kRowBits), sy};
+}
+
 template <int RHM, int NHM, bool MW>
 __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs a) {
     extern __shared__ double lds_raw[];
@@ -430,7 +517,6 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
     const Lane l = frame_lane<MW>(F, M, a.B, blockIdx.x);
     const int n = l.n, f = l.f;
     const bool valid = l.valid;
-    auto sat = [&](int x) { return x > max_data ? max_data : (x < -max_data ? -max_data : x); };  // limit_val :4308
 
     // :5472-5500 energy-normalised quantiser.  Every lane of a frame walks the frame's LLRs in index order (same
     // addresses within the frame: broadcast loads), so all of them hold the identical, sequentially rounded sum.
@@ -468,19 +554,10 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
         }
         if (MW) __syncthreads();
 #pragma unroll
-        for (int j = 0; j < RHM; ++j) {   // STATE1 :5540-5576
+        for (int j = 0; j < RHM; ++j) {   // STATE1
             if (j < rh) {
                 const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const int addr = edge_idx(a.edges[e0 + idx], n, M, F, f);
-                    int tmp = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    tmp = (tmp * ialpha) >> 4;
-                    const int cv = (((mt >> idx) ^ par) & 1u) ? -tmp : tmp;
-                    if (wr) lds[addr] = sat(lds[addr] + cv);
-                }
+                ims_row_add(a.edges, e0, rw, RowRec<int>{(m1[j] * ialpha) >> 4, (m2[j] * ialpha) >> 4, meta[j], 0u}, wr, lds, max_data, l, M, F);
                 if (MW) __syncthreads();
             }
         }
@@ -489,36 +566,19 @@ __global__ void __launch_bounds__(MW ? 512 : 64) ims_flood_kernel(const DecArgs 
             for (int k = 0; k < NHM; ++k) {
                 if (k < nh) {
                     const int o = (k * M + n) * F + f;
-                    lds[o] = sat(iy[k] + lds[o]);
+                    lds[o] = ims_sat(iy[k] + lds[o], max_data);
                 }
             }
         }
         if (MW) __syncthreads();
         uint32_t failw = 0;
 #pragma unroll
-        for (int j = 0; j < RHM; ++j) {   // STATE3 :5610-5678
+        for (int j = 0; j < RHM; ++j) {   // STATE3
             if (j < rh) {
                 const int e0 = a.row_start[j], rw = a.row_start[j + 1] - e0;
-                const uint32_t mt = meta[j];
-                const uint32_t par = __popc(mt & 0xffffu) & 1u;
-                const uint32_t pos = mt >> kRowBits;
-                int nm1 = max_data, nm2 = max_data;
-                uint32_t npos = 0, nS = 0, sy = 0;
-                for (int idx = 0; idx < rw; ++idx) {
-                    const int r = lds[edge_idx(a.edges[e0 + idx], n, M, F, f)];
-                    sy ^= (uint32_t)r;
-                    const int aa = (pos == (uint32_t)idx) ? m2[j] : m1[j];
-                    const int val = (aa * ialpha) >> 4;
-                    const int t = (((mt >> idx) ^ par) & 1u) ? -val : val;
-                    const int msg = r - t;
-                    nS |= ((uint32_t)msg >> 31) << idx;
-                    int v = msg < 0 ? -msg : msg;
-                    v = v > max_data ? max_data : v;
-                    if (v < nm1) { npos = idx; nm2 = nm1; nm1 = v; }
-                    else if (v < nm2) nm2 = v;
-                }
-                failw |= sy;
-                if (!st.done) { m1[j] = nm1; m2[j] = nm2; meta[j] = nS | (npos << kRowBits); }
+                const RowRec<int> nr = ims_row_scan(a.edges, e0, rw, RowRec<int>{(m1[j] * ialpha) >> 4, (m2[j] * ialpha) >> 4, meta[j], 0u}, lds, max_data, l, M, F);
+                failw |= nr.sy;
+                if (!st.done) { m1[j] = nr.m1; m2[j] = nr.m2; meta[j] = nr.meta; }
             }
         }
         stop_vote<MW>(st, valid && (failw >> 31), l, F, sh_flag, iter + 1);  // :5684-5689

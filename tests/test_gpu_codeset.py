@@ -130,6 +130,7 @@ def oracle_decode(H, M, dec, llr, maxiter, alpha=0.8):
 
 
 _REF = {}
+SNR_LADDER = (2.0, 1.0, 3.0, 0.0, 4.0, -1.0, 5.0, -2.0, 6.0, 1.5, 2.5, 0.5, 3.5)
 
 
 def reference(case):
@@ -140,7 +141,7 @@ def reference(case):
     M, rh, nh = case
     codes = make_code_set(100 + M, rh, nh, M)
     H0 = codes[0].astype(np.int32)
-    for snr in (2.0, 1.0, 3.0, 0.0, 4.0, -1.0, 5.0, -2.0, 6.0, 1.5, 2.5, 0.5, 3.5):
+    for snr in SNR_LADDER:
         shared = awgn_llr(H0, M, snr, 300 + M, NFRAMES, burn_codeword=False)
         percode = awgn_llr(H0, M, snr, 400 + M, NCODES * NFRAMES, burn_codeword=False).reshape(NCODES, NFRAMES, -1)
         ref, mixed = {}, True
