@@ -82,7 +82,8 @@ int ldpc_hip_set_jit_mode(int mode);
  * override.  The C++ harnesses use this around their ldpc_hip_open_multi so that concurrent callers do not see each other's mode. */
 int ldpc_hip_set_jit_mode_thread(int mode);
 /* Name of the kernel the last ldpc_hip_decode_dev call on this context launched.  It differs from ldpc_hip_kernel_name only
- * for IMS_DEC with parameters beyond int8 (MS_DBITS > 8, MS_QBITS > 8 or alpha > 1), which run on the table-driven int32 kernel. */
+ * for IMS_DEC with parameters beyond int8 (MS_DBITS > 8, MS_QBITS > 8, alpha > 1 or alpha < 0), which run on the table-driven int32
+ * kernel, and for MS_DEC with an alpha that is not above zero, which runs on ms_global_kernel (see ldpc_hip_decode_dev). */
 const char *ldpc_hip_last_launch(const ldpc_hip_ctx *ctx);
 /* 1 when that launch ran the instance of its kernel that holds no soft values: the M = 64 min-sum body has one (same name, same
  * bits) and takes it when the call passes no soft_out; 0 for every other launch. */
@@ -118,6 +119,9 @@ int ldpc_hip_last_launch_without_soft(const ldpc_hip_ctx *ctx);
  * BP: likewise bit for bit (its exp / log are glibc's algorithms on the device too).
  *   d_soft  [B][N] float64 out, or NULL: the a-posteriori values upstream writes to decword[] when decision==1
  *           (MS/LMS: LLR; SP: likelihood ratio = what upstream leaves in soft[])
+ * alpha: read by MS_DEC and IMS_DEC only.  Any alpha > 0 runs on the context's own kernel.  MS_DEC with alpha <= 0 (-0.0 included:
+ * upstream keeps the sign of m * alpha, decoders.cpp:4719-4720, and its y + acc * alpha can be -0.0) gives upstream's bits too, from the
+ * shape-unlimited tier's kernel, whatever tier the context is on.  NaN is LDPC_HIP_EINVAL for MS_DEC and IMS_DEC.
  */
 int ldpc_hip_decode_dev(ldpc_hip_ctx *ctx, const double *d_llr, long long B, int maxiter, double alpha,
                         uint32_t *d_hard, int32_t *d_iters, double *d_soft, void *stream);

@@ -472,6 +472,14 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
                           int32_t *d_iters, double *d_soft, hipStream_t stream, const int32_t *code_list, int n_slots) {
     if (B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: bad argument");
     if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
+    if (int rc = alpha_refusal("ldpc_hip_decode_codes_dev", c->decoder_id, alpha)) return rc;
+    // MS_DEC with an alpha that is not above zero (ms_alpha_not_positive): ms_flood_codes_kernel and ms_flood_wide_codes_kernel keep the
+    // sign of m * alpha as upstream does, but start from y + 0.0 and return +0.0 where upstream's y + acc * alpha is -0.0.
+    // ms_global_codes_kernel (ms_global_frame) is upstream's arithmetic as written; a set's tables are those of its route, so the other
+    // routes refuse
+    if (ms_alpha_not_positive(c->decoder_id, alpha) && !(codeset_kind_of(c).is & CS_GLOBAL))
+        return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: alpha = %g is not above zero; %s gives upstream's bits for alpha > 0 only, "
+                    "a set opened with ldpc_hip_open_codes_global takes any alpha", alpha, c->kernel_name.c_str());
     if (B == 0) return 0;
     if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
     ldpc_codeset_state *s = c->codes;

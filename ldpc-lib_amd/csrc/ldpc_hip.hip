@@ -574,6 +574,22 @@ int ims_scale(ldpc_hip_ctx *c, const double *d_llr, long long B, hipStream_t str
 
 int ims_ialpha(double alpha) { return (int)(alpha * (1 << 4)); }   // decoders.cpp:5458, MS_ALPHA_FPP = 4
 
+// MS_DEC with an alpha that is not above zero (negative, -0.0 or +0.0; NaN is refused before).  Upstream's c2v value is
+// sign ? -(m * alpha) : m * alpha (decoders.cpp:4719-4720), so a sign bit on alpha flips the message; and its soft value
+// y + acc * alpha (:4674) is -0.0 where y is and the product is too, which a negative alpha gives with acc = +0.0 and a zero alpha
+// with any acc < 0.  Every min-sum kernel but ms_global_frame takes |m * alpha| or starts from y + 0.0 (its sign-bit arithmetic needs
+// the canonical zero): upstream's bits for alpha > 0 only.  ms_global_frame is upstream's arithmetic as written.
+bool ms_alpha_not_positive(int decoder_id, double alpha) { return decoder_id == LDPC_HIP_MS_DEC && !(alpha > 0.0); }
+
+// NaN: every value the two min-sum decoders form from alpha is then a NaN (MS_DEC; the GPU's default NaN and the host's differ in the
+// sign bit, so upstream's bits cannot be given) or comes from a conversion that C leaves undefined (IMS_DEC's (int)(alpha * 16)).  The
+// other decoders do not read alpha (decoders.cpp:5159-5169).
+int alpha_refusal(const char *who, int decoder_id, double alpha) {
+    if ((decoder_id == LDPC_HIP_MS_DEC || decoder_id == LDPC_HIP_IMS_DEC) && std::isnan(alpha))
+        return fail(LDPC_HIP_EINVAL, "%s: alpha is NaN; decoder %d takes a number", who, decoder_id);
+    return 0;
+}
+
 // One decode call (ldpc_hip_decode_dev, after its argument checks) and the three tiers that serve it
 struct DecodeCall {
     const double *llr; long long B; int maxiter; double alpha;
@@ -858,7 +874,8 @@ int ldpc_hip_open(int decoder_id, int rh, int nh, int M, const int16_t *hd, int 
         c->spec_aot = nullptr; c->spec_jit = nullptr;
         c->kernel_name = kind->global_name;
     }
-    if (c->global_tier || decoder_id == LDPC_HIP_IMS_DEC)   // IMS: parameters beyond int8 may send a launch to the global tier later
+    // IMS: parameters beyond int8 may send a launch to the global tier later; MS: an alpha that is not above zero (ldpc_hip_decode_dev)
+    if (c->global_tier || decoder_id == LDPC_HIP_IMS_DEC || decoder_id == LDPC_HIP_MS_DEC)
         c->glob_stride = ldpc::glob_ws_bytes(c->N, c->R, t.ne, M, kind->glob_edge_arrays);
     if (!c->spec_aot && !c->spec_jit && !c->global_tier) {
         if (!have_generic)
@@ -953,6 +970,7 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
     // (decoders.cpp:4602-4625,4766): there is nothing meaningful to reproduce, so it is rejected instead
     if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_dev: maxiter must be >= 1 (got %d)", maxiter);
     if (int rc = set_device(c)) return rc;
+    if (int rc = alpha_refusal("ldpc_hip_decode_dev", c->decoder_id, alpha)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     adopt_jit(c);
 
@@ -966,6 +984,10 @@ int ldpc_hip_decode_dev(ldpc_hip_ctx *c, const double *d_llr, long long B, int m
     if (use_spec && c->decoder_id == LDPC_HIP_IMS_DEC && (c->ims_dbits > 8 || c->ims_qbits > 8 || ialpha < 0 || ialpha > 16)) {
         use_spec = false;   // values beyond int8 (messages, or quantised inputs): table-driven int32 kernel, or the global tier's
         if (!c->have_generic) use_global = true;
+    }
+    if (ms_alpha_not_positive(c->decoder_id, alpha)) {   // only ms_global_kernel gives upstream's bits then
+        use_spec = false;
+        use_global = true;
     }
     c->last_launch = use_global ? kind.global_name : use_spec ? c->kernel_name.c_str() : c->generic_name.c_str();
     c->last_without_soft = false;   // launch_spec says otherwise

@@ -760,7 +760,11 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         //   - x = keep * |alpha|.  The second decode is x = +-|(pos == s ? m2 : m1) * alpha| (signed_mag drops the product's
         //     sign); nm1 and nm2 are finite and in [0, 32767]; IEEE multiplication is sign-symmetric, so (+-m) * |alpha| and
         //     +-(m * |alpha|) are the same bits, zeros and denormals included; -ffp-contract=off keeps this product and the
-        //     subtraction after it apart, as it does for the second decode.
+        //     subtraction after it apart, as it does for the second decode.  All of this is upstream's c2v value for alpha > 0
+        //     only: upstream keeps the sign of m * alpha (:4719-4720), so an alpha with its sign bit set flips the message, and
+        //     its y + acc * alpha is -0.0 where the `+ 0.0` on the channel value leaves +0.0 once the product can be -0.0 (alpha
+        //     negative, or zero and acc < 0).  ldpc_hip_decode_dev sends such a launch to ms_global_kernel; no
+        //     instance of this file sees an alpha that is not above zero.
         // A carried edge costs 2 VGPRs for the whole iteration, STATE2 with its channel values in flight included, and a carried
         // row gives back the 5 of its record: ms_m64_keep_budget.  Two tiers only: a row past KR decodes its record twice.
         // An edge of a LOCAL column is not scattered in STATE1 at all (no LDS operation).  STATE3 at the column's first block row

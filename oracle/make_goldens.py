@@ -17,7 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from ldpc_testlib import (ASP_DEC, BP_DEC, GOLDEN_DIR, IMS_DEC, LMS_DEC, MS_DEC, SP_DEC, TASP_DEC, Reference, awgn_llr, load_base_matrix,  # noqa: E402
+from ldpc_testlib import (ASP_DEC, BP_DEC, GOLDEN_DIR, IMS_DEC, LMS_DEC, MS_DEC, SP_DEC, TASP_DEC, Reference, alpha_sweep_llr, awgn_llr, load_base_matrix,  # noqa: E402
                           oracle_lib, pack_bits, ref_lib, relift, _as_double_p)
 
 SETS = [
@@ -59,6 +59,18 @@ def _cycle_code(M):
 EXTRA_SETS = [
     # every block column holds exactly two circulants: sum_prod_gf2_decod_qc_lm's own branch (asp_all_cw_2, decoders.cpp:1027-1044, :2431-2480)
     ("asp_cw2_m64_2p0", ASP_DEC, _cycle_code, 64, 2.0, 24, 40, 4),
+]
+# min-sum and integer min-sum at other normalisation factors than MS_ALPHA = 0.8 (ref_decode_alpha), on the example code: the batch of
+# ldpc_testlib.alpha_sweep_llr with two frames per SNR (13 frames: failing frames, converging ones, codewords at the input, ties).
+# The factor is stored as `alpha`; the tests that walk the golden directory decode with it.
+ALPHA_SETS = [
+    # name,             dec,     M,  alpha, maxiter, soft_frames
+    ("ms_m64_a1p0",     MS_DEC,  64, 1.0,   30, 3),
+    ("ms_m64_a0p5",     MS_DEC,  64, 0.5,   30, 3),
+    ("ms_m64_a1p25",    MS_DEC,  64, 1.25,  30, 3),   # messages reach the 32767 clamp
+    ("ms_m64_aneg0p8",  MS_DEC,  64, -0.8,  30, 3),   # the product's sign flips the message (decoders.cpp:4719-4720)
+    ("ms_m24_a0p75",    MS_DEC,  24, 0.75,  30, 4),
+    ("ims_m64_a0p5",    IMS_DEC, 64, 0.5,   30, 3),
 ]
 ONLY = set(sys.argv[1:])  # optional: regenerate just the named sets
 
@@ -104,6 +116,23 @@ def main():
             llr=llr, iters=it0.astype(np.int32), hard=pack_bits(dec0), soft=dec1,
         )
         print(f"{name}: frames={frames} iters={it0.tolist()[:12]}... fail={(it0 < 0).sum()} errbits={int((dec0 != 0).sum())}")
+        ref.close()
+
+    for name, dec, M, alpha, maxiter, soft_frames in ALPHA_SETS:
+        if ONLY and name not in ONLY:
+            continue
+        H = relift(H0, M)
+        llr = alpha_sweep_llr(H, M, per_snr=2)
+        ref = Reference(dec, H, M)
+        dec0, it0, _ = ref.decode(dec, llr, maxiter, 0, alpha=alpha)
+        dec1, it1, _ = ref.decode(dec, llr[:soft_frames], maxiter, 1, alpha=alpha)
+        assert np.array_equal(it0[:soft_frames], it1)
+        np.savez_compressed(
+            os.path.join(GOLDEN_DIR, name + ".npz"),
+            H=H.astype(np.int16), M=np.int32(M), dec_id=np.int32(dec), alpha=np.float64(alpha), maxiter=np.int32(maxiter),
+            llr=llr, iters=it0.astype(np.int32), hard=pack_bits(dec0), soft=dec1,
+        )
+        print(f"{name}: frames={len(llr)} alpha={alpha} iters={it0.tolist()} fail={(it0 < 0).sum()} errbits={int((dec0 != 0).sum())}")
         ref.close()
 
     if ONLY and "qam_frontend" not in ONLY:

@@ -51,6 +51,24 @@ int ref_decode(void *h, int dec_id, double *y_inout, double *decword, int maxite
     return iter;
 }
 
+// The two min-sum decoders with the caller's parameters where ref_decode passes upstream's defaults: alpha for MS_DEC, and
+// alpha / thr / qbits / dbits for IMS_DEC.  Everything else as ref_decode.
+int ref_decode_alpha(void *h, int dec_id, double *y_inout, double *decword, int maxiter, int decision, double alpha, double thr,
+                     int qbits, int dbits) {
+    DEC_STATE *st = (DEC_STATE *)h;
+    const int N = st->n;
+    int iter = -12345;
+    std::memcpy(st->y, y_inout, sizeof(double) * N);
+    switch (dec_id) {
+    case MS_DEC:  iter = min_sum_decod_qc_lm(st, st->y, st->decword, maxiter, decision, alpha); break;
+    case IMS_DEC: iter = imin_sum_decod_qc_lm(st, st->y, st->decword, maxiter, decision, alpha, thr, qbits, dbits); break;
+    default: return -12345;
+    }
+    std::memcpy(decword, st->decword, sizeof(double) * N);
+    std::memcpy(y_inout, st->y, sizeof(double) * N);
+    return iter;
+}
+
 // QAM mapper: in = nbits doubles (0/1), out = 2*ns doubles, returns ns.
 int ref_qam_modulate(int Q, const double *bits, int nbits, double *out) {
     int m = 0; while ((1 << m) < Q) m++;

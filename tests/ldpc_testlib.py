@@ -97,15 +97,22 @@ def ref_lib():
     lib.ref_open.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_short_p]
     lib.ref_close.argtypes = [C.c_void_p]
     lib.ref_decode.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int]
+    if hasattr(lib, "ref_decode_alpha"):
+        lib.ref_decode_alpha.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     lib.ref_qam_modulate.argtypes = [C.c_int, c_double_p, C.c_int, c_double_p]
     lib.ref_qam_demodulate.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, C.c_int, c_double_p, C.c_int]
     return lib
 
 
-class _Decoder:
-    """Common batch front end: decode(llr[B,N]) -> (decword[B,N] float64, iters[B] int32, llr_after[B,N])."""
+IMS_DEFAULTS = (1.4, 6, 8)   # decoders.cpp MS_THR, MS_QBITS, MS_DBITS
 
-    def decode(self, dec_id, llr, maxiter, decision=0):
+
+class _Decoder:
+    """Common batch front end: decode(llr[B,N]) -> (decword[B,N] float64, iters[B] int32, llr_after[B,N]).
+    alpha: the normalisation factor of MS_DEC and IMS_DEC (upstream's MS_ALPHA by default); ims = (thr, qbits, dbits) of IMS_DEC.  The
+    other decoders ignore both, as upstream's do."""
+
+    def decode(self, dec_id, llr, maxiter, decision=0, alpha=0.8, ims=IMS_DEFAULTS):
         llr = np.ascontiguousarray(llr, dtype=np.float64)
         single = llr.ndim == 1
         if single:
@@ -116,7 +123,7 @@ class _Decoder:
         its = np.empty(B, dtype=np.int32)
         after = llr.copy()
         for b in range(B):
-            its[b] = self._one(dec_id, after[b], dec[b], maxiter, decision)
+            its[b] = self._one(dec_id, after[b], dec[b], maxiter, decision, alpha, ims)
         if single:
             return dec[0], int(its[0]), after[0]
         return dec, its, after
@@ -144,16 +151,16 @@ class Oracle(_Decoder):
         except Exception:
             pass
 
-    def _one(self, dec_id, y, dec, maxiter, decision):
+    def _one(self, dec_id, y, dec, maxiter, decision, alpha=0.8, ims=IMS_DEFAULTS):
         yp, dp = _as_double_p(y), _as_double_p(dec)
         if dec_id == MS_DEC:
-            return self.lib.orc_min_sum(self.h, yp, dp, maxiter, decision, 0.8)
+            return self.lib.orc_min_sum(self.h, yp, dp, maxiter, decision, alpha)
         if dec_id == LMS_DEC:
             return self.lib.orc_lmin_sum(self.h, yp, dp, maxiter, decision)
         if dec_id == SP_DEC:
             return self.lib.orc_sum_prod(self.h, yp, dp, maxiter, decision)
         if dec_id == IMS_DEC:
-            return self.lib.orc_imin_sum(self.h, yp, dp, maxiter, decision, 0.8, 1.4, 6, 8)
+            return self.lib.orc_imin_sum(self.h, yp, dp, maxiter, decision, alpha, *ims)
         if dec_id == BP_DEC:
             return self.lib.orc_bp(self.h, yp, dp, maxiter, decision)
         if dec_id == ASP_DEC:
@@ -191,8 +198,10 @@ class Reference(_Decoder):
         except Exception:
             pass
 
-    def _one(self, dec_id, y, dec, maxiter, decision):
+    def _one(self, dec_id, y, dec, maxiter, decision, alpha=0.8, ims=IMS_DEFAULTS):
         assert dec_id == self.dec_id
+        if dec_id in (MS_DEC, IMS_DEC) and (alpha != 0.8 or np.signbit(alpha) or tuple(ims) != IMS_DEFAULTS):
+            return self.lib.ref_decode_alpha(self.h, dec_id, _as_double_p(y), _as_double_p(dec), maxiter, decision, alpha, *ims)
         return self.lib.ref_decode(self.h, dec_id, _as_double_p(y), _as_double_p(dec), maxiter, decision)
 
 
@@ -367,6 +376,27 @@ def assert_bits_equal(got, want, what="", nan_ok=False):
         i = np.unravel_index(flat[0], got.shape)
         raise AssertionError(f"{what}: {flat.size} of {got.size} values differ; first at {tuple(int(x) for x in i)}: got {got[i]!r} "
                              f"(0x{int(g[i]):016x}), want {want[i]!r} (0x{int(w[i]):016x})")
+
+
+# ---- min-sum normalisation factors other than upstream's MS_ALPHA = 0.8 ---------------------------------------------------------------
+# 1.0: no scaling; 0.5: an exact power of two; 0.75: a second inexact factor; 1.25, 2.0: messages grow into the 32767 clamp of STATE3 on
+# their own; 1e-310: denormal products; 0.0: zero factor; -0.0, -0.8: sign bit set (upstream's product keeps it, decoders.cpp:4719-4720)
+MS_ALPHAS = (1.0, 0.5, 0.75, 1.25, 2.0, 1e-310, 0.0, -0.0, -0.8)
+# integer min-sum: ialpha = (int)(alpha * 16) = 8, 15, 16, 0, and 20 and -12, which an int8 message does not hold
+IMS_ALPHAS = (0.5, 0.99, 1.0, 0.03, 1.25, -0.8)
+ALPHA_SWEEP_SNRS = (1.4, 3.0, 4.5, 6.0, 8.0, 15.0)
+
+
+def alpha_sweep_llr(H, M, seed=0, per_snr=4):
+    """The batch the alpha tests decode: per_snr AWGN frames at each of ALPHA_SWEEP_SNRS (at 15 dB the frames arrive as codewords: with a
+    zero, denormal or negative factor nothing else returns 1), zeros of both signs, values beyond the clamp and a denormal-ish value at
+    the start of frame 0, and one frame of adversarial_llr's "alphabet {1}" family (min1 == min2 in every check, at every alpha)."""
+    Hi = np.asarray(H, dtype=np.int32)
+    llr = np.concatenate([awgn_llr(Hi, M, s, 700 + 10 * seed + i, per_snr) for i, s in enumerate(ALPHA_SWEEP_SNRS)])
+    llr[0, :5] = [0.0, -0.0, 40000.0, -40000.0, 1e-300]
+    adv, labels = adversarial_llr(H, M, seed)
+    tie = adv[labels.index("alphabet {1}: min1 == min2 everywhere")]
+    return np.ascontiguousarray(np.concatenate([llr, tie[None, :]]))
 
 
 # default integer min-sum parameters (decoders.cpp MS_THR / MS_QBITS): the quantiser-boundary frames are tuned for them

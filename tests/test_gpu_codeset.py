@@ -230,6 +230,30 @@ def test_alpha_is_honoured(L, torch):
         assert_bits_equal(soft[c].cpu().numpy(), ref[c][2])
 
 
+@pytest.mark.parametrize("alpha", [-0.8, -0.0, 0.0])
+def test_alpha_that_is_not_above_zero_is_refused(L, torch, alpha):
+    """Upstream's c2v value is sign ? -(m * alpha) : m * alpha (decoders.cpp:4719-4720) and its soft value y + acc * alpha is -0.0 where
+    y is and the product is too (a negative factor and acc = +0.0, a zero factor and acc < 0).  ms_flood_codes_kernel keeps the
+    product's sign (ms_row_scan) but starts from y + 0.0, so it returns +0.0 there.  Upstream's bits or an error: this route refuses
+    (the set kernels of the global tier take any alpha, test_gpu_codeset_global.py).  The refusal names alpha, comes from every entry
+    that decodes, and leaves the context as it was."""
+    case = (32, 4, 8)
+    r = reference(case)
+    codes, llr = r["codes"], r["shared"]
+    with L.LdpcHipCodes(MS_DEC, codes, 32) as cs:
+        assert cs.kernel_name == "ms_flood_codes_kernel", cs.kernel_name
+        with pytest.raises(L.LdpcHipError, match="alpha = -?0.* is not above zero"):
+            cs.decode(torch.from_numpy(llr).cuda(), MAXITER, alpha=alpha, want_soft=True)
+        with pytest.raises(L.LdpcHipError, match="alpha = -?0.* is not above zero"):
+            cs.simulate(2.0, MAXITER, 5, 0, 8, alpha=alpha)
+        hard, iters, soft = cs.decode(torch.from_numpy(llr).cuda(), MAXITER, want_soft=True)
+        torch.cuda.synchronize()
+    ref = r["ref"][MS_DEC, "shared"]
+    for c in range(NCODES):
+        assert np.array_equal(iters[c].cpu().numpy(), ref[c][1])
+        assert_bits_equal(soft[c].cpu().numpy(), ref[c][2])
+
+
 @pytest.mark.parametrize("punct", [0, 1])
 @pytest.mark.parametrize("dec", [MS_DEC, LMS_DEC], ids=["ms", "lms"])
 def test_simulate(L, torch, dec, punct, monkeypatch):

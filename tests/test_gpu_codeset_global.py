@@ -161,6 +161,26 @@ def test_alpha_and_ims_params(L, torch):
         check_against(run_set(cs, torch, llr), [S.oracle(S.IMS_DEC, H, 67, llr, ims=params) for H in codes], "IMS, thr 2.0, 5 and 7 bits")
 
 
+def test_alpha_that_is_not_above_zero(L, torch):
+    """Upstream's c2v value keeps the sign of m * alpha (decoders.cpp:4719-4720) and its y + acc * alpha is -0.0 where y and the
+    product are; ms_global_frame is that arithmetic as written (the set kernels of the other routes refuse such an alpha), and the
+    integer decoder's (m * ialpha) >> 4 with ialpha = -12 is the arithmetic shift of a negative product."""
+    codes = S.small_set(67, "B")
+    llr = np.array(S.ladder_llr(codes[0], 67, 99))
+    llr[0, 1] = -0.0; llr[1, ::7] = -0.0; llr[2, ::5] = 0.0
+    for dec, alpha in ((S.MS_DEC, -0.8), (S.MS_DEC, -0.0), (S.MS_DEC, 0.0), (S.IMS_DEC, -0.8)):
+        ref = [S.oracle(dec, H, 67, llr, alpha=alpha) for H in codes]
+        assert any(not np.array_equal(a[2], b[2]) for a, b in zip(ref, [S.oracle(dec, H, 67, llr, alpha=0.8) for H in codes])), "alpha must matter"
+        if dec == S.MS_DEC:
+            assert any(np.signbit(a[2][a[2] == 0]).any() for a in ref), "soft values of -0.0"
+        with L.LdpcHipCodes(dec, codes, 67, tier="global") as cs:
+            assert cs.kernel_name == S.KERNEL[dec]
+            check_against(run_set(cs, torch, llr, alpha=alpha), ref, f"{S.DEC_IDS[dec]}, alpha {alpha!r}")
+    with L.LdpcHipCodes(S.MS_DEC, codes, 67, tier="global") as cs:
+        with pytest.raises(L.LdpcHipError, match="alpha"):
+            run_set(cs, torch, llr, alpha=float("nan"))
+
+
 @pytest.mark.parametrize("dec", S.DECS, ids=IDS)
 def test_nan_and_inf(L, torch, dec):
     """NaN and +-Inf channel values.  Every decoder against one LdpcHip per matrix; against the CPU oracle where that is compiled C with

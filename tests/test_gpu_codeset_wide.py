@@ -82,6 +82,22 @@ def _decode_one(L, torch, dec, H, M, llr, maxiter, alpha=0.8):
     return out
 
 
+@pytest.mark.parametrize("alpha", [-0.8, -0.0, 0.0])
+def test_alpha_that_is_not_above_zero_is_refused(L, torch, alpha):
+    """ms_flood_wide_codes_kernel starts from y + 0.0 as ms_flood_codes_kernel does: where upstream's y + acc * alpha is -0.0 (y is and
+    the product is too, which takes a negative alpha, or a zero one and acc < 0) it returns +0.0.  Upstream's bits or an error: the
+    wide route refuses, and names alpha."""
+    r = S.reference("rows17_M20", MS_DEC)
+    M, codes, llr = r["M"], r["codes"], r["shared"]
+    with L.LdpcHipCodes(MS_DEC, codes, M, wide=True) as cs:
+        assert cs.kernel_name == S.kernel_name(MS_DEC, M)
+        with pytest.raises(L.LdpcHipError, match="alpha = -?0.* is not above zero"):
+            _set_decode(cs, torch, llr, MAXITER, alpha=alpha)
+        got = _set_decode(cs, torch, llr, MAXITER)
+    for c in range(len(codes)):
+        _same(got[c], r["ref"]["shared"][c], f"code {c} against the oracle, after the refusal")
+
+
 @pytest.mark.parametrize("layout", ["shared", "percode"])
 @pytest.mark.parametrize("name,dec", S.PARITY, ids=S.PARITY_IDS)
 def test_parity(L, torch, name, dec, layout):

@@ -52,12 +52,13 @@ def torch():
 def test_golden_vectors_host_api(L, name):
     g = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
     H, M, dec_id, maxiter = g["H"], int(g["M"]), int(g["dec_id"]), int(g["maxiter"])
+    alpha = float(g["alpha"]) if "alpha" in g else 0.8   # the min-sum sets recorded at another factor carry it
     with L.LdpcHip(dec_id, H, M) as dec:
-        d0, it0, after = dec.decode_host(g["llr"], maxiter, decision=0)
+        d0, it0, after = dec.decode_host(g["llr"], maxiter, decision=0, alpha=alpha)
         assert np.array_equal(it0, g["iters"]), (it0, g["iters"])
         assert np.array_equal(pack_bits(d0), g["hard"])
         ns = g["soft"].shape[0]
-        d1, it1, _ = dec.decode_host(g["llr"][:ns], maxiter, decision=1)
+        d1, it1, _ = dec.decode_host(g["llr"][:ns], maxiter, decision=1, alpha=alpha)
         assert np.array_equal(it1, g["iters"][:ns])
         if dec_id == SP_DEC:
             _close(d1, g["soft"], SP_RTOL)

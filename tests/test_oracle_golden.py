@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from ldpc_testlib import (BP_DEC, GOLDEN_DIR, SP_DEC, TASP_DEC, Oracle, awgn_llr, load_base_matrix, oracle_lib, pack_bits, relift,
+from ldpc_testlib import (BP_DEC, GOLDEN_DIR, SP_DEC, TASP_DEC, Oracle, assert_bits_equal, awgn_llr, load_base_matrix, oracle_lib, pack_bits, relift,
                           _as_double_p)
 
 DECODER_SETS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
@@ -22,12 +22,13 @@ def test_golden_sets_present():
 def test_oracle_matches_reference_golden(name):
     g = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
     H, M, dec_id, maxiter = g["H"], int(g["M"]), int(g["dec_id"]), int(g["maxiter"])
+    alpha = float(g["alpha"]) if "alpha" in g else 0.8   # the min-sum sets recorded at another factor carry it
     o = Oracle(H, M)
-    dec, its, _ = o.decode(dec_id, g["llr"], maxiter, 0)
+    dec, its, _ = o.decode(dec_id, g["llr"], maxiter, 0, alpha=alpha)
     assert np.array_equal(its, g["iters"])
     assert np.array_equal(pack_bits(dec), g["hard"])
     nsoft = g["soft"].shape[0]
-    soft, its1, _ = o.decode(dec_id, g["llr"][:nsoft], maxiter, 1)
+    soft, its1, _ = o.decode(dec_id, g["llr"][:nsoft], maxiter, 1, alpha=alpha)
     assert np.array_equal(its1, g["iters"][:nsoft])
     if dec_id == TASP_DEC:
         # upstream ignores `decision` for this decoder (decoders.cpp:2737-2738): the golden "soft" output is the hard
@@ -36,6 +37,8 @@ def test_oracle_matches_reference_golden(name):
         return
     # same libm on both sides in this container, so even sum-product is bit-identical here
     assert np.array_equal(soft, g["soft"], equal_nan=True)
+    if "alpha" in g:
+        assert_bits_equal(soft, g["soft"], "soft values")   # zeros by their sign too: a negative factor turns it
 
 
 def test_qam_frontend_matches_reference_golden():

@@ -3,8 +3,8 @@ random batches beyond the committed goldens.  Skipped wherever oracle/_ref was n
 import numpy as np
 import pytest
 
-from ldpc_testlib import (ASP_DEC, BP_DEC, IMS_DEC, LMS_DEC, MS_DEC, SP_DEC, TASP_DEC, Oracle, Reference, awgn_llr, load_base_matrix, ref_lib,
-                          relift)
+from ldpc_testlib import (ASP_DEC, BP_DEC, IMS_ALPHAS, IMS_DEC, LMS_DEC, MS_ALPHAS, MS_DEC, SP_DEC, TASP_DEC, Oracle, Reference, alpha_sweep_llr,
+                          assert_bits_equal, awgn_llr, load_base_matrix, ref_lib, relift)
 
 pytestmark = pytest.mark.skipif(ref_lib() is None, reason="oracle/_ref not built (needs the upstream tree)")
 
@@ -28,6 +28,24 @@ def test_restatement_equals_compiled_reference(dec_id, M, snr, frames, maxiter, 
         assert np.array_equal(i1, i2)
         assert np.array_equal(d1, d2, equal_nan=True)
         assert np.array_equal(a1, a2, equal_nan=True)  # SP clobbers its input identically
+
+
+@pytest.mark.parametrize("M", [64, 24, 126])
+@pytest.mark.parametrize("dec_id,alpha", [(MS_DEC, a) for a in MS_ALPHAS] + [(IMS_DEC, a) for a in IMS_ALPHAS])
+def test_min_sum_restatements_equal_compiled_reference_at_other_alphas(dec_id, alpha, M):
+    """min_sum_decod_qc_lm and imin_sum_decod_qc_lm with the caller's alpha (ref_decode_alpha passes it on where ref_decode passes
+    MS_ALPHA): return values, hard decisions and soft values bit for bit, zeros by their sign too.  The oracle is what the GPU tests
+    compare with at these factors (tests/test_gpu_alpha.py)."""
+    H = relift(load_base_matrix(), M)
+    llr = alpha_sweep_llr(H, M)
+    o, r = Oracle(H, M), Reference(dec_id, H, M)
+    for decision in (0, 1):
+        d1, i1, a1 = o.decode(dec_id, llr, 30, decision, alpha=alpha)
+        d2, i2, a2 = r.decode(dec_id, llr, 30, decision, alpha=alpha)
+        assert np.array_equal(i1, i2), (i1, i2)
+        assert_bits_equal(d1, d2, f"decision {decision}")
+        assert_bits_equal(a1, a2, "the input stays as it was")
+    assert (i1 > 0).any() and (i1 < 0).any(), i1
 
 
 def test_irregular_small_matrix():
