@@ -863,6 +863,44 @@ int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int target_girth,
  * attempts checked (whole rounds). */
 void ldpc_hip_label_last_stats(long long stats[4]);
 
+/* ---- Every lifting a labelling allows: upstream's equation_builder::check_voltages / check_voltages_and_coefs (equations.cpp:150-267,
+ * what its `ggp` command turns on) for K labellings in one call (csrc/ldpc_voltage.hpp).  proto HOST [rh][nh]: any positive entry is
+ * an edge, the value is not otherwise read; E edges, numbered column by column with the rows ascending.  The equations are those of
+ * ldpc_hip_label_equations_host with every edge counted as random; with *tree_girth < target_girth they are the ones shorter than
+ * *tree_girth, as `ggp` works with them (no early return).  voltages HOST [K][E] in 0 .. 32767; coefs HOST [K][E] in 0 .. 32767, or
+ * NULL for the binary check.  Per labelling, with s_e the sum of an equation over the voltages and c_e the same plain integer sum over
+ * the coefficients (not reduced mod q - 1, as upstream does not):
+ *   status [K]       0 = upstream's first_failed_equation == -1; 1 = its first_failed_equation == 0 (some s_e == 0 -- with
+ *                    coefficients: some s_e == 0 with c_e == 0); 2 = with coefficients only, DEFINED HERE: no equation has s_e == 0 and
+ *                    c_e == 0 but at least one has s_e == 0 and c_e != 0.  Upstream exits there ("global_divisor_table is called with
+ *                    the argument 0"); here those equations contribute no divisor and the other fields are those of the rest.
+ *   failed [K][W]    W = max_modulo / 64 + 1; bit m says m is in failed_modulos: the divisors <= max_modulo of the |s_e|.  May be NULL.
+ *   max_nonok [K]    the largest member of that set, 1 when it is empty;  min_ok [K]: the smallest m >= 2 not in it.
+ *   max_abs_sum [K]  max |s_e|: where it is <= max_modulo the result is that of upstream's unbounded check_voltages(v).
+ * For status 1 min_ok, max_nonok and the bitmap are 0 (upstream leaves them uninitialised).  *tree_girth, *n_equations: may be NULL.
+ * LDPC_HIP_EINVAL, found before any device call: what ldpc_hip_label_equations_host refuses, max_modulo < 1, K < 1, a NULL voltages,
+ * status, min_ok, max_nonok or max_abs_sum, a voltage or coefficient outside 0 .. 32767.  LDPC_HIP_EUNSUPPORTED, also before any
+ * device call: max_modulo > 65535, more than 4096 edges, and the limits of the equation table.  A batch is worked off in pieces of at
+ * most 2^20 labellings (one launch) and at most 256 MiB of device memory -- per labelling its voltages, its coefficients where given,
+ * its bitmap where failed is not NULL, and 16 bytes of results -- (LDPC_HIP_VOLTAGE_PIECE=n: n labellings per piece, still at most
+ * 2^20, read per call); the result does not depend on the pieces.  LDPC_HIP_VOLTAGE_LAYOUT=moduli, for measurements and tests
+ * only, runs the slower kernel layout that the shipped one was measured against (same results).  Synchronous and stateless. */
+int ldpc_hip_check_voltages(int rh, int nh, const int16_t *proto, int target_girth, int max_modulo, const int32_t *voltages,
+                            const int32_t *coefs, long long K, int device, int32_t *status, int32_t *min_ok, int32_t *max_nonok,
+                            int32_t *max_abs_sum, uint64_t *failed, int *tree_girth, int *n_equations);
+/* The loop of upstream's random_search_bank_good_codes (search_ggp/) with a budget, on the device.  The arguments, the draws, the
+ * outputs, the attempt indices and the generator afterwards are those of ldpc_hip_label_codes with T (the tailbite length,
+ * 2 .. 32767) in place of M: attempt a draws uniform_int_distribution<int>(0, T - 1) per edge with proto == 1 and takes 0 for any
+ * other edge.  An attempt is accepted iff its voltage check -- as ldpc_hip_check_voltages, bounded at max(T, exact_modulo), which
+ * decides exactly as upstream's unbounded call -- has status 0, min_ok <= T and, unless exact_modulo == 0, check_modulo(exact_modulo)
+ * (exact_modulo: 0, or T .. 65535; LDPC_HIP_EINVAL otherwise, as for a NULL min_ok_out).  min_ok_out HOST [want]: min_ok of the
+ * accepted attempts (what upstream writes in front of each labelling of its bank).  There is no equal-columns test, and no early
+ * return for *tree_girth < target_girth: the search then runs on the equations shorter than *tree_girth.  Rounds, their knob and the
+ * statistics are those of ldpc_hip_label_codes. */
+int ldpc_hip_label_bank(int rh, int nh, const int16_t *proto, int target_girth, int T, int exact_modulo, long long max_attempts, int want,
+                        const uint32_t state_in[624], int pos_in, int device, int16_t *hd_out, int32_t *min_ok_out, long long *attempt_index,
+                        int *found, long long *attempts_tested, int *tree_girth, uint32_t state_out[624], int *pos_out);
+
 /* Timing aid for bench.py: average duration in milliseconds of the decode kernel launches recorded with
  * HIP events on their own stream since the last reset (events are only recorded while enabled). */
 int ldpc_hip_profile_enable(ldpc_hip_ctx *ctx, int enable);

@@ -229,6 +229,9 @@ def load_library():
     lib.ldpc_hip_label_codes.argtypes = [i32, i32, vp, i32, i32, i64, i32, vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), vp,
                                          C.POINTER(i32)]
     lib.ldpc_hip_label_last_stats.argtypes = [vp]
+    lib.ldpc_hip_check_voltages.argtypes = [i32, i32, vp, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    lib.ldpc_hip_label_bank.argtypes = [i32, i32, vp, i32, i32, i32, i64, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), vp,
+                                        C.POINTER(i32)]
     lib.ldpc_hip_label_last_stats.restype = None
     lib.ldpc_hip_trace_matrix_host.argtypes = [vp, vp, i32, C.POINTER(i32), vp, vp]
     if lib.ldpc_hip_abi_version() != 4:
@@ -1385,6 +1388,61 @@ def label_last_stats():
     s = np.zeros(4, dtype=np.int64)
     load_library().ldpc_hip_label_last_stats(s.ctypes.data)
     return tuple(int(v) for v in s)
+
+
+def check_voltages(proto, target_girth, voltages, max_modulo, coefs=None, device=0):
+    """Upstream's check_voltages (coefs=None) / check_voltages_and_coefs for a batch of labellings on the device
+    (ldpc_hip_check_voltages): proto [rh, nh] (any positive entry is an edge), voltages and coefs int32 [K, E] or [E] in 0 .. 32767
+    over the edges column by column.  Returns a dict: status, min_ok, max_nonok, max_abs_sum int32 [K], failed uint64
+    [K, max_modulo // 64 + 1] (bit m: m is a failed modulo), tree_girth, n_equations.  status 0 = ok, 1 = an identically zero sum,
+    2 = a zero sum rescued by its coefficients (upstream exits there)."""
+    lib = load_library()
+    P = np.ascontiguousarray(proto, dtype=np.int16)
+    rh, nh = P.shape
+    V = np.ascontiguousarray(np.atleast_2d(np.asarray(voltages)), dtype=np.int32)
+    K = V.shape[0]
+    Cf = None if coefs is None else np.ascontiguousarray(np.atleast_2d(np.asarray(coefs)), dtype=np.int32)
+    assert V.ndim == 2 and V.shape[1] == int((P > 0).sum()), "voltages: [K, E], one per edge"
+    assert Cf is None or Cf.shape == V.shape, "coefs: as voltages"
+    W = int(max_modulo) // 64 + 1 if 1 <= int(max_modulo) <= 65535 else 1
+    status, min_ok, max_nonok, max_abs = (np.zeros(K, dtype=np.int32) for _ in range(4))
+    failed = np.zeros((K, W), dtype=np.uint64)
+    tg, ne = C.c_int(), C.c_int()
+    rc = lib.ldpc_hip_check_voltages(rh, nh, P.ctypes.data, int(target_girth), int(max_modulo), V.ctypes.data, None if Cf is None else Cf.ctypes.data, K,
+                                     int(device), status.ctypes.data, min_ok.ctypes.data, max_nonok.ctypes.data, max_abs.ctypes.data, failed.ctypes.data,
+                                     C.byref(tg), C.byref(ne))
+    _check(lib, rc, "ldpc_hip_check_voltages")
+    return {"status": status, "min_ok": min_ok, "max_nonok": max_nonok, "max_abs_sum": max_abs, "failed": failed, "tree_girth": tg.value,
+            "n_equations": ne.value}
+
+
+def failed_moduli(failed_row):
+    """The members of one labelling's failed set, ascending, from its bitmap row of check_voltages."""
+    bits = np.unpackbits(np.ascontiguousarray(failed_row, dtype="<u8").view(np.uint8), bitorder="little")
+    return np.flatnonzero(bits)
+
+
+def label_bank(proto, target_girth, T, max_attempts, state, pos, want=1, exact_modulo=0, device=0):
+    """The loop of upstream's random_search_bank_good_codes with a budget (ldpc_hip_label_bank): as label_codes with shifts below the
+    tailbite length T, an attempt being accepted when its voltage check is ok, its smallest lifting min_ok <= T and, with
+    exact_modulo != 0, check_modulo(exact_modulo).  Returns (codes int16 [found, rh, nh], min_ok int32 [found], attempt_index int64
+    [found], attempts_tested, tree_girth, (state, pos) of the generator afterwards)."""
+    lib = load_library()
+    P = np.ascontiguousarray(proto, dtype=np.int16)
+    rh, nh = P.shape
+    st = np.ascontiguousarray(state, dtype=np.uint32)
+    assert st.shape == (624,), "state: the 624 words of std::mt19937"
+    want = int(want)
+    codes = np.zeros((max(want, 0), rh, nh), dtype=np.int16)
+    min_ok = np.zeros(max(want, 0), dtype=np.int32)
+    index = np.zeros(max(want, 0), dtype=np.int64)
+    out = np.zeros(624, dtype=np.uint32)
+    found, tg, pos_out, tested = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+    rc = lib.ldpc_hip_label_bank(rh, nh, P.ctypes.data, int(target_girth), int(T), int(exact_modulo), int(max_attempts), want, st.ctypes.data, int(pos),
+                                 int(device), codes.ctypes.data, min_ok.ctypes.data, index.ctypes.data, C.byref(found), C.byref(tested), C.byref(tg),
+                                 out.ctypes.data, C.byref(pos_out))
+    _check(lib, rc, "ldpc_hip_label_bank")
+    return codes[:found.value], min_ok[:found.value], index[:found.value], tested.value, tg.value, (out, pos_out.value)
 
 
 def qam_modulate(bits, Q, device=0, stream=None):

@@ -40,6 +40,7 @@
 #include "ldpc_gfq_codeset.hpp"
 #include "ldpc_girth.hpp"
 #include "ldpc_label.hpp"
+#include "ldpc_voltage.hpp"
 
 namespace {
 
@@ -1464,3 +1465,4 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_gfq_codeset_api.hpp"
 #include "ldpc_girth_api.hpp"
 #include "ldpc_label_api.hpp"
+#include "ldpc_voltage_api.hpp"

@@ -195,6 +195,8 @@ struct Args {
     uint32_t thresh;             // 2^32 mod M
     uint32_t er_magic;           // floor(2^32 / Er) + 1: j / Er for j < 64 * Er (Er >= 2; one edge needs no division)
     unsigned long long m_magic;  // floor(2^40 / M) + 1: s / M for s < 62 * M, exact as 62 * M * M < 2^40
+    uint32_t div_M;              // an attempt dies on a sum divisible by div_M: M; the bank search (ldpc_voltage.hpp) passes 2^22 with
+                                 // m_magic = 2^18 + 1, so that s / div_M is 0 for every s < 2^21 and only a zero sum is divisible
     uint32_t *rej_raw, *rej;     // rejected words of the round, as found and ascending
     uint32_t rej_cap;
     int n_eq;
@@ -209,6 +211,8 @@ struct Args {
     int n_pairs;
     int16_t *hd_out;             // [want][rh][nh]
     long long *attempt_index;    // [want]
+    const int32_t *min_ok_att;   // [n] per attempt of the round, and
+    int32_t *min_ok_out;         // [want]: the bank search's smallest lifting; NULL otherwise
     long long p;                 // tape index of xw[0]
     uint32_t *state_next;        // [624] raw words behind the last word drawn
 };
@@ -312,7 +316,7 @@ __global__ void __launch_bounds__(64) check_kernel(const Args a) {
         const uint32_t s = (uint32_t)(sum < 0 ? -sum : sum);
         const uint32_t q = (uint32_t)(((unsigned long long)s * a.m_magic) >> 40);
         evaluated += alive ? 1u : 0u;
-        alive = alive && s != q * (uint32_t)a.M;
+        alive = alive && s != q * a.div_M;
     }
     const unsigned long long mask = __ballot(alive);
 #pragma unroll
@@ -380,6 +384,7 @@ __global__ void __launch_bounds__(kSelectThreads) select_kernel(const Args a) {
                     if (tid == 0) {
                         const uint32_t att = wave * 64u + (uint32_t)l;
                         a.attempt_index[k] = a.att_base + att;
+                        if (a.min_ok_out) a.min_ok_out[k] = a.min_ok_att[att];
                         if (k == a.want - 1) s_end = a.p + word_of_draw(a, nrej, (att + 1u) * (uint32_t)a.Er - 1u) + 1;
                     }
                 }

@@ -1,7 +1,10 @@
 // Host side of the labelling search (enumeration and kernels: ldpc_label.hpp): the argument checks, the equation table, the rounds of
-// attempts over the mt19937 word tape of ldpc_mt_api.hpp, and the generator handed back where upstream's loop leaves it.
+// attempts over the mt19937 word tape of ldpc_mt_api.hpp, and the generator handed back where upstream's loop leaves it.  The search
+// serves generate_code here and, through a second pass it knows nothing about, the bank search of ldpc_voltage_api.hpp.
 // Included from ldpc_hip.hip after ldpc_mt_api.hpp.
 #pragma once
+
+#include <functional>
 
 namespace {
 
@@ -60,13 +63,26 @@ extern "C" void ldpc_hip_label_last_stats(long long stats[4]) {
     if (stats) std::copy(t_label_stats, t_label_stats + 4, stats);
 }
 
-extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int target_girth, int M, long long max_attempts, int want,
-                                    const uint32_t state_in[624], int pos_in, int device, int16_t *hd_out, long long *attempt_index, int *found,
-                                    long long *attempts_tested, int *tree_girth, uint32_t state_out[624], int *pos_out) {
+namespace {
+
+// The search: attempts drawn from the tape in rounds, tested, selected in attempt order, the generator handed back.  Without a
+// second pass it is generate_code (ldpc_hip_label_codes): an attempt passes when no sum is divisible by M and no two columns are
+// equal.  A caller with another test (ldpc_hip_label_bank, ldpc_voltage_api.hpp) hands in a SecondPass: check_kernel then drops only
+// the attempts with a zero sum, the caller's kernel narrows the round's bitmap to what it accepts and notes a min_ok per attempt,
+// there is no equal-columns test and no early return for a tree girth below the target.
+struct SecondPass {
+    const char *m_name;                                                                            // what M is called in messages
+    int32_t *min_ok_out;                                                                           // HOST [want]
+    std::function<hipError_t(GirthBuffers &buf, long long n_max, int32_t **min_ok_att)> prepare;   // device [n_max], once per call
+    std::function<void(const ldpc_label::Args &a, unsigned nwaves, hipStream_t st)> launch;        // once per round
+};
+
+int label_search(const char *who, int rh, int nh, const int16_t *proto, int target_girth, int M, const SecondPass *second, long long max_attempts, int want,
+                 const uint32_t state_in[624], int pos_in, int device, int16_t *hd_out, long long *attempt_index, int *found,
+                 long long *attempts_tested, int *tree_girth, uint32_t state_out[624], int *pos_out) {
     using namespace ldpc_label;
-    const char *who = "ldpc_hip_label_codes";
     if (int rc = label_check(who, rh, nh, proto, target_girth)) return rc;
-    if (M < 2 || M > 32767) return fail(LDPC_HIP_EINVAL, "%s: M = %d outside 2 .. 32767", who, M);
+    if (M < 2 || M > 32767) return fail(LDPC_HIP_EINVAL, "%s: %s = %d outside 2 .. 32767", who, second ? second->m_name : "M", M);
     if (max_attempts < 1) return fail(LDPC_HIP_EINVAL, "%s: max_attempts = %lld, must be >= 1", who, max_attempts);
     if (want < 1) return fail(LDPC_HIP_EINVAL, "%s: want = %d, at least one labelling must be asked for", who, want);
     if (!state_in || pos_in < 0 || pos_in > 624) return fail(LDPC_HIP_EINVAL, "%s: state_in is NULL or pos_in = %d outside 0 .. 624", who, pos_in);
@@ -83,15 +99,16 @@ extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int ta
     *attempts_tested = 0;
     std::copy(state_in, state_in + 624, state_out);
     *pos_out = pos_in;
-    if (t.tree_girth < target_girth) return 0;   // upstream returns before any draw
+    if (!second && t.tree_girth < target_girth) return 0;   // upstream returns before any draw
     const int Er = t.n_random;
     if (Er == 0) {   // nothing is drawn: every attempt is the all-zero labelling
         std::vector<int> by_col((size_t)nh * rh);
         for (size_t i = 0; i < by_col.size(); ++i) by_col[i] = t.cell[i] == -1 ? -1 : 0;
-        const bool ok = t.n_equations == 0 && !same_columns(rh, nh, by_col);
+        const bool ok = t.n_equations == 0 && (second || !same_columns(rh, nh, by_col));   // every sum would be 0
         const long long k = ok ? std::min<long long>(want, max_attempts) : 0;
         for (long long c = 0; c < k; ++c) {
             attempt_index[c] = c;
+            if (second) second->min_ok_out[c] = 2;   // no equation: the failed set is empty
             for (int i = 0; i < rh; ++i)
                 for (int j = 0; j < nh; ++j) hd_out[((size_t)c * rh + i) * nh + j] = (int16_t)by_col[(size_t)j * rh + i];
         }
@@ -113,7 +130,7 @@ extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int ta
     GirthBuffers buf;
     Args a{};
     int32_t *d_eq_begin = nullptr, *d_terms = nullptr, *d_cell = nullptr, *d_pairs = nullptr;
-    const std::vector<int32_t> pairs = column_pairs(rh, nh, t.cell);
+    const std::vector<int32_t> pairs = second ? std::vector<int32_t>() : column_pairs(rh, nh, t.cell);
     std::vector<int32_t> terms(t.term_edge.size());
     for (size_t i = 0; i < terms.size(); ++i) terms[i] = (t.term_edge[i] << 8) | (t.term_mult[i] & 0xff);
     HIP_TRY(buf.get(&d_eq_begin, sizeof(int32_t) * t.eq_begin.size()));
@@ -131,18 +148,23 @@ extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int ta
     a.Er = Er; a.M = M;
     a.thresh = (uint32_t)((1ull << 32) % (unsigned long long)M);
     a.er_magic = Er >= 2 ? (uint32_t)((1ull << 32) / (unsigned long long)Er + 1ull) : 0u;
-    a.m_magic = (1ull << 40) / (unsigned long long)M + 1ull;
+    a.div_M = second ? 1u << 22 : (uint32_t)M;
+    a.m_magic = (1ull << 40) / (unsigned long long)a.div_M + 1ull;
     a.n_eq = t.n_equations; a.eq_begin = d_eq_begin; a.terms = d_terms;
     a.rh = rh; a.nh = nh; a.want = want; a.cell = d_cell;
     a.pairs = d_pairs; a.n_pairs = (int)(pairs.size() / 2);
     a.state_next = c->mt.d_state_next;
     const size_t lds = sizeof(int16_t) * (size_t)kRowStride * (size_t)Er;
+    if (second) HIP_TRY(buf.get(&a.min_ok_out, sizeof(int32_t) * (size_t)want));
 
     // the largest round of this call sizes the redraw lists and the survivor bitmap
     const long long n_max = std::min(std::min(forced ? forced : round_cap, round_cap), max_attempts);
     HIP_TRY(buf.get(&a.rej_raw, sizeof(uint32_t) * (size_t)(64 + n_max * Er / 8192 + 1)));
     HIP_TRY(buf.get(&a.rej, sizeof(uint32_t) * (size_t)(64 + n_max * Er / 8192 + 1)));
     HIP_TRY(buf.get(&a.bitmap, sizeof(unsigned long long) * (size_t)((n_max + 63) / 64)));
+    int32_t *min_ok_att = nullptr;
+    if (second) HIP_TRY(second->prepare(buf, n_max, &min_ok_att));
+    a.min_ok_att = min_ok_att;
 
     long long tested = 0, accepted = 0;
     long long n_next = forced ? forced : kLabelFirstRound;
@@ -169,6 +191,7 @@ extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int ta
         hipLaunchKernelGGL(mark_kernel, dim3(mark_blocks), dim3(256), 0, st, a);
         hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(256), 0, st, a);
         hipLaunchKernelGGL(check_kernel, dim3((unsigned)nwaves), dim3(64), lds, st, a);
+        if (second) second->launch(a, (unsigned)nwaves, st);
         hipLaunchKernelGGL(select_kernel, dim3(1), dim3(kSelectThreads), lds, st, a);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(c->mt.d_state, c->mt.d_state_next, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToDevice, st));
@@ -194,10 +217,20 @@ extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int ta
     if (accepted > 0) {
         HIP_TRY(hipMemcpy(hd_out, a.hd_out, sizeof(int16_t) * (size_t)accepted * rh * nh, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(attempt_index, a.attempt_index, sizeof(long long) * (size_t)accepted, hipMemcpyDeviceToHost));
+        if (second) HIP_TRY(hipMemcpy(second->min_ok_out, a.min_ok_out, sizeof(int32_t) * (size_t)accepted, hipMemcpyDeviceToHost));
     }
     HIP_TRY(hipMemcpy(state_out, c->mt.d_state, sizeof(uint32_t) * ldpc_mt::MTN, hipMemcpyDeviceToHost));
     *pos_out = 0;
     *found = (int)accepted;
     *attempts_tested = tested;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int ldpc_hip_label_codes(int rh, int nh, const int16_t *proto, int target_girth, int M, long long max_attempts, int want,
+                                    const uint32_t state_in[624], int pos_in, int device, int16_t *hd_out, long long *attempt_index, int *found,
+                                    long long *attempts_tested, int *tree_girth, uint32_t state_out[624], int *pos_out) {
+    return label_search("ldpc_hip_label_codes", rh, nh, proto, target_girth, M, nullptr, max_attempts, want, state_in, pos_in, device, hd_out, attempt_index,
+                        found, attempts_tested, tree_girth, state_out, pos_out);
 }
