@@ -70,6 +70,12 @@ __device__ __forceinline__ void static_for(F &&f) {
         static_for<B + 1, E>(f);
     }
 }
+// f(IC<B>{}), ..., f(IC<E - 1>{}) in turn while they return false: true when none returned true
+template <int B, int E, class F>
+__device__ __forceinline__ bool static_none(F &&f) {
+    if constexpr (B < E) return f(IC<B>{}) ? false : static_none<B + 1, E>(f);
+    else return true;
+}
 
 __device__ __forceinline__ u32 hi32(double x) { return (u32)__double2hiint(x); }
 __device__ __forceinline__ u32 lo32(double x) { return (u32)__double2loint(x); }
@@ -111,9 +117,21 @@ __device__ __forceinline__ u32 sel32_tied(u32 if0, u32 if1, mask64 m, u32 tie) {
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(if0), "v"(if1), "s"(m), "v"(tie));
     return d;
 }
+// A use of v where it stands, and no instruction: what v is computed from cannot be moved behind it.
+template <class T>
+__device__ __forceinline__ void pin(T v) { asm volatile("" : : "v"(v)); }
+// signed_mag as ONE v_bfi_b32, said so.  Where the compiler can tell that mag >= 0 (a minimum of absolute values) it drops the mask on
+// mag and is left with v_and_b32 + v_or_b32; whether it can tell has turned on instructions that have nothing to do with the value
+// (ms_m64_body, the syndrome word of a block row).  The mask is a scalar operand: a VOP3 of gfx9 takes no literal.
+__device__ __forceinline__ double signed_mag_bfi(double mag, u32 sign_src) {
+    u32 h;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(h) : "s"(0x7fffffffu), "v"(hi32(mag)), "v"(sign_src));
+    return mk(h, lo32(mag));
+}
 // LDS byte address <-> pointer.  An address formed as an integer reaches ds_* as it is: register + constant = the instruction's
 // offset field, and no late `v_add_u32 v, <base of the dynamic LDS>, v` per access (the base resolves to 0 but is not folded).
 typedef __attribute__((address_space(3))) double lds_f64;
+typedef __attribute__((address_space(3), may_alias)) int lds_i32;   // one dword of an fp64 image value, read as it is
 __device__ __forceinline__ u32 lds_addr(const double *p) { return (u32)(unsigned long)(const lds_f64 *)p; }
 __device__ __forceinline__ double *lds_at(u32 addr) { return (double *)(lds_f64 *)(unsigned long)addr; }
 
@@ -434,6 +452,12 @@ constexpr int ms_m64_first_row(int k) {        // first block row with an edge i
     return -1;
 }
 template <class C>
+constexpr int ms_m64_first_row_from(int k, int j0) {   // first block row >= j0 with an edge in block column k, or -1
+    for (int j = j0; j < C::RH; ++j)
+        if (ms_m64_slot_of<C>(j, k) >= 0) return j;
+    return -1;
+}
+template <class C>
 constexpr int ms_m64_last_row(int k) {
     for (int j = C::RH - 1; j >= 0; --j)
         if (ms_m64_slot_of<C>(j, k) >= 0) return j;
@@ -615,6 +639,20 @@ constexpr int ms_m64_carry_rows() {
     return rows;
 }
 
+// FILTER ROWS.  The syndrome has one consumer, the vote "did every check pass?", and the answer is no in every iteration of a frame
+// but its last (at 0 dB: in all of them).  Only block rows [0, FR) form their syndrome word inside STATE3; a failing check among
+// them already says "not converged".  The other rows' checks are looked at on demand, behind the vote over the filter rows, from
+// the soft values where the outputs will read them (see the pass in ms_m64_body): the same bits, the same decision.  FR is the
+// same for every code, kMsM64FilterRows or all RH rows of a code that has no more.  Measured on the example code at 0, 1, 2 and 4
+// rows, at 0 and 2 dB (profiles/r32_flagship_variants.txt): one row is enough at 0 dB, where some check of any row fails in every
+// iteration, but at 2 dB a single row passes often enough while a later one fails to send the wave into the pass for nothing.
+// The pass leaves at the first group of kMsM64ExitRows block rows with a failing check (a scalar branch per group): frames that
+// never converge sit on a few failing checks and enter the pass in most of their iterations.  One exit at the end was as fast at
+// 0 dB and 2.4 % slower at 2 dB than an exit every 4 rows; every row and every 2 rows were no faster than 4 (same file).
+constexpr int kMsM64FilterRows = 2, kMsM64ExitRows = 4;
+template <class C>
+constexpr int ms_m64_filter_rows() { return kMsM64FilterRows < C::RH ? kMsM64FilterRows : C::RH; }
+
 // KPCAP, YD, YROW and KRSET are switches for tools/ab_flagship.hip, defaulted to what ships: the cap of ms_m64_prefix_rows; the
 // depth of STATE2's stream of channel loads; where its first group is issued (-1: at the start of STATE2, j >= 0: after block row
 // j of STATE1); the number of carried rows (-1: ms_m64_carry_rows).
@@ -622,13 +660,19 @@ constexpr int ms_m64_carry_rows() {
 // That instance never writes the soft value of a local column to the image; it folds the value's sign into the bit word `hb`, the
 // outputs ballot that bit, and the image slots of the local columns hold resident channel values (ms_m64_resident_cols).  RSET and
 // BITW are switches for the tool again: the number of resident columns (-1: the rule; at most the rule's), and whether the hard
-// bits of the local columns come from the bit word (-1: exactly when SOFT is false, which cannot do without).
-template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1, bool SOFT = true, int RSET = -1, int BITW = -1>
+// bits of the local columns come from the bit word (-1: exactly when SOFT is false, which cannot do without).  FRSET and XGSET: the
+// number of filter rows (-1: ms_m64_filter_rows; RH or more: every row forms its syndrome word in STATE3, the body before round 32)
+// and the block rows per exit of the on-demand pass (-1: kMsM64ExitRows).
+template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1, bool SOFT = true, int RSET = -1, int BITW = -1,
+          int FRSET = -1, int XGSET = -1>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     static_assert(YD >= 1 && YROW >= -1 && YROW < C::RH && KRSET <= C::RH, "ms_m64_body: switch out of range");
     static_assert(RSET <= ms_m64_resident_cols<C, SOFT>() && (SOFT || BITW != 0), "ms_m64_body: switch out of range");
+    static_assert(FRSET >= -1 && XGSET >= -1 && XGSET != 0, "ms_m64_body: switch out of range");
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
+    constexpr int FR = FRSET < 0 ? ms_m64_filter_rows<C>() : FRSET < C::RH ? FRSET : C::RH;   // block rows [0, FR) form their syndrome word in STATE3
+    constexpr int XG = XGSET < 0 ? kMsM64ExitRows : XGSET;
     constexpr int RES = RSET >= 0 ? RSET : ms_m64_resident_cols<C, SOFT>();   // non-local columns number [0, RES) are resident
     constexpr bool BITS = BITW < 0 ? !SOFT : BITW != 0;
     constexpr int NLOC = ms_m64_local_cols<C>(), HBW = BITS ? (NLOC + 31) / 32 : 0;
@@ -926,7 +970,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     double pf[RW > 1 ? RW - 1 : 1];
                     static_for<0, RW>([&](auto S) {
                         constexpr int s = decltype(S)::value;
-                        sy ^= hi32(r[s]);
+                        if constexpr (j < FR) sy ^= hi32(r[s]);
                         const double tt = r[s] - keep[j][s] * alpha_mag;   // v2c; the carried value: no decode, see `keep`
                         nS ^= hi32(tt);
                         tt_[s] = tt;
@@ -942,12 +986,12 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                         else if constexpr (s == 0) mag = suf;
                         else mag = fmin(pf[s - 1], suf);
                         if constexpr (s > 0) suf = fmin(fabs(tt_[s]), suf);
-                        keep[j][s] = signed_mag(mag, hi32(tt_[s]) ^ nS);   // own v2c sign xor row parity, on bit 31
+                        keep[j][s] = signed_mag_bfi(mag, hi32(tt_[s]) ^ nS);   // own v2c sign xor row parity, on bit 31
                     });
                 } else {
                     static_for<0, RW>([&](auto S) {
                         constexpr int s = decltype(S)::value;
-                        sy ^= hi32(r[s]);
+                        if constexpr (j < FR) sy ^= hi32(r[s]);
                         step(S, keep[j][s] * alpha_mag);     // the carried value: no decode, see `keep`
                     });
                 }
@@ -958,7 +1002,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 asm volatile("" : "+v"(a1), "+v"(a2));  // two products per ROW, not one per edge
                 static_for<0, RW>([&](auto S) {
                     constexpr int s = decltype(S)::value;
-                    sy ^= hi32(r[s]);
+                    if constexpr (j < FR) sy ^= hi32(r[s]);
                     if constexpr (ms_m64_local_col<C>(C::COL[j][s])) {
                         Wt = twice(Wt);
                         step(S, keep[j][s] * alpha_mag);     // decoded at the column's first block row
@@ -974,14 +1018,16 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             // both stay 32 bits wide.  Left to itself the compiler xors whole doubles (a second chain over the LOW words of
             // the soft values: 96 v_xor_b32 per iteration), ors the rows' words as 64-bit values, keeps all RH of them live
             // to the end of STATE3 and ends the loop in a 64-bit compare (profiles/r18_flagship_isa_histogram.txt).
-            failw |= sy;
+            // Only a filter row has a word at all (ms_m64_filter_rows); the others are looked at behind the vote, and only on demand.
+            // The opaque point stays on every row: it is no instruction.
+            if constexpr (j < FR) failw |= sy;
             asm volatile("" : "+v"(failw));
             if constexpr (j < KR) {
                 if constexpr (j >= KP::value) {             // a row below KP has formed its new c2v values above
                     u32 W = (nS ^ (0u - (__popc(nS) & 1u))) << (32 - RW);   // slot s on bit 31 - s, row parity folded in
                     static_for<0, RW>([&](auto S) {
                         constexpr int s = decltype(S)::value;
-                        keep[j][s] = signed_mag(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
+                        keep[j][s] = signed_mag_bfi(sel64(nm1, nm2, lanes_oeq(fabs(tt_[s]), nm1)), W);
                         W = twice(W);
                     });
                 }
@@ -990,7 +1036,65 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if (__ballot((failw >> 31) != 0) == 0ull) { res = iter + 1; break; }  // :4761-4766
+        // The vote over the filter rows (all rows of a code with RH <= FR).  A failing check there: not converged, as a vote over all
+        // rows would have found.  Otherwise the checks of rows [FR, RH) ON DEMAND, a cold block behind this scalar branch.  The soft
+        // values of this iteration are still where the outputs read them -- STATE3 writes the image of no column that is not
+        // local -- and STATE3 folded nothing but their signs into sy.  The body has no vector register to spare at this point (255
+        // of 256 are carried values), so the pass forms no rotated address.  It takes the signs of a block column as the outputs
+        // do, as ONE lane mask: a ballot over the high dword of the lane's own slot (at most one VGPR in flight), over a local
+        // column's own slot (SOFT) or over the column's bit of its bit word (BITS).  Check `lane` of a block row meets variable
+        // (lane + c) mod 64 of the column, bit `lane` of the mask rotated right by c: the rotation, the xor over the row's edges
+        // and the or over a group's rows are scalar instructions.  A column's mask is formed in the group that needs it first.
+        // The pass leaves at the first group of XG block rows with a failing check.
+        if constexpr (FR >= RH) {
+            if (__ballot((failw >> 31) != 0) == 0ull) { res = iter + 1; break; }  // :4761-4766
+        } else {
+          // What STATE3 hands to the next iteration is used here, in front of the branch.  Its only other uses are in the next
+          // iteration, and left alone the compiler sinks the arithmetic of rows [FR, RH) behind the pass, to the loop's end, with
+          // every image value that STATE3 read live across the pass (some 330 VGPRs spilled).  No instruction comes of it.
+          static_for<0, RH>([&](auto J) {
+              constexpr int j = decltype(J)::value;
+              if constexpr (j < KR) static_for<0, C::RW[j]>([&](auto S) { pin(keep[j][decltype(S)::value]); });
+              else { pin(m1[j]); pin(m2[j]); pin(meta[j]); }
+          });
+          // One way back to the loop's head: the exits of the pass meet in front of a vote on `more`, which the compiler cannot
+          // fold on the paths that go on (a ballot of `true` is the exec mask): the loop keeps a single back edge.
+          bool more = true;
+          if (__ballot((failw >> 31) != 0) == 0ull) {
+            u64 sg[NH];
+            u32 own_hi = hi + 4u;   // opaque, behind the branch: none of the pass's loads is moved up into the iteration
+            asm volatile("" : "+v"(own_hi));
+            if (static_none<0, (RH - FR + XG - 1) / XG>([&](auto G) -> bool {   // true: a check of the group fails
+                    constexpr int j0 = FR + decltype(G)::value * XG, j1 = j0 + XG < RH ? j0 + XG : RH;
+                    // the masks of the columns that this group is the first to need: two loads in flight, not a group's worth
+                    static_for<0, NH>([&](auto K) {
+                        constexpr int k = decltype(K)::value, jf = ms_m64_first_row_from<C>(k, FR);
+                        if constexpr (jf >= j0 && jf < j1) {
+                            if constexpr (!ms_m64_local_col<C>(k) || !BITS) {
+                                sg[k] = __ballot(*(const lds_i32 *)(unsigned long)(own_hi + (u32)(k * 512)) < 0);
+                            } else {
+                                constexpr int w = ms_m64_local_place<C>(k) / 32, up = 31 - ms_m64_local_bit<C>(k);   // constants, not code
+                                sg[k] = __ballot((int)(hb[w] << up) < 0);
+                            }
+                            if constexpr (k % 2 == 1) __builtin_amdgcn_sched_barrier(0);
+                        }
+                    });
+                    u64 bad = 0ull;
+                    static_for<j0, j1>([&](auto J) {
+                        constexpr int j = decltype(J)::value;
+                        u64 par = 0ull;
+                        static_for<0, C::RW[j]>([&](auto S) {
+                            constexpr int s = decltype(S)::value, k = C::COL[j][s], c = C::SH[j][s];
+                            if constexpr (c == 0) par ^= sg[k];
+                            else par ^= (sg[k] >> c) | (sg[k] << (64 - c));
+                        });
+                        bad |= par;
+                    });
+                    return bad != 0ull;
+                })) more = false;
+          }
+          if (__ballot(more) == 0ull) { res = iter + 1; break; }  // :4761-4766
+        }
     }
 
     // ---------------- outputs

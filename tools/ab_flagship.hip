@@ -2,7 +2,8 @@
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
 // -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds] [persistent 0|1] [first variant timed in every round]
-// Results: profiles/r26_flagship_variants.txt: resident channel values, soft values kept or not, the bit word -- the SOFT, RSET and
+// Results: profiles/r32_flagship_variants.txt: the filter rows and the on-demand syndrome pass -- the FRSET and XGSET parameters of the
+// header's body -- at 0 and 2 dB.  profiles/r26_flagship_variants.txt: resident channel values, soft values kept or not, the bit word -- the SOFT, RSET and
 // BITW parameters of the header's body -- in both launch forms (argument 4).  profiles/r25_flagship_variants.txt: STATE2 of ms_m64_body streams its channel loads over the non-local block columns, YD
 // of them ahead, first group at the start of STATE2 or after a block row of STATE1 (YROW), and the body carries KR block rows -- the
 // YD, YROW and KRSET parameters of the header's body; depth 32 issues every load at once, which is what the schedule before round 25
@@ -724,6 +725,28 @@ RESIDENT(k_h_r12, false, 12, 1)
 RESIDENT(k_h_r17, false, 17, 1)
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped_hard(const SpecArgs a) { ldpc_spec::ms_m64_hard_body<Code>(a); }
 
+// round 32: how many block rows form their syndrome word inside STATE3 (FRSET; 16 = all of them, the body round 26 shipped; 0 = none,
+// the pass runs in every iteration) and after how many block rows the on-demand pass over the others can leave (XGSET); with and
+// without soft values.  profiles/r32_flagship_variants.txt
+#define FILTER(name, soft, fr, xg) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, ldpc_spec::kMsM64YDepth, -1, -1, soft, -1, -1, fr, xg>(a); }
+FILTER(k_s_f16, true, 16, 2)
+FILTER(k_s_f0, true, 0, 2)
+FILTER(k_s_f1, true, 1, 2)
+FILTER(k_s_f2, true, 2, 2)
+FILTER(k_s_f4, true, 4, 2)
+FILTER(k_h_f16, false, 16, 2)
+FILTER(k_h_f0, false, 0, 2)
+FILTER(k_h_f1, false, 1, 2)
+FILTER(k_h_f2, false, 2, 2)
+FILTER(k_h_f4, false, 4, 2)
+FILTER(k_h_f1_x1, false, 1, 1)
+FILTER(k_h_f1_x4, false, 1, 4)
+FILTER(k_h_f1_x16, false, 1, 16)
+FILTER(k_h_f2_x1, false, 2, 1)
+FILTER(k_h_f2_x4, false, 2, 4)
+FILTER(k_h_f2_x16, false, 2, 16)
+
 struct Variant { const void *kern; const char *name; size_t lds; bool soft = true; };   // soft: the kernel writes soft_out
 
 int main(int argc, char **argv) {
@@ -765,6 +788,22 @@ int main(int argc, char **argv) {
         {(const void *)k_h_r12, "no soft values, 12 resident columns", L, false},
         {(const void *)k_h_r17, "no soft values, 17 resident columns (all)", L, false},
         {(const void *)k_shipped_hard, "ms_m64_hard_body as shipped (ldpc_spec.hpp)", L, false},
+        {(const void *)k_s_f16, "soft values, every row's syndrome in STATE3 (round 26's body)", L},
+        {(const void *)k_s_f0, "soft values, no filter row: the pass in every iteration", L},
+        {(const void *)k_s_f1, "soft values, 1 filter row, exit every 2 rows", L},
+        {(const void *)k_s_f2, "soft values, 2 filter rows, exit every 2 rows", L},
+        {(const void *)k_s_f4, "soft values, 4 filter rows, exit every 2 rows", L},
+        {(const void *)k_h_f16, "no soft values, every row's syndrome in STATE3 (round 26's body)", L, false},
+        {(const void *)k_h_f0, "no soft values, no filter row: the pass in every iteration", L, false},
+        {(const void *)k_h_f1, "no soft values, 1 filter row, exit every 2 rows", L, false},
+        {(const void *)k_h_f2, "no soft values, 2 filter rows, exit every 2 rows", L, false},
+        {(const void *)k_h_f4, "no soft values, 4 filter rows, exit every 2 rows", L, false},
+        {(const void *)k_h_f1_x1, "no soft values, 1 filter row, exit every row", L, false},
+        {(const void *)k_h_f1_x4, "no soft values, 1 filter row, exit every 4 rows", L, false},
+        {(const void *)k_h_f1_x16, "no soft values, 1 filter row, one exit at the end", L, false},
+        {(const void *)k_h_f2_x1, "no soft values, 2 filter rows, exit every row", L, false},
+        {(const void *)k_h_f2_x4, "no soft values, 2 filter rows, exit every 4 rows", L, false},
+        {(const void *)k_h_f2_x16, "no soft values, 2 filter rows, one exit at the end", L, false},
     };
     constexpr int NV = sizeof var / sizeof var[0];
     const long long distinct = std::min<long long>(B, 4096);
