@@ -575,26 +575,48 @@ constexpr int ms_m64_resident_slot(int i) {   // image slot (512 B units from `h
         if (ms_m64_local_col<C>(k) && n-- == 0) return k;
     return -1;
 }
-// The hard bits of the local columns without LDS: STATE3 forms the soft value of a local column at the column's first block row,
-// in ascending (block row, slot) order, and shifts its sign into word p / 32 of `hb`, p = the column's place in that order.
+// A local column that STATE1 FILLS (kMsM64State1Fill below): its whole work stands among STATE1's LDS operations, not in STATE3.
+// Every one of its rows is carried (below kr: the work reads and writes `keep` of those rows and nothing else), and none of them is
+// a filter row (below fr: such a row folds the sign of the column's soft value into its syndrome word, and STATE3 would have to
+// hold that value, or a register for its sign, for nothing else).  kr = 0: no column.
+template <class C>
+constexpr bool ms_m64_fill_col(int k, int kr, int fr) {
+    return ms_m64_local_col<C>(k) && ms_m64_last_row<C>(k) < kr && ms_m64_first_row<C>(k) >= fr;
+}
+// The hard bits of the local columns without LDS: the body forms the soft value of a local column once per iteration -- the columns
+// that STATE1 fills first, then the others in STATE3 at the column's first block row, both in ascending (block row, slot) order --
+// and shifts its sign into word p / 32 of `hb`, p = the column's place in that order.
 // Which place, and which bit of its word the column has once the word's last column is in (the first one in sits highest).
 template <class C>
-constexpr int ms_m64_local_place(int k) {
+constexpr int ms_m64_local_place(int k, int kr = 0, int fr = 0) {
     int p = 0;
-    for (int j = 0; j < C::RH; ++j)
-        for (int s = 0; s < C::RW[j]; ++s) {
-            const int kk = C::COL[j][s];
-            if (ms_m64_local_col<C>(kk) && ms_m64_first_row<C>(kk) == j) {
-                if (kk == k) return p;
-                ++p;
+    for (int filled = 1; filled >= 0; --filled)
+        for (int j = 0; j < C::RH; ++j)
+            for (int s = 0; s < C::RW[j]; ++s) {
+                const int kk = C::COL[j][s];
+                if (ms_m64_local_col<C>(kk) && ms_m64_first_row<C>(kk) == j && ms_m64_fill_col<C>(kk, kr, fr) == (filled != 0)) {
+                    if (kk == k) return p;
+                    ++p;
+                }
             }
-        }
     return -1;
 }
 template <class C>
-constexpr int ms_m64_local_bit(int k) {
-    const int p = ms_m64_local_place<C>(k), w = p / 32, left = ms_m64_local_cols<C>() - 32 * w;
+constexpr int ms_m64_local_bit(int k, int kr = 0, int fr = 0) {
+    const int p = ms_m64_local_place<C>(k, kr, fr), w = p / 32, left = ms_m64_local_cols<C>() - 32 * w;
     return (left < 32 ? left : 32) - 1 - (p - 32 * w);
+}
+template <class C>
+constexpr int ms_m64_fill_cols(int kr, int fr) {   // how many columns STATE1 fills, and the i-th of them in the order of their places
+    int n = 0;
+    for (int k = 0; k < C::NH; ++k) n += ms_m64_fill_col<C>(k, kr, fr) ? 1 : 0;
+    return n;
+}
+template <class C>
+constexpr int ms_m64_fill_col_at(int i, int kr, int fr) {
+    for (int k = 0; k < C::NH; ++k)
+        if (ms_m64_fill_col<C>(k, kr, fr) && ms_m64_local_place<C>(k, kr, fr) == i) return k;
+    return -1;
 }
 
 // The loads are a stream over those columns, kMsM64YDepth of them ahead: the first min(depth, count) are issued together, two
@@ -653,6 +675,19 @@ constexpr int kMsM64FilterRows = 2, kMsM64ExitRows = 4;
 template <class C>
 constexpr int ms_m64_filter_rows() { return kMsM64FilterRows < C::RH ? kMsM64FilterRows : C::RH; }
 
+// STATE1 FILL.  STATE1 of a carried row is a run of LDS stores and atomics with 64 address selects as its only vector work, and
+// STATE3 holds nearly all of an iteration's arithmetic.  Part of STATE3's arithmetic needs nothing that STATE1 or STATE2 produce
+// and can issue under STATE1's LDS operations, in the registers it already occupies (see `keep` in ms_m64_body):
+//   1  x = keep * |alpha| of a carried edge that goes through LDS, right behind the edge's own store or atomic;
+//   2  and the whole of a local column whose rows are all carried (ms_m64_fill_col): sum, soft value, hard bit and the v2c
+//      values tt = soft - x of its edges.
+// Every moved instruction keeps its operands, its operation and its rounding order.  0 is the body without either.  The columns
+// take their turns one per carried row (more where a code has more of them than carried rows), behind the row's LDS operations;
+// each column's channel value is loaded kMsM64FillAhead columns ahead.  Measured on the example code, whose columns 2 to 13
+// move (profiles/r33_flagship_variants.txt): 1 alone gains less than three spreads, 2 clears them with and without soft
+// values, and the same columns in front of the row's LDS operations (S1SET = 3 of the body) gain no more than 1 does.
+constexpr int kMsM64State1Fill = 2, kMsM64FillAhead = 2;
+
 // KPCAP, YD, YROW and KRSET are switches for tools/ab_flagship.hip, defaulted to what ships: the cap of ms_m64_prefix_rows; the
 // depth of STATE2's stream of channel loads; where its first group is issued (-1: at the start of STATE2, j >= 0: after block row
 // j of STATE1); the number of carried rows (-1: ms_m64_carry_rows).
@@ -662,14 +697,19 @@ constexpr int ms_m64_filter_rows() { return kMsM64FilterRows < C::RH ? kMsM64Fil
 // BITW are switches for the tool again: the number of resident columns (-1: the rule; at most the rule's), and whether the hard
 // bits of the local columns come from the bit word (-1: exactly when SOFT is false, which cannot do without).  FRSET and XGSET: the
 // number of filter rows (-1: ms_m64_filter_rows; RH or more: every row forms its syndrome word in STATE3, the body before round 32)
-// and the block rows per exit of the on-demand pass (-1: kMsM64ExitRows).
+// and the block rows per exit of the on-demand pass (-1: kMsM64ExitRows).  S1SET: what of STATE3's arithmetic stands among STATE1's LDS
+// operations (-1: kMsM64State1Fill; 0: nothing, the body before round 33; 1: the products x; 2: and the local columns of
+// ms_m64_fill_col behind the LDS operations of a carried row; 3: the same columns in front of them).
 template <class C, int KPCAP = 1 << 30, int YD = kMsM64YDepth, int YROW = -1, int KRSET = -1, bool SOFT = true, int RSET = -1, int BITW = -1,
-          int FRSET = -1, int XGSET = -1>
+          int FRSET = -1, int XGSET = -1, int S1SET = -1>
 __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     static_assert(C::M == 64, "ms_m64_body: one frame per wavefront needs M == 64");
     static_assert(YD >= 1 && YROW >= -1 && YROW < C::RH && KRSET <= C::RH, "ms_m64_body: switch out of range");
     static_assert(RSET <= ms_m64_resident_cols<C, SOFT>() && (SOFT || BITW != 0), "ms_m64_body: switch out of range");
-    static_assert(FRSET >= -1 && XGSET >= -1 && XGSET != 0, "ms_m64_body: switch out of range");
+    static_assert(FRSET >= -1 && XGSET >= -1 && XGSET != 0 && S1SET >= -1 && S1SET <= 3, "ms_m64_body: switch out of range");
+    // (a body whose filter rows the tool sets is the body of an earlier round and keeps that round's STATE1 unless S1SET says otherwise:
+    // with every row's syndrome word in STATE3 the instance with soft values has no registers for the fill, it spills 2)
+    constexpr int S1 = S1SET >= 0 ? S1SET : FRSET < 0 ? kMsM64State1Fill : 0;
     constexpr int RH = C::RH, NH = C::NH, N = C::NH * 64;
     constexpr int FR = FRSET < 0 ? ms_m64_filter_rows<C>() : FRSET < C::RH ? FRSET : C::RH;   // block rows [0, FR) form their syndrome word in STATE3
     constexpr int XG = XGSET < 0 ? kMsM64ExitRows : XGSET;
@@ -680,6 +720,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // rows [0, KP) of them by prefix / suffix minima.  A type, not a second constant: STATE3's closure would capture the constant, and
     // with that one pointer more a 30 x 60 protograph that carries no row spilled 240 VGPRs (profiles/r23_flagship_isa_histogram.txt).
     typedef IC<ms_m64_prefix_rows<KPCAP>(KR)> KP;
+    // STATE1 fills the NF local columns ms_m64_fill_col(k, KF, FR), FPER of them per carried row, each column's channel value loaded
+    // kMsM64FillAhead columns ahead
+    constexpr int KF = S1 >= 2 ? KR : 0, NF = ms_m64_fill_cols<C>(KF, FR), FPER = KR > 0 ? (NF + KR - 1) / KR : 0;
     extern __shared__ double lds[];  // 512 B unused, then [N] soft / acc (fp64): kMsM64LdsBytes(N); then the spare slots, up to kMsM64FrameLdsBytes(N)
     const int lane = threadIdx.x;
     const double alpha = a.alpha, alpha_mag = fabs(a.alpha);
@@ -769,7 +812,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 asm volatile("" : "+s"(so));   // opaque where it stands, as yo above, but on the scalar side
                 static_for<0, C::RW[jn]>([&](auto S) {
                     constexpr int k = C::COL[jn][decltype(S)::value];
-                    if constexpr (ms_m64_local_col<C>(k) && ms_m64_first_row<C>(k) == jn) {
+                    if constexpr (ms_m64_local_col<C>(k) && ms_m64_first_row<C>(k) == jn && !ms_m64_fill_col<C>(k, KF, FR)) {
                         typedef u32 u32x2 __attribute__((ext_vector_type(2)));
                         const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
                         yl[k] = mk(v.y, v.x);
@@ -777,6 +820,52 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 });
             }
         };
+        // A local column that STATE1 fills (ms_m64_fill_col), number i of them: what STATE3 did for it at its first block row and at
+        // each of its rows, here, from the same operands in the same order.  The old c2v values of its edges are in keep of its
+        // rows, all carried: added in ascending block row, the first one taken as it is; pr = acc * alpha; soft = (y + 0.0) + pr;
+        // the sign into the bit word or the value into the image, for the outputs and the on-demand pass; and per edge the v2c value
+        // tt = soft - keep * |alpha|, which takes the place of the keep it came from.  Nothing here touches the image slot of
+        // another column, and STATE3 finds tt where it found the operand of x.  The value is pinned where it stands.
+        auto load_fill_y = [&](auto I) {
+            if constexpr (decltype(I)::value < NF) {
+                constexpr int k = ms_m64_fill_col_at<C>(decltype(I)::value, KF, FR);
+                u32 so = 0;
+                asm volatile("" : "+s"(so));
+                typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ybuf, (int)lane8, (int)(so + (u32)(k * 512)), 0);
+                yl[k] = mk(v.y, v.x);
+            }
+        };
+        auto fill = [&](auto I) {
+            constexpr int i = decltype(I)::value, k = ms_m64_fill_col_at<C>(i, KF, FR), j0 = ms_m64_first_row<C>(k);
+            load_fill_y(IC<i + kMsM64FillAhead>{});
+            double acc = 0.0;
+            static_for<j0, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
+                constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
+                if constexpr (ss >= 0) {
+                    if constexpr (jj == j0) acc = keep[jj][ss];
+                    else acc = acc + keep[jj][ss];
+                }
+            });
+            const double pr = acc * alpha;
+            const double soft = (yl[k] + 0.0) + pr;
+            if constexpr (BITS) {
+                constexpr int w = ms_m64_local_place<C>(k, KF, FR) / 32;
+                hb[w] = __builtin_amdgcn_alignbit(hb[w], hi32(soft), 31);
+            }
+            if constexpr (SOFT) *own(IC<k>{}) = soft;
+            static_for<j0, ms_m64_last_row<C>(k) + 1>([&](auto JJ) {
+                constexpr int jj = decltype(JJ)::value, ss = ms_m64_slot_of<C>(jj, k);
+                if constexpr (ss >= 0) {
+                    // (a use, not an opaque copy: behind a copy the compiler no longer knows the value for the result of a
+                    // subtraction and canonicalises it, one v_max_f64 each, in front of STATE3's minima)
+                    const double tt = soft - keep[jj][ss] * alpha_mag;
+                    pin(tt);
+                    keep[jj][ss] = tt;
+                }
+            });
+        };
+        static_for<0, (kMsM64FillAhead < NF ? kMsM64FillAhead : NF)>([&](auto I) { load_fill_y(I); });
         // The decoded c2v value of an edge, cv = +-(s == pos ? m2 : m1), is needed twice: in STATE1 (added into the variable) and
         // in STATE3 (x = alpha * cv, taken out of the variable's sum again).  STATE3 of the iteration before had everything cv is
         // made of in registers.  Block rows [0, KR) therefore form cv there, once, and CARRY it in keep[j][s] to the next
@@ -814,12 +903,23 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
         // An edge of a LOCAL column is not scattered in STATE1 at all (no LDS operation).  STATE3 at the column's first block row
         // takes the carried value of a row below KR as it is, decodes the record of a row past KR and puts that value into
         // keep[j][s] for the edge's own row (within the iteration only).
+        // WHAT keep[j][s] HOLDS, with the fill of STATE1 (S1, kMsM64State1Fill), slot s of a carried row j:
+        //   an edge that goes through LDS:   from STATE3 of row j to the edge's LDS operation in STATE1 of the next iteration the
+        //       c2v value cv (+0.0 in a frame's first iteration); from right behind that operation to STATE3 of row j the
+        //       product x = cv * |alpha| (S1 >= 1), which STATE3 subtracts as it is.  The scatter was cv's only other use;
+        //   an edge of a column that STATE1 fills (S1 >= 2):   cv up to the column's turn in STATE1, from there to STATE3 of row j
+        //       the v2c value tt = soft - cv * |alpha|, which STATE3 takes as it is: it reads no soft value for the slot;
+        //   an edge of any other local column:   cv, from STATE3 of row j to STATE3 of row j of the next iteration, as before
+        //       (x is formed there, from an operand that is opaque where it stands).
+        //   The moved instructions have the operands, the operation and the order they had in STATE3: the arguments above hold
+        //   word for word.  A new frame starts from +0.0 in every slot, whatever of x and tt the frame before left there.
         // ---------------- STATE1 (:4633-4667): acc[v] = sum of c2v, ascending block row
         static_for<0, RH>([&](auto J) {
             constexpr int j = decltype(J)::value;
             if constexpr (j < KR) {
                 u32 tie;
                 asm volatile("" : "=v"(tie));   // ties the rotated addresses to this row, as mt does below; its value is not used
+                if constexpr (S1 == 3) static_for<j * FPER, ((j + 1) * FPER < NF ? (j + 1) * FPER : NF)>(fill);
                 static_for<0, C::RW[j]>([&](auto S) {
                     constexpr int s = decltype(S)::value;
                     if constexpr (!ms_m64_local_col<C>(C::COL[j][s])) {
@@ -827,8 +927,20 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                         double *p = at(tie, IC<C::SH[j][s]>{}, IC<C::COL[j][s]>{});
                         if constexpr (C::FIRST[j][s]) *p = cv;
                         else __hip_atomic_fetch_add(p, cv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if constexpr (S1 >= 1) {
+                            // the scatter was the value's last use but one: STATE3's product, here, in the same registers.  Opaque
+                            // where it stands (a volatile asm keeps its place among the LDS operations): behind the edge's own
+                            // LDS operation, not gathered in front of the row's or sunk into STATE3.  Opaque on both sides: a product
+                            // formed in front of the LDS operation is a second pair of registers beside the value it came from
+                            double x = cv;
+                            asm volatile("" : "+v"(x));
+                            x = x * alpha_mag;
+                            asm volatile("" : "+v"(x));
+                            keep[j][s] = x;
+                        }
                     }
                 });
+                if constexpr (S1 == 2) static_for<j * FPER, ((j + 1) * FPER < NF ? (j + 1) * FPER : NF)>(fill);
             } else {
                 u32 mt = meta[j];
                 // A volatile asm is ordered with the LDS operations around it, and everything this block row computes
@@ -902,7 +1014,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 constexpr int k = C::COL[j][s];
                 if constexpr (!ms_m64_local_col<C>(k)) {
                     r[s] = *at(mt, IC<C::SH[j][s]>{}, IC<k>{});
-                } else {
+                } else if constexpr (!ms_m64_fill_col<C>(k, KF, FR)) {   // (a column that STATE1 fills has tt in keep: nothing to gather)
                     // A local column: variable `lane` meets check `lane` in every one of its rows.  At its FIRST block row the
                     // column's STATE1 and STATE2 happen here, in registers: the old c2v values of all its edges -- this row's and
                     // later ones, which STATE3 has not reached, so they still hold the previous iteration -- are taken from keep
@@ -933,7 +1045,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                         // for the outputs.  The hard decision needs the sign alone: one v_alignbit_b32 as nS has it, (word << 1) | sign,
                         // and without soft values no store -- the slot then belongs to a resident channel value
                         if constexpr (BITS) {
-                            constexpr int w = ms_m64_local_place<C>(k) / 32;
+                            constexpr int w = ms_m64_local_place<C>(k, KF, FR) / 32;
                             hb[w] = __builtin_amdgcn_alignbit(hb[w], hi32(soft_l[k]), 31);
                         }
                         if constexpr (SOFT) *own(IC<k>{}) = soft_l[k];
@@ -944,7 +1056,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
             // slot s with its old c2v value x taken out: sign word, min1 / min2, and for a row with a record the min1 slot
             auto step = [&](auto S, double x) {
                 constexpr int s = decltype(S)::value;
-                const double tt = r[s] - x;              // v2c
+                double tt;                               // v2c
+                if constexpr (ms_m64_fill_col<C>(C::COL[j][s], KF, FR)) tt = keep[j][s];   // formed in STATE1; x is not looked at
+                else tt = r[s] - x;
                 nS = __builtin_amdgcn_alignbit(nS, hi32(tt), 31);  // (nS << 1) | sign(tt): slot s lands on bit RW-1-s
                 const double v = fabs(tt);
                 if constexpr (j < KR) tt_[s] = tt;
@@ -962,6 +1076,17 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     nm1 = fmin(v, nm1);
                 }
             };
+            // x = (old c2v value) * |alpha| of slot s of a carried row.  With S1 an edge that goes through LDS holds the product already
+            // (STATE1).  An edge of a local column forms it here, from an operand that is opaque where it stands: left alone, the
+            // compiler forms these products beside STATE1's, in registers of their own, across STATE2.
+            auto old_x = [&](auto S) -> double {
+                constexpr int s = decltype(S)::value;
+                if constexpr (S1 >= 1 && !ms_m64_local_col<C>(C::COL[j][s])) return keep[j][s];
+                else {
+                    if constexpr (S1 >= 1) asm volatile("" : "+v"(keep[j][s]));
+                    return keep[j][s] * alpha_mag;
+                }
+            };
             if constexpr (j < KR) {
                 if constexpr (j < KP::value) {
                     // A carried row below KP: no min1 / min2, no `step`.  Ascending s leaves the prefix minima pf[s] = min(K, v_0 .. v_s)
@@ -971,7 +1096,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     static_for<0, RW>([&](auto S) {
                         constexpr int s = decltype(S)::value;
                         if constexpr (j < FR) sy ^= hi32(r[s]);
-                        const double tt = r[s] - keep[j][s] * alpha_mag;   // v2c; the carried value: no decode, see `keep`
+                        double tt;                                      // v2c; the carried value: no decode, see `keep`
+                        if constexpr (ms_m64_fill_col<C>(C::COL[j][s], KF, FR)) tt = keep[j][s];   // formed in STATE1
+                        else tt = r[s] - old_x(S);
                         nS ^= hi32(tt);
                         tt_[s] = tt;
                         if constexpr (s == 0 && RW > 1) pf[0] = fmin(fabs(tt), kMaxVal);
@@ -992,7 +1119,8 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                     static_for<0, RW>([&](auto S) {
                         constexpr int s = decltype(S)::value;
                         if constexpr (j < FR) sy ^= hi32(r[s]);
-                        step(S, keep[j][s] * alpha_mag);     // the carried value: no decode, see `keep`
+                        if constexpr (ms_m64_fill_col<C>(C::COL[j][s], KF, FR)) step(S, 0.0);
+                        else step(S, old_x(S));     // the carried value: no decode, see `keep`
                     });
                 }
             } else {
@@ -1062,7 +1190,11 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
           bool more = true;
           if (__ballot((failw >> 31) != 0) == 0ull) {
             u64 sg[NH];
-            u32 own_hi = hi + 4u;   // opaque, behind the branch: none of the pass's loads is moved up into the iteration
+            // opaque, behind the branch: none of the pass's loads is moved up into the iteration.  With S1 the copy is of `hi` itself and
+            // the high dword's 4 bytes go into the loads' offset field: hi + 4, invariant, was formed in front of the frame loop and
+            // held across it, the register that STATE1's products are short of
+            constexpr u32 PO = S1 >= 1 ? 4u : 0u;
+            u32 own_hi = hi + (4u - PO);
             asm volatile("" : "+v"(own_hi));
             if (static_none<0, (RH - FR + XG - 1) / XG>([&](auto G) -> bool {   // true: a check of the group fails
                     constexpr int j0 = FR + decltype(G)::value * XG, j1 = j0 + XG < RH ? j0 + XG : RH;
@@ -1071,9 +1203,9 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                         constexpr int k = decltype(K)::value, jf = ms_m64_first_row_from<C>(k, FR);
                         if constexpr (jf >= j0 && jf < j1) {
                             if constexpr (!ms_m64_local_col<C>(k) || !BITS) {
-                                sg[k] = __ballot(*(const lds_i32 *)(unsigned long)(own_hi + (u32)(k * 512)) < 0);
+                                sg[k] = __ballot(*(const lds_i32 *)(unsigned long)(own_hi + (u32)(k * 512) + PO) < 0);
                             } else {
-                                constexpr int w = ms_m64_local_place<C>(k) / 32, up = 31 - ms_m64_local_bit<C>(k);   // constants, not code
+                                constexpr int w = ms_m64_local_place<C>(k, KF, FR) / 32, up = 31 - ms_m64_local_bit<C>(k, KF, FR);   // constants, not code
                                 sg[k] = __ballot((int)(hb[w] << up) < 0);
                             }
                             if constexpr (k % 2 == 1) __builtin_amdgcn_sched_barrier(0);
@@ -1102,9 +1234,15 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
     // iterations, not hoisted in front of the frame loop and held (or spilled) across it -- 2 VGPRs and 64 SGPRs that the 15th
     // carried row of the example code needs.  Only where rows are carried: a body that carries none has the registers, and the
     // synthetic 30 x 60 protograph, sensitive as ever (see KP above), spilled 245 VGPRs with the asm in place.
+    // With S1 the lane is counted again here (the workgroup is one wave): nothing of it lives across the iterations.
     int ol = lane;
+    if constexpr (KR > 0 && S1 >= 1) {
+        u32 all = ~0u;
+        asm volatile("" : "+s"(all));   // (opaque: counted here, once per frame, not in front of the frame loop)
+        ol = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+    }
     if constexpr (KR > 0) asm volatile("" : "+v"(ol));
-    if (lane == 0 && a.iters) a.iters[fr] = res;
+    if (ol == 0 && a.iters) a.iters[fr] = res;
     if (a.hard) {
         // bit 31: the sign of the lane's variable of block column k.  Two closures, chosen outside them: where the bit words are not
         // used, nothing names them (a name in a discarded branch of a generic closure is still a capture, and see KP on those).
@@ -1117,7 +1255,7 @@ __device__ __forceinline__ void ms_m64_body(const SpecArgs &a) {
                 return [&, ho](auto K) -> u32 {
                     constexpr int k = decltype(K)::value;
                     if constexpr (ms_m64_local_col<C>(k)) {
-                        constexpr int w = ms_m64_local_place<C>(k) / 32, up = 31 - ms_m64_local_bit<C>(k);   // constants, not code
+                        constexpr int w = ms_m64_local_place<C>(k, KF, FR) / 32, up = 31 - ms_m64_local_bit<C>(k, KF, FR);   // constants, not code
                         return ho[w] << up >> 31;
                     } else return hi32(*own(K)) >> 31;
                 };

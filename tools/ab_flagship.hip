@@ -1,8 +1,10 @@
 // ab_flagship.hip -- A/B harness for variants of the flagship min-sum body (ldpc_spec::ms_m64_body) on the shipped example code:
 // every variant decodes the SAME 65536 frames (Eb/N0 0 dB: all 50 iterations run), outputs are compared bit for bit with the
 // baseline, rounds are interleaved in one process (guide rule 24).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17
-// -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin.   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds] [persistent 0|1] [first variant timed in every round]
-// Results: profiles/r32_flagship_variants.txt: the filter rows and the on-demand syndrome pass -- the FRSET and XGSET parameters of the
+// -ffp-contract=off tools/ab_flagship.hip -o tools/ab_flagship.bin (with -DAB_LATEST: the baseline, the shipped bodies and the newest round's
+// variants only, a quarter of the compile time).   usage: ab_flagship.bin [frames] [Eb/N0 dB] [rounds] [persistent 0|1] [first variant timed in every round]
+// Results: profiles/r33_flagship_variants.txt: what of STATE3's arithmetic stands among STATE1's LDS operations -- the S1SET parameter of the header's
+// body -- at 0 and 2 dB.  profiles/r32_flagship_variants.txt: the filter rows and the on-demand syndrome pass -- the FRSET and XGSET parameters of the
 // header's body -- at 0 and 2 dB.  profiles/r26_flagship_variants.txt: resident channel values, soft values kept or not, the bit word -- the SOFT, RSET and
 // BITW parameters of the header's body -- in both launch forms (argument 4).  profiles/r25_flagship_variants.txt: STATE2 of ms_m64_body streams its channel loads over the non-local block columns, YD
 // of them ahead, first group at the start of STATE2 or after a block row of STATE1 (YROW), and the body carries KR block rows -- the
@@ -683,6 +685,7 @@ typedef ldpc_spec::CodeAppendixCM64 Code;
 #define VARIANT(name, ...) \
     extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body_y<Code, __VA_ARGS__>(a); }
 extern "C" __global__ void __launch_bounds__(64, 2) k_parent(const SpecArgs a) { ldpc_spec::ms_m64_body_parent<Code>(a); }
+#ifndef AB_LATEST
 //               A32   CARRY budget SMASK LOCAL PLAIN  EQ    INTER
 VARIANT(k_l57,   true, false, 57, false, true, false)
 VARIANT(k_lc61,  true, true, 61, false, true, false)
@@ -711,9 +714,11 @@ STREAM(k_y8_15, 8, -1, 15)
 STREAM(k_y8r12_15, 8, 12, 15)
 STREAM(k_y8r15_15, 8, 15, 15)
 STREAM(k_y4r15_15, 4, 15, 15)
+#endif
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped(const SpecArgs a) { ldpc_spec::ms_m64_body<Code>(a); }
 // round 26: how many non-local columns keep their channel value in LDS (RSET), whether the local columns' soft values are stored
 // (SOFT), whether their hard bits come from the bit word (BITW).  15 carried rows, stream depth 8 for what is not resident.
+#ifndef AB_LATEST
 #define RESIDENT(name, soft, rset, bitw) \
     extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, 8, -1, 15, soft, rset, bitw>(a); }
 RESIDENT(k_s_r0, true, 0, 0)
@@ -723,6 +728,7 @@ RESIDENT(k_h_r0, false, 0, 1)
 RESIDENT(k_h_r6, false, 6, 1)
 RESIDENT(k_h_r12, false, 12, 1)
 RESIDENT(k_h_r17, false, 17, 1)
+#endif
 extern "C" __global__ void __launch_bounds__(64, 2) k_shipped_hard(const SpecArgs a) { ldpc_spec::ms_m64_hard_body<Code>(a); }
 
 // round 32: how many block rows form their syndrome word inside STATE3 (FRSET; 16 = all of them, the body round 26 shipped; 0 = none,
@@ -730,6 +736,7 @@ extern "C" __global__ void __launch_bounds__(64, 2) k_shipped_hard(const SpecArg
 // without soft values.  profiles/r32_flagship_variants.txt
 #define FILTER(name, soft, fr, xg) \
     extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, ldpc_spec::kMsM64YDepth, -1, -1, soft, -1, -1, fr, xg>(a); }
+#ifndef AB_LATEST
 FILTER(k_s_f16, true, 16, 2)
 FILTER(k_s_f0, true, 0, 2)
 FILTER(k_s_f1, true, 1, 2)
@@ -746,6 +753,21 @@ FILTER(k_h_f1_x16, false, 1, 16)
 FILTER(k_h_f2_x1, false, 2, 1)
 FILTER(k_h_f2_x4, false, 2, 4)
 FILTER(k_h_f2_x16, false, 2, 16)
+#endif
+
+// round 33: STATE1 fill (S1SET).  0: the body round 32 shipped; 1: x = keep * |alpha| of a carried edge behind the edge's own LDS
+// operation; 2: and the local columns whose rows are all carried, each behind the LDS operations of a carried row; 3: the same
+// columns in front of the row's LDS operations.  profiles/r33_flagship_variants.txt
+#define FILL(name, soft, s1) \
+    extern "C" __global__ void __launch_bounds__(64, 2) name(const SpecArgs a) { ldpc_spec::ms_m64_body<Code, 1 << 30, ldpc_spec::kMsM64YDepth, -1, -1, soft, -1, -1, -1, -1, s1>(a); }
+FILL(k_s_s0, true, 0)
+FILL(k_s_s1, true, 1)
+FILL(k_s_s2, true, 2)
+FILL(k_s_s3, true, 3)
+FILL(k_h_s0, false, 0)
+FILL(k_h_s1, false, 1)
+FILL(k_h_s2, false, 2)
+FILL(k_h_s3, false, 3)
 
 struct Variant { const void *kern; const char *name; size_t lds; bool soft = true; };   // soft: the kernel writes soft_out
 
@@ -759,6 +781,7 @@ int main(int argc, char **argv) {
     const size_t L = ldpc_spec::kMsM64FrameLdsBytes(N);   // what the library passes: the frame's share of the CU (the older bodies use less of it)
     const Variant var[] = {
         {(const void *)k_parent, "baseline: the body round 19 shipped (rows 0-10 kept, 57 edges)", L},
+#ifndef AB_LATEST
         {(const void *)k_l57, "round 20's switches off, 57 edges (must equal the baseline)", L},
         {(const void *)k_lc61, "carried, mask chain, rows 0-11 (61 edges)", L},
         {(const void *)k_le57, "carried, equality, rows 0-10 (57 edges)", L},
@@ -779,7 +802,9 @@ int main(int argc, char **argv) {
         {(const void *)k_y8r12_15, "stream depth 8, first group after STATE1 row 12, 15 carried rows", L},
         {(const void *)k_y8r15_15, "stream depth 8, first group after STATE1 row 15, 15 carried rows", L},
         {(const void *)k_y4r15_15, "stream depth 4, first group after STATE1 row 15, 15 carried rows", L},
+#endif
         {(const void *)k_shipped, "ms_m64_body as shipped (ldpc_spec.hpp)", L},
+#ifndef AB_LATEST
         {(const void *)k_s_r0, "soft values, no resident column, no bit word (round 25's body)", L},
         {(const void *)k_s_r0_b, "soft values, no resident column, hard bits from the bit word", L},
         {(const void *)k_s_r6, "soft values, 6 resident columns", L},
@@ -787,7 +812,9 @@ int main(int argc, char **argv) {
         {(const void *)k_h_r6, "no soft values, 6 resident columns", L, false},
         {(const void *)k_h_r12, "no soft values, 12 resident columns", L, false},
         {(const void *)k_h_r17, "no soft values, 17 resident columns (all)", L, false},
+#endif
         {(const void *)k_shipped_hard, "ms_m64_hard_body as shipped (ldpc_spec.hpp)", L, false},
+#ifndef AB_LATEST
         {(const void *)k_s_f16, "soft values, every row's syndrome in STATE3 (round 26's body)", L},
         {(const void *)k_s_f0, "soft values, no filter row: the pass in every iteration", L},
         {(const void *)k_s_f1, "soft values, 1 filter row, exit every 2 rows", L},
@@ -804,6 +831,15 @@ int main(int argc, char **argv) {
         {(const void *)k_h_f2_x1, "no soft values, 2 filter rows, exit every row", L, false},
         {(const void *)k_h_f2_x4, "no soft values, 2 filter rows, exit every 4 rows", L, false},
         {(const void *)k_h_f2_x16, "no soft values, 2 filter rows, one exit at the end", L, false},
+#endif
+        {(const void *)k_s_s0, "soft values, STATE1 fill off (round 32's body)", L},
+        {(const void *)k_s_s1, "soft values, STATE1 fill: the products x", L},
+        {(const void *)k_s_s2, "soft values, STATE1 fill: x and 12 local columns behind a row's LDS operations", L},
+        {(const void *)k_s_s3, "soft values, STATE1 fill: x and 12 local columns in front of a row's LDS operations", L},
+        {(const void *)k_h_s0, "no soft values, STATE1 fill off (round 32's body)", L, false},
+        {(const void *)k_h_s1, "no soft values, STATE1 fill: the products x", L, false},
+        {(const void *)k_h_s2, "no soft values, STATE1 fill: x and 12 local columns behind a row's LDS operations", L, false},
+        {(const void *)k_h_s3, "no soft values, STATE1 fill: x and 12 local columns in front of a row's LDS operations", L, false},
     };
     constexpr int NV = sizeof var / sizeof var[0];
     const long long distinct = std::min<long long>(B, 4096);
