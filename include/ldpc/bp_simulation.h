@@ -24,6 +24,7 @@
  *                                      to ldpc::bp_simulation_gfq_t<Mat, Env>(), upstream's q-ary harness on the GF(q) decoder.
  *   ldpc::bp_simulation_codes_exact()  a set of candidate codes of one shape in exact-replay mode: the stream of the reset generator
  *                                      drawn once and decoded by every candidate in one launch per batch (_t: generic as above).
+ *   ldpc::bp_simulation_codes_grid() / _grid_exact()  a set of candidate codes at every point of an SNR grid over one noise draw.
  *   ldpc::bp_simulation_codes_gfq_exact()  the same for candidates over GF(q): upstream's q-ary set-up and an own word per candidate.
  * The drop-in definition of upstream's exact `bp_simulation(int, matrix<int> const&, matrix<int>&, ...)` symbol is
  * csrc/compat/bp_simulation_dropin.cpp (compiled inside the upstream tree).
@@ -525,6 +526,28 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
     return out;
 }
 
+// Does the device draw the noise of an exact replay on a code set?  Not with LDPC_HIP_EXACT_NOISE=host, not when std::mt19937 does not
+// export its state, and not on a host whose stream the device does not reproduce: that is probed once per process, on a single-code
+// context opened with `code` (the probe draws plain samples).
+template <class Mat, class Env>
+bool code_set_device_noise(Mat const &code, int M, int decoder_type, int device, bool exported) {
+    const char *noise_env = getenv("LDPC_HIP_EXACT_NOISE");
+    bool device_noise = exported && !(noise_env && std::string(noise_env) == "host");
+    if (device_noise && device_stream_verdict().load() < 0) {
+        const int b = code.n_rows(), c = code.n_cols();
+        std::vector<int16_t> hd((size_t)b * c);
+        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[(size_t)i * c + j] = (int16_t)code(i, j);
+        ldpc_hip_ctx *probe = nullptr;
+        const int jit_before = ldpc_hip_set_jit_mode_thread(0);   // the probe decodes nothing
+        const int open_rc = ldpc_hip_open(decoder_type, b, c, M, hd.data(), device, &probe);
+        (void)ldpc_hip_set_jit_mode_thread(jit_before);
+        if (open_rc != 0) Env::fail(ldpc_hip_last_error());
+        (void)device_stream_matches_host(probe);
+        ldpc_hip_close(probe);
+    }
+    return device_noise && device_stream_verdict().load() == 1;
+}
+
 // A set of candidate codes of one shape in EXACT-REPLAY mode: what `for (candidate) { reset_random(); bp_simulation(...); }` computes
 // (search_ggp/scenario_based_code_generation.cpp:851, main_simulation.cpp:483/492, ldpc_sim.cpp:148), with the noise of upstream's
 // own stream drawn once per batch and decoded by all codes in one launch.  Call it where the loop would call reset_random() for its
@@ -538,7 +561,9 @@ std::vector<std::pair<double, double>> bp_simulation_codes_t(std::vector<Mat> co
 // above leaves behind).
 // NOT covered: a caller that goes on with the stream from one SNR to the next per candidate WITHOUT a reset
 // (main_good_code_search.cpp:316-338).  There the candidates' streams part after the first SNR, because each code stops at a
-// frame of its own, and there is no shared noise left to draw once; such a caller stays with bp_simulation_t per candidate.
+// frame of its own, and there is no shared noise left to draw once; such a caller stays with bp_simulation_t per candidate.  The SNR
+// grid below (bp_simulation_codes_grid_exact_t) does not change that: it shares noise between SNRs only where every SNR starts from
+// the reset generator.
 template <class Mat, class Env>
 std::vector<std::pair<double, double>> bp_simulation_codes_exact_t(std::vector<Mat> const &codes, int tailbite_length, int max_iterations,
                                                                    int n_frame_errors, long long n_experiments, double snr,
@@ -557,20 +582,7 @@ std::vector<std::pair<double, double>> bp_simulation_codes_exact_t(std::vector<M
     uint32_t words[624];
     int pos = 0;
     const bool exported = mt_export(Env::generator(), words, pos);
-    const char *noise_env = getenv("LDPC_HIP_EXACT_NOISE");
-    bool device_noise = exported && !(noise_env && std::string(noise_env) == "host");
-    if (device_noise && device_stream_verdict().load() < 0) {   // once per process, on a single-code context: the probe draws plain samples
-        std::vector<int16_t> hd((size_t)b * c);
-        for (int i = 0; i < b; ++i) for (int j = 0; j < c; ++j) hd[(size_t)i * c + j] = (int16_t)codes[0](i, j);
-        ldpc_hip_ctx *probe = nullptr;
-        const int jit_before = ldpc_hip_set_jit_mode_thread(0);   // the probe decodes nothing
-        const int open_rc = ldpc_hip_open(decoder_type, b, c, M, hd.data(), device, &probe);
-        (void)ldpc_hip_set_jit_mode_thread(jit_before);
-        if (open_rc != 0) Env::fail(ldpc_hip_last_error());
-        (void)device_stream_matches_host(probe);
-        ldpc_hip_close(probe);
-    }
-    device_noise = device_noise && device_stream_verdict().load() == 1;
+    const bool device_noise = code_set_device_noise<Mat, Env>(codes[0], M, decoder_type, device, exported);
 
     std::vector<SimCounters> cnt((size_t)C);
     const bool nothing = n_frame_errors <= 0 || n_experiments < 0;   // :591 fails before the first frame
@@ -670,6 +682,153 @@ inline std::vector<std::pair<double, double>> bp_simulation_codes_exact(std::vec
     return bp_simulation_codes_exact_t<Matrix, OwnRngEnv>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snr,
                                                           reference_frame_error, decoder_type, modulation_type, permutation_type, punctured_blocks,
                                                           show_process, device, counters_out, first_batch, max_batch, leave_at);
+}
+
+// AN SNR GRID on a set of candidate codes, throughput mode: bp_simulation_codes_t at every entry of `snrs` with the reference frame
+// error of that entry, the P x C (point, code) pairs as ONE set of work items over one noise draw (ldpc_hip_simulate_codes_grid_stop;
+// 1 <= P <= 64).  out[p][q] is what bp_simulation_codes_t returns for code q at snrs[p] with reference_frame_errors[p] and the same
+// seed; counters_out likewise [P][C].  With show_process != 0 the function calls bp_simulation_codes_t once per point, which keeps the
+// printed lines and their order.
+template <class Mat, class Env>
+std::vector<std::vector<std::pair<double, double>>> bp_simulation_codes_grid_t(
+    std::vector<Mat> const &codes, int tailbite_length, int max_iterations, int n_frame_errors, long long n_experiments, std::vector<double> const &snrs,
+    std::vector<double> const &reference_frame_errors, int decoder_type, int modulation_type, int permutation_type, int punctured_blocks, int show_process,
+    unsigned long long seed, int device = 0, std::vector<std::vector<SimCounters>> *counters_out = nullptr, long long first_batch = 1024,
+    long long max_batch = 65536) {
+    const int P = (int)snrs.size();
+    if (P < 1 || P > 64 || reference_frame_errors.size() != snrs.size())
+        Env::fail("bp_simulation_codes_grid: 1 .. 64 SNRs and one reference frame error per SNR");
+    std::vector<std::vector<std::pair<double, double>>> out((size_t)P);
+    std::vector<std::vector<SimCounters>> cnt((size_t)P);
+    if (show_process) {
+        for (int p = 0; p < P; ++p)
+            out[(size_t)p] = bp_simulation_codes_t<Mat, Env>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snrs[(size_t)p],
+                                                             reference_frame_errors[(size_t)p], decoder_type, modulation_type, permutation_type,
+                                                             punctured_blocks, show_process, seed, device, &cnt[(size_t)p], first_batch, max_batch);
+    } else {
+        ldpc_hip_ctx *ctx = open_code_set<Mat, Env>(codes, tailbite_length, decoder_type, modulation_type, permutation_type, first_batch, max_batch, device);
+        const int C = (int)codes.size(), b = codes[0].n_rows(), c = codes[0].n_cols();
+        const long long info_len = (long long)(c - b) * tailbite_length;
+        std::vector<unsigned long long> state((size_t)P * C * 4);
+        if (ldpc_hip_simulate_codes_grid_stop(ctx, snrs.data(), P, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, seed, 0, n_frame_errors, n_experiments,
+                                              reference_frame_errors.data(), first_batch, max_batch, state.data()) != 0)
+            Env::fail(ldpc_hip_last_error());
+        ldpc_hip_close(ctx);
+        for (int p = 0; p < P; ++p) {
+            cnt[(size_t)p].resize((size_t)C);
+            for (int q = 0; q < C; ++q) {
+                const unsigned long long *s = state.data() + ((size_t)p * C + q) * 4;
+                SimCounters &k = cnt[(size_t)p][(size_t)q];
+                k.experiment = (long long)s[0]; k.nse = (long long)s[1]; k.nde = (long long)s[2];
+                out[(size_t)p].push_back(std::make_pair((double)k.nse / k.experiment / (double)info_len, (double)k.nde / k.experiment));
+            }
+        }
+    }
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+// How often bp_simulation_codes_grid_exact_t has taken its one-call route in this process (and not the per-SNR loop it falls back to):
+// both give the same numbers, so a caller or a test that wants to know which one ran reads this.
+inline std::atomic<long long> &codes_grid_device_runs() {
+    static std::atomic<long long> n{0};
+    return n;
+}
+
+// AN SNR GRID on a set of candidate codes in EXACT-REPLAY mode: what
+//     for (candidate) for (snr) { reset_random(); bp_simulation(candidate, snr, reference[snr]); }
+// computes (upstream's `simulation` command, main_simulation.cpp:477-518): every (code, SNR) pair starts from the reset generator, so
+// all of them see the same unit-variance samples and only sigma differs.  Call it where the loop would call reset_random() first:
+// Env::generator() is the generator every pair starts from.  The P x C pairs are ONE set of work items over one noise draw
+// (ldpc_hip_mt_simulate_codes_grid_stop; 1 <= P <= 64); the codeword draws are burnt once.  out[p][q] and (*counters_out)[p][q] are
+// what bp_simulation_codes_exact_t gives for code q at snrs[p] with reference_frame_errors[p] from that generator state.
+// Afterwards Env::generator() holds the state after the last frame that pair (leave_point, leave_at) consumed; -1 names the last
+// point and the last code, where the loop above over the last code leaves it.
+// With show_process != 0, and with host-drawn noise (LDPC_HIP_EXACT_NOISE=host, or a host whose stream the device does not reproduce),
+// the function calls bp_simulation_codes_exact_t once per point, each from the generator at entry: that keeps upstream's printed lines
+// in their order, and the host draws stay one stream per SNR.  Binary sets, BPSK, permutation_type 0, the all-zero word.
+template <class Mat, class Env>
+std::vector<std::vector<std::pair<double, double>>> bp_simulation_codes_grid_exact_t(
+    std::vector<Mat> const &codes, int tailbite_length, int max_iterations, int n_frame_errors, long long n_experiments, std::vector<double> const &snrs,
+    std::vector<double> const &reference_frame_errors, int decoder_type, int modulation_type, int permutation_type, int punctured_blocks, int show_process,
+    int device = 0, std::vector<std::vector<SimCounters>> *counters_out = nullptr, long long first_batch = 1024, long long max_batch = 65536,
+    int leave_at = -1, int leave_point = -1) {
+    const int P = (int)snrs.size(), C = (int)codes.size(), M = tailbite_length;
+    if (P < 1 || P > 64 || reference_frame_errors.size() != snrs.size())
+        Env::fail("bp_simulation_codes_grid_exact: 1 .. 64 SNRs and one reference frame error per SNR");
+    if (codes.empty()) Env::fail("bp_simulation_codes: empty code set");
+    if (leave_at < -1 || leave_at >= C) Env::fail("bp_simulation_codes_grid_exact: leave_at names no code of the set");
+    if (leave_point < -1 || leave_point >= P) Env::fail("bp_simulation_codes_grid_exact: leave_point names no point of the grid");
+    const int leave = leave_at < 0 ? C - 1 : leave_at, leave_p = leave_point < 0 ? P - 1 : leave_point;
+    std::vector<std::vector<std::pair<double, double>>> out((size_t)P);
+    std::vector<std::vector<SimCounters>> cnt((size_t)P);
+    const std::mt19937 entry = Env::generator();
+    uint32_t words[624];
+    int pos = 0;
+    const bool device_noise = !show_process && code_set_device_noise<Mat, Env>(codes[0], M, decoder_type, device, mt_export(entry, words, pos));
+    if (!device_noise) {   // one call per point, each from the reset generator, as the loop itself runs
+        std::mt19937 left = entry;
+        for (int p = 0; p < P; ++p) {
+            Env::generator() = entry;
+            out[(size_t)p] = bp_simulation_codes_exact_t<Mat, Env>(codes, M, max_iterations, n_frame_errors, n_experiments, snrs[(size_t)p],
+                                                                   reference_frame_errors[(size_t)p], decoder_type, modulation_type, permutation_type,
+                                                                   punctured_blocks, show_process, device, &cnt[(size_t)p], first_batch, max_batch, leave);
+            if (p == leave_p) left = Env::generator();
+        }
+        Env::generator() = left;
+    } else {
+        ldpc_hip_ctx *ctx = open_code_set<Mat, Env>(codes, M, decoder_type, modulation_type, permutation_type, first_batch, max_batch, device);
+        const int b = codes[0].n_rows(), c = codes[0].n_cols();
+        const long long info_len = (long long)(c - b) * M;
+        if (punctured_blocks < 0 || punctured_blocks >= c) Env::fail("bp_simulation_codes_exact: punctured_blocks outside [0, nh)");
+        Env::burn_codeword_draws(codes[0], M);   // :512, once: the count depends on the shape only
+        if (!mt_export(Env::generator(), words, pos)) Env::fail("bp_simulation_codes_grid_exact: std::mt19937 does not export its state");
+        if (ldpc_hip_mt_set_state_codes(ctx, words, pos) != 0) Env::fail(ldpc_hip_last_error());
+        std::vector<unsigned long long> state((size_t)P * C * 6);
+        if (ldpc_hip_mt_simulate_codes_grid_stop(ctx, snrs.data(), P, punctured_blocks, max_iterations, 0.8 /*MS_ALPHA*/, n_frame_errors, n_experiments,
+                                                 reference_frame_errors.data(), first_batch, max_batch, state.data()) != 0)
+            Env::fail(ldpc_hip_last_error());
+        for (int p = 0; p < P; ++p) {
+            cnt[(size_t)p].resize((size_t)C);
+            for (int q = 0; q < C; ++q) {
+                const unsigned long long *s = state.data() + ((size_t)p * C + q) * 6;
+                SimCounters &k = cnt[(size_t)p][(size_t)q];
+                k.experiment = (long long)s[0]; k.nse = (long long)s[1]; k.nde = (long long)s[2]; k.nue = (long long)s[3];
+                k.sum_abs_iters = (long long)s[4];
+                out[(size_t)p].push_back(std::make_pair((double)k.nse / k.experiment / (double)info_len, (double)k.nde / k.experiment));   // :840
+            }
+        }
+        // the generator where upstream's loop leaves it for the pair (leave_p, leave)
+        if (ldpc_hip_mt_advance_codes(ctx, snrs[(size_t)leave_p], punctured_blocks, cnt[(size_t)leave_p][(size_t)leave].experiment) != 0)
+            Env::fail(ldpc_hip_last_error());
+        if (ldpc_hip_mt_get_state_codes(ctx, words, &pos) != 0) Env::fail(ldpc_hip_last_error());
+        if (!mt_import(Env::generator(), words, pos)) Env::fail("bp_simulation_codes_grid_exact: could not hand the generator state back to std::mt19937");
+        ldpc_hip_close(ctx);
+        ++codes_grid_device_runs();
+    }
+    if (counters_out) *counters_out = cnt;
+    return out;
+}
+
+// the standalone forms: ldpc::Matrix and the library's own generator
+inline std::vector<std::vector<std::pair<double, double>>> bp_simulation_codes_grid(
+    std::vector<Matrix> const &codes, int tailbite_length, int max_iterations, int n_frame_errors, long long n_experiments, std::vector<double> const &snrs,
+    std::vector<double> const &reference_frame_errors, int decoder_type, int modulation_type, int permutation_type, int punctured_blocks, int show_process,
+    unsigned long long seed, int device = 0, std::vector<std::vector<SimCounters>> *counters_out = nullptr, long long first_batch = 1024,
+    long long max_batch = 65536) {
+    return bp_simulation_codes_grid_t<Matrix, OwnRngEnv>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snrs, reference_frame_errors,
+                                                         decoder_type, modulation_type, permutation_type, punctured_blocks, show_process, seed, device,
+                                                         counters_out, first_batch, max_batch);
+}
+
+inline std::vector<std::vector<std::pair<double, double>>> bp_simulation_codes_grid_exact(
+    std::vector<Matrix> const &codes, int tailbite_length, int max_iterations, int n_frame_errors, long long n_experiments, std::vector<double> const &snrs,
+    std::vector<double> const &reference_frame_errors, int decoder_type, int modulation_type, int permutation_type, int punctured_blocks, int show_process,
+    int device = 0, std::vector<std::vector<SimCounters>> *counters_out = nullptr, long long first_batch = 1024, long long max_batch = 65536,
+    int leave_at = -1, int leave_point = -1) {
+    return bp_simulation_codes_grid_exact_t<Matrix, OwnRngEnv>(codes, tailbite_length, max_iterations, n_frame_errors, n_experiments, snrs,
+                                                               reference_frame_errors, decoder_type, modulation_type, permutation_type, punctured_blocks,
+                                                               show_process, device, counters_out, first_batch, max_batch, leave_at, leave_point);
 }
 
 // The same for a set of candidate codes over GF(q), q = q_mod = 2^p (FHT_DEC): what upstream's ggp search does when it scores every

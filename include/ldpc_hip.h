@@ -726,6 +726,40 @@ int ldpc_hip_mt_simulate_codes(ldpc_hip_ctx *ctx, double snr_db, int punctured_b
 int ldpc_hip_mt_simulate_codes_stop(ldpc_hip_ctx *ctx, double snr_db, int punctured_blocks, int maxiter, double alpha, int n_frame_errors,
                                     long long n_experiments, double reference_frame_error, long long first_batch, long long max_batch,
                                     unsigned long long *state);
+/* AN SNR GRID on a binary code set (csrc/ldpc_codeset_grid_api.hpp): P points (1 <= P <= 64, snr_db [P], any order) x C
+ * codes are P * C independent work items over ONE noise draw.  Upstream's `simulation` command resets its generator before every
+ * (code, SNR) pair (main_simulation.cpp:477-518), so every point of every curve sees the same unit-variance samples and only sigma
+ * differs: the channel kernel draws a sample once and writes the LLR of every point from it, llr = -2.0 * (sigma_p * g - 1.0) /
+ * (sigma_p * sigma_p), one launch decodes the items still running, and the rule of ldpc_hip_*_codes_stop runs per item with the
+ * reference of its point.  All eight set decoders, all three routes (resident, wide, global).  Every (point, code) result is
+ * bit-identical to what the single-SNR twin returns for snr_db[p] from the same seed or generator state, whatever the pieces.
+ * Arrays are indexed [p][c]: counters [P][C][5], frame_info / iters [P][C][B] (HOST, may be NULL), state [P][C][4] (Philox) or
+ * [P][C][6] (exact replay), reference_frame_error [P] (upstream's best_errors[s], :510).  n_frame_errors, n_experiments and the batch
+ * schedule are shared by the points.  A piece holds the buffers of all points: the 1 GiB bound and LDPC_HIP_CODES_PIECE apply to
+ * P times the bytes per frame of the twin.
+ * ldpc_hip_mt_simulate_codes_grid leaves the generator B frames further on, ONCE.  ldpc_hip_mt_simulate_codes_grid_stop puts it back
+ * to where it was at entry; ldpc_hip_mt_advance_codes(ctx, snr_db[p], punctured_blocks, state[p][c][0]) then takes it to the end of
+ * item (p, c).  n_frame_errors <= 0 or n_experiments < 0: state is zero, nothing is drawn.
+ * LDPC_HIP_EINVAL, before anything is drawn, reserved or launched and with the outputs untouched: not a binary code-set context, P
+ * outside 1 .. 64, NULL snr_db or reference_frame_error, a point that is not finite (the message names its index), and whatever the
+ * twin refuses: maxiter < 1, the batches, a NaN alpha, alpha <= 0 for MS_DEC off the global route, a generator without state,
+ * punctured_blocks outside [0, nh).  Not built: GF(q) sets, QAM, interleavers and transmitted codewords (the all-zero word, BPSK).
+ * Measured (profiles/r34_codeset_grid_time.txt; exact replay, 8 points from 1.0 dB, against the loop of 8 single-SNR calls on the same
+ * context).  Min-sum, 16 x 32, M = 64, 50 iterations, 4001 frames per item: 14.4 against 37.6 ms for one code (2.61x), 45.5 against 67.6 ms at
+ * 4 codes (1.48x), 169.4 against 185.8 ms at 16 (1.10x), 2676 against 2696 ms at 256 (1.01x).  TDMP, M = 126, 15 iterations, 50 error
+ * frames: 47.9 against 73.8 ms for one code (1.54x), 3525 against 3784 ms at 4 (1.07x), 13 698 against 14 349 ms at 16 (1.05x); 256 codes: not
+ * measured.  No measured row is slower.
+ * Synchronous, one call at a time per context, on the null stream. */
+int ldpc_hip_simulate_codes_grid(ldpc_hip_ctx *ctx, const double *snr_db, int P, int punctured_blocks, int maxiter, double alpha, uint64_t seed,
+                                 long long first_frame, long long B, unsigned long long *counters, int32_t *frame_info);
+int ldpc_hip_simulate_codes_grid_stop(ldpc_hip_ctx *ctx, const double *snr_db, int P, int punctured_blocks, int maxiter, double alpha,
+                                      uint64_t seed, long long first_frame, int n_frame_errors, long long n_experiments,
+                                      const double *reference_frame_error, long long first_batch, long long max_batch, unsigned long long *state);
+int ldpc_hip_mt_simulate_codes_grid(ldpc_hip_ctx *ctx, const double *snr_db, int P, int punctured_blocks, int maxiter, double alpha, long long B,
+                                    unsigned long long *counters, int32_t *frame_info, int32_t *iters);
+int ldpc_hip_mt_simulate_codes_grid_stop(ldpc_hip_ctx *ctx, const double *snr_db, int P, int punctured_blocks, int maxiter, double alpha,
+                                         int n_frame_errors, long long n_experiments, const double *reference_frame_error, long long first_batch,
+                                         long long max_batch, unsigned long long *state);
 
 /* ---- GF(q) code sets: C candidate codes over GF(q) of one shape x B frames in one launch (csrc/ldpc_gfq_codeset.hpp) ----------------
  * What upstream's second search driver does (search_ggp/scenario_based_code_generation.cpp:692-940): every candidate comes from one

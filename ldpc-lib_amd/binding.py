@@ -210,6 +210,10 @@ def load_library():
     lib.ldpc_hip_mt_advance_codes.argtypes = [vp, f64, i32, i64]
     lib.ldpc_hip_mt_simulate_codes.argtypes = [vp, f64, i32, i32, f64, i64, vp, vp, vp]
     lib.ldpc_hip_mt_simulate_codes_stop.argtypes = [vp, f64, i32, i32, f64, i32, i64, f64, i64, i64, vp]
+    lib.ldpc_hip_simulate_codes_grid.argtypes = [vp, vp, i32, i32, i32, f64, u64, i64, i64, vp, vp]
+    lib.ldpc_hip_simulate_codes_grid_stop.argtypes = [vp, vp, i32, i32, i32, f64, u64, i64, i32, i64, vp, i64, i64, vp]
+    lib.ldpc_hip_mt_simulate_codes_grid.argtypes = [vp, vp, i32, i32, i32, f64, i64, vp, vp, vp]
+    lib.ldpc_hip_mt_simulate_codes_grid_stop.argtypes = [vp, vp, i32, i32, i32, f64, i32, i64, vp, i64, i64, vp]
     lib.ldpc_hip_open_codes_gfq.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, C.POINTER(vp)]
     lib.ldpc_hip_codes_gfq_table_host.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, C.POINTER(i64)]
     lib.ldpc_hip_decode_codes_gfq_dev.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, vp]
@@ -946,6 +950,68 @@ class LdpcHipCodes:
                                                       int(n_experiments), float(reference_frame_error), int(first_batch), int(max_batch),
                                                       state.ctypes.data)
         _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_stop")
+        return state
+
+    # ---- an SNR grid: P points x C codes as P * C work items over one noise draw (ldpc_hip_*_codes_grid) ---------------
+    @staticmethod
+    def _points(snr_db):
+        pts = np.ascontiguousarray(np.atleast_1d(snr_db), dtype=np.float64)
+        assert pts.ndim == 1
+        return pts
+
+    def simulate_grid(self, snr_db, maxiter, seed, first_frame, frames, punctured_blocks=0, alpha=0.8, records=False):
+        """simulate at every point of snr_db [P] (1 <= P <= 64) over one noise draw.  Returns counters uint64 [P, C, 5], and with
+        records=True also frame_info int32 [P, C, frames]: row p is what simulate(snr_db[p], ...) returns."""
+        pts = self._points(snr_db)
+        P = len(pts)
+        cnt = np.zeros((P, self.C, 5), dtype=np.uint64)
+        info = np.empty((P, self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_simulate_codes_grid(self.h, pts.ctypes.data, P, int(punctured_blocks), int(maxiter), float(alpha), int(seed),
+                                                   int(first_frame), int(frames), cnt.ctypes.data, info.ctypes.data if records else None)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes_grid")
+        return (cnt, info) if records else cnt
+
+    def simulate_grid_until(self, snr_db, maxiter, seed, n_frame_errors, n_experiments, reference_frame_error, first_frame=0, first_batch=1024,
+                            max_batch=65536, punctured_blocks=0, alpha=0.8):
+        """simulate_until at every point of snr_db [P] with reference_frame_error [P], the P * C items in one launch per piece.  Returns
+        uint64 [P, C, 4]: row p is what simulate_until(snr_db[p], ..., reference_frame_error[p]) returns."""
+        pts = self._points(snr_db)
+        ref = np.ascontiguousarray(np.atleast_1d(reference_frame_error), dtype=np.float64)
+        assert ref.shape == pts.shape
+        state = np.zeros((len(pts), self.C, 4), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_simulate_codes_grid_stop(self.h, pts.ctypes.data, len(pts), int(punctured_blocks), int(maxiter), float(alpha), int(seed),
+                                                        int(first_frame), int(n_frame_errors), int(n_experiments), ref.ctypes.data, int(first_batch),
+                                                        int(max_batch), state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_simulate_codes_grid_stop")
+        return state
+
+    def mt_simulate_grid(self, snr_db, maxiter, frames, punctured_blocks=0, alpha=0.8, records=False):
+        """mt_simulate at every point of snr_db [P] over the next `frames` frames of the stream, drawn once.  Returns counters uint64
+        [P, C, 5], and with records=True also frame_info and iters int32 [P, C, frames]: row p is what mt_simulate(snr_db[p], ...) returns
+        from the same generator state.  The generator is `frames` frames further on afterwards, once."""
+        pts = self._points(snr_db)
+        P = len(pts)
+        cnt = np.zeros((P, self.C, 5), dtype=np.uint64)
+        info = np.empty((P, self.C, int(frames)), dtype=np.int32) if records else None
+        its = np.empty((P, self.C, int(frames)), dtype=np.int32) if records else None
+        rc = self.lib.ldpc_hip_mt_simulate_codes_grid(self.h, pts.ctypes.data, P, int(punctured_blocks), int(maxiter), float(alpha), int(frames),
+                                                      cnt.ctypes.data, info.ctypes.data if records else None, its.ctypes.data if records else None)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_grid")
+        return (cnt, info, its) if records else cnt
+
+    def mt_simulate_grid_until(self, snr_db, maxiter, n_frame_errors, n_experiments, reference_frame_error, first_batch=1024, max_batch=65536,
+                               punctured_blocks=0, alpha=0.8):
+        """mt_simulate_until at every point of snr_db [P] with reference_frame_error [P].  Returns uint64 [P, C, 6]: row p is what
+        mt_simulate_until(snr_db[p], ..., reference_frame_error[p]) returns.  The generator is back at its state at entry afterwards;
+        mt_advance(snr_db[p], state[p, c, 0]) takes it to the end of item (p, c)."""
+        pts = self._points(snr_db)
+        ref = np.ascontiguousarray(np.atleast_1d(reference_frame_error), dtype=np.float64)
+        assert ref.shape == pts.shape
+        state = np.zeros((len(pts), self.C, 6), dtype=np.uint64)
+        rc = self.lib.ldpc_hip_mt_simulate_codes_grid_stop(self.h, pts.ctypes.data, len(pts), int(punctured_blocks), int(maxiter), float(alpha),
+                                                           int(n_frame_errors), int(n_experiments), ref.ctypes.data, int(first_batch), int(max_batch),
+                                                           state.ctypes.data)
+        _check(self.lib, rc, "ldpc_hip_mt_simulate_codes_grid_stop")
         return state
 
     def set_ims_params(self, thr=1.4, qbits=6, dbits=8):

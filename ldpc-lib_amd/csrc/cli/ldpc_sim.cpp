@@ -15,6 +15,12 @@
 //                  scored as ONE set per SNR (ldpc::bp_simulation_codes_exact: the noise of the reset generator drawn once, all codes
 //                  of the group in one launch); the result file is the one without the flag except for `time`.  Codes over GF(q) of
 //                  one q are grouped the same way into ldpc::bp_simulation_codes_gfq_exact
+//   --snr-grid     implies the grouping of --code-sets; every binary group -- a group of ONE code too -- goes
+//                  through one ldpc::bp_simulation_codes_grid_exact call for all its SNRs instead of one call per SNR: the (SNR, code)
+//                  pairs are one set of work items over one draw of the reset generator's noise.  Up to 64 SNRs per code; a group with
+//                  more, and a group over GF(q), runs per SNR as with --code-sets.  A line says whether the group ran as one call or, with
+//                  host-drawn noise, as the per-SNR loop inside that function.  The result file differs from the one without the
+//                  flag in `time` only; --code-sets alone behaves as it always did
 //   --girth        upstream's trace_matrix per code (:148-205, :496) on the device (ldpc::trace_matrix, include/ldpc/girth.h): every
 //                  record gains girth_, girth_ACE and girth_spectrum behind `girth` (:600-603).  The trace depends on the code alone,
 //                  so it runs once per code and not once per SNR; with --code-sets once per group (ldpc::trace_matrices).  A code
@@ -139,7 +145,7 @@ bool set_takes(const SetGroup &g, int rows, int columns) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool throughput = false, code_sets = false, girth = false;
+    bool throughput = false, code_sets = false, girth = false, snr_grid = false;
     int random_codewords = 0;   // --throughput only: transmit this many random codewords encoded on the device instead of the all-zero word
     int device = 0;
     std::string devices_arg;
@@ -147,6 +153,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--throughput")) throughput = true;
         else if (!strcmp(argv[i], "--code-sets")) code_sets = true;
+        else if (!strcmp(argv[i], "--snr-grid")) snr_grid = code_sets = true;
         else if (!strcmp(argv[i], "--girth")) girth = true;
         else if (!strcmp(argv[i], "--random-codewords") && i + 1 < argc) random_codewords = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
@@ -234,10 +241,23 @@ int main(int argc, char **argv) {
                 if (q_mod > 2) groups[g].coefs.push_back(HC);
             }
             for (const SetGroup &g : groups) {
-                if (g.members.size() < 2 || g.key.punctured_blocks < 0 || g.key.punctured_blocks >= columns0 || !set_takes(g, rows0, columns0)) continue;
+                const bool grid = snr_grid && g.key.q_mod <= 2 && !g.key.snrs.empty() && g.key.snrs.size() <= 64;
+                if ((g.members.size() < 2 && !grid) || g.key.punctured_blocks < 0 || g.key.punctured_blocks >= columns0 || !set_takes(g, rows0, columns0)) continue;
                 const auto t0 = std::chrono::steady_clock::now();
                 for (size_t m : g.members) from_set[m].per_snr.resize(g.key.snrs.size());
-                for (size_t s = 0; s < g.key.snrs.size(); ++s) {
+                if (grid) {
+                    printf("set of %zu codes from code #%zu on, grid of %zu SNRs\n", g.members.size(), g.members[0], g.key.snrs.size());
+                    ldpc::initial_random_seed = seed;
+                    ldpc::reset_random();                                                                                     // :483, the state every (code, SNR) pair starts from
+                    const long long runs_before = ldpc::codes_grid_device_runs().load();
+                    const std::vector<std::vector<std::pair<double, double>>> p = ldpc::bp_simulation_codes_grid_exact(
+                        g.codes, g.key.lifting, g.key.iterations, num_frame_errors, (int)num_experiments, g.key.snrs,
+                        std::vector<double>(g.key.snrs.size(), error_rate_threshold), g.key.decoder_type, modulation_type, permutation_type,
+                        g.key.punctured_blocks, 0, devices[0]);
+                    for (size_t s = 0; s < g.key.snrs.size(); ++s)
+                        for (size_t q = 0; q < g.members.size(); ++q) from_set[g.members[q]].per_snr[s] = {p[s][q].first, p[s][q].second};
+                    printf("  %s\n", ldpc::codes_grid_device_runs().load() > runs_before ? "one grid call" : "per-SNR calls (host-drawn noise)");
+                } else for (size_t s = 0; s < g.key.snrs.size(); ++s) {
                     printf("set of %zu codes from code #%zu on, SNR = %6.3f\n", g.members.size(), g.members[0], g.key.snrs[s]);
                     ldpc::initial_random_seed = seed;
                     ldpc::reset_random();                                                                                     // :483 all codes are tested with same noise

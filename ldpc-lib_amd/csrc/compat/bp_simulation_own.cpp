@@ -103,6 +103,39 @@ extern "C" int ldpc_bp_simulation_codes_exact(int C, int rh, int nh, const int *
     return 0;
 }
 
+// A code set on an SNR grid (ldpc::bp_simulation_codes_grid_exact, or with exact == 0 ldpc::bp_simulation_codes_grid with `seed` as the
+// Philox seed): snrs [P], refs [P]; seeds the generator once.  out [P][C][7] as above per (point, code); *rng_next = next raw mt19937
+// output after the run of pair (leave_point, leave_at) (-1: the last), exact mode only.
+extern "C" int ldpc_bp_simulation_codes_grid(int exact, int C, int rh, int nh, const int *codes, int M, int max_iterations, int n_frame_errors,
+                                             int n_experiments, int P, const double *snrs, const double *refs, int decoder_type, int punctured_blocks,
+                                             int show_process, unsigned seed, int device, long long first_batch, long long max_batch, int leave_at,
+                                             int leave_point, double *out, unsigned *rng_next) {
+    std::vector<ldpc::Matrix> set((size_t)C, ldpc::Matrix(rh, nh));
+    for (int q = 0; q < C; ++q)
+        for (int i = 0; i < rh * nh; ++i) set[(size_t)q].v[(size_t)i] = codes[(size_t)q * rh * nh + i];
+    const std::vector<double> snr(snrs, snrs + P), ref(refs, refs + P);
+    ldpc::initial_random_seed = (int)seed;
+    ldpc::reset_random();
+    std::vector<std::vector<ldpc::SimCounters>> cnt;
+    const std::vector<std::vector<std::pair<double, double>>> res =
+        exact ? ldpc::bp_simulation_codes_grid_exact(set, M, max_iterations, n_frame_errors, n_experiments, snr, ref, decoder_type, 0, 0, punctured_blocks,
+                                                     show_process, device, &cnt, first_batch, max_batch, leave_at, leave_point)
+              : ldpc::bp_simulation_codes_grid(set, M, max_iterations, n_frame_errors, n_experiments, snr, ref, decoder_type, 0, 0, punctured_blocks,
+                                               show_process, seed, device, &cnt, first_batch, max_batch);
+    for (int p = 0; p < P; ++p)
+        for (int q = 0; q < C; ++q) {
+            double *o = out + ((size_t)p * C + q) * 7;
+            const ldpc::SimCounters &k = cnt[(size_t)p][(size_t)q];
+            o[0] = res[(size_t)p][(size_t)q].first; o[1] = res[(size_t)p][(size_t)q].second; o[2] = (double)k.nse; o[3] = (double)k.nde;
+            o[4] = (double)k.nue; o[5] = (double)k.experiment; o[6] = (double)k.sum_abs_iters;
+        }
+    if (rng_next) *rng_next = (unsigned)ldpc::random_generator()();
+    return 0;
+}
+
+// ldpc::codes_grid_device_runs(): the exact grid calls of this process that ran as one call and not as the per-SNR loop
+extern "C" long long ldpc_bp_simulation_codes_grid_device_runs() { return ldpc::codes_grid_device_runs().load(); }
+
 // Throughput mode (device-side noise, frames sharded over `devices`, upstream's sequential stopping rule on the ordered records).
 // devices == NULL: LDPC_HIP_DEVICES or device 0.  codewords: [ncw][nh*M] 0/1 bytes or NULL (all-zero codeword).
 extern "C" int ldpc_bp_simulation_throughput(int rh, int nh, const int *H, int M, int max_iterations, int n_frame_errors,

@@ -13,6 +13,8 @@
 //   * outputs: hard [C][B][hard_words], iters [C][B], soft [C][B][N];
 //   * a launch may cover a subset of the codes: code_list[n_active] names the code of every slot blockIdx.x / blocks_per_code (null =
 //     the identity).  The graph table and the per-code LLR slice follow the code, the outputs follow the slot ([n_active][B]...).
+//   * an SNR grid of P points over one noise draw makes the entries of the list ITEMS i = p * C + c: the table follows the code c, the
+//     received words follow the point p (llr + p * llr_point_stride).  With one point an item is its code and the stride is 0.
 // The decoder bodies compute what ms_flood_kernel / lms_layered_kernel / tasp_global_kernel / iasp_global_kernel / lche_global_kernel /
 // ims_flood_kernel compute (fp64, reference operation order, contraction off; IASP: the integer arithmetic of ldpc_spec::iasp; LCHE:
 // ldpc_spec::lche; IMS: integers behind a quantiser that runs once per received word); only the frame index and the table base differ
@@ -47,6 +49,7 @@ struct CodesetArgs {
     int C, rh, nh, M, N, F, maxiter, hard_words;
     double alpha;
     int ne_max;               // tasp_layered_codes_kernel, iasp_codes_kernel, lche_layered_codes_kernel: the largest edge count of the set (size of the per-edge LDS image)
+    long long llr_point_stride;   // an SNR grid: the list names ITEMS p * C + c and point p reads llr + p * llr_point_stride; one point: 0
 };
 
 // The graph table is read-only for the whole launch and its addresses are wave-uniform: reading it through the constant address
@@ -60,10 +63,12 @@ __device__ __forceinline__ TabPtr tab_ptr(const void *p) { return (TabPtr)(uintp
 __device__ __forceinline__ DecArgs codeset_view(const CodesetArgs &s, int &w) {
     const int slot = blockIdx.x / s.blocks_per_code;
     w = blockIdx.x - slot * s.blocks_per_code;
-    const int c = s.code_list ? tab_ptr(s.code_list)[slot] : slot;
+    const unsigned item = s.code_list ? (unsigned)tab_ptr(s.code_list)[slot] : (unsigned)slot;
+    const unsigned p = item / (unsigned)s.C;      // the point of an SNR grid; 0 without one
+    const int c = (int)(item - p * (unsigned)s.C);
     const long long fo = (long long)slot * s.B;   // first frame of the slot in the [n_active][B] outputs
     DecArgs a{};
-    a.llr = s.llr + (long long)c * s.llr_code_stride;
+    a.llr = s.llr + (long long)c * s.llr_code_stride + (long long)p * s.llr_point_stride;
     a.hard = s.hard ? s.hard + fo * s.hard_words : nullptr;
     a.iters = s.iters ? s.iters + fo : nullptr;
     a.soft_out = s.soft_out ? s.soft_out + fo * s.N : nullptr;
@@ -742,17 +747,30 @@ struct CodesetRuleFullArgs : CodesetRuleArgs {   // state is [C][6]
 // the slot's iteration counts iters [n_active][B] are read next to its records: nue counts the error frames with iters >= 0
 // (:809-810) and sum |iters| every frame (:799), both over exactly the frames that reach the state (`take`), with the ballot and the
 // 64-bit sum of nse.  !FULL is the rule of the Philox entry points, state [C][4], and reads no iteration count.
+// GRID: the rule on an SNR grid.  The list holds items p * C + c, the state and the flags have P * C rows, and point p has a reference
+// of its own, reference[item / C] (upstream's best_errors[s], main_simulation.cpp:510); reference_frame_error is not read.  The kernel
+// itself is the template (a body in a __device__ function that both forms call gave the existing instances another order of the
+// 64-bit additions, profiles/r21_codeset_exact_resource_usage.txt): <FULL, false> is the kernel of the existing entry points.
 template <bool FULL>
-__global__ void __launch_bounds__(64) stop_rule_codes_kernel(const std::conditional_t<FULL, CodesetRuleFullArgs, CodesetRuleArgs> a) {
+struct CodesetRuleGridArgs : std::conditional_t<FULL, CodesetRuleFullArgs, CodesetRuleArgs> {
+    const double *reference;       // [P]
+    int C;
+};
+
+template <bool FULL, bool GRID = false>
+__global__ void __launch_bounds__(64)
+stop_rule_codes_kernel(const std::conditional_t<GRID, CodesetRuleGridArgs<FULL>, std::conditional_t<FULL, CodesetRuleFullArgs, CodesetRuleArgs>> a) {
     constexpr int kWords = FULL ? 6 : 4;
     const int lane = threadIdx.x;
-    const int code = tab_ptr(a.code_list)[blockIdx.x];
+    const int code = tab_ptr(a.code_list)[blockIdx.x];   // GRID: the item
+    double reference_frame_error = a.reference_frame_error;
+    if constexpr (GRID) reference_frame_error = a.reference[(unsigned)code / (unsigned)a.C];
     const int32_t *const rec = a.frame_info + (long long)blockIdx.x * a.B;
     unsigned long long *const st = a.state + kWords * (size_t)code;
     long long experiment = (long long)st[0], nde = (long long)st[2];
     unsigned long long nse = st[1];
     unsigned long long nue = 0, sit = 0;   // FULL: what this piece adds
-    const double thr = 2.5 * a.reference_frame_error;
+    const double thr = 2.5 * reference_frame_error;
     const unsigned long long below = (1ull << lane) - 1;
     bool stopped = false;
     for (long long base = 0; base < a.B && !stopped; base += 64) {

@@ -9,6 +9,8 @@ struct codeset_rule_ws {
     unsigned long long *rule = nullptr;              // [C][4]: experiment, nse, nde, frames_decoded; the exact-replay run: [C][6] (room for 6)
     int32_t *running = nullptr, *list = nullptr;     // [C] each
     int32_t *nactive = nullptr;                      // [1]
+    double *reference = nullptr;                     // an SNR grid (ldpc_codeset_grid_api.hpp): [64], one reference frame error per point
+    size_t rows = 0;                                 // the rows rule, running and list hold: C, or P * C once a grid has run
 };
 
 // what every code-set state holds
@@ -20,7 +22,8 @@ struct codeset_common {
     // workspace of the simulate entry points for w_frames frames per code, next to the decoder's own input and decisions
     int32_t *w_iters = nullptr, *w_info = nullptr;   // [C][w_frames]
     unsigned long long *w_cnt = nullptr;             // [C][5]
-    long long w_frames = 0;
+    long long w_frames = 0;                          // input rows the workspace holds: frames per code, times the points of an SNR grid
+    int w_points = 1;                                // the points w_cnt holds rows for: [w_points * C][5]
     codeset_rule_ws stop;                            // the *_stop entry points
 };
 
@@ -39,7 +42,7 @@ struct ldpc_codeset_state : codeset_common {
 };
 
 void codeset_common_release(codeset_common &s) {
-    void *dev[] = {s.d_off, s.d_tab, s.w_iters, s.w_info, s.w_cnt, s.stop.rule, s.stop.running, s.stop.list, s.stop.nactive};
+    void *dev[] = {s.d_off, s.d_tab, s.w_iters, s.w_info, s.w_cnt, s.stop.rule, s.stop.running, s.stop.list, s.stop.nactive, s.stop.reference};
     for (void *p : dev)
         if (p) (void)hipFree(p);
 }
@@ -285,10 +288,11 @@ int codeset_count_blocks(long long B, int C) {
     return (int)(bpc > cap ? cap : bpc);
 }
 
-// code_list / n_slots: the codes of the [n_slots][B] inputs (null: all C codes in order), see ldpc_codeset.hpp
+// code_list / n_slots: the codes of the [n_slots][B] inputs (null: all C codes in order), see ldpc_codeset.hpp.  points: an SNR grid,
+// the list names items and a null list stands for all points * C of them
 int codeset_count_launch(const ldpc_hip_ctx *c, const uint32_t *d_hard, const int32_t *d_iters, long long B, int32_t *d_frame_info,
-                         unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0) {
-    const int C = code_list ? n_slots : c->codes->C;
+                         unsigned long long *d_counters, hipStream_t stream, const int32_t *code_list = nullptr, int n_slots = 0, int points = 1) {
+    const int C = code_list ? n_slots : c->codes->C * points;
     const int bpc = codeset_count_blocks(B, C);
     ldpc::CodesetCountArgs a{d_hard, d_iters, d_frame_info, d_counters, code_list, B, bpc, c->hard_words, c->R};
     hipLaunchKernelGGL(ldpc::count_errors_codes_kernel, dim3((unsigned)((long long)bpc * C)), dim3(256), 0, stream, a);
@@ -468,8 +472,9 @@ int codeset_glob_reserve(ldpc_codeset_state *s, long long &grid) {
 }
 
 // The decode launch over n_slots codes: code_list [n_slots] (DEVICE) names them, null = all C codes in order.  Outputs [n_slots][B]...
+// points > 1: an SNR grid on shared LLRs [points][B][N]; the list names items p * C + c, null = all points * C in order.
 int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, long long B, int maxiter, double alpha, uint32_t *d_hard,
-                          int32_t *d_iters, double *d_soft, hipStream_t stream, const int32_t *code_list, int n_slots) {
+                          int32_t *d_iters, double *d_soft, hipStream_t stream, const int32_t *code_list, int n_slots, int points = 1) {
     if (B < 0) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: bad argument");
     if (maxiter < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: maxiter must be >= 1 (got %d)", maxiter);
     if (int rc = alpha_refusal("ldpc_hip_decode_codes_dev", c->decoder_id, alpha)) return rc;
@@ -483,7 +488,7 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     if (B == 0) return 0;
     if (!d_llr) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: null llr");
     ldpc_codeset_state *s = c->codes;
-    if (!code_list) n_slots = s->C;
+    if (!code_list) n_slots = s->C * points;
     if (n_slots < 1) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: a launch covers at least one code");   // never a grid of 0 blocks
     const long long bpc = (B + c->F - 1) / c->F;
     if (bpc * n_slots > 0x7fffffffLL) return fail(LDPC_HIP_EINVAL, "ldpc_hip_decode_codes_dev: %d codes x %lld frames is more than one launch takes", n_slots, B);
@@ -492,6 +497,7 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.soft_out = d_soft;
     a.tab = s->d_tab; a.code_off = s->d_off; a.code_list = code_list;
     a.B = B; a.llr_code_stride = shared_llr ? 0 : B * (long long)c->N; a.blocks_per_code = (int)bpc;
+    a.llr_point_stride = points > 1 ? B * (long long)c->N : 0;
     a.C = s->C; a.rh = c->rh; a.nh = c->nh; a.M = c->M; a.N = c->N; a.F = c->F; a.maxiter = maxiter; a.hard_words = c->hard_words;
     a.alpha = alpha; a.ne_max = s->ne_max;
     const codeset_kind &kind = codeset_kind_of(c);
@@ -501,7 +507,7 @@ int codeset_decode_launch(ldpc_hip_ctx *c, const double *d_llr, int shared_llr, 
     if (int rc = timer.begin(c, stream)) return rc;
     ldpc::ImsCodesArgs ia{};   // the second argument of a CS_QUANT kernel; the others take the first alone
     if (kind.is & CS_QUANT) {   // once per received word: B of them when the codes share the LLRs, C * B otherwise
-        if (int rc = codeset_ims_quantise(c, d_llr, shared_llr ? B : B * (long long)s->C, stream)) return rc;
+        if (int rc = codeset_ims_quantise(c, d_llr, shared_llr ? B * points : B * (long long)s->C, stream)) return rc;
         ia.q = s->w_q; ia.max_data = (1 << (c->ims_dbits - 1)) - 1; ia.ialpha = (int)(alpha * (1 << 4));   // decoders.cpp:5445, :5458
     }
     long long grid = bpc * n_slots;
@@ -526,32 +532,42 @@ long long codeset_piece(size_t bytes_per_frame, const char *cap_env, long long B
     return piece > B ? B : piece;
 }
 
-long long codeset_piece(const ldpc_hip_ctx *c, long long B) {
+long long codeset_piece(const ldpc_hip_ctx *c, long long B, int points = 1) {
     size_t per_frame = (size_t)c->codes->C * (sizeof(uint32_t) * (size_t)c->hard_words + 2 * sizeof(int32_t)) + sizeof(double) * (size_t)c->N;
     if (codeset_kind_of(c).is & CS_QUANT) per_frame += sizeof(double) + sizeof(int16_t) * (size_t)c->N;   // the quantiser's coef and int16 word
-    return codeset_piece(per_frame, "LDPC_HIP_CODES_PIECE", B);
+    return codeset_piece(per_frame * (size_t)points, "LDPC_HIP_CODES_PIECE", B);   // an SNR grid: the bytes of every point's frame
 }
 
 // The workspace for `piece` frames per code (grown, never shrunk): the decoder's input [piece] of in_bytes per frame, shared by the
-// codes, its decisions [C][piece] of out_bytes per frame, and the iteration counts and records [C][piece].
-int codeset_reserve(codeset_common &s, long long piece, void **w_in, size_t in_bytes, void **w_out, size_t out_bytes) {
-    if (piece <= s.w_frames) return 0;
+// codes, its decisions [C][piece] of out_bytes per frame, and the iteration counts and records [C][piece].  points > 1 (an SNR grid):
+// the call needs points * piece input rows and C times as many rows of the rest.  w_frames counts INPUT ROWS, so the capacity is
+// that of the largest call so far and a single-SNR call after a grid call is sized by its own piece, as it always was; only the
+// counters [points * C][5] keep the largest grid's rows.
+int codeset_reserve(codeset_common &s, long long piece, void **w_in, size_t in_bytes, void **w_out, size_t out_bytes, int points = 1) {
+    if (points > s.w_points) {
+        if (s.w_cnt) (void)hipFree(s.w_cnt);
+        s.w_cnt = nullptr;
+        HIP_TRY(hipMalloc(&s.w_cnt, sizeof(unsigned long long) * 5 * (size_t)s.C * (size_t)points));
+        s.w_points = points;
+    }
+    const long long rows = piece * points;
+    if (rows <= s.w_frames) return 0;
     const size_t C = (size_t)s.C;
     void *old[] = {*w_in, *w_out, s.w_iters, s.w_info};
     for (void *p : old)
         if (p) (void)hipFree(p);
     *w_in = nullptr; *w_out = nullptr; s.w_iters = nullptr; s.w_info = nullptr; s.w_frames = 0;
-    HIP_TRY(hipMalloc(w_in, in_bytes * (size_t)piece));
-    HIP_TRY(hipMalloc(w_out, out_bytes * C * (size_t)piece));
-    HIP_TRY(hipMalloc(&s.w_iters, sizeof(int32_t) * C * (size_t)piece));
-    HIP_TRY(hipMalloc(&s.w_info, sizeof(int32_t) * C * (size_t)piece));
-    s.w_frames = piece;
+    HIP_TRY(hipMalloc(w_in, in_bytes * (size_t)rows));
+    HIP_TRY(hipMalloc(w_out, out_bytes * C * (size_t)rows));
+    HIP_TRY(hipMalloc(&s.w_iters, sizeof(int32_t) * C * (size_t)rows));
+    HIP_TRY(hipMalloc(&s.w_info, sizeof(int32_t) * C * (size_t)rows));
+    s.w_frames = rows;
     return 0;
 }
 
-int codeset_reserve(ldpc_hip_ctx *c, long long piece) {
+int codeset_reserve(ldpc_hip_ctx *c, long long piece, int points = 1) {
     ldpc_codeset_state *s = c->codes;
-    return codeset_reserve(*s, piece, (void **)&s->w_llr, sizeof(double) * (size_t)c->N, (void **)&s->w_hard, sizeof(uint32_t) * (size_t)c->hard_words);
+    return codeset_reserve(*s, piece, (void **)&s->w_llr, sizeof(double) * (size_t)c->N, (void **)&s->w_hard, sizeof(uint32_t) * (size_t)c->hard_words, points);
 }
 
 // The channel of ldpc_hip_channel_llr_dev with modulation 0 on the all-zero word for the simulate entry points: noise keyed by
@@ -585,9 +601,11 @@ int codeset_piece_launch(ldpc_hip_ctx *c, ldpc::ChannelArgs &ch, int maxiter, do
 // The fixed-length run of the simulate entry points in pieces: run_piece(first, nb) draws, decodes and counts frames [first, first + nb)
 // of the call for all codes, leaving their records in w_info [C][nb] where frame_info is asked for.  The device is the caller's
 // current one; counters [C][5] and frame_info [C][B] (may be null) are the HOST results.
+// points > 1: an SNR grid, P * C rows everywhere: counters [P][C][5], frame_info [P][C][B].
 template <class Piece>
-int codeset_simulate_loop(codeset_common &s, long long piece, long long B, unsigned long long *counters, int32_t *frame_info, Piece run_piece) {
-    const size_t C = (size_t)s.C;
+int codeset_simulate_loop(codeset_common &s, long long piece, long long B, unsigned long long *counters, int32_t *frame_info, Piece run_piece,
+                          int points = 1) {
+    const size_t C = (size_t)s.C * (size_t)points;
     HIP_TRY(hipMemsetAsync(s.w_cnt, 0, sizeof(unsigned long long) * 5 * C, nullptr));
     for (long long done = 0; done < B; done += piece) {
         const long long nb = (B - done) < piece ? (B - done) : piece;
@@ -613,16 +631,28 @@ int codeset_stop_args(const char *who, const unsigned long long *state, long lon
 // n_active) draws, decodes and counts frames [first, first + nb) of the run for the n_active codes of `list` (DEVICE), leaving their
 // records in w_info [n_active][nb].  The device is the caller's current one; w_cnt [C][5] is cleared; state [C][4] is the HOST result.
 // full: the rule of an exact replay (stop_rule_codes_kernel<true>), which reads w_iters [n_active][nb] too; state is [C][6].
+// references [points] (HOST), points >= 1: an SNR grid -- the rows are the P * C items, point p's rule reads references[p]
+// (stop_rule_codes_kernel<FULL, true>) and reference_frame_error is not read; state is [P][C][4 or 6].
 template <class Piece>
 int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, long long n_experiments, double reference_frame_error, long long first_batch,
-                      long long max_batch, unsigned long long *state, Piece run_piece, bool full = false) {
-    const size_t C = (size_t)s.C, words = full ? 6 : 4;
+                      long long max_batch, unsigned long long *state, Piece run_piece, bool full = false, const double *references = nullptr,
+                      int points = 1) {
+    const size_t C = (size_t)s.C * (size_t)points, words = full ? 6 : 4;
     codeset_rule_ws &w = s.stop;
-    if (!w.rule) {
+    if (C > w.rows) {
+        void *old[] = {w.rule, w.running, w.list};
+        for (void *p : old)
+            if (p) (void)hipFree(p);
+        w.rule = nullptr; w.running = nullptr; w.list = nullptr; w.rows = 0;
         HIP_TRY(hipMalloc(&w.rule, sizeof(unsigned long long) * 6 * C));
         HIP_TRY(hipMalloc(&w.running, sizeof(int32_t) * C));
         HIP_TRY(hipMalloc(&w.list, sizeof(int32_t) * C));
-        HIP_TRY(hipMalloc(&w.nactive, sizeof(int32_t)));
+        if (!w.nactive) HIP_TRY(hipMalloc(&w.nactive, sizeof(int32_t)));
+        w.rows = C;
+    }
+    if (references) {
+        if (!w.reference) HIP_TRY(hipMalloc(&w.reference, sizeof(double) * ldpc::kGridPoints));
+        HIP_TRY(hipMemcpy(w.reference, references, sizeof(double) * (size_t)points, hipMemcpyHostToDevice));
     }
     std::vector<int32_t> ident(C), ones(C, 1);
     for (size_t q = 0; q < C; ++q) ident[q] = (int32_t)q;
@@ -641,7 +671,16 @@ int codeset_stop_loop(codeset_common &s, long long piece, int n_frame_errors, lo
             if (int rc = run_piece(first + done, nb, w.list, n_active)) return rc;
             const ldpc::CodesetRuleArgs ra{s.w_info, w.list, w.rule, w.running, nb, n_frame_errors, n_experiments, reference_frame_error};
             const ldpc::CodesetRuleFullArgs fa{ra, s.w_iters};
-            if (full) hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel<true>, dim3((unsigned)n_active), dim3(64), 0, nullptr, fa);
+            if (references && full) {
+                ldpc::CodesetRuleGridArgs<true> ga{};
+                static_cast<ldpc::CodesetRuleFullArgs &>(ga) = fa; ga.reference = w.reference; ga.C = s.C;
+                hipLaunchKernelGGL((ldpc::stop_rule_codes_kernel<true, true>), dim3((unsigned)n_active), dim3(64), 0, nullptr, ga);
+            } else if (references) {
+                ldpc::CodesetRuleGridArgs<false> ga{};
+                static_cast<ldpc::CodesetRuleArgs &>(ga) = ra; ga.reference = w.reference; ga.C = s.C;
+                hipLaunchKernelGGL((ldpc::stop_rule_codes_kernel<false, true>), dim3((unsigned)n_active), dim3(64), 0, nullptr, ga);
+            }
+            else if (full) hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel<true>, dim3((unsigned)n_active), dim3(64), 0, nullptr, fa);
             else hipLaunchKernelGGL(ldpc::stop_rule_codes_kernel<false>, dim3((unsigned)n_active), dim3(64), 0, nullptr, ra);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(ldpc::running_codes_kernel, dim3(1), dim3(64), 0, nullptr, w.running, (int)C, w.list, w.nactive);

@@ -51,12 +51,14 @@ __device__ __forceinline__ GlobCode<TabPtr, TabWords> codeset_glob_view(const Co
     const CodesetArgs &s = g.s;
     const int slot = (int)(item / s.B);
     const long long fr = item - (long long)slot * s.B;
-    const int c = s.code_list ? tab_ptr(s.code_list)[slot] : slot;
+    const unsigned list_item = s.code_list ? (unsigned)tab_ptr(s.code_list)[slot] : (unsigned)slot;   // p * C + c on an SNR grid
+    const unsigned p = __builtin_amdgcn_readfirstlane(list_item / (unsigned)s.C);   // wave-uniform, like the list itself
+    const int c = (int)(list_item - p * (unsigned)s.C);
     const TabPtr rec = tab_ptr(s.tab + tab_ptr(s.code_off)[c]);
     const int ne = rec[s.rh];
     GlobCode<TabPtr, TabWords> a;
     a.w = GlobFrame{glob_view(g.ws + (size_t)blockIdx.x * g.ws_stride, s.N, s.rh * s.M, ne, s.M, edge_arrays), s.M, s.N, s.rh * s.M, ne};
-    a.llr = s.llr + (long long)c * s.llr_code_stride + fr * s.N;
+    a.llr = s.llr + (long long)c * s.llr_code_stride + (long long)p * s.llr_point_stride + fr * s.N;
     a.hard = s.hard; a.iters = s.iters; a.soft_out = s.soft_out;   // [slot][frame]: row `item`
     a.out = item;
     a.row_start = rec;

@@ -237,6 +237,44 @@ __global__ void __launch_bounds__(256) channel_llr_kernel(const ChannelArgs a) {
     }
 }
 
+// channel_llr_kernel<0> on the all-zero word for an SNR grid of P points over ONE noise draw (upstream's `simulation` resets its
+// generator before every SNR, so all points of a curve see the same unit-variance samples and only sigma differs): one Box-Muller
+// pair per (frame, pair), then per point the two LLRs of that pair, -2.0 * (sigma_p * g + 2.0 * c - 1.0) / (sigma_p * sigma_p) with
+// c = 0, into llr [P][B][N] (point_stride = B * N).  The same punctured tail and 16-byte stores; no codewords, no interleaver.
+constexpr int kGridPoints = 64;
+struct ChannelGridArgs {
+    ChannelArgs c;             // sigma, tx, ncw, ntx, scatter and T are not read
+    long long point_stride;
+    int P;
+    double sigma[kGridPoints];
+};
+
+__global__ void __launch_bounds__(256) channel_llr_grid_kernel(const ChannelGridArgs g) {
+    const ChannelArgs &a = g.c;
+    const int units = (a.N + 1) / 2;
+    const long long total = a.B * (long long)units;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / units;
+        const int u = (int)(i - b * units);
+        double g0, g1;
+        gauss_pair(a.seed, (uint64_t)(a.first_frame + b), (uint32_t)u, 0u, g0, g1);
+        const double c0 = 0.0, c1 = 0.0;
+        const int j0 = 2 * u;
+        const bool p0 = j0 >= a.punct_start, p1 = j0 + 1 >= a.punct_start;
+        double *row = a.llr + b * (long long)a.N + j0;
+        for (int p = 0; p < g.P; ++p, row += g.point_stride) {
+            const double sigma = g.sigma[p], s2 = sigma * sigma;
+            const double v0 = p0 ? a.punct_val : -2.0 * (sigma * g0 + 2.0 * c0 - 1.0) / s2;
+            const double v1 = p1 ? a.punct_val : -2.0 * (sigma * g1 + 2.0 * c1 - 1.0) / s2;
+            if (j0 + 2 <= a.N && (a.N & 1) == 0) *reinterpret_cast<double2 *>(row) = make_double2(v0, v1);
+            else {
+                row[0] = v0;
+                if (j0 + 1 < a.N) row[1] = v1;
+            }
+        }
+    }
+}
+
 // QAM_modulator() at function level: bits [ns][m] (0/1 bytes, I rail first, MSB first) -> x [ns][2] (I, Q)
 struct ModArgs {
     const uint8_t *bits;

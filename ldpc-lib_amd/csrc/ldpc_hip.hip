@@ -1462,6 +1462,7 @@ int ldpc_hip_profile_read(ldpc_hip_ctx *c, double *total_ms, long long *launches
 #include "ldpc_gfq_chain_api.hpp"
 #include "ldpc_gfq_exact_api.hpp"
 #include "ldpc_codeset_api.hpp"
+#include "ldpc_codeset_grid_api.hpp"
 #include "ldpc_gfq_codeset_api.hpp"
 #include "ldpc_girth_api.hpp"
 #include "ldpc_label_api.hpp"

@@ -30,6 +30,7 @@
 
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace ldpc_mt {
@@ -435,6 +436,14 @@ struct PolarArgs {
     double sigma, punct_val;
 };
 
+// MODE 2 of mt_polar_kernel: the frame mode on the all-zero word for an SNR grid -- every accepted sample becomes one LLR per point
+constexpr int kPolarGridPoints = 64;
+struct PolarGridArgs : PolarArgs {   // sigma, tx and scatter of the base are not read; out is [P][row_hi - row_lo][N] with point_stride between the points
+    long long point_stride;
+    int P;
+    double sigmas[kPolarGridPoints];
+};
+
 constexpr int kPolarSub = 8;                       // a wave takes 64 * 8 consecutive attempts, a workgroup 4 waves
 constexpr int kPolarBlock = 256 * kPolarSub;       // attempts per workgroup
 constexpr unsigned long long kStAgg = 1ull << 62, kStPrefix = 2ull << 62, kStMask = (1ull << 62) - 1ull;
@@ -450,15 +459,16 @@ __device__ __forceinline__ unsigned long long mt_wave_sum(unsigned long long v) 
 // (Merrill & Garland 2016: a workgroup publishes its own count at once, then sums its predecessors' counts backwards until it
 // meets one that already knows its prefix), and emits.  The word stream is read once.  Workgroups number themselves from an atomic
 // ticket, so every predecessor of a running workgroup is itself running or done and none of them waits for a successor: the
-// look-back always terminates.
+// look-back always terminates.  MODE 2: MODE 1 in frame mode whose emit step writes, from the one `ret` of an accepted sample, the LLR
+// of every point of an SNR grid (the expression of MODE 1 per sigma_p): the tape is read once and the look-back runs once.
 template <int MODE>
-__global__ void __launch_bounds__(256) mt_polar_kernel(const PolarArgs a) {
+__global__ void __launch_bounds__(256) mt_polar_kernel(const std::conditional_t<MODE == 2, PolarGridArgs, PolarArgs> a) {
     __shared__ uint32_t wsum[4];
     __shared__ unsigned long long s_excl;
     __shared__ unsigned s_block;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned block = blockIdx.x;
-    if (MODE == 1) {
+    if (MODE != 0) {
         if (tid == 0) s_block = atomicAdd(a.ticket, 1u);
         __syncthreads();
         block = s_block;
@@ -567,7 +577,15 @@ __global__ void __launch_bounds__(256) mt_polar_kernel(const PolarArgs a) {
         const double mult = sqrt(ldpc_spec::div_ranged(-2.0 * ldpc_spec::log_glibc(r2), r2));
         double ret = ys[sub] * mult;                                         // :1830
         ret = ret * 1.0 + 0.0;                                               // :1833 stddev 1, mean 0
-        if (!pf) {
+        if constexpr (MODE == 2) {
+            const bool punct = (int)i >= a.punct_start;
+            double *o = a.out + (f - a.row_lo) * (long long)pf + i;
+            for (int p = 0; p < a.P; ++p, o += a.point_stride) {
+                const double sigma = a.sigmas[p];
+                const double v = -2.0 * (sigma * ret + 2.0 * 0.0 - 1.0) / (sigma * sigma);   // bp_simulation.cpp:603, the all-zero word
+                *o = punct ? a.punct_val : v;
+            }
+        } else if (!pf) {
             a.out[g] = ret;
         } else {
             double c = 0.0;

@@ -165,8 +165,16 @@ int mt_count(ldpc_hip_ctx *c, const MtPlan &pl, const MtWindow &w, long long at_
     return 0;
 }
 
-// the fused pass over the window's attempts; base0 = accepted attempts in front of w.at_lo (asynchronous)
-int mt_emit(ldpc_hip_ctx *c, const MtPlan &pl, const MtWindow &w, ldpc_mt::PolarArgs a, unsigned long long base0, hipStream_t st) {
+// An SNR grid on a binary code set: the points that one emit pass writes from the same samples (mt_polar_kernel<2>)
+struct MtGrid {
+    int P = 0;
+    long long point_stride = 0;   // doubles between the rows of two points
+    const double *sigma = nullptr;   // [P]
+};
+
+// the fused pass over the window's attempts; base0 = accepted attempts in front of w.at_lo (asynchronous).  grid: every point's rows
+int mt_emit(ldpc_hip_ctx *c, const MtPlan &pl, const MtWindow &w, ldpc_mt::PolarArgs a, unsigned long long base0, hipStream_t st,
+            const MtGrid *grid = nullptr) {
     using namespace ldpc_mt;
     mt_fill(c, pl, w, a);
     a.at_lo = w.at_lo; a.at_hi = w.at_hi; a.base0 = base0;
@@ -174,7 +182,17 @@ int mt_emit(ldpc_hip_ctx *c, const MtPlan &pl, const MtWindow &w, ldpc_mt::Polar
     HIP_TRY(hipMemsetAsync(c->mt.d_ticket, 0, sizeof(unsigned), st));
     if (nb > 0) {
         HIP_TRY(hipMemsetAsync(c->mt.d_status, 0, sizeof(unsigned long long) * (size_t)nb, st));
-        hipLaunchKernelGGL(mt_polar_kernel<1>, dim3((unsigned)nb), dim3(256), 0, st, a);
+        if (grid) {
+            static_assert(kPolarGridPoints == ldpc::kGridPoints, "one limit for the points of an SNR grid: the channel kernels of both noise sources");
+            if (grid->P < 1 || grid->P > kPolarGridPoints) return fail(LDPC_HIP_EINVAL, "exact-replay emit pass: %d points; 1 .. %d", grid->P, kPolarGridPoints);
+            PolarGridArgs ga{};
+            static_cast<PolarArgs &>(ga) = a;
+            ga.P = grid->P; ga.point_stride = grid->point_stride;
+            for (int p = 0; p < grid->P; ++p) ga.sigmas[p] = grid->sigma[p];
+            hipLaunchKernelGGL(mt_polar_kernel<2>, dim3((unsigned)nb), dim3(256), 0, st, ga);
+        } else {
+            hipLaunchKernelGGL(mt_polar_kernel<1>, dim3((unsigned)nb), dim3(256), 0, st, a);
+        }
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -198,14 +216,15 @@ int mt_finish(ldpc_hip_ctx *c, const MtPlan &pl, const MtWindow &w, ldpc_mt::Pol
 // One generation round on one context, whole tape: draws from the context's generator until `need` items exist or the round's
 // words run out, emits min(need, produced) items (whole frames when proto.per_frame != 0) through proto.out, and moves the generator
 // to the word after the last emitted item.  Synchronises the stream (the count of accepted attempts decides how far the round got).
-int mt_round(ldpc_hip_ctx *c, unsigned long long need, ldpc_mt::PolarArgs proto, unsigned long long *emitted, hipStream_t st) {
+int mt_round(ldpc_hip_ctx *c, unsigned long long need, ldpc_mt::PolarArgs proto, unsigned long long *emitted, hipStream_t st,
+             const MtGrid *grid = nullptr) {
     using namespace ldpc_mt;
     DeviceState &m = c->mt;
     const MtPlan pl = mt_plan(m.pos, need);
     const MtWindow w = mt_window(pl, 0, pl.pos + 4 * pl.attempts + MTN);
     if (int rc = mt_ensure(c, w)) return rc;
     if (int rc = mt_generate(c, w, st)) return rc;
-    if (int rc = mt_emit(c, pl, w, proto, 0ull, st)) return rc;
+    if (int rc = mt_emit(c, pl, w, proto, 0ull, st, grid)) return rc;
     if (int rc = mt_finish(c, pl, w, proto, 0ull, -1, st)) return rc;
     HIP_TRY(hipMemcpyAsync(m.d_state, m.d_state_next, sizeof(uint32_t) * MTN, hipMemcpyDeviceToDevice, st));
     unsigned long long tot[2] = {0, 0};
@@ -291,9 +310,11 @@ inline long long mt_frames_per_round(const ldpc_hip_ctx *c) {
 }
 
 // LLR rows of the next B frames of the generator's stream; of those, frames [lo, hi) are written to d_rows ([hi - lo][N]); d_rows
-// may be null (the frames are drawn and dropped).
+// may be null (the frames are drawn and dropped).  grid (a binary code set, modulation 0, with d_rows): the rows of every point from
+// the same samples, point p's at d_rows + p * grid->point_stride; snr_db then only passes mt_frame_proto's checks, the generator
+// advances by B frames once.
 int mt_llr_rows(ldpc_hip_ctx *c, double snr_db, int modulation_type, int punctured_blocks, long long B, long long lo, long long hi,
-                double *d_rows, hipStream_t st) {
+                double *d_rows, hipStream_t st, const MtGrid *grid = nullptr) {
     using namespace ldpc_mt;
     DeviceState &m = c->mt;
     PolarArgs a{};
@@ -308,7 +329,7 @@ int mt_llr_rows(ldpc_hip_ctx *c, double snr_db, int modulation_type, int punctur
         if (d_rows && r_lo < r_hi) { a.row_lo = r_lo - done; a.row_hi = r_hi - done; a.out = d_rows + (r_lo - lo) * (long long)c->N; }
         else { a.row_lo = 0; a.row_hi = 0; a.out = nullptr; }
         unsigned long long emitted = 0;
-        if (int rc = mt_round(c, (unsigned long long)fr * (unsigned long long)c->N, a, &emitted, st)) return rc;
+        if (int rc = mt_round(c, (unsigned long long)fr * (unsigned long long)c->N, a, &emitted, st, a.out ? grid : nullptr)) return rc;
         const long long fdone = (long long)(emitted / (unsigned long long)c->N);
         done += fdone;
         m.frames_taken += fdone;
